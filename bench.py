@@ -12,7 +12,17 @@ per-GPU work is fixed as N grows ("weak").
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the fc1
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps
+and prints the line (`value`, `ms_per_step`, `roofline` from the events of the timed
+region with the committed traffic figure, finite-logit checks); with --dump-outputs DIR
+it first writes the last timed step's logits and probabilities to DIR/<name>.npy.
+Everything else described below -- the per-operator table, the live PMC traffic, the
+CPU baseline and parity, the secondary legs, the in-library multi-GPU leg, the
+sustained leg and (N > 1) the bitwise check of the gathered rows -- runs with --full:
+
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full
+
+`roofline` is for the dominant kernel (the fc1
 GEMM: gemm_p3_kernel<8,256,EPI_GELU,OUT_P3> plus its 128x128-tile launch for the last
 partial scheduling round, csrc/gemm_p3.hip): algorithmic FLOPs per launch divided by
 its mean launch duration, measured with HIP events recorded on the launch stream
@@ -220,6 +230,23 @@ def measure_fc1_traffic(B: int):
                      f"Infinity-Cache hits included); FETCH_SIZE {means['FETCH_SIZE']:.0f} KiB, WRITE_SIZE {means['WRITE_SIZE']:.0f} KiB")
 
 
+DUMP_LIMIT_BYTES = 60_000_000      # all arrays together, .npy headers included: under 64 MB
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """Write each array as out_dir/<name>.npy in float32.  Past DUMP_LIMIT_BYTES in all, each array keeps a fixed, seeded
+    sample of its rows (in order), the same from run to run for the same arguments."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.shape[0] * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def spawn_ranks(n: int) -> int:
     """Start `n` ranks of this script under torch.distributed.run (one per GPU, rendezvous on 127.0.0.1) as a child
     process and wait for it.  Called before anything in this process has initialised the GPU; nothing is re-exec'd."""
@@ -340,6 +367,12 @@ def main() -> None:
     ap.add_argument("--sustain-s", type=float, default=30.0,
                     help="seconds of the same step behind the timed region for the `sustained` leg (0 = skip)")
     ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with rocprofv3 PMC passes (child process)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run every other measurement and check (per-operator table, live PMC "
+                         "traffic, CPU baseline and parity, secondary legs, in-library multi-GPU, sustained, gather check); "
+                         "the --no-* and --sustain-s options above apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's logits and probabilities to DIR/<name>.npy (float32)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--in-library-multi-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--first-device", type=int, default=0, help=argparse.SUPPRESS)
@@ -442,13 +475,20 @@ def main() -> None:
     fence()
     elapsed = time.perf_counter() - t0
     prof_timed = model.profile_read()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the class logits (N > 1: every rank's rows, as
+        # gathered on rank 0) and the probabilities of this rank's images
+        logits_all = np.concatenate([t.cpu().numpy() for t in gathered[0]]) if comm is not None else logits_host()
+        dump_outputs(args.dump_outputs, {"logits": logits_all, "probs": d_probs.to_numpy((B, NC))})
     PROF_STEPS = 3
-    model.profile_select(None)
-    model.profile_enable(PROF_STEPS)
-    for _ in range(PROF_STEPS):
-        step()
-    fence()
-    prof = model.profile_read()
+    prof = {}
+    if args.full:
+        model.profile_select(None)
+        model.profile_enable(PROF_STEPS)
+        for _ in range(PROF_STEPS):
+            step()
+        fence()
+        prof = model.profile_read()
     model.profile_enable(0)
 
     if comm is not None:
@@ -458,7 +498,7 @@ def main() -> None:
     # it recomputes that rank's first and last images (global index r*B + i) ON THE SAME BATCH POSITIONS -- so the
     # same tiles and launches produce them -- and requires the gathered rows to equal them bit for bit.
     gathered_ok = None
-    if comm is not None and rank == 0:
+    if args.full and comm is not None and rank == 0:
         rows_all = [np.ascontiguousarray(t.cpu().numpy()) for t in gathered[0]]
         assert len(rows_all) == world and all(r.shape == (B, NC) for r in rows_all), "gather returned the wrong shapes"
         own = logits_host()
@@ -550,7 +590,7 @@ def main() -> None:
     # Opt-in leg (never `value`): the last encoder layer's output projection and MLP evaluated for the class-token
     # rows only -- the rows the classifier reads; logits identical bit for bit (checked here).
     cls_leg = None
-    if comm is None and args.dtype == "f32":
+    if args.full and comm is None and args.dtype == "f32":
         l_full = logits_host()
         if model.set_last_layer_cls_only(True) is False:
             for _ in range(2):
@@ -570,7 +610,7 @@ def main() -> None:
         pkg.binding.check(L.vh_device_sync(), "sync")
 
     emu_logits0 = None
-    if comm is None and args.dtype == "f32":
+    if args.full and comm is None and args.dtype == "f32":
         def leg(*a):
             """a secondary leg that fails is reported in its place (and on stderr); `value` and the line do not depend on it"""
             try:
@@ -591,7 +631,7 @@ def main() -> None:
         pkg.binding.check(L.vh_device_sync(), "sync")
 
     e2e = None
-    if comm is None and args.model == "vit_b_16" and not args.no_end_to_end:
+    if args.full and comm is None and args.model == "vit_b_16" and not args.no_end_to_end:
         e2e = end_to_end(model)
         # restore the device-resident outputs the checks below read
         model.forward_device(d_images.ptr, B, d_logits_ptr, d_probs.ptr, stream)
@@ -600,7 +640,7 @@ def main() -> None:
     # What a Main.c user sees (Main.c:51-57 times the whole call): ViT_opencl() on 100 host images, context creation
     # (weight upload + repack + arenas) included, split into setup and forward by the library's own clock.
     drop_in = None
-    if comm is None and args.dtype == "f32" and args.model == "vit_b_16" and not args.no_end_to_end:
+    if args.full and comm is None and args.dtype == "f32" and args.model == "vit_b_16" and not args.no_end_to_end:
         import ctypes as C
         n_di = 100
         host = pkg.synth_images(cfg, 0, n_di)
@@ -643,7 +683,7 @@ def main() -> None:
     # the max-over-ranks time above), synchronised about once a second; fc1's per-launch time (HIP events, as in the
     # timed region) is the clock proxy.  No reference counterpart (Main.c:51-57 times one shot).
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         step_s = elapsed / args.steps
         chunk = max(1, int(round(1.0 / step_s)))
         n_chunks = max(2, int(np.ceil(args.sustain_s / (chunk * step_s))))
@@ -759,10 +799,10 @@ def main() -> None:
         # of csrc/gemm_p3.hip; when the file has changed since, the figure is withheld and marked stale.
         traffic, traffic_src, traffic_stale = None, None, None
         if B == 512 and args.model == "vit_b_16" and p3:
-            if comm is None and not args.no_pmc and "VIT_HIP_P3" not in os.environ:
+            if args.full and comm is None and not args.no_pmc and "VIT_HIP_P3" not in os.environ:
                 traffic, traffic_src = measure_fc1_traffic(B)      # live: PMC passes over a child process of this very run
                 traffic_stale = False if traffic is not None else None
-            if traffic is None:     # N > 1, --no-pmc, or the profiler could not run: the committed passes, tied to the kernel source
+            if traffic is None:     # plain run, N > 1, --no-pmc, or the profiler could not run: the committed passes, tied to the kernel source
                 live_note = traffic_src
                 traffic, traffic_src, traffic_stale = committed_traffic(ROOT)
                 if live_note and traffic_src:
@@ -819,10 +859,12 @@ def main() -> None:
             "model_tflops": round(total_flops * B * args.steps * world / elapsed / 1e12, 2),
             "model_frac_of_f32_mfma_peak": round(total_flops * B * args.steps / elapsed / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
             "layer_norms_folded": bool(L.vit_hip_ln_fold(model.ctx)),
-            "roofline": roofline, "kernels": kernels,
-            "kernels_note": f"per-operator averages from a separate pass of {PROF_STEPS} steps with every launch bracketed "
-                            "by HIP events; the roofline kernel is bracketed inside the timed region",
+            "roofline": roofline,
         }
+        if args.full:
+            out["kernels"] = kernels
+            out["kernels_note"] = (f"per-operator averages from a separate pass of {PROF_STEPS} steps with every launch "
+                                   "bracketed by HIP events; the roofline kernel is bracketed inside the timed region")
         if sustained is not None:
             sustained["last_5s_vs_value"] = round(sustained["last_5s"]["value"] / value, 4)
             sustained["last_5s_more_than_3pct_below_value"] = bool(sustained["last_5s"]["value"] < 0.97 * value)
@@ -845,7 +887,7 @@ def main() -> None:
                              "what": "rank 0 recomputed the first and last 4 images of every other rank's shard (global "
                                      "index rank*B+i) on the same batch positions and found the gathered rows bit-identical"}
         parity_failed = None
-        if not args.no_cpu_baseline and args.model == "vit_b_16":
+        if args.full and not args.no_cpu_baseline and args.model == "vit_b_16":
             # rank 0 only; at N > 1 the other ranks wait at the closing barrier meanwhile
             base, ref_logits = cpu_baseline(B, args.cpu_procs)
             out["cpu_baseline"] = base
@@ -871,7 +913,7 @@ def main() -> None:
                     parity_failed = f"parity {out['parity']['max_abs_dlogit_vs_ViT_seq']:.3e} exceeds {tol} (or arg-max differs)"
         out["checks"] = {"logits_finite": bool(np.isfinite(logits0).all()),
                          "prob_sum_image0": float(probs0.sum())}
-        if args.dtype == "f32" and args.model == "vit_b_16" and not args.no_in_library_multi:
+        if args.full and args.dtype == "f32" and args.model == "vit_b_16" and not args.no_in_library_multi:
             # the library's own multi-GPU entry (RCCL gather in C) on the same devices, in a child process, while the
             # other ranks wait on the host (Comm.rank0_says_done): beside `value`, never instead of it
             one_card = "VIT_BENCH_DEVICE" in os.environ

@@ -28,6 +28,11 @@ Fixtures (inputs are regenerated from seeds, never stored):
                   224x224 photograph (spatially correlated pixels, unlike every synthetic image) -- kept as a data fixture,
                   with the logits / probabilities the reference's ViT_seq.c gives for it on the seed-0 synthetic weights
                   (its pretrained answer Data/answer_result_1.txt cannot be reproduced: 36 weight files are absent)
+  b16_stages_sha256.json  (`make_golden.py stage_digests`) sha256 of every element of the reference's per-stage outputs
+                  for image 0 / layer 0 (the tensors b16_stages.npz only samples), so that the element-by-element check of
+                  the port's stages runs where the reference is absent
+  ref_abi_layout.json  (`make_golden.py abi_layout <reference dir>`) sizeof / offsetof of ImageData and Network as the reference's own
+                  Network.h declares them (x86-64, gcc), the layout include/Network.h must keep
 """
 from __future__ import annotations
 
@@ -125,7 +130,67 @@ def other_seed() -> None:
     print("seed 1: argmax", rec["logits"].reshape(2, 1000).argmax(1))
 
 
+STAGES = ("conv", "tokens", "ln", "mha", "mlp", "enc0")
+
+
+def stage_digests() -> None:
+    """The reference's ViT_seq.c stage outputs for image 0 / layer 0 -> sha256 of their float32 bytes, every element."""
+    import hashlib
+    import json
+    orc.build()
+    if not orc.have_reference():
+        sys.exit("needs the build container (oracle/_ref/ref_harness)")
+    with tempfile.TemporaryDirectory() as td:
+        st = orc.run_reference("stages", 0, out_path=Path(td) / "stages.bin")
+    rec = {"what": "sha256 of the float32 bytes of the reference's own ViT_seq.c stage outputs, synthetic image 0, weights "
+                   "seed_base 0, encoder layer 0 (oracle/make_golden.py stage_digests)",
+           "stages": {n: {"count": int(st[n].size), "sha256": hashlib.sha256(np.ascontiguousarray(st[n], np.float32).tobytes())
+                          .hexdigest()} for n in STAGES}}
+    (GOLD / "b16_stages_sha256.json").write_text(json.dumps(rec, indent=1) + "\n")
+    print("wrote b16_stages_sha256.json")
+
+
+LAYOUT_PROBE = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "%s"
+int main(void)
+{
+    printf("{\"ImageData\": {\"sizeof\": %%zu, \"offsetof\": {\"n\": %%zu, \"c\": %%zu, \"h\": %%zu, \"w\": %%zu, "
+           "\"data\": %%zu}}, \"Network\": {\"sizeof\": %%zu, \"offsetof\": {\"data\": %%zu, \"size\": %%zu}}}\n",
+           sizeof(ImageData), offsetof(ImageData, n), offsetof(ImageData, c), offsetof(ImageData, h),
+           offsetof(ImageData, w), offsetof(ImageData, data), sizeof(Network), offsetof(Network, data),
+           offsetof(Network, size));
+    return 0;
+}
+'''
+
+
+def abi_layout(ref_dir: str) -> None:
+    """sizeof / offsetof of the reference's ImageData and Network, compiled from its own Network.h (in ref_dir, the
+    reference's MulticoreMainProject directory) -> ref_abi_layout.json."""
+    import json
+    import subprocess
+    header = Path(ref_dir) / "Network.h"
+    if not header.is_file():
+        sys.exit(f"{header}: not found (usage: make_golden.py abi_layout <the reference's MulticoreMainProject directory>)")
+    with tempfile.TemporaryDirectory() as td:
+        (Path(td) / "probe.c").write_text(LAYOUT_PROBE % header)
+        subprocess.run(["gcc", "-fcommon", "-o", str(Path(td) / "probe"), str(Path(td) / "probe.c")], check=True)
+        layout = json.loads(subprocess.run([str(Path(td) / "probe")], check=True, capture_output=True, text=True).stdout)
+    rec = {"what": "sizeof / offsetof of ImageData and Network as the reference's Network.h declares them, x86-64 gcc "
+                   "(oracle/make_golden.py abi_layout)", **layout}
+    (GOLD / "ref_abi_layout.json").write_text(json.dumps(rec, indent=1) + "\n")
+    print("wrote ref_abi_layout.json:", layout)
+
+
 def main() -> None:
+    if len(sys.argv) > 1 and sys.argv[1] == "stage_digests":
+        stage_digests()
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == "abi_layout":
+        abi_layout(sys.argv[2])
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "other_seed":
         other_seed()
         return

@@ -46,7 +46,7 @@ def test_bench_two_ranks_launch_themselves_verify_the_gather_and_report_the_cpu_
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(VIT_DIST_BACKEND="gloo", VIT_BENCH_DEVICE="0")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "64", "--cpu-procs", "2", "--sustain-s", "3"], env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", "64", "--cpu-procs", "2", "--sustain-s", "3", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -72,7 +72,7 @@ def test_bench_single_gpu_line_carries_every_leg_without_errors():
     reported in its place), so this test is what keeps a broken leg from passing silently."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "64", "--sustain-s", "0",
-                        "--no-pmc", "--no-cpu-baseline", "--no-in-library-multi"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-pmc", "--no-cpu-baseline", "--no-in-library-multi", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -96,8 +96,33 @@ def test_bench_rccl_branch_with_a_group_of_one():
     env = {k: v for k, v in os.environ.items() if k not in ("VIT_DIST_BACKEND", "VIT_BENCH_DEVICE")}
     env.update(VIT_DIST_FORCE="1", WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64",
-                        "--no-cpu-baseline", "--no-in-library-multi", "--sustain-s", "2"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--no-in-library-multi", "--sustain-s", "2", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["gather"]["backend"] == "rccl" and out["gather"]["rccl_ranks"] == 1
     assert out["value"] > 0 and out["checks"]["logits_finite"] and abs(out["checks"]["prob_sum_image0"] - 1.0) < 1e-5
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py --gpus 1` (no --full): the headline line only -- none of the legs that take runs of their own --
+    and, with --dump-outputs, the logits and probabilities of the last timed step as float32 .npy files."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64",
+                        "--dump-outputs", str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert out["value"] > 0 and out["unit"] == "images/sec" and out["ms_per_step"] > 0
+    assert abs(out["value"] - 64 * 1e3 / out["ms_per_step"]) < 1e-2 * out["value"]
+    assert 0 < out["roofline"]["frac"] < 1 and out["checks"]["logits_finite"]
+    for key in ("kernels", "cpu_baseline", "parity", "sustained", "bf16_gemm_mode", "end_to_end", "drop_in_100",
+                "in_library_multi_gpu", "class_token_rows_only_last_layer"):
+        assert key not in out, key
+    import numpy as np
+    logits, probs = np.load(tmp_path / "dump" / "logits.npy"), np.load(tmp_path / "dump" / "probs.npy")
+    assert logits.shape == probs.shape == (64, 1000) and logits.dtype == probs.dtype == np.float32
+    assert np.isfinite(logits).all() and np.allclose(probs.sum(1), 1.0, atol=1e-4)
+    assert abs(float(probs[0].sum()) - out["checks"]["prob_sum_image0"]) < 1e-6

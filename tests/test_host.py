@@ -38,10 +38,33 @@ def test_struct_layout_is_the_reference_abi(pkg):
     assert C.sizeof(b.Network) == 16 and b.Network.data.offset == 0 and b.Network.size.offset == 8
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference tree not present")
 def test_struct_layout_against_reference_header(tmp_path):
-    """Compile a probe that includes the reference's own Network.h next to ours and
-    static-asserts identical sizes/offsets (header only; nothing is copied)."""
+    """Our include/Network.h, compiled, lays out ImageData and Network exactly as the reference's own Network.h does:
+    sizeof / offsetof from a compiled probe against tests/golden/ref_abi_layout.json, which oracle/make_golden.py
+    abi_layout took from the reference header.  Where the reference tree is present, a second probe includes its
+    Network.h next to ours and static-asserts identical sizes/offsets (header only; nothing is copied)."""
+    import json
+    probe = tmp_path / "layout.c"
+    probe.write_text(r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "%s/include/Network.h"
+int main(void)
+{
+    printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu %%zu %%zu\n", sizeof(ImageData), offsetof(ImageData, n),
+           offsetof(ImageData, c), offsetof(ImageData, h), offsetof(ImageData, w), offsetof(ImageData, data),
+           sizeof(Network), offsetof(Network, data), offsetof(Network, size));
+    return 0;
+}
+''' % ROOT)
+    subprocess.run(["gcc", "-o", str(tmp_path / "layout"), str(probe)], check=True)
+    ours = [int(v) for v in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.split()]
+    gold = json.loads((ROOT / "tests" / "golden" / "ref_abi_layout.json").read_text())
+    img, net = gold["ImageData"], gold["Network"]
+    assert ours == [img["sizeof"], *(img["offsetof"][f] for f in ("n", "c", "h", "w", "data")),
+                    net["sizeof"], net["offsetof"]["data"], net["offsetof"]["size"]]
+    if not os.path.isdir(REF):      # absent, or not readable by this user
+        return
     src = tmp_path / "probe.c"
     src.write_text(r'''
 #include <stddef.h>
@@ -494,3 +517,27 @@ def test_drop_in_with_zero_images_returns_without_a_device(pkg, capfd):
     su, fw = C.c_double(-1), C.c_double(-1)
     L.vit_hip_last_call_seconds(C.byref(su), C.byref(fw))
     assert su.value == 0.0 and fw.value == 0.0
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_the_same_rows_past_64_mb(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float32; past the size limit each array keeps a fixed,
+    seeded sample of its rows, so two runs with the same arguments write the same files, and all of them stay under 64 MB."""
+    import importlib
+    bench = importlib.import_module("bench")
+    small = {"logits": np.arange(12, dtype=np.float64).reshape(3, 4), "probs": np.ones((3, 4), np.float32)}
+    bench.dump_outputs(tmp_path / "small", small)
+    for name, a in small.items():
+        got = np.load(tmp_path / "small" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    big = {"logits": np.arange(1000 * 8, dtype=np.float32).reshape(1000, 8), "probs": np.arange(500 * 8).reshape(500, 8)}
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, big)
+    total = 0
+    for name, a in big.items():
+        got_a, got_b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(got_a, got_b) and 1 <= got_a.shape[0] < a.shape[0] and got_a.shape[1] == 8
+        rows = got_a[:, 0].astype(np.int64) // 8
+        assert np.array_equal(got_a, a[rows].astype(np.float32)) and (np.diff(rows) > 0).all()
+        total += got_a.nbytes
+    assert total <= 4000
