@@ -87,8 +87,8 @@ int vit_hip_create_ex(vit_hip_ctx **out, const vit_config *cfg, const Network *n
                       int n_tensors, int device, int max_batch, int precision);
 int vit_hip_precision(const vit_hip_ctx *ctx);
 /* 1 when the context folds every LayerNorm but the final one into the projection behind it (csrc/norm_fold.h): the
- * default of BF16_GEMM and FP8_GEMM ($VIT_HIP_LN_FOLD=0 at creation keeps the separate LayerNorm launches); never for
- * the fp32 paths. */
+ * default of BF16_GEMM and FP8_GEMM ($VIT_HIP_LN_FOLD=0 at creation keeps the separate LayerNorm launches); on F32 only
+ * as a lab variant on the three-part planes ($VIT_HIP_LN_FOLD=1); never for F32_FP16X2. */
 int vit_hip_ln_fold(const vit_hip_ctx *ctx);
 
 /* Repacked weights on disk (the offline half of the weight-format tooling): export writes what the context holds in HBM

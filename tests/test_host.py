@@ -288,11 +288,12 @@ def test_shards_are_entered_concurrently_and_timed(pkg):
     assert L.vit_shard_run_timed(4, 4, b.SHARD_FN(slow_or_fail), None, None) == 5      # the times are optional
 
 
-def test_planes_file_header_is_checked_before_anything_is_allocated(pkg, tmp_path):
+def test_planes_file_header_is_checked_before_anything_is_allocated(pkg, tmp_path, monkeypatch):
     """vit_hip_create_from_planes on files that must be refused -- without a GPU, i.e. before the library has touched a
     device or allocated a slab: a foreign file, another operand-layout version, a header asking for absurd dimensions
     (a corrupt or hostile file must not be able to request arbitrary host and HBM allocations), and a header whose slab
-    sizes are not the ones this library derives from (shape, precision, fold flag)."""
+    sizes are not the ones this library derives from (shape, precision, fold flag), and a fold flag the shape, precision
+    or planes path cannot honour."""
     import struct
     L, b = pkg.lib(), pkg.binding
     L.vit_hip_create_from_planes.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_int]
@@ -322,6 +323,16 @@ def test_planes_file_header_is_checked_before_anything_is_allocated(pkg, tmp_pat
     assert rc == 125 and "slab sizes" in msg                             # a petabyte of weights: refused by the size check
     rc, msg = load(header(precision=7))
     assert rc != 0
+    # a LayerNorm fold the context could not run: refused with the shape, not at the slab sizes or the first forward
+    for precision in (0, 1, 2):                                          # embed 2304: 18 partial sums per row, at most 16
+        rc, msg = load(header(precision=precision, ints=(224, 16, 3, 1000, 2304, 12, 12, 3072), fold=(0, 1)))
+        assert rc == 2 and "shape or precision" in msg
+    rc, msg = load(header(ints=(224, 16, 3, 1000, 768, 12, 12, 3000), fold=(0, 1)))
+    assert rc == 2 and "shape or precision" in msg                      # fp32 fold: mlp_hidden % 128 != 0
+    monkeypatch.setenv("VIT_HIP_P3", "0")
+    rc, msg = load(header(fold=(0, 1)))
+    assert rc == 2 and "shape or precision" in msg                      # fp32 fold without the planes path
+    monkeypatch.delenv("VIT_HIP_P3")
     ctx = C.c_void_p()
     assert L.vit_hip_create_from_planes(C.byref(ctx), str(tmp_path / "missing.planes").encode(), 0, 4) == 123
 

@@ -36,6 +36,28 @@
         }                         \
     } while (0)
 
+/* The mode's GEMM-operand copy of one of the four big matrices of a layer (in_proj, out_proj, fc1, fc2) */
+struct operand
+{
+    void *w;             /* three-part planes (F32; NULL for shapes the planes cannot take), one-part planes (BF16_GEMM),
+                          * two fp16 parts (F32_FP16X2) or MX e4m3 values (FP8_GEMM) */
+    void *scales;        /* FP8_GEMM: the e8m0 block scales of w */
+    float pair_scale;    /* F32_FP16X2: the power of two the fp16 parts were scaled by */
+    /* ln_fold, in_proj and fc1 only (csrc/norm_fold.h): w holds the gamma-scaled matrix; colsum [N] of its rounded values
+     * and the folded bias [N] */
+    float *colsum, *bias_folded;
+};
+
+/* The weight slabs, one device allocation each, in the order a planes file stores them */
+enum { SLAB_F32, SLAB_OPERAND, SLAB_CONV, SLAB_FOLD, N_SLABS };
+
+/* How the planes paths (F32 on planes, BF16_GEMM, FP8_GEMM) run attention: Q|K|V as one-part fp16 planes into a resident
+ * kernel -- head_dim 64, or head_dim 80 (ViT-H/14, reduced modes only) which writes the output projection's operand
+ * itself -- or fp32 rows through the streaming kernel */
+enum { ATTN_STREAMING, ATTN_HD64, ATTN_HD80 };
+
+enum { MAX_DEPTH = 256, MAX_TENSORS = 4 + 12 * MAX_DEPTH + 4 };
+
 struct vit_hip_ctx
 {
     vit_config cfg;
@@ -45,29 +67,19 @@ struct vit_hip_ctx
     int n_tensors;
     vh_stream_t stream;
 
-    float *w_slab;      /* all weights, one allocation */
-    float **w;          /* device pointer per tensor index */
-    int precision;      /* VIT_PRECISION_F32 or VIT_PRECISION_BF16_GEMM */
-    void *w16_slab;     /* bf16 copies of the four big matrices of every layer */
-    void **w16;         /* per tensor index (NULL where no bf16 copy exists) */
-    /* F32: the same four matrices pre-split into three bf16 planes each (vh_launch_linear_w3) */
-    void *w3_slab;
-    void **w3;          /* per tensor index (NULL: use the fp32 tensor) */
-    float *w3_scale;    /* F32_FP16X2: per tensor index, the power of two its fp16 parts were scaled by */
+    /* the plan: everything a forward branches on, fixed by ctx_new before anything is allocated */
+    int precision;      /* VIT_PRECISION_* */
+    int ln_fold;        /* every LayerNorm but the final one folded into the projection behind it (csrc/norm_fold.h) */
     int use_p3;         /* F32: GEMM inputs travel as three-part bf16 planes (y, attn, hid hold 6 bytes per value) */
     int cls_only_last;  /* use_p3: the last layer's output projection and MLP run on the class-token rows only */
-    /* FP8_GEMM: block-scaled e4m3 copies of the same four matrices (values, then their e8m0 block scales) */
-    void *w8_slab;
-    void **w8, **w8s;   /* per tensor index: values, scales */
-    /* conv_proj as planes [Kp/32][parts][E][32]: one part (bf16) for BF16_GEMM / FP8_GEMM (vh_launch_patch_embed_planes),
-     * the exact three-part split for the fp32 path on planes (vh_launch_patch_embed_planes3) */
-    void *wconv16;
-    /* BF16_GEMM / FP8_GEMM with the LayerNorms folded into the projections behind them (csrc/norm_fold.h): the QKV and fc1
-     * operand copies hold gamma-scaled weights; per such matrix, colsum [N] of the rounded values and the folded bias [N] */
-    int ln_fold;
-    float *fold_slab;
-    float **fold_cs, **fold_b;   /* per tensor index (in_proj and fc1 weights only) */
-    size_t w_slab_bytes, planes_bytes, wconv16_bytes, fold_bytes;   /* sizes of w_slab, of the mode's repacked slab, of wconv16, of fold_slab */
+    int attn_form;      /* ATTN_*, for the planes paths */
+
+    void *slab[N_SLABS];
+    size_t slab_bytes[N_SLABS];
+    float **w;          /* SLAB_F32: device pointer per tensor index, every tensor in fp32 */
+    struct operand *op; /* SLAB_OPERAND and SLAB_FOLD: [depth][4] (in_proj, out_proj, fc1, fc2) */
+    /* SLAB_CONV: conv_proj as planes [Kp/32][parts][E][32]: one part (bf16) for BF16_GEMM / FP8_GEMM
+     * (vh_launch_patch_embed_planes), the exact three-part split for F32 (vh_launch_patch_embed_planes3) */
 
     /* activation arena (rows = max_batch * tokens) */
     float *x;           /* residual stream      [rows][E]   */
@@ -160,28 +172,16 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
 {
     if (!ctx)
         return;
-    if (ctx->stream || ctx->w_slab)   /* a context that never reached the device (refused header, bad arguments) leaves the
-                                       * device -- and the caller's error text -- alone */
+    if (ctx->stream) {   /* a context that never reached the device (refused header, bad arguments) leaves the device --
+                          * and the caller's error text -- alone */
         vh_set_device(ctx->device);
-    if (ctx->stream)
         vh_stream_sync(ctx->stream);
+    }
     prof_release(ctx);
-    if (ctx->w16_slab)
-        vh_free(ctx->w16_slab);
-    free(ctx->w16);
-    if (ctx->w3_slab)
-        vh_free(ctx->w3_slab);
-    free(ctx->w3);
-    free(ctx->w3_scale);
-    if (ctx->w8_slab)
-        vh_free(ctx->w8_slab);
-    if (ctx->wconv16)
-        vh_free(ctx->wconv16);
-    free(ctx->w8);
-    free(ctx->w8s);
-    free(ctx->fold_cs);
-    free(ctx->fold_b);
-    float *dev[] = {ctx->w_slab, ctx->x, ctx->y, ctx->attn, ctx->qkv, ctx->hid, ctx->fold_slab, ctx->stats,
+    for (int i = 0; i < N_SLABS; ++i)
+        if (ctx->slab[i])
+            vh_free(ctx->slab[i]);
+    float *dev[] = {ctx->x, ctx->y, ctx->attn, ctx->qkv, ctx->hid, ctx->stats,
                     ctx->cls, ctx->d_logits, ctx->d_probs, ctx->d_images[0], ctx->d_images[1]};
     for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); ++i)
         if (dev[i])
@@ -201,114 +201,67 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     if (ctx->stream)
         vh_stream_destroy(ctx->stream);
     free(ctx->w);
+    free(ctx->op);
     free(ctx);
 }
 
 static const int BIG[4] = {2, 4, 8, 10};   /* in_proj, out_proj, fc1, fc2 weights within a layer's 12 tensors */
 
-/* bytes per weight of the mode's repacked copy of the four big matrices (0: none) */
-static size_t repack_bytes_per_weight(const vit_hip_ctx *ctx)
+/* a layer's 12 fp32 tensors: ln1 w,b; in w,b; out w,b; ln2 w,b; fc1 w,b; fc2 w,b */
+static float **layer_tensors(const vit_hip_ctx *ctx, int l) { return ctx->w + 4 + 12 * l; }
+
+/* the tensor index of operand m = 4 * layer + (0 in_proj, 1 out_proj, 2 fc1, 3 fc2) */
+static int operand_tensor(int m) { return 4 + 12 * (m / 4) + BIG[m % 4]; }
+
+/* The next 256-byte aligned piece of a slab: its address once the slab exists, NULL while only sizing. */
+static void *place(void *slab, size_t *off, size_t bytes)
 {
-    const vit_config *cfg = &ctx->cfg;
-    switch (ctx->precision) {
-    case VIT_PRECISION_BF16_GEMM: return 2;                                                   /* one-part planes */
-    case VIT_PRECISION_F32: return (cfg->embed_dim % 128 == 0 && cfg->mlp_hidden % 128 == 0) ? 6 : 0;   /* three-part planes */
-    case VIT_PRECISION_F32_FP16X2: return 4;                                                  /* two fp16 parts */
-    default: return 0;                                                                        /* FP8: values + scales, below */
-    }
+    void *p = slab ? (char *)slab + *off : NULL;
+    *off += align_up(bytes, 256);
+    return p;
 }
 
-/* The sizes of a context's weight slabs: w_slab, the mode's repacked slab, wconv16, fold_slab.  A function of (cfg,
- * precision, ln_fold) alone and free of side effects: vit_hip_create_from_planes checks a file's header against it
- * BEFORE anything is allocated. */
-static void weight_slab_sizes(const vit_hip_ctx *ctx, size_t sizes[4])
+/* Every tensor's place in the four weight slabs, from (cfg, precision, ln_fold) alone, so a planes file written by one
+ * context (vit_hip_export_planes) drops into another's slabs byte for byte.  Called before the slabs exist it only sums
+ * their sizes into bytes[] (vit_hip_create_from_planes checks a file's header against them BEFORE anything is
+ * allocated); called again once they are allocated, it points ctx->w and ctx->op into them. */
+static void layout_weights(vit_hip_ctx *ctx, size_t bytes[N_SLABS])
 {
     const vit_config *cfg = &ctx->cfg;
-    size_t total = 0;
+    const int p = ctx->precision;
+    const int f32_planes = p == VIT_PRECISION_F32 && cfg->embed_dim % 128 == 0 && cfg->mlp_hidden % 128 == 0;
+    /* bytes per weight of the operand copies; FP8_GEMM adds one e8m0 scale per 32 values */
+    const size_t per = p == VIT_PRECISION_BF16_GEMM ? 2 : p == VIT_PRECISION_FP8_GEMM ? 1 : p == VIT_PRECISION_F32_FP16X2 ? 4
+                     : f32_planes ? 6 : 0;
+    const size_t conv_parts = (p == VIT_PRECISION_BF16_GEMM || p == VIT_PRECISION_FP8_GEMM) ? 1 : f32_planes ? 3 : 0;
+    size_t off[N_SLABS] = {0};
     for (int i = 0; i < ctx->n_tensors; ++i)
-        total += align_up(vit_config_tensor_size(cfg, i) * sizeof(float), 256);
-    const size_t per = repack_bytes_per_weight(ctx);
-    size_t planes = 0, fold = 0;
-    for (int l = 0; l < cfg->depth; ++l)
-        for (int k = 0; k < 4; ++k) {
-            const size_t cnt = vit_config_tensor_size(cfg, 4 + 12 * l + BIG[k]);
-            planes += ctx->precision == VIT_PRECISION_FP8_GEMM ? align_up(cnt, 256) + align_up(cnt / 32, 256) : align_up(cnt * per, 256);
-            if (ctx->ln_fold && (k == 0 || k == 2))   /* in_proj and fc1: colsum and folded bias, one float per output feature each */
-                fold += 2 * align_up(vit_config_tensor_size(cfg, 4 + 12 * l + BIG[k] + 1) * sizeof(float), 256);
-        }
-    sizes[0] = total;
-    sizes[1] = planes;
-    const size_t conv_parts = (ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM) ? 1
-                            : (ctx->precision == VIT_PRECISION_F32 && per == 6) ? 3 : 0;
-    sizes[2] = cfg->embed_dim % 128 == 0 ? (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * (size_t)cfg->embed_dim * 2 * conv_parts : 0;
-    sizes[3] = fold;
+        ctx->w[i] = (float *)place(ctx->slab[SLAB_F32], &off[SLAB_F32], vit_config_tensor_size(cfg, i) * sizeof(float));
+    for (int m = 0; m < 4 * cfg->depth; ++m) {
+        struct operand *o = &ctx->op[m];
+        const size_t cnt = vit_config_tensor_size(cfg, operand_tensor(m));
+        o->w = place(ctx->slab[SLAB_OPERAND], &off[SLAB_OPERAND], cnt * per);
+        if (p == VIT_PRECISION_FP8_GEMM)
+            o->scales = place(ctx->slab[SLAB_OPERAND], &off[SLAB_OPERAND], cnt / 32);
+    }
+    place(ctx->slab[SLAB_CONV], &off[SLAB_CONV],   /* E % 128 == 0 wherever there are parts: already 256-byte aligned */
+          (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * (size_t)cfg->embed_dim * 2 * conv_parts);
+    for (int m = 0; ctx->ln_fold && m < 4 * cfg->depth; m += 2) {   /* in_proj and fc1: one float per output feature each */
+        const size_t nb = vit_config_tensor_size(cfg, operand_tensor(m) + 1) * sizeof(float);
+        ctx->op[m].colsum = (float *)place(ctx->slab[SLAB_FOLD], &off[SLAB_FOLD], nb);
+        ctx->op[m].bias_folded = (float *)place(ctx->slab[SLAB_FOLD], &off[SLAB_FOLD], nb);
+    }
+    memcpy(bytes, off, sizeof(off));
 }
 
-/* Allocate the weight slabs and fix every tensor's place in them.  Depends on (cfg, precision, ln_fold) only, so a planes
- * file written by one context (vit_hip_export_planes) drops into another's slabs byte for byte. */
-static int layout_weights(vit_hip_ctx *ctx)
+static int alloc_weights(vit_hip_ctx *ctx)
 {
     int rc = 0;
-    const vit_config *cfg = &ctx->cfg;
-    const int n_tensors = ctx->n_tensors;
-    size_t sizes[4];
-    weight_slab_sizes(ctx, sizes);
-    const size_t total = sizes[0], planes = sizes[1];
-    ctx->w_slab_bytes = total;
-    TRY(vh_malloc((void **)&ctx->w_slab, total));
-    size_t off = 0;
-    for (int i = 0; i < n_tensors; ++i) {
-        ctx->w[i] = (float *)((char *)ctx->w_slab + off);
-        off += align_up(vit_config_tensor_size(cfg, i) * sizeof(float), 256);
-    }
-    const size_t per = repack_bytes_per_weight(ctx);
-    ctx->planes_bytes = planes;
-    ctx->fold_bytes = sizes[3];
-    if (ctx->fold_bytes) {
-        TRY(vh_malloc((void **)&ctx->fold_slab, ctx->fold_bytes));
-        size_t fo = 0;
-        for (int l = 0; l < cfg->depth; ++l)
-            for (int k = 0; k < 4; k += 2) {
-                const int idx = 4 + 12 * l + BIG[k];
-                const size_t nb = align_up(vit_config_tensor_size(cfg, idx + 1) * sizeof(float), 256);
-                ctx->fold_cs[idx] = (float *)((char *)ctx->fold_slab + fo);
-                ctx->fold_b[idx] = (float *)((char *)ctx->fold_slab + fo + nb);
-                fo += 2 * nb;
-            }
-    }
-    if (planes) {
-        void *slab = NULL;
-        TRY(vh_malloc(&slab, planes));
-        if (ctx->precision == VIT_PRECISION_BF16_GEMM)
-            ctx->w16_slab = slab;
-        else if (ctx->precision == VIT_PRECISION_FP8_GEMM)
-            ctx->w8_slab = slab;
-        else
-            ctx->w3_slab = slab;
-        size_t o = 0;
-        for (int l = 0; l < cfg->depth; ++l)
-            for (int k = 0; k < 4; ++k) {
-                const int idx = 4 + 12 * l + BIG[k];
-                const size_t cnt = vit_config_tensor_size(cfg, idx);
-                if (ctx->precision == VIT_PRECISION_BF16_GEMM) {
-                    ctx->w16[idx] = (char *)slab + o;
-                    o += align_up(cnt * 2, 256);
-                } else if (ctx->precision == VIT_PRECISION_FP8_GEMM) {
-                    /* values (1 byte per weight) then the e8m0 scales (1 byte per 32 weights), both 256-byte aligned */
-                    ctx->w8[idx] = (char *)slab + o;
-                    ctx->w8s[idx] = (char *)slab + o + align_up(cnt, 256);
-                    o += align_up(cnt, 256) + align_up(cnt / 32, 256);
-                } else {
-                    ctx->w3[idx] = (char *)slab + o;
-                    o += align_up(cnt * per, 256);
-                }
-            }
-    }
-    if (sizes[2]) {
-        /* the reduced modes' patch embedding: conv weights rounded to bf16 planes, K padded to the one-part K step */
-        ctx->wconv16_bytes = sizes[2];
-        TRY(vh_malloc(&ctx->wconv16, ctx->wconv16_bytes));
-    }
+    layout_weights(ctx, ctx->slab_bytes);
+    for (int i = 0; i < N_SLABS; ++i)
+        if (ctx->slab_bytes[i])
+            TRY(vh_malloc(&ctx->slab[i], ctx->slab_bytes[i]));
+    layout_weights(ctx, ctx->slab_bytes);
     return 0;
 fail:
     return rc;
@@ -319,78 +272,69 @@ static int fill_weights(vit_hip_ctx *ctx, const Network *networks)
 {
     int rc = 0;
     const vit_config *cfg = &ctx->cfg;
+    const int p = ctx->precision;
+    float *d_amax = NULL, *d_scaled = NULL;
     for (int i = 0; i < ctx->n_tensors; ++i)
         TRY(vh_h2d(ctx->w[i], networks[i].data, networks[i].size * sizeof(float), ctx->stream));
-    float *d_amax = NULL, *d_scaled = NULL;
-    if (ctx->precision == VIT_PRECISION_F32_FP16X2)
+    if (p == VIT_PRECISION_F32_FP16X2)
         TRY(vh_malloc((void **)&d_amax, sizeof(float)));
     if (ctx->ln_fold)   /* gamma-scaled copy of one matrix at a time, before its rounding (the largest is fc1 / in_proj) */
         TRY(vh_malloc((void **)&d_scaled, (size_t)cfg->embed_dim * (size_t)(cfg->mlp_hidden > 3 * cfg->embed_dim ? cfg->mlp_hidden : 3 * cfg->embed_dim) * sizeof(float)));
-    for (int l = 0; l < cfg->depth && rc == 0; ++l)
-        for (int k = 0; k < 4 && rc == 0; ++k) {
-            const int idx = 4 + 12 * l + BIG[k];
-            const int out_f = (int)networks[idx + 1].size, in_f = (int)(networks[idx].size / networks[idx + 1].size);
-            if (ctx->ln_fold && (k == 0 || k == 2)) {
-                /* the LayerNorm in front of this projection moves into it (csrc/norm_fold.h): W' = gamma . W rounded to the
-                 * mode's operand format, colsum of the ROUNDED values, bias' = bias + beta W^T from the fp32 weights.
-                 * ln1 (tensors 0, 1 of the layer) feeds in_proj, ln2 (6, 7) feeds fc1. */
-                const float *gamma = ctx->w[4 + 12 * l + (k == 0 ? 0 : 6)], *beta = ctx->w[4 + 12 * l + (k == 0 ? 1 : 7)];
-                if ((rc = vh_launch_fold_gamma(ctx->stream, ctx->w[idx], gamma, d_scaled, out_f, in_f)) != 0)
-                    break;
-                if (ctx->precision == VIT_PRECISION_BF16_GEMM)
-                    rc = vh_launch_split_rows(ctx->stream, d_scaled, ctx->w16[idx], out_f, in_f, 1);
-                else if (ctx->precision == VIT_PRECISION_F32)
-                    rc = vh_launch_split3_planes(ctx->stream, d_scaled, ctx->w3[idx], out_f, in_f);
-                else
-                    rc = vh_launch_quantize_mx_rows(ctx->stream, d_scaled, ctx->w8[idx], ctx->w8s[idx], out_f, in_f);
-                if (rc == 0)
-                    rc = ctx->precision == VIT_PRECISION_BF16_GEMM
-                             ? vh_launch_colsum_operand(ctx->stream, ctx->w16[idx], NULL, ctx->fold_cs[idx], out_f, in_f)
-                         : ctx->precision == VIT_PRECISION_F32
-                             ? vh_launch_colsum_planes3(ctx->stream, ctx->w3[idx], ctx->fold_cs[idx], out_f, in_f)
-                             : vh_launch_colsum_operand(ctx->stream, ctx->w8[idx], ctx->w8s[idx], ctx->fold_cs[idx], out_f, in_f);
-                if (rc == 0)
-                    rc = vh_launch_fold_bias(ctx->stream, ctx->w[idx], beta, ctx->w[idx + 1], ctx->fold_b[idx], out_f, in_f);
-            } else if (ctx->precision == VIT_PRECISION_BF16_GEMM) {
-                /* one-part planes [K/32][1][N][32] (gemm_p3.hip); everything else (norms, biases, embeddings, classifier) stays fp32 */
-                rc = vh_launch_split_rows(ctx->stream, ctx->w[idx], ctx->w16[idx], out_f, in_f, 1);
-            } else if (ctx->precision == VIT_PRECISION_F32 && ctx->w3_slab) {
-                /* the constant GEMM operand split once (exact 3-way bf16 split, 6 bytes per weight) */
-                rc = vh_launch_split3_planes(ctx->stream, ctx->w[idx], ctx->w3[idx], out_f, in_f);
-            } else if (ctx->precision == VIT_PRECISION_FP8_GEMM) {
-                rc = vh_launch_quantize_mx_rows(ctx->stream, ctx->w[idx], ctx->w8[idx], ctx->w8s[idx], out_f, in_f);
-            } else if (ctx->precision == VIT_PRECISION_F32_FP16X2) {
-                /* two fp16 parts of w * 2^k per weight (4 bytes), k per tensor such that max|w| * 2^k lands in
-                 * [8192, 16384): the low part stays clear of fp16's subnormals, nothing overflows */
-                float amax = 0.0f;
-                if ((rc = vh_memset(d_amax, 0, sizeof(float), ctx->stream)) != 0 ||
-                    (rc = vh_launch_absmax(ctx->stream, ctx->w[idx], networks[idx].size, d_amax)) != 0 ||
-                    (rc = vh_d2h(&amax, d_amax, sizeof(float), ctx->stream)) != 0 ||
-                    (rc = vh_stream_sync(ctx->stream)) != 0)
-                    break;
-                int e = 0;
-                float scale = 1.0f;
-                if (amax > 0.0f && amax < 3.0e38f) {
-                    (void)frexpf(amax, &e);                 /* amax = m * 2^e, m in [0.5, 1) */
-                    scale = ldexpf(1.0f, 14 - e);           /* amax * scale in [8192, 16384) */
-                }
-                ctx->w3_scale[idx] = scale;
-                rc = vh_launch_split2h_planes(ctx->stream, ctx->w[idx], ctx->w3[idx], out_f, in_f, scale);
-            }
+    for (int m = 0; m < 4 * cfg->depth; ++m) {
+        struct operand *o = &ctx->op[m];
+        float **lw = layer_tensors(ctx, m / 4);
+        const int idx = operand_tensor(m), k = m % 4, fold = o->colsum != NULL;
+        const int out_f = (int)networks[idx + 1].size, in_f = (int)(networks[idx].size / networks[idx + 1].size);
+        const float *src = ctx->w[idx];
+        if (fold) {
+            /* the LayerNorm in front of this projection moves into it (csrc/norm_fold.h): W' = gamma . W rounded to the
+             * mode's operand format, colsum of the ROUNDED values, bias' = bias + beta W^T from the fp32 weights.
+             * ln1 (tensors 0, 1 of the layer) feeds in_proj, ln2 (6, 7) feeds fc1. */
+            TRY(vh_launch_fold_gamma(ctx->stream, ctx->w[idx], lw[k == 0 ? 0 : 6], d_scaled, out_f, in_f));
+            src = d_scaled;
         }
-    if (rc == 0 && d_scaled)
-        rc = vh_stream_sync(ctx->stream);   /* the scratch copy is freed below */
-    if (d_amax)
-        vh_free(d_amax);
+        switch (p) {
+        case VIT_PRECISION_BF16_GEMM:
+            /* one-part planes [K/32][1][N][32] (gemm_p3.hip); everything else (norms, biases, embeddings, classifier) stays fp32 */
+            TRY(vh_launch_split_rows(ctx->stream, src, o->w, out_f, in_f, 1));
+            break;
+        case VIT_PRECISION_FP8_GEMM:
+            TRY(vh_launch_quantize_mx_rows(ctx->stream, src, o->w, o->scales, out_f, in_f));
+            break;
+        case VIT_PRECISION_F32:
+            /* the constant GEMM operand split once (exact 3-way bf16 split, 6 bytes per weight) */
+            if (o->w)
+                TRY(vh_launch_split3_planes(ctx->stream, src, o->w, out_f, in_f));
+            break;
+        case VIT_PRECISION_F32_FP16X2: {
+            /* two fp16 parts of w * 2^k per weight (4 bytes), k per tensor such that max|w| * 2^k lands in
+             * [8192, 16384): the low part stays clear of fp16's subnormals, nothing overflows */
+            float amax = 0.0f;
+            TRY(vh_memset(d_amax, 0, sizeof(float), ctx->stream));
+            TRY(vh_launch_absmax(ctx->stream, src, networks[idx].size, d_amax));
+            TRY(vh_d2h(&amax, d_amax, sizeof(float), ctx->stream));
+            TRY(vh_stream_sync(ctx->stream));
+            int e = 0;
+            o->pair_scale = 1.0f;
+            if (amax > 0.0f && amax < 3.0e38f) {
+                (void)frexpf(amax, &e);                     /* amax = m * 2^e, m in [0.5, 1) */
+                o->pair_scale = ldexpf(1.0f, 14 - e);       /* amax * scale in [8192, 16384) */
+            }
+            TRY(vh_launch_split2h_planes(ctx->stream, src, o->w, out_f, in_f, o->pair_scale));
+            break;
+        }
+        }
+        if (fold) {
+            TRY(p == VIT_PRECISION_F32 ? vh_launch_colsum_planes3(ctx->stream, o->w, o->colsum, out_f, in_f)
+                                       : vh_launch_colsum_operand(ctx->stream, o->w, o->scales, o->colsum, out_f, in_f));
+            TRY(vh_launch_fold_bias(ctx->stream, ctx->w[idx], lw[k == 0 ? 1 : 7], ctx->w[idx + 1], o->bias_folded, out_f, in_f));
+        }
+    }
     if (d_scaled)
-        vh_free(d_scaled);
-    d_amax = d_scaled = NULL;
-    if (rc)
-        return rc;
-    if (ctx->wconv16)
-        TRY(vh_launch_conv_weight_planes_parts(ctx->stream, ctx->w[1], ctx->wconv16, cfg->embed_dim, cfg->in_chans, cfg->patch_size,
-                                               ctx->precision == VIT_PRECISION_F32 ? 3 : 1));
-    return 0;
+        TRY(vh_stream_sync(ctx->stream));   /* the scratch copy is freed below */
+    if (ctx->slab[SLAB_CONV])
+        TRY(vh_launch_conv_weight_planes_parts(ctx->stream, ctx->w[1], ctx->slab[SLAB_CONV], cfg->embed_dim, cfg->in_chans,
+                                               cfg->patch_size, p == VIT_PRECISION_F32 ? 3 : 1));
 fail:
     if (d_amax)
         vh_free(d_amax);
@@ -419,26 +363,9 @@ int vit_hip_create(vit_hip_ctx **out, const vit_config *cfg, const Network *netw
 int vit_hip_precision(const vit_hip_ctx *ctx) { return ctx->precision; }
 int vit_hip_ln_fold(const vit_hip_ctx *ctx) { return ctx ? ctx->ln_fold : 0; }
 
-/* The reduced modes fold every LayerNorm but the final one into the projection behind it (csrc/norm_fold.h) unless
- * $VIT_HIP_LN_FOLD=0 (the separate LayerNorm launches of rounds 1-3: the A/B of tests and bench).  The fp32 paths never fold. */
-static int want_ln_fold(const vit_config *cfg, int precision)
-{
-    const char *env = getenv("VIT_HIP_LN_FOLD");
-    if (precision == VIT_PRECISION_F32) {
-        /* LAB VARIANT, off unless asked for ($VIT_HIP_LN_FOLD=1): the same fold on the exact three-part planes.  It keeps the
-         * 1e-4 parity on the goldens, but puts it behind the x - mean cancellation for ~1 % (docs/LABBOOK.md R4.6). */
-        const char *p3 = getenv("VIT_HIP_P3"), *native = getenv("VIT_HIP_GEMM_FP32");
-        return env && env[0] == '1' && !(p3 && p3[0] == '0') && !(native && native[0] == 'n') && cfg->embed_dim % 128 == 0 &&
-               cfg->mlp_hidden % 128 == 0 && cfg->embed_dim / 128 <= 16;
-    }
-    if (precision != VIT_PRECISION_BF16_GEMM && precision != VIT_PRECISION_FP8_GEMM)
-        return 0;
-    if (env && env[0] == '0')
-        return 0;
-    return cfg->embed_dim % 128 == 0 && cfg->embed_dim / 128 <= 16;   /* row_norm_terms: at most 16 partial sums per row */
-}
-
-/* Argument checks shared by both ways of making a context, and the empty context itself. */
+/* Argument checks shared by both ways of making a context, the plan of its forward pass, and the empty context itself.
+ * ln_fold < 0: decide the fold here ($VIT_HIP_LN_FOLD, vit_hip_create_ex); 0 or 1: a planes file's header fixed it, and a
+ * fold this context cannot run is refused like any other bad header.  Nothing is allocated on the device. */
 static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int device, int max_batch, int precision, int ln_fold)
 {
     if (!out)
@@ -459,43 +386,58 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
         cfg->in_chans <= 0 || cfg->num_classes <= 0 || cfg->mlp_hidden <= 0)
         return 2;
     /* sane sizes: what a context may be asked to allocate is bounded whatever a caller or a file header says */
-    if (cfg->depth > 256 || cfg->embed_dim > 16384 || cfg->mlp_hidden > 65536 || cfg->img_size > 4096 || cfg->in_chans > 64 ||
+    if (cfg->depth > MAX_DEPTH || cfg->embed_dim > 16384 || cfg->mlp_hidden > 65536 || cfg->img_size > 4096 || cfg->in_chans > 64 ||
         cfg->num_classes > (1 << 20) || cfg->num_heads > 1024 || max_batch > (1 << 20))
         return 2;
     if (n_tensors != vit_config_num_tensors(cfg))
         return 2;
     if (cfg->embed_dim % cfg->num_heads != 0 || cfg->img_size % cfg->patch_size != 0)
         return 2;
-    if (ln_fold && ((precision != VIT_PRECISION_BF16_GEMM && precision != VIT_PRECISION_FP8_GEMM && precision != VIT_PRECISION_F32) ||
-                    cfg->embed_dim % 128 != 0))
-        return 2;
+
+    const int E = cfg->embed_dim, F = cfg->mlp_hidden, H = cfg->num_heads, T = vit_config_tokens(cfg);
+    const int reduced = precision == VIT_PRECISION_BF16_GEMM || precision == VIT_PRECISION_FP8_GEMM;
+    /* F32 by default writes every GEMM input as the exact three-part bf16 split (csrc/gemm_p3.hip), 6 bytes per value;
+     * $VIT_HIP_P3=0 keeps fp32 activations and the in-loop split (csrc/gemm_mfma.hip), $VIT_HIP_GEMM_FP32=native the fp32
+     * matrix instruction (read again by the kernels) */
+    const char *env_p3 = getenv("VIT_HIP_P3"), *env_native = getenv("VIT_HIP_GEMM_FP32");
+    const int planes_wanted = !(env_p3 && env_p3[0] == '0') && !(env_native && env_native[0] == 'n');
+    const int use_p3 = precision == VIT_PRECISION_F32 && E % 128 == 0 && F % 128 == 0 && planes_wanted &&
+                       (size_t)max_batch * (size_t)T * 64 <= 0xffffffffull;
+    /* the fold's row terms take at most 16 partial sums per row (row_norm_terms); on F32 it needs the planes path */
+    const int fold_fits = E % 128 == 0 && E / 128 <= 16 && (reduced || (precision == VIT_PRECISION_F32 && F % 128 == 0));
+    if (ln_fold < 0) {
+        /* the reduced modes fold unless $VIT_HIP_LN_FOLD=0 (the separate LayerNorm launches of rounds 1-3: the A/B of tests
+         * and bench).  On F32 the fold is a LAB VARIANT, off unless $VIT_HIP_LN_FOLD=1: the same fold on the exact
+         * three-part planes keeps the 1e-4 parity on the goldens, but puts it behind the x - mean cancellation for ~1 %
+         * (docs/LABBOOK.md R4.6). */
+        const char *env = getenv("VIT_HIP_LN_FOLD");
+        ln_fold = fold_fits && (reduced ? !(env && env[0] == '0') : env && env[0] == '1' && planes_wanted);
+    }
+    if (ln_fold && (!fold_fits || (precision == VIT_PRECISION_F32 && !use_p3)))
+        return vh_set_error(2, "vit_hip_create: this shape, precision and batch cannot fold the LayerNorms (the fp32 path "
+                               "needs the planes path)");
+    const char *env_ll = getenv("VIT_HIP_LAST_LAYER");
+
     vit_hip_ctx *ctx = (vit_hip_ctx *)calloc(1, sizeof(*ctx));
     if (!ctx)
         return 4;
     ctx->cfg = *cfg;
     ctx->device = device;
     ctx->max_batch = max_batch;
-    ctx->tokens = vit_config_tokens(cfg);
+    ctx->tokens = T;
     ctx->n_tensors = n_tensors;
     ctx->precision = precision;
-    ctx->ln_fold = ln_fold;
-    ctx->fold_cs = (float **)calloc((size_t)n_tensors, sizeof(float *));
-    ctx->fold_b = (float **)calloc((size_t)n_tensors, sizeof(float *));
+    ctx->ln_fold = ln_fold ? 1 : 0;
+    ctx->use_p3 = use_p3;
+    ctx->cls_only_last = use_p3 && !ln_fold && env_ll && strcmp(env_ll, "cls") == 0;
+    ctx->attn_form = !(use_p3 || reduced) ? ATTN_STREAMING
+              : (E == 64 * H && T <= 208) ? ATTN_HD64
+              : (reduced && E == 80 * H && T <= 272) ? ATTN_HD80 : ATTN_STREAMING;
     ctx->w = (float **)calloc((size_t)n_tensors, sizeof(float *));
-    ctx->w16 = (void **)calloc((size_t)n_tensors, sizeof(void *));
-    ctx->w3 = (void **)calloc((size_t)n_tensors, sizeof(void *));
-    ctx->w3_scale = (float *)calloc((size_t)n_tensors, sizeof(float));
-    ctx->w8 = (void **)calloc((size_t)n_tensors, sizeof(void *));
-    ctx->w8s = (void **)calloc((size_t)n_tensors, sizeof(void *));
-    if (!ctx->w || !ctx->w16 || !ctx->w3 || !ctx->w3_scale || !ctx->w8 || !ctx->w8s || !ctx->fold_cs || !ctx->fold_b) {
-        free(ctx->fold_cs);
-        free(ctx->fold_b);
+    ctx->op = (struct operand *)calloc((size_t)4 * cfg->depth, sizeof(struct operand));
+    if (!ctx->w || !ctx->op) {
         free(ctx->w);
-        free(ctx->w16);
-        free(ctx->w3);
-        free(ctx->w3_scale);
-        free(ctx->w8);
-        free(ctx->w8s);
+        free(ctx->op);
         free(ctx);
         return 4;
     }
@@ -523,11 +465,11 @@ int vit_hip_create_ex(vit_hip_ctx **out, const vit_config *cfg, const Network *n
             return 3;
         }
     vit_hip_ctx *ctx = NULL;
-    if ((rc = ctx_new(&ctx, cfg, n_tensors, device, max_batch, precision, want_ln_fold(cfg, precision))) != 0)
+    if ((rc = ctx_new(&ctx, cfg, n_tensors, device, max_batch, precision, -1)) != 0)
         return rc;
     TRY(vh_init(device));
     TRY(vh_stream_create(&ctx->stream));
-    TRY(layout_weights(ctx));
+    TRY(alloc_weights(ctx));
     TRY(fill_weights(ctx, networks));
     TRY(alloc_arena(ctx));
     *out = ctx;
@@ -540,11 +482,11 @@ fail:
 /* ---- repacked weights on disk (the offline half of the weight-format tooling) --------------------------
  * vit_hip_export_planes writes what a context holds in HBM after its repack -- the fp32 slab (all tensors, the
  * reference's order, 256-byte aligned) followed by the mode's operand slab for the four big matrices of every layer
- * (three-part bf16 planes, one-part planes, two fp16 parts, or MX values + scales: csrc/gemm_p3.hip, gemm_mx.hip) and,
- * in the reduced modes, the conv_proj planes -- behind a header that pins model shape and precision.  Both slabs'
- * layouts follow from (config, precision) alone (layout_weights), so vit_hip_create_from_planes is three reads into
- * three allocations: no fp32 -> format pass, no per-tensor files (the reference's loader opens 152 of them,
- * Network.c:134-218). */
+ * (three-part bf16 planes, one-part planes, two fp16 parts, or MX values + scales: csrc/gemm_p3.hip, gemm_mx.hip), the
+ * conv_proj planes and, with ln_fold, the fold terms -- behind a header that pins model shape and precision.  Every
+ * slab's layout follows from (config, precision, ln_fold) alone (layout_weights), so vit_hip_create_from_planes is one
+ * read per slab into its allocation: no fp32 -> format pass, no per-tensor files (the reference's loader opens 152 of
+ * them, Network.c:134-218). */
 /* Bumped whenever a repack kernel changes what it writes for the same (config, precision): the slab sizes alone would
  * not notice (csrc/gemm_p3.hip planes, csrc/gemm_mx.hip MX values / scale order, the fold terms of csrc/norm_fold.h). */
 #define VIT_PLANES_LAYOUT_VERSION 2
@@ -556,7 +498,7 @@ struct planes_header
     int precision, n_tensors;
     int cfg_ints[8];               /* img, patch, chans, classes, embed, depth, heads, mlp_hidden */
     double eps;
-    unsigned long long w_slab_bytes, planes_bytes, wconv16_bytes, scale_floats;   /* scale_floats = n_tensors (w3_scale) */
+    unsigned long long w_slab_bytes, planes_bytes, wconv16_bytes, scale_floats;   /* scale_floats = n_tensors (pair_scales) */
     unsigned long long fold_bytes; /* colsum + folded bias of the gamma-scaled matrices (ln_fold) */
     int ln_fold, layout_version;
     unsigned long long checksum;   /* of everything behind the header, in file order (planes_hash) */
@@ -607,9 +549,12 @@ fail:
     return rc;
 }
 
-static void *planes_slab(const vit_hip_ctx *ctx)
+/* The planes file keeps one fp16-pair scale per tensor index: zero but at the big matrices of F32_FP16X2. */
+static void pair_scales(const vit_hip_ctx *ctx, float scales[MAX_TENSORS])
 {
-    return ctx->precision == VIT_PRECISION_BF16_GEMM ? ctx->w16_slab : ctx->precision == VIT_PRECISION_FP8_GEMM ? ctx->w8_slab : ctx->w3_slab;
+    memset(scales, 0, sizeof(float) * (size_t)ctx->n_tensors);
+    for (int m = 0; m < 4 * ctx->cfg.depth; ++m)
+        scales[operand_tensor(m)] = ctx->op[m].pair_scale;
 }
 
 /* Written to `path`.tmp and renamed over `path` when complete: an interrupted export never leaves a truncated file
@@ -641,25 +586,21 @@ int vit_hip_export_planes(vit_hip_ctx *ctx, const char *path)
     const int ints[8] = {c->img_size, c->patch_size, c->in_chans, c->num_classes, c->embed_dim, c->depth, c->num_heads, c->mlp_hidden};
     memcpy(h.cfg_ints, ints, sizeof(ints));
     h.eps = c->eps;
-    h.w_slab_bytes = ctx->w_slab_bytes;
-    h.planes_bytes = ctx->planes_bytes;
-    h.wconv16_bytes = ctx->wconv16_bytes;
-    h.fold_bytes = ctx->fold_bytes;
+    h.w_slab_bytes = ctx->slab_bytes[SLAB_F32];
+    h.planes_bytes = ctx->slab_bytes[SLAB_OPERAND];
+    h.wconv16_bytes = ctx->slab_bytes[SLAB_CONV];
+    h.fold_bytes = ctx->slab_bytes[SLAB_FOLD];
     h.ln_fold = ctx->ln_fold;
     h.layout_version = VIT_PLANES_LAYOUT_VERSION;
     h.scale_floats = (unsigned long long)ctx->n_tensors;
-    unsigned long long hash = planes_hash(PLANES_HASH_SEED, ctx->w3_scale, sizeof(float) * (size_t)ctx->n_tensors);
+    float scales[MAX_TENSORS];
+    pair_scales(ctx, scales);
+    unsigned long long hash = planes_hash(PLANES_HASH_SEED, scales, sizeof(float) * (size_t)ctx->n_tensors);
     /* the header goes first with a zero checksum and is rewritten once the payload has been hashed */
-    if (fwrite(&h, sizeof(h), 1, fp) != 1 || fwrite(ctx->w3_scale, sizeof(float), (size_t)ctx->n_tensors, fp) != (size_t)ctx->n_tensors)
+    if (fwrite(&h, sizeof(h), 1, fp) != 1 || fwrite(scales, sizeof(float), (size_t)ctx->n_tensors, fp) != (size_t)ctx->n_tensors)
         rc = vh_set_error(120, "vit_hip_export_planes: short write");
-    if (rc == 0)
-        rc = copy_file_and_device(ctx, fp, ctx->w_slab, ctx->w_slab_bytes, 1, &hash);
-    if (rc == 0)
-        rc = copy_file_and_device(ctx, fp, planes_slab(ctx), ctx->planes_bytes, 1, &hash);
-    if (rc == 0)
-        rc = copy_file_and_device(ctx, fp, ctx->wconv16, ctx->wconv16_bytes, 1, &hash);
-    if (rc == 0)
-        rc = copy_file_and_device(ctx, fp, ctx->fold_slab, ctx->fold_bytes, 1, &hash);
+    for (int i = 0; i < N_SLABS && rc == 0; ++i)
+        rc = copy_file_and_device(ctx, fp, ctx->slab[i], ctx->slab_bytes[i], 1, &hash);
     if (rc == 0) {
         h.checksum = hash;
         if (fseek(fp, 0, SEEK_SET) != 0 || fwrite(&h, sizeof(h), 1, fp) != 1)
@@ -697,33 +638,33 @@ int vit_hip_create_from_planes(vit_hip_ctx **out, const char *path, int device, 
     }
     vit_config cfg = {h.cfg_ints[0], h.cfg_ints[1], h.cfg_ints[2], h.cfg_ints[3], h.cfg_ints[4], h.cfg_ints[5], h.cfg_ints[6],
                       h.cfg_ints[7], h.eps};
-    /* ctx_new bounds every dimension and allocates only the per-tensor pointer tables (n_tensors is tied to depth) */
-    if (h.n_tensors <= 0 || h.n_tensors > 4 + 12 * 256 + 4 ||
+    /* ctx_new bounds every dimension, checks the fold flag and allocates only the host-side tables (n_tensors is tied to depth) */
+    if (h.n_tensors <= 0 || h.n_tensors > MAX_TENSORS ||
         (rc = ctx_new(&ctx, &cfg, h.n_tensors, device, max_batch, h.precision, h.ln_fold ? 1 : 0)) != 0) {
         fclose(fp);
         return vh_set_error(rc ? rc : 2, "vit_hip_create_from_planes: the header's model shape or precision is not one this library takes");
     }
-    {   /* the slab sizes this library derives from (shape, precision, fold) against the header's, BEFORE anything is allocated */
-        size_t sizes[4];
-        weight_slab_sizes(ctx, sizes);
-        if (h.w_slab_bytes != sizes[0] || h.planes_bytes != sizes[1] || h.wconv16_bytes != sizes[2] || h.fold_bytes != sizes[3] ||
-            h.scale_floats != (unsigned long long)ctx->n_tensors) {
-            rc = vh_set_error(125, "vit_hip_create_from_planes: slab sizes in the file do not match this library's layout");
-            goto fail;
-        }
+    /* the slab sizes this library derives from (shape, precision, fold) against the header's, BEFORE anything is allocated */
+    size_t sizes[N_SLABS];
+    layout_weights(ctx, sizes);
+    if (h.w_slab_bytes != sizes[SLAB_F32] || h.planes_bytes != sizes[SLAB_OPERAND] || h.wconv16_bytes != sizes[SLAB_CONV] ||
+        h.fold_bytes != sizes[SLAB_FOLD] || h.scale_floats != (unsigned long long)ctx->n_tensors) {
+        rc = vh_set_error(125, "vit_hip_create_from_planes: slab sizes in the file do not match this library's layout");
+        goto fail;
     }
-    if (fread(ctx->w3_scale, sizeof(float), (size_t)ctx->n_tensors, fp) != (size_t)ctx->n_tensors) {
+    float scales[MAX_TENSORS];
+    if (fread(scales, sizeof(float), (size_t)ctx->n_tensors, fp) != (size_t)ctx->n_tensors) {
         rc = vh_set_error(124, "vit_hip_create_from_planes: truncated header");
         goto fail;
     }
-    unsigned long long hash = planes_hash(PLANES_HASH_SEED, ctx->w3_scale, sizeof(float) * (size_t)ctx->n_tensors);
+    unsigned long long hash = planes_hash(PLANES_HASH_SEED, scales, sizeof(float) * (size_t)ctx->n_tensors);
+    for (int m = 0; m < 4 * cfg.depth; ++m)
+        ctx->op[m].pair_scale = scales[operand_tensor(m)];
     TRY(vh_init(device));
     TRY(vh_stream_create(&ctx->stream));
-    TRY(layout_weights(ctx));
-    TRY(copy_file_and_device(ctx, fp, ctx->w_slab, ctx->w_slab_bytes, 0, &hash));
-    TRY(copy_file_and_device(ctx, fp, planes_slab(ctx), ctx->planes_bytes, 0, &hash));
-    TRY(copy_file_and_device(ctx, fp, ctx->wconv16, ctx->wconv16_bytes, 0, &hash));
-    TRY(copy_file_and_device(ctx, fp, ctx->fold_slab, ctx->fold_bytes, 0, &hash));
+    TRY(alloc_weights(ctx));
+    for (int i = 0; i < N_SLABS; ++i)
+        TRY(copy_file_and_device(ctx, fp, ctx->slab[i], ctx->slab_bytes[i], 0, &hash));
     if (hash != h.checksum) {
         rc = vh_set_error(126, "vit_hip_create_from_planes: payload checksum mismatch (corrupt file)");
         goto fail;
@@ -747,20 +688,6 @@ static int alloc_arena(vit_hip_ctx *ctx)
     const size_t E = (size_t)cfg->embed_dim, F = (size_t)cfg->mlp_hidden, NC = (size_t)cfg->num_classes;
     const size_t rows = (size_t)max_batch * ctx->tokens;
     const size_t img = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
-    {   /* the default fp32 path: every GEMM input is written by its producer as the exact three-part
-         * bf16 split (csrc/gemm_p3.hip), 6 bytes per value; VIT_HIP_P3=0 keeps fp32 activations and
-         * the in-loop split (csrc/gemm_mfma.hip) */
-        const char *env_p3 = getenv("VIT_HIP_P3");
-        const char *env_native = getenv("VIT_HIP_GEMM_FP32");   /* "native": the fp32 matrix instruction (gemm_mfma.hip) */
-        ctx->use_p3 = ctx->w3_slab && precision == VIT_PRECISION_F32 && !(env_p3 && env_p3[0] == '0') &&
-                      !(env_native && env_native[0] == 'n') && rows * 64 <= 0xffffffffull;
-    }
-    if (precision == VIT_PRECISION_F32 && ctx->ln_fold && !ctx->use_p3)
-        return vh_set_error(2, "vit_hip_create: $VIT_HIP_LN_FOLD=1 on the fp32 path needs the planes path (batch too large for it)");
-    {
-        const char *env_ll = getenv("VIT_HIP_LAST_LAYER");
-        ctx->cls_only_last = ctx->use_p3 && !ctx->ln_fold && env_ll && strcmp(env_ll, "cls") == 0;
-    }
     const size_t act = ctx->use_p3 ? 6 : sizeof(float);   /* bytes per GEMM-input value */
     TRY(vh_malloc((void **)&ctx->x, rows * E * sizeof(float)));
     TRY(vh_malloc((void **)&ctx->y, rows * E * act));
@@ -768,7 +695,7 @@ static int alloc_arena(vit_hip_ctx *ctx)
     TRY(vh_malloc((void **)&ctx->qkv, rows * 3 * E * act));
     {   /* patch geometries that need gathered rows (H/14) borrow the MLP hidden buffer, idle at that point */
         size_t ws = vh_patch_embed_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->patch_size, cfg->embed_dim);
-        if (ctx->wconv16) {   /* the im2row producer's planes: patches x Kp x 2 bytes x parts (a small MLP can be smaller than that) */
+        if (ctx->slab[SLAB_CONV]) {   /* the im2row producer's planes: patches x Kp x 2 bytes x parts (a small MLP can be smaller than that) */
             const size_t grid = (size_t)(cfg->img_size / cfg->patch_size);
             const size_t planes = (size_t)max_batch * grid * grid * (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * 2 *
                                   (precision == VIT_PRECISION_F32 ? 3 : 1);
@@ -805,30 +732,21 @@ fail:
  * ctx->ln_fold the two LayerNorms are not launched: whoever wrote x also left it as the projection's operand in ctx->y
  * with the rows' partial sums in ctx->stats, and the QKV / fc1 launches apply the row terms (csrc/norm_fold.h). */
 
-/* Q|K|V as one-part fp16 planes for the planes attention kernels (head_dim 64 with T <= 208; head_dim 80 with T <= 272:
- * ViT-H/14), fp32 rows for the streaming kernel */
-static int qkv_as_planes(const vit_hip_ctx *ctx)
-{
-    const int E = ctx->cfg.embed_dim, H = ctx->cfg.num_heads, T = ctx->tokens;
-    return (E == 64 * H && T <= 208) || (E == 80 * H && T <= 272);
-}
-
 /* The reduced modes' attention on fp16-rounded operands, writing the output projection's operand: one-part bf16 planes
- * (attn_scales NULL) or an MX tensor.  The planes kernels write it themselves; the streaming kernel (and head_dim 80 with
- * an odd head count) leaves fp32 rows in the idle MLP buffer, which are then rounded / quantised (one timed operator). */
+ * (attn_scales NULL) or an MX tensor.  The resident kernels write it themselves; the streaming kernel leaves fp32 rows in
+ * the idle MLP buffer, which are then rounded / quantised (one timed operator). */
 static int attention_reduced(vit_hip_ctx *ctx, vh_stream_t s, int n, char *attn_scales)
 {
     int rc = 0;
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, T = ctx->tokens, H = c->num_heads, rows = n * T;
-    if (E == 64 * H && T <= 208)
+    if (ctx->attn_form == ATTN_HD64)
         OP(VIT_OP_ATTENTION, attn_scales ? vh_launch_attention_planes_f16_mx(s, ctx->qkv, ctx->attn, attn_scales, n, T, E, H)
                                          : vh_launch_attention_planes_f16(s, ctx->qkv, ctx->attn, 1, n, T, E, H));
-    else if (qkv_as_planes(ctx) && (H & 1) == 0)
+    else if (ctx->attn_form == ATTN_HD80)
         OP(VIT_OP_ATTENTION, vh_launch_attention_planes_f16_hd80_operand(s, ctx->qkv, ctx->attn, attn_scales, attn_scales ? 2 : 1, n, T, E, H));
     else
-        OP(VIT_OP_ATTENTION, (rc = qkv_as_planes(ctx) ? vh_launch_attention_planes_f16_hd80(s, ctx->qkv, ctx->hid, n, T, E, H)
-                                                      : vh_launch_attention_f16(s, ctx->qkv, ctx->hid, n, T, E, H)) != 0 ? rc :
+        OP(VIT_OP_ATTENTION, (rc = vh_launch_attention_f16(s, ctx->qkv, ctx->hid, n, T, E, H)) != 0 ? rc :
                              attn_scales ? vh_launch_quantize_mx_act(s, ctx->hid, ctx->attn, attn_scales, rows, E)
                                          : vh_launch_split_rows(s, ctx->hid, ctx->attn, rows, E, 1));
     return 0;
@@ -842,27 +760,26 @@ static int layer_fp8(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     int rc = 0;
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, F = c->mlp_hidden, rows = n * ctx->tokens, fold = ctx->ln_fold, last = l == c->depth - 1;
-    float **lw = ctx->w + 4 + 12 * l;
-    void **l8 = ctx->w8 + 4 + 12 * l, **l8s = ctx->w8s + 4 + 12 * l;
-    float **cs = ctx->fold_cs + 4 + 12 * l, **bf = ctx->fold_b + 4 + 12 * l;
+    float **lw = layer_tensors(ctx, l);
+    const struct operand *op = ctx->op + 4 * l;
     char *ys = (char *)ctx->y + align_up((size_t)rows * E, 256), *as_ = (char *)ctx->attn + align_up((size_t)rows * E, 256);
     char *hs = (char *)ctx->hid + align_up((size_t)rows * F, 256);
-    const int kind = qkv_as_planes(ctx) ? 2 : 0;
+    const int kind = ctx->attn_form == ATTN_STREAMING ? 0 : 2;
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_mx(s, ctx->x, lw[0], lw[1], ctx->y, ys, rows, E, E, c->eps));
-    OP(VIT_OP_QKV, fold ? vh_launch_linear_mx_norm(s, ctx->qkv, NULL, kind, l8[2], l8s[2], ctx->y, ys, ctx->stats, cs[2], bf[2], c->eps, rows, E, 3 * E, 0)
-                 : kind ? vh_launch_linear_mx_planes_f16(s, ctx->qkv, l8[2], l8s[2], ctx->y, ys, lw[3], rows, E, 3 * E)
-                        : vh_launch_linear_mx(s, ctx->qkv, NULL, l8[2], l8s[2], ctx->y, ys, lw[3], rows, E, 3 * E, 0, NULL));
+    OP(VIT_OP_QKV, fold ? vh_launch_linear_mx_norm(s, ctx->qkv, NULL, kind, op[0].w, op[0].scales, ctx->y, ys, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
+                 : kind ? vh_launch_linear_mx_planes_f16(s, ctx->qkv, op[0].w, op[0].scales, ctx->y, ys, lw[3], rows, E, 3 * E)
+                        : vh_launch_linear_mx(s, ctx->qkv, NULL, op[0].w, op[0].scales, ctx->y, ys, lw[3], rows, E, 3 * E, 0, NULL));
     TRY(attention_reduced(ctx, s, n, as_));
-    OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_mx_resid_norm(s, ctx->x, l8[4], l8s[4], ctx->attn, as_, lw[5], ctx->x, rows, E, E, ctx->y, ys, ctx->stats)
-                             : vh_launch_linear_mx(s, ctx->x, NULL, l8[4], l8s[4], ctx->attn, as_, lw[5], rows, E, E, 0, ctx->x));
+    OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_mx_resid_norm(s, ctx->x, op[1].w, op[1].scales, ctx->attn, as_, lw[5], ctx->x, rows, E, E, ctx->y, ys, ctx->stats)
+                             : vh_launch_linear_mx(s, ctx->x, NULL, op[1].w, op[1].scales, ctx->attn, as_, lw[5], rows, E, E, 0, ctx->x));
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_mx(s, ctx->x, lw[6], lw[7], ctx->y, ys, rows, E, E, c->eps));
-    OP(VIT_OP_FC1, fold ? vh_launch_linear_mx_norm(s, ctx->hid, hs, 1, l8[8], l8s[8], ctx->y, ys, ctx->stats, cs[8], bf[8], c->eps, rows, E, F, 1)
-                        : vh_launch_linear_mx(s, ctx->hid, hs, l8[8], l8s[8], ctx->y, ys, lw[9], rows, E, F, 1, NULL));
+    OP(VIT_OP_FC1, fold ? vh_launch_linear_mx_norm(s, ctx->hid, hs, 1, op[2].w, op[2].scales, ctx->y, ys, ctx->stats, op[2].colsum, op[2].bias_folded, c->eps, rows, E, F, 1)
+                        : vh_launch_linear_mx(s, ctx->hid, hs, op[2].w, op[2].scales, ctx->y, ys, lw[9], rows, E, F, 1, NULL));
     /* nothing reads the operand behind the last layer: the final LayerNorm takes the fp32 rows */
-    OP(VIT_OP_FC2, fold && !last ? vh_launch_linear_mx_resid_norm(s, ctx->x, l8[10], l8s[10], ctx->hid, hs, lw[11], ctx->x, rows, F, E, ctx->y, ys, ctx->stats)
-                                 : vh_launch_linear_mx(s, ctx->x, NULL, l8[10], l8s[10], ctx->hid, hs, lw[11], rows, F, E, 0, ctx->x));
+    OP(VIT_OP_FC2, fold && !last ? vh_launch_linear_mx_resid_norm(s, ctx->x, op[3].w, op[3].scales, ctx->hid, hs, lw[11], ctx->x, rows, F, E, ctx->y, ys, ctx->stats)
+                                 : vh_launch_linear_mx(s, ctx->x, NULL, op[3].w, op[3].scales, ctx->hid, hs, lw[11], rows, F, E, 0, ctx->x));
     return 0;
 fail:
     return rc;
@@ -875,23 +792,22 @@ static int layer_bf16(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     int rc = 0;
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, F = c->mlp_hidden, rows = n * ctx->tokens, fold = ctx->ln_fold, last = l == c->depth - 1;
-    float **lw = ctx->w + 4 + 12 * l;
-    void **lw16 = ctx->w16 + 4 + 12 * l;
-    float **cs = ctx->fold_cs + 4 + 12 * l, **bf = ctx->fold_b + 4 + 12 * l;
-    const int kind = qkv_as_planes(ctx) ? 2 : 0;
+    float **lw = layer_tensors(ctx, l);
+    const struct operand *op = ctx->op + 4 * l;
+    const int kind = ctx->attn_form == ATTN_STREAMING ? 0 : 2;
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_planes(s, ctx->x, lw[0], lw[1], ctx->y, 1, rows, E, E, c->eps));
-    OP(VIT_OP_QKV, fold ? vh_launch_linear_planes_norm(s, ctx->qkv, kind, lw16[2], ctx->y, ctx->stats, cs[2], bf[2], c->eps, rows, E, 3 * E, 0)
-                        : vh_launch_linear_planes(s, ctx->qkv, kind, lw16[2], ctx->y, 1, lw[3], rows, E, 3 * E, 0, NULL));
+    OP(VIT_OP_QKV, fold ? vh_launch_linear_planes_norm(s, ctx->qkv, kind, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
+                        : vh_launch_linear_planes(s, ctx->qkv, kind, op[0].w, ctx->y, 1, lw[3], rows, E, 3 * E, 0, NULL));
     TRY(attention_reduced(ctx, s, n, NULL));
-    OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_planes_resid_norm(s, ctx->x, lw16[4], ctx->attn, lw[5], ctx->x, rows, E, E, ctx->y, NULL, ctx->stats)
-                             : vh_launch_linear_planes(s, ctx->x, 0, lw16[4], ctx->attn, 1, lw[5], rows, E, E, 0, ctx->x));
+    OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_planes_resid_norm(s, ctx->x, op[1].w, ctx->attn, lw[5], ctx->x, rows, E, E, ctx->y, NULL, ctx->stats)
+                             : vh_launch_linear_planes(s, ctx->x, 0, op[1].w, ctx->attn, 1, lw[5], rows, E, E, 0, ctx->x));
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_planes(s, ctx->x, lw[6], lw[7], ctx->y, 1, rows, E, E, c->eps));
-    OP(VIT_OP_FC1, fold ? vh_launch_linear_planes_norm(s, ctx->hid, 1, lw16[8], ctx->y, ctx->stats, cs[8], bf[8], c->eps, rows, E, F, 1)
-                        : vh_launch_linear_planes(s, ctx->hid, 1, lw16[8], ctx->y, 1, lw[9], rows, E, F, 1, NULL));
-    OP(VIT_OP_FC2, fold && !last ? vh_launch_linear_planes_resid_norm(s, ctx->x, lw16[10], ctx->hid, lw[11], ctx->x, rows, F, E, ctx->y, NULL, ctx->stats)
-                                 : vh_launch_linear_planes(s, ctx->x, 0, lw16[10], ctx->hid, 1, lw[11], rows, F, E, 0, ctx->x));
+    OP(VIT_OP_FC1, fold ? vh_launch_linear_planes_norm(s, ctx->hid, 1, op[2].w, ctx->y, ctx->stats, op[2].colsum, op[2].bias_folded, c->eps, rows, E, F, 1)
+                        : vh_launch_linear_planes(s, ctx->hid, 1, op[2].w, ctx->y, 1, lw[9], rows, E, F, 1, NULL));
+    OP(VIT_OP_FC2, fold && !last ? vh_launch_linear_planes_resid_norm(s, ctx->x, op[3].w, ctx->hid, lw[11], ctx->x, rows, F, E, ctx->y, NULL, ctx->stats)
+                                 : vh_launch_linear_planes(s, ctx->x, 0, op[3].w, ctx->hid, 1, lw[11], rows, F, E, 0, ctx->x));
     return 0;
 fail:
     return rc;
@@ -903,16 +819,15 @@ static int layer_fp16x2(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     int rc = 0;
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->tokens, rows = n * T;
-    float **lw = ctx->w + 4 + 12 * l;
-    void **l3 = ctx->w3 + 4 + 12 * l;
-    const float *ws = ctx->w3_scale + 4 + 12 * l;
+    float **lw = layer_tensors(ctx, l);
+    const struct operand *op = ctx->op + 4 * l;
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, E, c->eps));
-    OP(VIT_OP_QKV, vh_launch_linear_h2(s, ctx->qkv, l3[2], ws[2], ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
+    OP(VIT_OP_QKV, vh_launch_linear_h2(s, ctx->qkv, op[0].w, op[0].pair_scale, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
     OP(VIT_OP_ATTENTION, vh_launch_attention_h2(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads));
-    OP(VIT_OP_OUT_PROJ, vh_launch_linear_h2(s, ctx->x, l3[4], ws[4], ctx->attn, lw[5], rows, E, E, 0, ctx->x));
+    OP(VIT_OP_OUT_PROJ, vh_launch_linear_h2(s, ctx->x, op[1].w, op[1].pair_scale, ctx->attn, lw[5], rows, E, E, 0, ctx->x));
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, E, c->eps));
-    OP(VIT_OP_FC1, vh_launch_linear_h2(s, ctx->hid, l3[8], ws[8], ctx->y, lw[9], rows, E, F, 1, NULL));
-    OP(VIT_OP_FC2, vh_launch_linear_h2(s, ctx->x, l3[10], ws[10], ctx->hid, lw[11], rows, F, E, 0, ctx->x));
+    OP(VIT_OP_FC1, vh_launch_linear_h2(s, ctx->hid, op[2].w, op[2].pair_scale, ctx->y, lw[9], rows, E, F, 1, NULL));
+    OP(VIT_OP_FC2, vh_launch_linear_h2(s, ctx->x, op[3].w, op[3].pair_scale, ctx->hid, lw[11], rows, F, E, 0, ctx->x));
     return 0;
 fail:
     return rc;
@@ -927,16 +842,15 @@ static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int *
     int rc = 0;
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->tokens, rows = n * T, fold = ctx->ln_fold, last = l == c->depth - 1;
-    float **lw = ctx->w + 4 + 12 * l;
-    void **l3 = ctx->w3 + 4 + 12 * l;
-    float **cs = ctx->fold_cs + 4 + 12 * l, **bf = ctx->fold_b + 4 + 12 * l;
-    /* head_dim 64, T <= 208: Q, K, V too travel as planes (only the probabilities are split inside the attention kernel);
-     * other shapes: the streaming kernel, fp32 rows in, fp32 out (into the idle MLP buffer), then split */
-    const int planes_attn = E == 64 * c->num_heads && T <= 208;
+    float **lw = layer_tensors(ctx, l);
+    const struct operand *op = ctx->op + 4 * l;
+    /* ATTN_HD64: Q, K, V too travel as planes (only the probabilities are split inside the attention kernel); otherwise
+     * the streaming kernel, fp32 rows in, fp32 out (into the idle MLP buffer), then split */
+    const int planes_attn = ctx->attn_form == ATTN_HD64;
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, c->eps));
-    OP(VIT_OP_QKV, fold ? vh_launch_linear_p3_norm(s, ctx->qkv, planes_attn, l3[2], ctx->y, ctx->stats, cs[2], bf[2], c->eps, rows, E, 3 * E, 0)
-                        : vh_launch_linear_p3(s, ctx->qkv, planes_attn, l3[2], ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
+    OP(VIT_OP_QKV, fold ? vh_launch_linear_p3_norm(s, ctx->qkv, planes_attn, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
+                        : vh_launch_linear_p3(s, ctx->qkv, planes_attn, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
     OP(VIT_OP_ATTENTION, planes_attn ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
                          : (rc = vh_launch_attention(s, ctx->qkv, ctx->hid, n, T, E, c->num_heads)) != 0 ? rc
                          : vh_launch_split3_rows(s, ctx->hid, ctx->attn, rows, E));
@@ -953,21 +867,21 @@ static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int *
         char *hid_cls = y_cls + align_up((size_t)n * E * 6, 256);
         OP(VIT_OP_OUT_PROJ, (rc = vh_launch_gather_rows(s, ctx->attn, attn_cls, 3 * (E / 32), rows, n, 64, T)) != 0 ? rc :
                             (rc = vh_launch_gather_rows(s, ctx->x, x_cls, 1, rows, n, 4 * E, T)) != 0 ? rc :
-                            vh_launch_linear_p3(s, x_cls, 0, l3[4], attn_cls, lw[5], n, E, E, 0, x_cls));
+                            vh_launch_linear_p3(s, x_cls, 0, op[1].w, attn_cls, lw[5], n, E, E, 0, x_cls));
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, x_cls, lw[6], lw[7], y_cls, n, E, E, c->eps));
-        OP(VIT_OP_FC1, vh_launch_linear_p3(s, hid_cls, 1, l3[8], y_cls, lw[9], n, E, F, 1, NULL));
-        OP(VIT_OP_FC2, vh_launch_linear_p3(s, x_cls, 0, l3[10], hid_cls, lw[11], n, F, E, 0, x_cls));
+        OP(VIT_OP_FC1, vh_launch_linear_p3(s, hid_cls, 1, op[2].w, y_cls, lw[9], n, E, F, 1, NULL));
+        OP(VIT_OP_FC2, vh_launch_linear_p3(s, x_cls, 0, op[3].w, hid_cls, lw[11], n, F, E, 0, x_cls));
         *cls_rows = 1;
         return 0;
     }
-    OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_p3_resid_norm(s, ctx->x, l3[4], ctx->attn, lw[5], ctx->x, rows, E, E, ctx->y, ctx->stats)
-                             : vh_launch_linear_p3(s, ctx->x, 0, l3[4], ctx->attn, lw[5], rows, E, E, 0, ctx->x));
+    OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_p3_resid_norm(s, ctx->x, op[1].w, ctx->attn, lw[5], ctx->x, rows, E, E, ctx->y, ctx->stats)
+                             : vh_launch_linear_p3(s, ctx->x, 0, op[1].w, ctx->attn, lw[5], rows, E, E, 0, ctx->x));
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, c->eps));
-    OP(VIT_OP_FC1, fold ? vh_launch_linear_p3_norm(s, ctx->hid, 1, l3[8], ctx->y, ctx->stats, cs[8], bf[8], c->eps, rows, E, F, 1)
-                        : vh_launch_linear_p3(s, ctx->hid, 1, l3[8], ctx->y, lw[9], rows, E, F, 1, NULL));
-    OP(VIT_OP_FC2, fold && !last ? vh_launch_linear_p3_resid_norm(s, ctx->x, l3[10], ctx->hid, lw[11], ctx->x, rows, F, E, ctx->y, ctx->stats)
-                                 : vh_launch_linear_p3(s, ctx->x, 0, l3[10], ctx->hid, lw[11], rows, F, E, 0, ctx->x));
+    OP(VIT_OP_FC1, fold ? vh_launch_linear_p3_norm(s, ctx->hid, 1, op[2].w, ctx->y, ctx->stats, op[2].colsum, op[2].bias_folded, c->eps, rows, E, F, 1)
+                        : vh_launch_linear_p3(s, ctx->hid, 1, op[2].w, ctx->y, lw[9], rows, E, F, 1, NULL));
+    OP(VIT_OP_FC2, fold && !last ? vh_launch_linear_p3_resid_norm(s, ctx->x, op[3].w, ctx->hid, lw[11], ctx->x, rows, F, E, ctx->y, ctx->stats)
+                                 : vh_launch_linear_p3(s, ctx->x, 0, op[3].w, ctx->hid, lw[11], rows, F, E, 0, ctx->x));
     return 0;
 fail:
     return rc;
@@ -980,18 +894,18 @@ static int layer_f32_rows(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     int rc = 0;
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->tokens, rows = n * T;
-    float **lw = ctx->w + 4 + 12 * l;   /* ln1 w,b; in w,b; out w,b; ln2 w,b; fc1 w,b; fc2 w,b */
-    void **l3 = ctx->w3 + 4 + 12 * l;   /* pre-split weight planes, when built */
+    float **lw = layer_tensors(ctx, l);
+    const struct operand *op = ctx->op + 4 * l;   /* pre-split weight planes, when built */
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, E, c->eps));
-    OP(VIT_OP_QKV, l3[2] ? vh_launch_linear_w3(s, ctx->qkv, l3[2], ctx->y, lw[3], rows, E, 3 * E, 0, NULL)
+    OP(VIT_OP_QKV, op[0].w ? vh_launch_linear_w3(s, ctx->qkv, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL)
                          : vh_launch_linear(s, ctx->qkv, lw[2], ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
     OP(VIT_OP_ATTENTION, vh_launch_attention(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads));
-    OP(VIT_OP_OUT_PROJ, l3[4] ? vh_launch_linear_w3(s, ctx->x, l3[4], ctx->attn, lw[5], rows, E, E, 0, ctx->x)
+    OP(VIT_OP_OUT_PROJ, op[1].w ? vh_launch_linear_w3(s, ctx->x, op[1].w, ctx->attn, lw[5], rows, E, E, 0, ctx->x)
                               : vh_launch_linear(s, ctx->x, lw[4], ctx->attn, lw[5], rows, E, E, 0, ctx->x));
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, E, c->eps));
-    OP(VIT_OP_FC1, l3[8] ? vh_launch_linear_w3(s, ctx->hid, l3[8], ctx->y, lw[9], rows, E, F, 1, NULL)
+    OP(VIT_OP_FC1, op[2].w ? vh_launch_linear_w3(s, ctx->hid, op[2].w, ctx->y, lw[9], rows, E, F, 1, NULL)
                          : vh_launch_linear(s, ctx->hid, lw[8], ctx->y, lw[9], rows, E, F, 1, NULL));
-    OP(VIT_OP_FC2, l3[10] ? vh_launch_linear_w3(s, ctx->x, l3[10], ctx->hid, lw[11], rows, F, E, 0, ctx->x)
+    OP(VIT_OP_FC2, op[3].w ? vh_launch_linear_w3(s, ctx->x, op[3].w, ctx->hid, lw[11], rows, F, E, 0, ctx->x)
                           : vh_launch_linear(s, ctx->x, lw[10], ctx->hid, lw[11], rows, F, E, 0, ctx->x));
     return 0;
 fail:
@@ -1005,21 +919,22 @@ static int patch_embedding(vit_hip_ctx *ctx, vh_stream_t s, const float *d_image
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim;
     float **w = ctx->w;
+    void *conv = ctx->slab[SLAB_CONV];
     /* ln_fold: y receives the token rows as the first projection's operand -- planes, or MX values with their scales behind
      * them -- and stats their partial sums (class-token rows included) */
     char *const y_scales = (char *)ctx->y + align_up((size_t)n * ctx->tokens * E, 256);
     if (ctx->ln_fold && ctx->precision == VIT_PRECISION_F32)   /* lab variant: the fold on three-part planes */
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes3_norm(s, d_images, ctx->wconv16, w[2], w[0], w[3], ctx->x, n, c->in_chans,
+        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes3_norm(s, d_images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans,
                                                                   c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes, ctx->y, ctx->stats));
     else if (ctx->ln_fold)
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes_norm(s, d_images, ctx->wconv16, w[2], w[0], w[3], ctx->x, n, c->in_chans,
+        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes_norm(s, d_images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans,
                                                                  c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes, ctx->y,
                                                                  ctx->precision == VIT_PRECISION_FP8_GEMM ? y_scales : NULL, ctx->stats));
-    else if (ctx->wconv16 && ctx->precision != VIT_PRECISION_F32)   /* reduced modes: im2row to one-part planes (in the MLP buffer, idle here) + the planes GEMM */
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes(s, d_images, ctx->wconv16, w[2], w[0], w[3], ctx->x, n, c->in_chans,
+    else if (ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM)   /* reduced modes: im2row to one-part planes (in the MLP buffer, idle here) + the planes GEMM */
+        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes(s, d_images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans,
                                                             c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes));
-    else if (ctx->wconv16 && ctx->use_p3)   /* the fp32 path on planes: im2row writes the exact three-part split, six products per block */
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes3(s, d_images, ctx->wconv16, w[2], w[0], w[3], ctx->x, n, c->in_chans,
+    else if (ctx->use_p3)   /* the fp32 path on planes: im2row writes the exact three-part split, six products per block */
+        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes3(s, d_images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans,
                                                              c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes));
     else
         OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_ws(s, d_images, w[1], w[2], w[0], w[3], ctx->x, n, c->in_chans,
