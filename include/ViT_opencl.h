@@ -42,7 +42,21 @@ typedef struct vit_config
 } vit_config;
 
 /* Fill `cfg` with a named preset: "vit_b_16" (the reference's only
- * configuration), "vit_l_16", "vit_h_14".  Returns 0, or -1 for an unknown name. */
+ * configuration), "vit_l_16", "vit_h_14" (224 px), and the higher-resolution
+ * fine-tuning shapes "vit_b_16_384" (T = 577), "vit_l_16_512" (T = 1025),
+ * "vit_h_14_518" (T = 1370).  Returns 0, or -1 for an unknown name.
+ *
+ * Attention by token count T and head_dim (fixed when a context is created):
+ *   T <= 208, head_dim 64, planes paths  resident kernel (attention_p3.hip)
+ *   T <= 272, head_dim 80, reduced modes resident kernel (attention_h16.hip)
+ *   otherwise up to T = 512              streaming kernel (attention_tiled.hip)
+ *   T > 512, head_dim 64 or 80           flash-style kernel (attention_long.hip) on
+ *                                        the planes paths: F32 (default planes),
+ *                                        BF16_GEMM, FP8_GEMM
+ * Above 512 tokens F32_FP16X2, the fp32-rows path ($VIT_HIP_P3=0,
+ * $VIT_HIP_GEMM_FP32=native, embed_dim or mlp_hidden not multiples of 128) and
+ * other head dims are refused at creation (code 2).  $VIT_HIP_ATTN=long selects
+ * attention_long.hip at any T on the planes paths with head_dim 64 or 80. */
 int vit_config_preset(vit_config *cfg, const char *name);
 
 /* Derived sizes. */

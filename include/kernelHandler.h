@@ -205,6 +205,13 @@ int vh_launch_attention_planes_f16_hd80(vh_stream_t s, const void *qkv_planes_f1
  * vh_launch_quantize_mx_rows, byte for byte.  head_dim 80, num_heads even, tokens <= 272. */
 int vh_launch_attention_planes_f16_hd80_operand(vh_stream_t s, const void *qkv_planes_f16, void *output, void *out_scales,
                                                 int output_kind, int n_images, int tokens, int embed_dim, int num_heads);
+/* Attention for any token count (csrc/attention_long.hip: flash-style, K and V stream through LDS in 64-key chunks, online
+ * softmax; nothing grows with tokens).  qkv_planes: the QKV projection's planes, parts 3 = the exact three-part bf16 split
+ * [3*embed_dim/32][3][rows][32] (the fp32 path; fp32 products of the splits), parts 1 = one-part fp16 [3*embed_dim/32][rows][32]
+ * (the reduced modes; the arithmetic of vh_launch_attention_f16).  output: fp32 rows [rows][embed_dim], rows =
+ * n_images*tokens.  head_dim 64 or 80, tokens >= 1. */
+int vh_launch_attention_long(vh_stream_t s, const void *qkv_planes, int parts, float *output, int n_images, int tokens,
+                             int embed_dim, int num_heads);
 /* vh_launch_linear on planes: input_planes [colA/32][3][rowA][32], weight_planes [colA/32][3][colB][32];
  * output fp32 [rowA][colB], or (output_planes != 0, no residual) planes [colB/32][3][rowA][32].
  * colA % 64 == 0, colB % 128 == 0. */

@@ -53,8 +53,13 @@ enum { SLAB_F32, SLAB_OPERAND, SLAB_CONV, SLAB_FOLD, N_SLABS };
 
 /* How the planes paths (F32 on planes, BF16_GEMM, FP8_GEMM) run attention: Q|K|V as one-part fp16 planes into a resident
  * kernel -- head_dim 64, or head_dim 80 (ViT-H/14, reduced modes only) which writes the output projection's operand
- * itself -- or fp32 rows through the streaming kernel */
-enum { ATTN_STREAMING, ATTN_HD64, ATTN_HD80 };
+ * itself -- or fp32 rows through the streaming kernel (T <= 512).  ATTN_LONG: Q|K|V as the mode's planes into the
+ * flash-style kernel (csrc/attention_long.hip; any T, head_dim 64 or 80), fp32 rows out into the idle MLP buffer, then
+ * rounded / split like the streaming kernel's -- every T > 512, and any T under $VIT_HIP_ATTN=long */
+enum { ATTN_STREAMING, ATTN_HD64, ATTN_HD80, ATTN_LONG };
+
+/* the largest T the streaming kernel (attention_tiled.hip) takes; beyond it only ATTN_LONG runs */
+enum { STREAMING_MAX_TOKENS = 512 };
 
 enum { MAX_DEPTH = 256, MAX_TENSORS = 4 + 12 * MAX_DEPTH + 4 };
 
@@ -417,6 +422,20 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
         return vh_set_error(2, "vit_hip_create: this shape, precision and batch cannot fold the LayerNorms (the fp32 path "
                                "needs the planes path)");
     const char *env_ll = getenv("VIT_HIP_LAST_LAYER");
+    /* attention: ATTN_LONG is the only kernel past STREAMING_MAX_TOKENS, and it reads the planes paths' Q|K|V with head_dim
+     * 64 or 80; $VIT_HIP_ATTN=long forces it at any T (tests, A/B).  Shapes no kernel runs are refused here, not at every
+     * forward. */
+    const char *env_attn = getenv("VIT_HIP_ATTN");
+    const int long_hd = E == 64 * H || E == 80 * H;
+    const int long_wanted = T > STREAMING_MAX_TOKENS || (env_attn && strcmp(env_attn, "long") == 0);
+    if (T > STREAMING_MAX_TOKENS && (precision == VIT_PRECISION_F32_FP16X2 || (precision == VIT_PRECISION_F32 && !use_p3) || !long_hd)) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "vit_hip_create: %d tokens: above %d tokens attention runs on the planes paths (F32 with "
+                 "embed_dim and mlp_hidden multiples of 128 and neither $VIT_HIP_P3=0 nor $VIT_HIP_GEMM_FP32=native, BF16_GEMM, "
+                 "FP8_GEMM; not F32_FP16X2) with head_dim 64 or 80 (precision %d, head_dim %d)",
+                 T, STREAMING_MAX_TOKENS, precision, E / H);
+        return vh_set_error(2, msg);
+    }
 
     vit_hip_ctx *ctx = (vit_hip_ctx *)calloc(1, sizeof(*ctx));
     if (!ctx)
@@ -431,6 +450,7 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
     ctx->use_p3 = use_p3;
     ctx->cls_only_last = use_p3 && !ln_fold && env_ll && strcmp(env_ll, "cls") == 0;
     ctx->attn_form = !(use_p3 || reduced) ? ATTN_STREAMING
+              : (long_wanted && long_hd) ? ATTN_LONG
               : (E == 64 * H && T <= 208) ? ATTN_HD64
               : (reduced && E == 80 * H && T <= 272) ? ATTN_HD80 : ATTN_STREAMING;
     ctx->w = (float **)calloc((size_t)n_tensors, sizeof(float *));
@@ -745,6 +765,10 @@ static int attention_reduced(vit_hip_ctx *ctx, vh_stream_t s, int n, char *attn_
                                          : vh_launch_attention_planes_f16(s, ctx->qkv, ctx->attn, 1, n, T, E, H));
     else if (ctx->attn_form == ATTN_HD80)
         OP(VIT_OP_ATTENTION, vh_launch_attention_planes_f16_hd80_operand(s, ctx->qkv, ctx->attn, attn_scales, attn_scales ? 2 : 1, n, T, E, H));
+    else if (ctx->attn_form == ATTN_LONG)
+        OP(VIT_OP_ATTENTION, (rc = vh_launch_attention_long(s, ctx->qkv, 1, ctx->hid, n, T, E, H)) != 0 ? rc :
+                             attn_scales ? vh_launch_quantize_mx_act(s, ctx->hid, ctx->attn, attn_scales, rows, E)
+                                         : vh_launch_split_rows(s, ctx->hid, ctx->attn, rows, E, 1));
     else
         OP(VIT_OP_ATTENTION, (rc = vh_launch_attention_f16(s, ctx->qkv, ctx->hid, n, T, E, H)) != 0 ? rc :
                              attn_scales ? vh_launch_quantize_mx_act(s, ctx->hid, ctx->attn, attn_scales, rows, E)
@@ -844,15 +868,17 @@ static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int *
     const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->tokens, rows = n * T, fold = ctx->ln_fold, last = l == c->depth - 1;
     float **lw = layer_tensors(ctx, l);
     const struct operand *op = ctx->op + 4 * l;
-    /* ATTN_HD64: Q, K, V too travel as planes (only the probabilities are split inside the attention kernel); otherwise
-     * the streaming kernel, fp32 rows in, fp32 out (into the idle MLP buffer), then split */
-    const int planes_attn = ctx->attn_form == ATTN_HD64;
+    /* ATTN_HD64, ATTN_LONG: Q, K, V too travel as planes (only the probabilities are split inside the attention kernel);
+     * otherwise the streaming kernel, fp32 rows in.  Both but the resident kernel write fp32 rows (into the idle MLP
+     * buffer), then split */
+    const int planes_attn = ctx->attn_form == ATTN_HD64 || ctx->attn_form == ATTN_LONG;
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, c->eps));
     OP(VIT_OP_QKV, fold ? vh_launch_linear_p3_norm(s, ctx->qkv, planes_attn, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
                         : vh_launch_linear_p3(s, ctx->qkv, planes_attn, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
-    OP(VIT_OP_ATTENTION, planes_attn ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
-                         : (rc = vh_launch_attention(s, ctx->qkv, ctx->hid, n, T, E, c->num_heads)) != 0 ? rc
+    OP(VIT_OP_ATTENTION, ctx->attn_form == ATTN_HD64 ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
+                         : (rc = ctx->attn_form == ATTN_LONG ? vh_launch_attention_long(s, ctx->qkv, 3, ctx->hid, n, T, E, c->num_heads)
+                                                             : vh_launch_attention(s, ctx->qkv, ctx->hid, n, T, E, c->num_heads)) != 0 ? rc
                          : vh_launch_split3_rows(s, ctx->hid, ctx->attn, rows, E));
     if (last && ctx->cls_only_last && T >= 4) {
         /* Opt-in (vit_hip_set_last_layer_cls_only / $VIT_HIP_LAST_LAYER=cls).  The classifier reads row 0 of every

@@ -29,6 +29,16 @@ int vit_config_preset(vit_config *cfg, const char *name)
     } else if (strcmp(name, "vit_h_14") == 0) {
         cfg->patch_size = 14; cfg->embed_dim = 1280; cfg->depth = 32;
         cfg->num_heads = 16; cfg->mlp_hidden = 5120;
+    } else if (strcmp(name, "vit_b_16_384") == 0) {
+        /* the fine-tuned higher-resolution shapes: T = 577, 1025, 1370 (attention_long.hip) */
+        vit_config_preset(cfg, "vit_b_16");
+        cfg->img_size = 384;
+    } else if (strcmp(name, "vit_l_16_512") == 0) {
+        vit_config_preset(cfg, "vit_l_16");
+        cfg->img_size = 512;
+    } else if (strcmp(name, "vit_h_14_518") == 0) {
+        vit_config_preset(cfg, "vit_h_14");
+        cfg->img_size = 518;
     } else {
         return -1;
     }
