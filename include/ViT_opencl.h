@@ -143,6 +143,27 @@ int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *log
 int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
                            float *d_probs, vh_stream_t stream);
 
+/* ---- 8-bit images (what a JPEG / PNG decoder hands over), normalised on the GPU ----
+ * x = (float)u * scale[c] + bias[c]; the product and the sum are each rounded to fp32 (no fused multiply-add), so the
+ * logits are bit-identical to the fp32 entry points fed the same images normalised on the host with that arithmetic. */
+typedef struct vit_pixel_norm { float scale[4]; float bias[4]; } vit_pixel_norm;
+/* [n][img][img][C] as PIL / NumPy / OpenCV give it (RGB order), or [n][C][img][img] as torchvision.io gives it */
+enum { VIT_PIXELS_HWC = 0, VIT_PIXELS_CHW = 1 };
+/* scale = 1 / (255 std[c]), bias = -mean[c] / std[c], both computed in double and then rounded to float;
+ * mean and std on the 0..1 scale, as torchvision's Normalize takes them; chans 1..4, std > 0; returns 0 or 1 */
+int vit_pixel_norm_from_mean_std(vit_pixel_norm *out, const float *mean, const float *std, int chans);
+/* Device-resident form: d_images contiguous [n][img][img][C] or [n][C][img][img] bytes in HBM, 16-byte aligned, geometry of
+ * the context's config (in_chans <= 4), n <= max_batch; otherwise as vit_hip_forward_device.  On the planes paths the
+ * patch embedding's gather reads the bytes and normalises them (no fp32 image in HBM); on the fp32-rows paths
+ * ($VIT_HIP_P3=0, $VIT_HIP_GEMM_FP32=native, F32_FP16X2) a small kernel expands them first.  Code 1 (with a message, no
+ * launch) for a NULL ctx / images / norm, n out of range, an unknown layout, in_chans > 4 or a misaligned pointer. */
+int vit_hip_forward_device_u8(vit_hip_ctx *ctx, const unsigned char *d_images, int n, int layout,
+                              const vit_pixel_norm *norm, float *d_logits, float *d_probs, vh_stream_t stream);
+/* Host form: `images` contiguous in host memory, any n, in chunks of <= max_batch through vit_hip_forward's pipeline
+ * (one byte per value crosses PCIe); synchronous; logits and probs as vit_hip_forward, each may be NULL. */
+int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int layout,
+                       const vit_pixel_norm *norm, float *logits, float **probs);
+
 /* ---- several GPUs behind one call (the reference takes exactly one device, ViT_opencl.c:803) ----
  * Batch shards only: images never interact (ViT_opencl.c:926), so n images are cut into n_devices
  * contiguous shards (shard s = images [s*ceil(n/G), ...)); every device holds a full replica of the weights

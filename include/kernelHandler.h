@@ -347,6 +347,22 @@ int vh_launch_linear_mx_resid_norm(vh_stream_t s, float *output, const void *wei
                                    const void *input_values, const void *input_scales, const float *bias, const float *residual,
                                    int rowA, int colA, int colB, void *operand_values, void *operand_scales, float *row_stats_out);
 
+/* ---- 8-bit pixels (vit_hip_forward_device_u8) ----
+ * images: [n][img][img][in_chans] (layout 0, HWC) or [n][in_chans][img][img] (layout 1, CHW) bytes, 16-byte aligned,
+ * in_chans 1..4; scale / bias: in_chans host floats.  Every value becomes x = (float)u * scale[c] + bias[c], the product
+ * and the sum each rounded to fp32 (no fused multiply-add).
+ * The planes paths' patch embedding: the im2row producer of vh_launch_patch_embed_planes reads the bytes and normalises as
+ * it gathers (no fp32 image anywhere), then the same planes GEMM.  parts 1 with operand_out NULL = _planes, 3 = _planes3;
+ * operand_out, operand_scales_out and row_stats_out as in _planes_norm (parts 1) and _planes3_norm (parts 3). */
+int vh_launch_patch_embed_planes_u8(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias,
+                                    const void *conv_w_planes, const float *conv_b, const float *cls_token, const float *pos_embed,
+                                    float *tokens, int n_images, int in_chans, int img_size, int patch_size, int embed_dim,
+                                    void *workspace, size_t workspace_bytes, int parts, void *operand_out, void *operand_scales_out,
+                                    float *row_stats_out);
+/* The same arithmetic into normalised fp32 [n][in_chans][img][img] at `out` (the fp32-rows paths' input). */
+int vh_launch_expand_u8(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias, float *out,
+                        int n_images, int in_chans, int img_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 
 #include <math.h>
 #include <pthread.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -699,6 +700,12 @@ fail:
     return rc;
 }
 
+/* 1 where the patch embedding runs on planes (an im2row producer); 0 on the fp32-rows paths */
+static int planes_patch_embed(const vit_hip_ctx *ctx)
+{
+    return ctx->ln_fold || ctx->use_p3 || ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
+}
+
 /* The activation arena and the host-pointer path's staging, sized for max_batch images. */
 static int alloc_arena(vit_hip_ctx *ctx)
 {
@@ -712,7 +719,11 @@ static int alloc_arena(vit_hip_ctx *ctx)
     TRY(vh_malloc((void **)&ctx->x, rows * E * sizeof(float)));
     TRY(vh_malloc((void **)&ctx->y, rows * E * act));
     TRY(vh_malloc((void **)&ctx->attn, rows * E * act));
-    TRY(vh_malloc((void **)&ctx->qkv, rows * 3 * E * act));
+    {   /* the fp32-rows paths expand 8-bit images into Q|K|V (vit_hip_forward_device_u8): room for max_batch fp32 images, more
+         * than Q|K|V only for tiny test configs */
+        const size_t qkv_bytes = rows * 3 * E * act, expanded = planes_patch_embed(ctx) ? 0 : (size_t)max_batch * img * sizeof(float);
+        TRY(vh_malloc((void **)&ctx->qkv, qkv_bytes > expanded ? qkv_bytes : expanded));
+    }
     {   /* patch geometries that need gathered rows (H/14) borrow the MLP hidden buffer, idle at that point */
         size_t ws = vh_patch_embed_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->patch_size, cfg->embed_dim);
         if (ctx->slab[SLAB_CONV]) {   /* the im2row producer's planes: patches x Kp x 2 bytes x parts (a small MLP can be smaller than that) */
@@ -938,50 +949,67 @@ fail:
     return rc;
 }
 
-/* patch embedding + class token + position embedding (ViT_seq.c:437-443), in the form the mode's first layer reads */
-static int patch_embedding(vit_hip_ctx *ctx, vh_stream_t s, const float *d_images, int n)
+/* What a forward reads: fp32 [n][C][H][W], or 8-bit pixels in `layout` with their normalisation (vit_hip_forward_device_u8) */
+struct pixel_src
 {
-    int rc = 0;
+    const float *f32;
+    const unsigned char *u8;
+    int layout;
+    const vit_pixel_norm *norm;
+};
+
+/* patch embedding + class token + position embedding (ViT_seq.c:437-443), in the form the mode's first layer reads.  8-bit
+ * pixels: the planes paths' im2row producer normalises them as it gathers; the fp32-rows paths expand them first into the
+ * Q|K|V buffer (idle here; alloc_arena makes it hold max_batch fp32 images).  All of it is one VIT_OP_PATCH_EMBED. */
+static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct pixel_src *src, int n)
+{
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim;
     float **w = ctx->w;
     void *conv = ctx->slab[SLAB_CONV];
+    const int reduced = ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
     /* ln_fold: y receives the token rows as the first projection's operand -- planes, or MX values with their scales behind
      * them -- and stats their partial sums (class-token rows included) */
-    char *const y_scales = (char *)ctx->y + align_up((size_t)n * ctx->tokens * E, 256);
+    char *const y_scales = ctx->precision == VIT_PRECISION_FP8_GEMM ? (char *)ctx->y + align_up((size_t)n * ctx->tokens * E, 256) : NULL;
+    if (src->u8 && planes_patch_embed(ctx))
+        return vh_launch_patch_embed_planes_u8(s, src->u8, src->layout, src->norm->scale, src->norm->bias, conv, w[2], w[0], w[3],
+                                               ctx->x, n, c->in_chans, c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes,
+                                               ctx->precision == VIT_PRECISION_F32 ? 3 : 1, ctx->ln_fold ? ctx->y : NULL,
+                                               ctx->ln_fold ? y_scales : NULL, ctx->ln_fold ? ctx->stats : NULL);
+    const float *images = src->f32;
+    if (src->u8) {
+        const int rc = vh_launch_expand_u8(s, src->u8, src->layout, src->norm->scale, src->norm->bias, ctx->qkv, n, c->in_chans,
+                                           c->img_size);
+        if (rc)
+            return rc;
+        images = ctx->qkv;
+    }
     if (ctx->ln_fold && ctx->precision == VIT_PRECISION_F32)   /* lab variant: the fold on three-part planes */
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes3_norm(s, d_images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans,
-                                                                  c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes, ctx->y, ctx->stats));
-    else if (ctx->ln_fold)
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes_norm(s, d_images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans,
-                                                                 c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes, ctx->y,
-                                                                 ctx->precision == VIT_PRECISION_FP8_GEMM ? y_scales : NULL, ctx->stats));
-    else if (ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM)   /* reduced modes: im2row to one-part planes (in the MLP buffer, idle here) + the planes GEMM */
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes(s, d_images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans,
-                                                            c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes));
-    else if (ctx->use_p3)   /* the fp32 path on planes: im2row writes the exact three-part split, six products per block */
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_planes3(s, d_images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans,
-                                                             c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes));
-    else
-        OP(VIT_OP_PATCH_EMBED, vh_launch_patch_embed_ws(s, d_images, w[1], w[2], w[0], w[3], ctx->x, n, c->in_chans,
-                                                        c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes));
-    return 0;
-fail:
-    return rc;
+        return vh_launch_patch_embed_planes3_norm(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size,
+                                                  c->patch_size, E, ctx->hid, ctx->ws_bytes, ctx->y, ctx->stats);
+    if (ctx->ln_fold)
+        return vh_launch_patch_embed_planes_norm(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size,
+                                                 c->patch_size, E, ctx->hid, ctx->ws_bytes, ctx->y, y_scales, ctx->stats);
+    if (reduced)   /* reduced modes: im2row to one-part planes (in the MLP buffer, idle here) + the planes GEMM */
+        return vh_launch_patch_embed_planes(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size,
+                                            E, ctx->hid, ctx->ws_bytes);
+    if (ctx->use_p3)   /* the fp32 path on planes: im2row writes the exact three-part split, six products per block */
+        return vh_launch_patch_embed_planes3(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size,
+                                             E, ctx->hid, ctx->ws_bytes);
+    return vh_launch_patch_embed_ws(s, images, w[1], w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size, E,
+                                    ctx->hid, ctx->ws_bytes);
 }
 
-int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
-                           float *d_probs, vh_stream_t stream)
+/* Everything after the argument checks of vit_hip_forward_device and vit_hip_forward_device_u8 */
+static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream)
 {
     int rc = 0;
-    if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
-        return 1;
     TRY(vh_set_device(ctx->device));   /* the current device is per host thread */
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, T = ctx->tokens, NC = c->num_classes;
     vh_stream_t s = stream ? stream : ctx->stream;
 
-    TRY(patch_embedding(ctx, s, d_images, n));
+    OP(VIT_OP_PATCH_EMBED, patch_embed_launches(ctx, s, src, n));
     int cls_rows = 0;   /* the last layer ran on the class-token rows only (opt-in, fp32 path on planes) */
     for (int l = 0; l < c->depth; ++l) {
         switch (ctx->precision) {
@@ -1009,6 +1037,57 @@ int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float
     return 0;
 fail:
     return rc;
+}
+
+int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
+                           float *d_probs, vh_stream_t stream)
+{
+    if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
+        return 1;
+    const struct pixel_src src = {d_images, NULL, 0, NULL};
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream);
+}
+
+int vit_pixel_norm_from_mean_std(vit_pixel_norm *out, const float *mean, const float *std, int chans)
+{
+    if (!out || !mean || !std || chans < 1 || chans > 4)
+        return vh_set_error(1, "vit_pixel_norm_from_mean_std: NULL argument, or chans not in 1..4");
+    for (int ch = 0; ch < chans; ++ch)
+        if (!(std[ch] > 0.0f) || !isfinite(std[ch]) || !isfinite(mean[ch]))
+            return vh_set_error(1, "vit_pixel_norm_from_mean_std: std must be positive and finite, mean finite");
+    memset(out, 0, sizeof(*out));
+    for (int ch = 0; ch < chans; ++ch) {
+        out->scale[ch] = (float)(1.0 / (255.0 * (double)std[ch]));
+        out->bias[ch] = (float)(-(double)mean[ch] / (double)std[ch]);
+    }
+    return 0;
+}
+
+/* The u8 forms' checks that need no device; device_ptr: the pointer is in HBM and must be 16-byte aligned */
+static int u8_args(const char *who, const vit_hip_ctx *ctx, const unsigned char *images, int n, int layout, const vit_pixel_norm *norm,
+                   int device_ptr)
+{
+    char msg[200];
+    const char *why = !ctx || !images || !norm ? "NULL context, images or norm"
+                      : n <= 0 ? "n must be positive"
+                      : device_ptr && n > ctx->max_batch ? "n exceeds the context's max_batch"
+                      : layout != VIT_PIXELS_HWC && layout != VIT_PIXELS_CHW ? "layout must be VIT_PIXELS_HWC or VIT_PIXELS_CHW"
+                      : ctx->cfg.in_chans > 4 ? "8-bit images take at most 4 channels"
+                      : device_ptr && ((uintptr_t)images & 15) ? "device images must be 16-byte aligned"
+                      : NULL;
+    if (!why)
+        return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return vh_set_error(1, msg);
+}
+
+int vit_hip_forward_device_u8(vit_hip_ctx *ctx, const unsigned char *d_images, int n, int layout,
+                              const vit_pixel_norm *norm, float *d_logits, float *d_probs, vh_stream_t stream)
+{
+    if (u8_args("vit_hip_forward_device_u8", ctx, d_images, n, layout, norm, 1))
+        return 1;
+    const struct pixel_src src = {NULL, d_images, layout, norm};
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream);
 }
 
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
@@ -1106,26 +1185,38 @@ static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, float 
             memcpy(probs[first + i], ctx->h_probs[slot] + (size_t)i * NC, NC * sizeof(float));
 }
 
-/* Gather of the separately allocated host images (Network.c:90) into one pinned staging slot, on
- * several host threads: a single memcpy stream moves ~3 GB/s, which would cap the host-pointer path
+/* Gather of the separately allocated host images (Network.c:90) -- or of a caller's contiguous 8-bit images -- into one
+ * pinned staging slot, on several host threads: a single memcpy stream moves ~3 GB/s, which would cap the host-pointer path
  * below the device-resident rate. */
+struct host_src
+{
+    const ImageData *images;   /* fp32: one allocation per image */
+    const unsigned char *u8;   /* or 8-bit, contiguous */
+    int layout;
+    const vit_pixel_norm *norm;
+};
+
 struct gather_job
 {
-    float *dst;
-    const ImageData *images;
-    int first, count;
-    size_t img;
+    char *dst;
+    const struct host_src *src;
+    int first, count;   /* images [first, first + count) of the chunk starting at image `base` */
+    int base;
+    size_t bytes;       /* per image */
 };
 
 static void *gather_worker(void *arg)
 {
     const struct gather_job *j = (const struct gather_job *)arg;
-    for (int i = 0; i < j->count; ++i)
-        memcpy(j->dst + (size_t)(j->first + i) * j->img, j->images[j->first + i].data, j->img * sizeof(float));
+    for (int i = j->first; i < j->first + j->count; ++i) {
+        const void *from = j->src->images ? (const void *)j->src->images[j->base + i].data
+                                          : (const void *)(j->src->u8 + (size_t)(j->base + i) * j->bytes);
+        memcpy(j->dst + (size_t)i * j->bytes, from, j->bytes);
+    }
     return NULL;
 }
 
-static void gather_images(float *dst, const ImageData *images, int m, size_t img)
+static void gather_images(void *dst, const struct host_src *src, int base, int m, size_t bytes)
 {
     enum { MAX_THREADS = 8 };
     int nt = m / 16;
@@ -1135,14 +1226,14 @@ static void gather_images(float *dst, const ImageData *images, int m, size_t img
     pthread_t tid[MAX_THREADS];
     int started = 0;
     if (nt < 2) {
-        struct gather_job all = {dst, images, 0, m, img};
+        struct gather_job all = {(char *)dst, src, 0, m, base, bytes};
         gather_worker(&all);
         return;
     }
     const int per = (m + nt - 1) / nt;
     for (int t = 0; t < nt; ++t) {
         const int first = t * per, count = first >= m ? 0 : (m - first < per ? m - first : per);
-        jobs[t] = (struct gather_job){dst, images, first, count, img};
+        jobs[t] = (struct gather_job){(char *)dst, src, first, count, base, bytes};
         if (count == 0)
             break;
         if (t == nt - 1 || pthread_create(&tid[started], NULL, gather_worker, &jobs[t]) != 0)
@@ -1154,34 +1245,30 @@ static void gather_images(float *dst, const ImageData *images, int m, size_t img
         pthread_join(tid[t], NULL);
 }
 
-int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs)
+/* The pipeline of vit_hip_forward and vit_hip_forward_u8: a u8 chunk fills a quarter of a staging slot */
+static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n, float *logits, float **probs)
 {
     int rc = 0;
-    if (!ctx || !images || n <= 0)
-        return 1;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
-    const size_t img = (size_t)c->in_chans * c->img_size * c->img_size;
+    const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->u8 ? 1 : sizeof(float));
     const size_t NC = (size_t)c->num_classes;
-    for (int i = 0; i < n; ++i)
-        if (!images[i].data || images[i].c != c->in_chans || images[i].h != c->img_size ||
-            images[i].w != c->img_size)
-            return 5;
 
     int prev_first = 0, prev_m = 0, k = 0;
     for (int first = 0; first < n; first += ctx->max_batch, ++k) {
         const int m = (n - first < ctx->max_batch) ? n - first : ctx->max_batch;
         const int s = k & 1;
         /* slot s was last used by chunk k-2, whose outputs were waited for below */
-        gather_images(ctx->h_images[s], images + first, m, img);
+        gather_images(ctx->h_images[s], src, first, m, bytes);
         if (k >= 2)
             TRY(vh_stream_wait_event(ctx->copy_stream, ctx->comp_done[s]));
-        TRY(vh_h2d(ctx->d_images[s], ctx->h_images[s], (size_t)m * img * sizeof(float), ctx->copy_stream));
+        TRY(vh_h2d(ctx->d_images[s], ctx->h_images[s], (size_t)m * bytes, ctx->copy_stream));
         TRY(vh_event_record(ctx->up_done[s], ctx->copy_stream));
 
         TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
-        TRY(vit_hip_forward_device(ctx, ctx->d_images[s], m, ctx->d_logits, probs ? ctx->d_probs : NULL,
-                                   ctx->stream));
+        const struct pixel_src dev = {src->u8 ? NULL : ctx->d_images[s], src->u8 ? (const unsigned char *)ctx->d_images[s] : NULL,
+                                      src->layout, src->norm};
+        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         if (logits)
             TRY(vh_d2h(ctx->h_logits[s], ctx->d_logits, (size_t)m * NC * sizeof(float), ctx->stream));
@@ -1203,6 +1290,28 @@ fail:
     vh_stream_sync(ctx->copy_stream);
     vh_stream_sync(ctx->stream);
     return rc;
+}
+
+int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs)
+{
+    if (!ctx || !images || n <= 0)
+        return 1;
+    const vit_config *c = &ctx->cfg;
+    for (int i = 0; i < n; ++i)
+        if (!images[i].data || images[i].c != c->in_chans || images[i].h != c->img_size ||
+            images[i].w != c->img_size)
+            return 5;
+    const struct host_src src = {images, NULL, 0, NULL};
+    return forward_pipelined(ctx, &src, n, logits, probs);
+}
+
+int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int layout,
+                       const vit_pixel_norm *norm, float *logits, float **probs)
+{
+    if (u8_args("vit_hip_forward_u8", ctx, images, n, layout, norm, 0))
+        return 1;
+    const struct host_src src = {NULL, images, layout, norm};
+    return forward_pipelined(ctx, &src, n, logits, probs);
 }
 
 /* ---- several GPUs behind one call -------------------------------------------------

@@ -946,6 +946,113 @@ __global__ void im2row_planes_kernel(const float *__restrict__ images, char *__r
     store_parts8<NPL>(planes, (size_t)kt, n_rows, m, c, u, v);
 }
 
+/* ---- 8-bit pixels (vh_launch_patch_embed_planes_u8, vh_launch_expand_u8) ----
+ * x = (float)u * scale[ch] + bias[ch], the product and the sum each rounded to fp32 (no FMA): the arithmetic of a caller
+ * that normalises on the host in fp32, so what is written below equals what the fp32 source gives for those values. */
+enum { PIXELS_HWC = 0, PIXELS_CHW = 1 };   /* VIT_PIXELS_* */
+
+struct PixelNorm
+{
+    float scale[4], bias[4];
+};
+
+__device__ __forceinline__ float pick4(const float (&a)[4], int i) { return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3]; }
+
+__device__ __forceinline__ float norm_pixel(unsigned u, int ch, const PixelNorm &nm)
+{
+    return __fadd_rn(__fmul_rn((float)u, pick4(nm.scale, ch)), pick4(nm.bias, ch));
+}
+
+/* eight pixels of one HWC image row, channel ic, from the 8*C bytes at src (8-byte aligned): C dwordx2 loads, the channel
+ * picked with constant byte offsets (ic is wave-uniform, see the caller) */
+template <int C>
+__device__ __forceinline__ void hwc_row8(const unsigned char *src, int ic, const PixelNorm &nm, float (&x)[8])
+{
+    unsigned w[2 * C];
+#pragma unroll
+    for (int q = 0; q < C; ++q) {
+        const uint2 d = reinterpret_cast<const uint2 *>(src)[q];
+        w[2 * q] = d.x;
+        w[2 * q + 1] = d.y;
+    }
+#pragma unroll
+    for (int IC = 0; IC < C; ++IC)
+        if (ic == IC) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int j = e * C + IC;
+                x[e] = norm_pixel((w[j >> 2] >> (8 * (j & 3))) & 255u, IC, nm);
+            }
+        }
+}
+
+/* im2row_planes_kernel on 8-bit pixels, normalised as they are gathered: the same threads, the same planes.  Images
+ * [n][img][img][chans] (HWC) or [n][chans][img][img] (CHW), chans <= 4, base 16-byte aligned.  With patch % 8 == 0 a
+ * lane's eight k lie in one image row of one channel (and the 32 k of a K step in one channel: ic is wave-uniform): one
+ * dwordx2 (CHW) or chans dwordx2 (HWC) where the row offsets are multiples of 8 bytes, one byte per k elsewhere (patch 14,
+ * K padding). */
+template <int NPL, int LAYOUT>
+__global__ void im2row_planes_u8_kernel(const unsigned char *__restrict__ images, PixelNorm nm, char *__restrict__ planes, int n_rows,
+                                        int chans, int img, int patch, int grid, int K, int Kp)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_rows * (Kp >> 3))
+        return;
+    const int c = (int)(i & 3);
+    const size_t rm = i >> 2;
+    const int kt = (int)(rm / n_rows), m = (int)(rm - (size_t)kt * n_rows);
+    const int k0 = 32 * kt + 8 * c;
+    const int np = grid * grid, b = m / np, pp = m - b * np, oh = pp / grid, ow = pp - oh * grid;
+    const unsigned char *base = LAYOUT == PIXELS_CHW
+                                    ? images + ((size_t)b * chans * img + (size_t)oh * patch) * img + (size_t)ow * patch
+                                    : images + (((size_t)b * img + (size_t)oh * patch) * img + (size_t)ow * patch) * chans;
+    const int pp2 = patch * patch;
+    float x[8];
+    if ((patch & 7) == 0 && k0 + 8 <= K && (LAYOUT == PIXELS_CHW ? (img & 7) == 0 : ((img * chans) & 7) == 0)) {
+        const int ic = k0 / pp2, rem = k0 - ic * pp2, kh = rem / patch, kw = rem - kh * patch;
+        if (LAYOUT == PIXELS_CHW) {
+            const uint2 d = *reinterpret_cast<const uint2 *>(base + ((size_t)ic * img + kh) * img + kw);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                x[e] = norm_pixel(((e < 4 ? d.x : d.y) >> (8 * (e & 3))) & 255u, ic, nm);
+        } else {
+            const unsigned char *src = base + ((size_t)kh * img + kw) * chans;
+            switch (chans) {
+            case 1: hwc_row8<1>(src, ic, nm, x); break;
+            case 2: hwc_row8<2>(src, ic, nm, x); break;
+            case 3: hwc_row8<3>(src, ic, nm, x); break;
+            default: hwc_row8<4>(src, ic, nm, x); break;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int k = k0 + e;
+            x[e] = 0.0f;
+            if (k < K) {
+                const int ic = k / pp2, rem = k - ic * pp2, kh = rem / patch, kw = rem - kh * patch;
+                x[e] = norm_pixel(LAYOUT == PIXELS_CHW ? base[((size_t)ic * img + kh) * img + kw] : base[((size_t)kh * img + kw) * chans + ic],
+                                  ic, nm);
+            }
+        }
+    }
+    const f32x4 u = {x[0], x[1], x[2], x[3]}, v = {x[4], x[5], x[6], x[7]};
+    store_parts8<NPL>(planes, (size_t)kt, n_rows, m, c, u, v);
+}
+
+/* 8-bit images -> normalised fp32 [n][chans][img][img], one output value per thread (the fp32-rows paths' input) */
+template <int LAYOUT>
+__global__ void expand_u8_kernel(const unsigned char *__restrict__ images, PixelNorm nm, float *__restrict__ out, int n, int chans, int img)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, hw = (size_t)img * img, chw = hw * chans;
+    if (i >= (size_t)n * chw)
+        return;
+    const size_t b = i / chw, r = i - b * chw;
+    const int ic = (int)(r / hw);
+    const size_t p = r - (size_t)ic * hw;
+    out[i] = norm_pixel(LAYOUT == PIXELS_CHW ? images[i] : images[(b * hw + p) * chans + ic], ic, nm);
+}
+
 /* fp32 [rows][K] -> planes [Kp/32][NPL][rows][32], zero beyond K (the conv weights, once) */
 template <int NPL>
 __global__ void pad_rows_planes_kernel(const float *__restrict__ in, char *__restrict__ planes, int rows, int K, int Kp)
@@ -999,11 +1106,36 @@ extern "C" int vh_launch_conv_weight_planes(vh_stream_t s, const float *conv_w, 
     return vh_launch_conv_weight_planes_parts(s, conv_w, planes, embed_dim, in_chans, patch_size, 1);
 }
 
-static int patch_embed_planes(vh_stream_t s, const float *images, const void *conv_w_planes, const float *conv_b,
+namespace {
+/* the pixels of a patch embedding: fp32 [n][C][H][W], or 8-bit in `layout` with their normalisation */
+struct PixelSrc
+{
+    const float *f32;
+    const unsigned char *u8;
+    int layout;
+    PixelNorm nm;
+};
+} // namespace
+
+static int launch_im2row_u8(hipStream_t st, const PixelSrc &src, char *planes, int parts, int M, int in_chans, int img_size,
+                            int patch_size, int grid, int K, int Kp)
+{
+    const dim3 blocks((unsigned)(((size_t)M * (Kp / 8) + 255) / 256));
+    const bool chw = src.layout == PIXELS_CHW;
+    void (*kernel)(const unsigned char *, PixelNorm, char *, int, int, int, int, int, int, int) =
+        parts == 3 ? (chw ? im2row_planes_u8_kernel<3, PIXELS_CHW> : im2row_planes_u8_kernel<3, PIXELS_HWC>)
+                   : (chw ? im2row_planes_u8_kernel<1, PIXELS_CHW> : im2row_planes_u8_kernel<1, PIXELS_HWC>);
+    hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, st, src.u8, src.nm, planes, M, in_chans, img_size, patch_size, grid, K, Kp);
+    VH_LAUNCH_CHECK("im2row_planes_u8_kernel");
+    return 0;
+}
+
+static int patch_embed_planes(vh_stream_t s, const PixelSrc &src, const void *conv_w_planes, const float *conv_b,
                               const float *cls_token, const float *pos_embed, float *tokens, int n_images, int in_chans,
                               int img_size, int patch_size, int embed_dim, void *workspace, size_t workspace_bytes,
                               void *operand_out, void *operand_scales_out, float *row_stats_out, int parts = 1)
 {
+    const void *images = src.u8 ? (const void *)src.u8 : (const void *)src.f32;
     if (!images || !conv_w_planes || !conv_b || !cls_token || !pos_embed || !tokens || !workspace)
         return vh_fail(1, "vh_launch_patch_embed_planes: null pointer argument");
     if (n_images <= 0 || in_chans <= 0 || img_size <= 0 || patch_size <= 0 || embed_dim <= 0 || img_size % patch_size != 0 ||
@@ -1034,13 +1166,18 @@ static int patch_embed_planes(vh_stream_t s, const float *images, const void *co
     } else if (int rc = vh_cls_rows(st, cls_token, pos_embed, tokens, n_images, grid * grid + 1, embed_dim))
         return rc;
     const size_t threads = (size_t)M * (Kp / 8);
-    if (parts == 3)
-        hipLaunchKernelGGL(im2row_planes_kernel<3>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, images,
-                           static_cast<char *>(workspace), (int)M, in_chans, img_size, patch_size, grid, K, Kp);
-    else
-        hipLaunchKernelGGL(im2row_planes_kernel<1>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, images,
-                           static_cast<char *>(workspace), (int)M, in_chans, img_size, patch_size, grid, K, Kp);
-    VH_LAUNCH_CHECK("im2row_planes_kernel");
+    if (src.u8) {
+        if (int rc = launch_im2row_u8(st, src, static_cast<char *>(workspace), parts, (int)M, in_chans, img_size, patch_size, grid, K, Kp))
+            return rc;
+    } else {
+        if (parts == 3)
+            hipLaunchKernelGGL(im2row_planes_kernel<3>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, src.f32,
+                               static_cast<char *>(workspace), (int)M, in_chans, img_size, patch_size, grid, K, Kp);
+        else
+            hipLaunchKernelGGL(im2row_planes_kernel<1>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, src.f32,
+                               static_cast<char *>(workspace), (int)M, in_chans, img_size, patch_size, grid, K, Kp);
+        VH_LAUNCH_CHECK("im2row_planes_kernel");
+    }
     P3Params p = {};
     p.A = static_cast<const char *>(workspace);
     p.W = static_cast<const char *>(conv_w_planes);
@@ -1062,7 +1199,7 @@ extern "C" int vh_launch_patch_embed_planes(vh_stream_t s, const float *images, 
                                             int in_chans, int img_size, int patch_size, int embed_dim, void *workspace,
                                             size_t workspace_bytes)
 {
-    return patch_embed_planes(s, images, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, nullptr, nullptr, nullptr);
 }
 
@@ -1074,7 +1211,7 @@ extern "C" int vh_launch_patch_embed_planes3(vh_stream_t s, const float *images,
                                              int in_chans, int img_size, int patch_size, int embed_dim, void *workspace,
                                              size_t workspace_bytes)
 {
-    return patch_embed_planes(s, images, conv_w_planes3, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes3, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, nullptr, nullptr, nullptr, 3);
 }
 
@@ -1086,7 +1223,7 @@ extern "C" int vh_launch_patch_embed_planes3_norm(vh_stream_t s, const float *im
 {
     if (!operand_planes3_out || !row_stats_out)
         return vh_fail(1, "vh_launch_patch_embed_planes3_norm: null pointer argument");
-    return patch_embed_planes(s, images, conv_w_planes3, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes3, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, operand_planes3_out, nullptr, row_stats_out, 3);
 }
 
@@ -1101,6 +1238,61 @@ extern "C" int vh_launch_patch_embed_planes_norm(vh_stream_t s, const float *ima
 {
     if (!operand_out || !row_stats_out)
         return vh_fail(1, "vh_launch_patch_embed_planes_norm: null pointer argument");
-    return patch_embed_planes(s, images, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, operand_out, operand_scales_out, row_stats_out);
+}
+
+/* 8-bit pixel arguments shared by the two launchers below */
+static int pixel_source(const char *who, const unsigned char *images, int layout, const float *scale, const float *bias, int in_chans,
+                        PixelSrc *src)
+{
+    if (!images || !scale || !bias)
+        return vh_fail(1, "%s: null pointer argument", who);
+    if (layout != PIXELS_HWC && layout != PIXELS_CHW)
+        return vh_fail(1, "%s: layout %d is neither 0 (HWC) nor 1 (CHW)", who, layout);
+    if (in_chans < 1 || in_chans > 4)
+        return vh_fail(1, "%s: 8-bit pixels take 1 to 4 channels, not %d", who, in_chans);
+    if ((uintptr_t)images & 15)
+        return vh_fail(1, "%s: the images must be 16-byte aligned", who);
+    *src = PixelSrc{nullptr, images, layout, {}};
+    for (int ch = 0; ch < 4; ++ch) {
+        src->nm.scale[ch] = ch < in_chans ? scale[ch] : 0.0f;
+        src->nm.bias[ch] = ch < in_chans ? bias[ch] : 0.0f;
+    }
+    return 0;
+}
+
+/* The patch embedding of the planes paths on 8-bit pixels: the im2row producer normalises as it gathers (one byte read per
+ * value) and writes the planes the fp32 source gives; parts, operand_out, operand_scales_out and row_stats_out select what
+ * vh_launch_patch_embed_planes / _planes3 / _planes_norm / _planes3_norm do. */
+extern "C" int vh_launch_patch_embed_planes_u8(vh_stream_t s, const unsigned char *images, int layout, const float *scale,
+                                               const float *bias, const void *conv_w_planes, const float *conv_b, const float *cls_token,
+                                               const float *pos_embed, float *tokens, int n_images, int in_chans, int img_size,
+                                               int patch_size, int embed_dim, void *workspace, size_t workspace_bytes, int parts,
+                                               void *operand_out, void *operand_scales_out, float *row_stats_out)
+{
+    PixelSrc src;
+    if (int rc = pixel_source("vh_launch_patch_embed_planes_u8", images, layout, scale, bias, in_chans, &src))
+        return rc;
+    if ((operand_out != nullptr) != (row_stats_out != nullptr))
+        return vh_fail(1, "vh_launch_patch_embed_planes_u8: operand and row statistics go together");
+    return patch_embed_planes(s, src, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+                              embed_dim, workspace, workspace_bytes, operand_out, operand_scales_out, row_stats_out, parts);
+}
+
+extern "C" int vh_launch_expand_u8(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias,
+                                   float *out, int n_images, int in_chans, int img_size)
+{
+    PixelSrc src;
+    if (int rc = pixel_source("vh_launch_expand_u8", images, layout, scale, bias, in_chans, &src))
+        return rc;
+    if (!out || n_images <= 0 || img_size <= 0)
+        return vh_fail(1, "vh_launch_expand_u8: bad argument");
+    const size_t total = (size_t)n_images * in_chans * img_size * img_size;
+    const dim3 blocks((unsigned)((total + 255) / 256));
+    void (*kernel)(const unsigned char *, PixelNorm, float *, int, int, int) =
+        layout == PIXELS_CHW ? expand_u8_kernel<PIXELS_CHW> : expand_u8_kernel<PIXELS_HWC>;
+    hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, (hipStream_t)s, images, src.nm, out, n_images, in_chans, img_size);
+    VH_LAUNCH_CHECK("expand_u8_kernel");
+    return 0;
 }

@@ -57,6 +57,8 @@ EXPORTS = [
     "vit_synth_fill", "vit_synth_tensor", "vit_synth_image",
     "load_image_data", "load_weights", "vit_write_image_file", "vit_write_weight_file",
     "vit_write_result_file", "vit_compare_rows",
+    "vh_launch_patch_embed_planes_u8", "vh_launch_expand_u8", "vit_pixel_norm_from_mean_std", "vit_hip_forward_device_u8",
+    "vit_hip_forward_u8",
 ]
 
 
@@ -68,6 +70,15 @@ class VitConfig(C.Structure):
         ("num_classes", C.c_int), ("embed_dim", C.c_int), ("depth", C.c_int),
         ("num_heads", C.c_int), ("mlp_hidden", C.c_int), ("eps", C.c_double),
     ]
+
+
+class PixelNorm(C.Structure):
+    """`vit_pixel_norm` (include/ViT_opencl.h): x = (float)u * scale[c] + bias[c], each step rounded to fp32."""
+
+    _fields_ = [("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+PIXEL_LAYOUTS = {"hwc": 0, "chw": 1}
 
 
 class CompareReport(C.Structure):
@@ -267,6 +278,12 @@ def lib() -> C.CDLL:
     L.vit_write_weight_file.argtypes = [C.c_char_p, i, C.c_char_p, f32p, sz]
     L.vit_write_result_file.argtypes = [C.c_char_p, C.POINTER(f32p), i, i]
     L.vit_compare_rows.argtypes = [f32p, f32p, i, i, C.c_double, C.POINTER(CompareReport)]
+    u8p = C.POINTER(C.c_ubyte)
+    L.vh_launch_patch_embed_planes_u8.argtypes = [voidp, voidp, i, f32p, f32p] + [voidp] * 5 + [i] * 5 + [voidp, sz, i] + [voidp] * 3
+    L.vh_launch_expand_u8.argtypes = [voidp, voidp, i, f32p, f32p, voidp, i, i, i]
+    L.vit_pixel_norm_from_mean_std.argtypes = [C.POINTER(PixelNorm), f32p, f32p, i]
+    L.vit_hip_forward_device_u8.argtypes = [voidp, voidp, i, i, C.POINTER(PixelNorm), voidp, voidp, voidp]
+    L.vit_hip_forward_u8.argtypes = [voidp, u8p, i, i, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
     _lib = L
     return L
 
@@ -310,6 +327,17 @@ def synth_images(cfg: VitConfig, first: int, count: int) -> np.ndarray:
     return a
 
 
+def pixel_norm(mean, std) -> PixelNorm:
+    """vit_pixel_norm_from_mean_std: mean and std per channel on the 0..1 scale (torchvision's Normalize)."""
+    mean = np.ascontiguousarray(mean, dtype=np.float32)
+    std = np.ascontiguousarray(std, dtype=np.float32)
+    if mean.shape != std.shape or mean.ndim != 1:
+        raise ValueError("mean and std: one value per channel each")
+    out = PixelNorm()
+    check(lib().vit_pixel_norm_from_mean_std(C.byref(out), fptr(mean), fptr(std), mean.size), "vit_pixel_norm_from_mean_std")
+    return out
+
+
 def networks(weights: list[np.ndarray]):
     arr = (Network * len(weights))()
     for i, w in enumerate(weights):
@@ -329,24 +357,26 @@ def image_array(images: np.ndarray):
 
 
 class DeviceBuffer:
-    """A vh_malloc'd float buffer with explicit copies (no hidden host mirror)."""
+    """A vh_malloc'd buffer of `count` float32 values (or of another dtype: np.uint8 for 8-bit images) with explicit copies
+    (no hidden host mirror)."""
 
-    def __init__(self, count: int):
+    def __init__(self, count: int, dtype=np.float32):
         self.count = int(count)
+        self.dtype = np.dtype(dtype)
         self.ptr = voidp()
-        check(lib().vh_malloc(C.byref(self.ptr), max(self.count, 1) * 4), "vh_malloc")
+        check(lib().vh_malloc(C.byref(self.ptr), max(self.count, 1) * self.dtype.itemsize), "vh_malloc")
 
     @classmethod
-    def from_numpy(cls, a: np.ndarray) -> "DeviceBuffer":
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        d = cls(a.size)
-        check(lib().vh_h2d(d.ptr, a.ctypes.data_as(voidp), a.size * 4, None), "vh_h2d")
+    def from_numpy(cls, a: np.ndarray, dtype=np.float32) -> "DeviceBuffer":
+        a = np.ascontiguousarray(a, dtype=dtype)
+        d = cls(a.size, dtype)
+        check(lib().vh_h2d(d.ptr, a.ctypes.data_as(voidp), a.nbytes, None), "vh_h2d")
         check(lib().vh_device_sync(), "vh_device_sync")
         return d
 
     def to_numpy(self, shape=None) -> np.ndarray:
-        out = np.empty(self.count, dtype=np.float32)
-        check(lib().vh_d2h(out.ctypes.data_as(voidp), self.ptr, self.count * 4, None), "vh_d2h")
+        out = np.empty(self.count, dtype=self.dtype)
+        check(lib().vh_d2h(out.ctypes.data_as(voidp), self.ptr, out.nbytes, None), "vh_d2h")
         check(lib().vh_device_sync(), "vh_device_sync")
         return out.reshape(shape) if shape is not None else out
 
@@ -410,6 +440,31 @@ class ViTHip:
         rows = (f32p * n)(*[fptr(probs[i]) for i in range(n)])
         check(self.L.vit_hip_forward(self.ctx, image_array(images), n, fptr(logits), rows), "vit_hip_forward")
         return logits, probs
+
+    def forward_u8(self, images: np.ndarray, mean, std, layout: str = "hwc", logits: bool = True, probs: bool = True):
+        """Host 8-bit path: [n][H][W][C] (layout "hwc") or [n][C][H][W] ("chw") uint8, normalised on the GPU with
+        pixel_norm(mean, std) -> (logits[n][classes], probs[n][classes]); logits=False / probs=False pass NULL and return
+        None in that place."""
+        cfg = self.cfg
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        n, S, Ch = images.shape[0], cfg.img_size, cfg.in_chans
+        want = (n, S, S, Ch) if layout == "hwc" else (n, Ch, S, S)
+        if images.shape != want:
+            raise ValueError(f"forward_u8: images of shape {images.shape}, the context's config takes {want} ({layout})")
+        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
+        nc = cfg.num_classes
+        out_l = np.empty((n, nc), dtype=np.float32) if logits else None
+        out_p = np.empty((n, nc), dtype=np.float32) if probs else None
+        rows = (f32p * n)(*[fptr(out_p[i]) for i in range(n)]) if probs else None
+        check(self.L.vit_hip_forward_u8(self.ctx, images.ctypes.data_as(C.POINTER(C.c_ubyte)), n, PIXEL_LAYOUTS[layout],
+                                        C.byref(norm), fptr(out_l) if logits else None, rows), "vit_hip_forward_u8")
+        return out_l, out_p
+
+    def forward_device_u8(self, d_images, n: int, norm: PixelNorm, layout: str = "hwc", d_logits=None, d_probs=None,
+                          stream=None):
+        """Device-resident 8-bit path (d_images: a uint8 DeviceBuffer's .ptr, or any device pointer)."""
+        check(self.L.vit_hip_forward_device_u8(self.ctx, d_images, n, PIXEL_LAYOUTS[layout], C.byref(norm), d_logits, d_probs,
+                                               stream), "vit_hip_forward_device_u8")
 
     def forward_device(self, d_images, n: int, d_logits=None, d_probs=None, stream=None):
         """Device-resident path; pointers are ints / c_void_p / DeviceBuffer.ptr."""
