@@ -31,6 +31,13 @@ Fixtures (inputs are regenerated from seeds, never stored):
   b16_stages_sha256.json  (`make_golden.py stage_digests`) sha256 of every element of the reference's per-stage outputs
                   for image 0 / layer 0 (the tensors b16_stages.npz only samples), so that the element-by-element check of
                   the port's stages runs where the reference is absent
+  ref_weight_stats.json  (`make_golden.py ref_weight_stats`) per tensor present in the reference's Network/ directory: its
+                  name, sigma, |max|/sigma and kurtosis -- recorded statistics that tests/realistic_weights.py is checked against
+  b16_realistic.npz  (`make_golden.py realistic`) the logits / probabilities the reference's ViT_seq.c gives on the heavy-
+                  tailed B/16 set of tests/realistic_weights.py (seed 0, default offset and massive channel) for synthetic
+                  images 0..2 and the real image of b16_real_image.npz, with the set's sha256, the exposure of the
+                  residual rows at every LayerNorm input and tools/quant_sensitivity.py's predicted relative L2 logit error
+                  of bf16 and fp8, LayerNorms folded and separate
   ref_abi_layout.json  (`make_golden.py abi_layout <reference dir>`) sizeof / offsetof of ImageData and Network as the reference's own
                   Network.h declares them (x86-64, gcc), the layout include/Network.h must keep
 """
@@ -150,6 +157,94 @@ def stage_digests() -> None:
     print("wrote b16_stages_sha256.json")
 
 
+REF_NETWORK = Path("/root/reference/MulticoreMainProject/Network")
+
+
+def ref_weight_stats() -> None:
+    """sigma, |max|/sigma and kurtosis of every tensor present under the reference's Network/ -> ref_weight_stats.json"""
+    import json
+    import re
+    sys.path.insert(0, str(ROOT / "tests"))
+    import realistic_weights as rw
+    files = sorted(REF_NETWORK.glob("Weight_*.bin"), key=lambda p: int(p.name.split("_")[1]))
+    if not files:
+        sys.exit(f"{REF_NETWORK}: no weight files (needs the build container)")
+    rows = []
+    for f in files:
+        m = re.fullmatch(r"Weight_(\d+)_(.*)\.bin", f.name)
+        a = np.fromfile(f, dtype=np.float32)
+        st = rw.tensor_stats(a)
+        rows.append({"index": int(m.group(1)), "name": m.group(2), "count": int(a.size),
+                     **{k: float("%.4g" % v) for k, v in st.items()}})
+    rec = {"what": "statistics of the reference's real ViT-B/16 tensors present in its Network/ directory (36 of 152 are "
+                   "absent), float64 over each tensor (oracle/make_golden.py ref_weight_stats)", "tensors": rows}
+    body = ",\n".join(json.dumps(r) for r in rows)
+    (GOLD / "ref_weight_stats.json").write_text(json.dumps(rec["what"]).join(['{"what": ', ', "tensors": [\n']) + body + "]}\n")
+    print(f"wrote ref_weight_stats.json: {len(rows)} tensors")
+
+
+REALISTIC_IMAGES = 3
+
+
+def realistic() -> None:
+    """The reference's ViT_seq.c on tests/realistic_weights.py's B/16 set -> b16_realistic.npz (see the module docstring)."""
+    import subprocess
+    import torch
+    sys.path.insert(0, str(ROOT / "tests"))
+    sys.path.insert(0, str(ROOT / "tools"))
+    import quant_sensitivity as qs
+    import realistic_weights as rw
+    orc.build()
+    if not orc.have_reference():
+        sys.exit("needs the build container (oracle/_ref/ref_harness)")
+    o = orc.Oracle("vit_b_16")
+    cfg, seed = o.cfg, 0
+    pl = rw.plan(cfg, seed)
+    ws = rw.realistic_weights(cfg, seed)
+    real = np.load(GOLD / "b16_real_image.npz")["image"]
+    images = np.stack([o.synth_image(i) for i in range(REALISTIC_IMAGES)] + [real])
+    with tempfile.TemporaryDirectory() as td:
+        wpath, ipath = Path(td) / "w.bin", Path(td) / "real.bin"
+        with open(wpath, "wb") as f:
+            for a in ws:
+                f.write(np.ascontiguousarray(a, np.float32).tobytes())
+        ipath.write_bytes(np.array([1, 3, 224, 224], np.int32).tobytes() + np.ascontiguousarray(real, np.float32).tobytes())
+        procs = [subprocess.Popen([str(orc.REF_HARNESS), "full_weights", str(wpath), str(i), "1", str(Path(td) / f"{i}.bin")])
+                 for i in range(REALISTIC_IMAGES)]
+        procs.append(subprocess.Popen([str(orc.REF_HARNESS), "full_weights_file", str(wpath), str(ipath), str(Path(td) / "r.bin")]))
+        assert all(p.wait() == 0 for p in procs)
+        recs = [orc.read_records(Path(td) / f"{i}.bin") for i in range(REALISTIC_IMAGES)] + [orc.read_records(Path(td) / "r.bin")]
+    logits = np.stack([r["logits"] for r in recs])
+    probs = np.stack([r["probs"] for r in recs])
+    exp = rw.exposure(cfg, ws, images, pl["dstar"])
+    # the independent error model (DESIGN 6): relative L2 of the logits, ||d|| / ||logits|| per image, against the
+    # unquantised fp32 restatement
+    w_t = [torch.from_numpy(np.ascontiguousarray(a)) for a in ws]
+    x_t = torch.from_numpy(images)
+    pred = {}
+    with torch.no_grad():
+        ref = qs.forward(cfg, w_t, x_t, {}, False)
+        for mode, fq in (("bf16", qs.bf16), ("fp8", qs.mx)):
+            out = {fold: qs.forward(cfg, w_t, x_t, {c: fq for c in qs.CLASSES}, bool(fold)) for fold in (1, 0)}
+            for fold in (1, 0):
+                pred[f"pred_{mode}_fold{fold}"] = ((out[fold] - ref).norm(dim=1) / ref.norm(dim=1)).numpy()
+            pred[f"pred_{mode}_fold_vs_separate"] = ((out[1] - out[0]).norm(dim=1) / ref.norm(dim=1)).numpy()
+    np.savez(GOLD / "b16_realistic.npz", logits=logits, probs=probs, synth_images=np.arange(REALISTIC_IMAGES),
+             seed=np.array(seed), offset=np.array(5.0), massive=np.array(90.0), dstar=np.array(pl["dstar"]),
+             weights_sha256=np.array(rw.weights_sha256(ws)),
+             **{f"exposure_{k}": np.array(v) for k, v in exp.items()}, **pred,
+             note=np.array("logits/probs: the reference's own ViT_seq.c on tests/realistic_weights.py's B/16 set (seed, offset, "
+                           "massive above), synthetic images 0..2 then the real image of b16_real_image.npz; exposure_*: per "
+                           "LayerNorm input (ln_1, ln_2 per layer, then the final one), float64 restatement over the four "
+                           "images; pred_*: tools/quant_sensitivity.py's fake-quantised relative L2 per image (fold_vs_separate: "
+                           "between its folded and separate passes)"))
+    print("argmax", logits.argmax(1), "sha", rw.weights_sha256(ws)[:16])
+    print("exposure mean/std max", np.round(exp["mean_std_max"], 2))
+    print("massive ratio", np.round(exp["massive_ratio"], 1))
+    for k, v in pred.items():
+        print(k, np.round(v, 4))
+
+
 LAYOUT_PROBE = r'''
 #include <stdio.h>
 #include <stddef.h>
@@ -190,6 +285,12 @@ def main() -> None:
         return
     if len(sys.argv) > 2 and sys.argv[1] == "abi_layout":
         abi_layout(sys.argv[2])
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "ref_weight_stats":
+        ref_weight_stats()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "realistic":
+        realistic()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "other_seed":
         other_seed()

@@ -11,6 +11,9 @@
  *   ref_harness time   <first_image> <count> <seed_base>       (prints seconds/image)
  *   ref_harness full_file <images.bin> <seed_base> <out.bin>   (images from a file in the reference's own format,
  *                       Network.c:41-71: int n, c, h, w, then n*c*h*w floats -- e.g. its Data/input-1.bin; synthetic weights)
+ *   ref_harness full_weights <weights.bin> <first_image> <count> <out.bin>   (weights from a raw float32 file: every tensor
+ *                       of vit_config_tensor_size in index order, nothing else -- e.g. tests/realistic_weights.py's set)
+ *   ref_harness full_weights_file <weights.bin> <images.bin> <out.bin>   (both from files)
  *
  * Logits are not observable through the reference's call surface
  * (ViT_seq.c:509-515 keeps them in a local).  The reference library is built
@@ -90,6 +93,26 @@ static double now_s(void)
 }
 
 static int g_round_weights = 0; /* emulate load_weights' rounding (reference Network.c:208-211) */
+static const char *g_weights_file = NULL; /* raw float32, the tensors back to back in index order */
+
+static void read_weights(Network *nets, int n)
+{
+    FILE *f = fopen(g_weights_file, "rb");
+    if (!f) {
+        perror(g_weights_file);
+        exit(2);
+    }
+    for (int i = 0; i < n; ++i)
+        if (fread(nets[i].data, sizeof(float), nets[i].size, f) != nets[i].size) {
+            fprintf(stderr, "ref_harness: %s is shorter than the model's %d tensors\n", g_weights_file, n);
+            exit(2);
+        }
+    if (fgetc(f) != EOF) {
+        fprintf(stderr, "ref_harness: %s is longer than the model's %d tensors\n", g_weights_file, n);
+        exit(2);
+    }
+    fclose(f);
+}
 
 static Network *make_weights(const vit_config *cfg, unsigned long long seed_base)
 {
@@ -98,11 +121,14 @@ static Network *make_weights(const vit_config *cfg, unsigned long long seed_base
     for (int i = 0; i < n; ++i) {
         nets[i].size = vit_config_tensor_size(cfg, i);
         nets[i].data = (float *)malloc(sizeof(float) * nets[i].size);
-        vit_synth_tensor(cfg, i, seed_base, nets[i].data);
+        if (!g_weights_file)
+            vit_synth_tensor(cfg, i, seed_base, nets[i].data);
         if (g_round_weights)
             for (size_t k = 0; k < nets[i].size; ++k)
                 nets[i].data[k] = roundf(nets[i].data[k] * 1000000.0f) / 1000000.0f;
     }
+    if (g_weights_file)
+        read_weights(nets, n);
     return nets;
 }
 
@@ -241,6 +267,15 @@ int main(int argc, char **argv)
         g_image_file = argv[2];
         return run_full(0, 0, strtoull(argv[3], NULL, 10), argv[4], 0);
     }
+    if (argc == 6 && strcmp(argv[1], "full_weights") == 0) {
+        g_weights_file = argv[2];
+        return run_full(atoi(argv[3]), atoi(argv[4]), 0, argv[5], 0);
+    }
+    if (argc == 5 && strcmp(argv[1], "full_weights_file") == 0) {
+        g_weights_file = argv[2];
+        g_image_file = argv[3];
+        return run_full(0, 0, 0, argv[4], 0);
+    }
     if (argc == 6 && strcmp(argv[1], "full") == 0)
         return run_full(atoi(argv[2]), atoi(argv[3]), strtoull(argv[4], NULL, 10), argv[5], 0);
     if (argc == 5 && strcmp(argv[1], "time") == 0)
@@ -249,6 +284,8 @@ int main(int argc, char **argv)
         return run_stages(strtoull(argv[2], NULL, 10), argv[3]);
     fprintf(stderr, "usage: ref_harness full <first> <count> <seed_base> <out.bin>\n"
                     "       ref_harness time <first> <count> <seed_base>\n"
-                    "       ref_harness stages <seed_base> <out.bin>\n");
+                    "       ref_harness stages <seed_base> <out.bin>\n"
+                    "       ref_harness full_weights <weights.bin> <first> <count> <out.bin>\n"
+                    "       ref_harness full_weights_file <weights.bin> <images.bin> <out.bin>\n");
     return 64;
 }

@@ -100,6 +100,10 @@ def _inputs(n, T, H, D, case, seed):
     elif case == "rising":    # the maxima rise in every chunk (~2 softmax units per chunk): a rescale at every chunk
         x[:, :, 0] += u
         x[:, :, 1] += ((key // 64) * (2.0 / np.sqrt(D))).astype(np.float32)[:, None, None] * u
+    elif case == "sink":      # key 3 outscores every other by >= 20 for every query; V has a channel at 40x
+        x[:, :, 0] += u
+        x[:, min(3, T - 1), 1] += (40.0 / np.sqrt(D)) * u
+        x[:, :, 2, :, 5] *= 40.0
     return np.ascontiguousarray(x.reshape(n * T, 3 * H * D))
 
 
@@ -108,7 +112,8 @@ def _inputs(n, T, H, D, case, seed):
 @pytest.mark.parametrize("T", [1, 65, 577, 1025, 1370, 4097])
 def test_long_attention_kernel_vs_fp64(pkg, device, T, D, parts):
     """vh_launch_attention_long on 2 images x 2 heads, gaussian Q/K/V and three inputs that steer the online softmax
-    (global maximum in the lone key of the ragged last chunk, maxima in chunk 0 only, maxima rising in every chunk).
+    (global maximum in the lone key of the ragged last chunk, maxima in chunk 0 only, maxima rising in every chunk, an
+    attention sink: one key 20+ softmax units above the rest for every query, with a V channel at 40x).
     parts 3 against fp64 on the fp32 values: the products are exact fp32 products of the splits, so what is left is fp32
     accumulation, the fp32 rounding of each score and exp2.  Measured 1e-6 - 4e-6 of max|O| up to T = 1370, 1e-5 at
     T = 4097 and 1.6e-5 for the rising maxima there (scores reach ~1100 before the 1/sqrt(D): one fp32 rounding of such a
@@ -118,7 +123,7 @@ def test_long_attention_kernel_vs_fp64(pkg, device, T, D, parts):
     n, H = 2, 2
     E = H * D
     worst = 0.0
-    for case in ("gauss", "last", "first", "rising"):
+    for case in ("gauss", "last", "first", "rising", "sink"):
         qkv = _inputs(n, T, H, D, case, seed=T * 7 + D + parts)
         planes = _planes(qkv, parts)
         ref_in = qkv.astype(np.float16).astype(np.float32) if parts == 1 else qkv
