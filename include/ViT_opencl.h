@@ -164,6 +164,36 @@ int vit_hip_forward_device_u8(vit_hip_ctx *ctx, const unsigned char *d_images, i
 int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int layout,
                        const vit_pixel_norm *norm, float *logits, float **probs);
 
+/* ---- 8-bit images of any size: resized (shorter side) and centre-cropped on the GPU, bit-exact with Pillow ----
+ * Each image: resized to (nh, nw) with the shorter side resize_short (torchvision's Resize(int) arithmetic), then the
+ * img x img crop at (round_half_even((nh - img) / 2), likewise for x) (CenterCrop), the pixels those of Pillow's
+ * Image.resize((nw, nh), BILINEAR | BICUBIC) on 8-bit channels; then normalised and run exactly as the u8 path.
+ * One image: data (device memory in the device forms, host memory in the host form, any alignment); HWC rows of
+ * row_stride >= width * in_chans bytes, or CHW planes of height rows of row_stride >= width bytes, height * row_stride
+ * bytes apart.  1 <= height, width <= 16384; img <= resize_short <= 4 * img; in_chans <= 4.  The descriptor arrays are
+ * host memory in every form.  Code 1 (with a message, no launch) for a NULL argument, n out of range, an unknown filter
+ * or layout, an out-of-range size or a row_stride that is too small. */
+typedef struct vit_image_u8 { const unsigned char *data; int height, width; long row_stride; } vit_image_u8;
+enum { VIT_RESIZE_BILINEAR = 0, VIT_RESIZE_BICUBIC = 1 };
+typedef struct vit_resize_crop { int resize_short; int filter; } vit_resize_crop;
+/* host only: the resized size and crop offsets of one height x width image for a crop x crop crop; 0, or 1 with a message */
+int vit_resize_crop_geometry(int height, int width, const vit_resize_crop *rc, int crop,
+                             int *resized_h, int *resized_w, int *top, int *left);
+/* The crops alone: [n][img][img][in_chans] bytes (HWC) into d_out; n <= max_batch; asynchronous on `stream` (0 = the
+ * context's).  The coefficient tables go into the context's MLP buffer: calls on one context are ordered by their streams. */
+int vit_hip_resize_crop_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n, int layout,
+                           const vit_resize_crop *rc, unsigned char *d_out, vh_stream_t stream);
+/* resize + crop + vit_hip_forward_device_u8's forward; n <= max_batch; asynchronous like vit_hip_forward_device_u8.  The
+ * descriptors travel through a ring of pinned slots, so calls may be queued back to back without a host sync. */
+int vit_hip_forward_device_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n, int layout,
+                                      const vit_resize_crop *rc, const vit_pixel_norm *norm,
+                                      float *d_logits, float *d_probs, vh_stream_t stream);
+/* Host form: any n, through vit_hip_forward's two staging slots; a chunk holds at most max_batch images whose packed bytes
+ * (rows without their padding) fit one slot (max_batch x in_chans x img^2 x 4 bytes); a larger image is refused (code 1).
+ * Synchronous; logits and probs as vit_hip_forward, each may be NULL. */
+int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int n, int layout,
+                               const vit_resize_crop *rc, const vit_pixel_norm *norm, float *logits, float **probs);
+
 /* ---- several GPUs behind one call (the reference takes exactly one device, ViT_opencl.c:803) ----
  * Batch shards only: images never interact (ViT_opencl.c:926), so n images are cut into n_devices
  * contiguous shards (shard s = images [s*ceil(n/G), ...)); every device holds a full replica of the weights

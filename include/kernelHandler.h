@@ -363,6 +363,26 @@ int vh_launch_patch_embed_planes_u8(vh_stream_t s, const unsigned char *images, 
 int vh_launch_expand_u8(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias, float *out,
                         int n_images, int in_chans, int img_size);
 
+/* ---- Pillow-exact resize + centre crop of 8-bit images (csrc/resize.hip; vit_hip_resize_crop_u8) ----
+ * One source image, its resized size and crop offsets (vit_resize_crop_geometry) and where its coefficient tables lie in
+ * the scratch.  Tables of one image, at coef + coef_offset (16-byte aligned): x bounds int2 [crop] (first tap, taps), y
+ * bounds int2 [crop], x weights int32 [kx][crop] (tap-major), y weights int32 [crop][ky]; weights in 22 fractional bits. */
+typedef struct vh_resize_desc
+{
+    const unsigned char *data;  /* device; any alignment */
+    long row_stride;            /* bytes between rows */
+    long plane_stride;          /* CHW: bytes between channel planes */
+    int height, width;
+    int resized_h, resized_w, top, left;
+    int kx, ky;                 /* Pillow's ksize along x and y */
+    long coef_offset;
+} vh_resize_desc;
+/* desc: n descriptors in device memory; filter 0 bilinear, 1 bicubic; layout 0 HWC, 1 CHW; chans 1..4; out: [n][crop][crop]
+ * [chans] bytes (HWC).  One setup launch writes every image's tables into coef (coef_bytes long), then one launch per
+ * (image, band of output rows) runs the horizontal pass into LDS and the vertical pass in int32 registers. */
+int vh_launch_resize_crop_u8(vh_stream_t s, const vh_resize_desc *desc, int n, int chans, int layout, int filter, int crop,
+                             void *coef, size_t coef_bytes, unsigned char *out);
+
 #ifdef __cplusplus
 }
 #endif

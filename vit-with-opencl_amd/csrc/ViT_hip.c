@@ -64,6 +64,9 @@ enum { STREAMING_MAX_TOKENS = 512 };
 
 enum { MAX_DEPTH = 256, MAX_TENSORS = 4 + 12 * MAX_DEPTH + 4 };
 
+/* resize + crop: descriptor slots in flight, and the largest source side */
+enum { DESC_RING = 8, RESIZE_MAX_SIDE = 16384 };
+
 struct vit_hip_ctx
 {
     vit_config cfg;
@@ -106,6 +109,16 @@ struct vit_hip_ctx
     float *h_probs[2];
     vh_stream_t copy_stream;
     vh_event_t up_done[2], comp_done[2], out_done[2];
+
+    /* resize + centre crop (vit_hip_resize_crop_u8, the _resized forwards): the crops land in Q|K|V at crop_off (behind
+     * the fp32 expansion on the fp32-rows paths), the coefficient tables in hid.  Per-call descriptors go up through a ring
+     * of pinned slots; a slot is refilled only once the event behind its last reader has completed. */
+    size_t crop_off;
+    vh_resize_desc *h_desc[DESC_RING];
+    vh_resize_desc *d_desc[DESC_RING];
+    vh_event_t desc_done[DESC_RING];
+    int desc_live[DESC_RING];
+    int desc_next;
 
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
@@ -197,6 +210,11 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     for (size_t i = 0; i < sizeof(host) / sizeof(host[0]); ++i)
         if (host[i])
             vh_host_free(host[i]);
+    for (int i = 0; i < DESC_RING; ++i) {
+        if (ctx->d_desc[i]) vh_free(ctx->d_desc[i]);
+        if (ctx->h_desc[i]) vh_host_free(ctx->h_desc[i]);
+        if (ctx->desc_done[i]) vh_event_destroy(ctx->desc_done[i]);
+    }
     for (int i = 0; i < 2; ++i) {
         if (ctx->up_done[i]) vh_event_destroy(ctx->up_done[i]);
         if (ctx->comp_done[i]) vh_event_destroy(ctx->comp_done[i]);
@@ -706,6 +724,27 @@ static int planes_patch_embed(const vit_hip_ctx *ctx)
     return ctx->ln_fold || ctx->use_p3 || ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
 }
 
+/* Pillow's ksize: taps per output index of one axis (in -> out) */
+static int resize_taps(int in, int out, int filter)
+{
+    const double scale = (double)(float)in / out;
+    const double support = (filter == VIT_RESIZE_BICUBIC ? 2.0 : 1.0) * (scale < 1.0 ? 1.0 : scale);
+    return (int)ceil(support) * 2 + 1;
+}
+
+/* bicubic taps at the steepest downscale a crop x crop crop can see: the short side 16384 -> resize_short >= crop, the
+ * long side's truncated size makes its scale at most 16384 / (crop - 1) */
+static int resize_max_taps(int crop)
+{
+    return resize_taps(RESIZE_MAX_SIDE, crop > 1 ? crop - 1 : 1, VIT_RESIZE_BICUBIC);
+}
+
+/* one image's coefficient tables (include/kernelHandler.h, vh_resize_desc) */
+static size_t resize_table_bytes(int crop, int kx, int ky)
+{
+    return align_up((size_t)crop * 16 + ((size_t)kx + ky) * crop * 4, 16);
+}
+
 /* The activation arena and the host-pointer path's staging, sized for max_batch images. */
 static int alloc_arena(vit_hip_ctx *ctx)
 {
@@ -720,9 +759,13 @@ static int alloc_arena(vit_hip_ctx *ctx)
     TRY(vh_malloc((void **)&ctx->y, rows * E * act));
     TRY(vh_malloc((void **)&ctx->attn, rows * E * act));
     {   /* the fp32-rows paths expand 8-bit images into Q|K|V (vit_hip_forward_device_u8): room for max_batch fp32 images, more
-         * than Q|K|V only for tiny test configs */
+         * than Q|K|V only for tiny test configs; resized crops (max_batch x img^2 x C bytes) go behind that expansion */
         const size_t qkv_bytes = rows * 3 * E * act, expanded = planes_patch_embed(ctx) ? 0 : (size_t)max_batch * img * sizeof(float);
-        TRY(vh_malloc((void **)&ctx->qkv, qkv_bytes > expanded ? qkv_bytes : expanded));
+        ctx->crop_off = align_up(expanded, 256);
+        const size_t crops = cfg->in_chans <= 4 ? ctx->crop_off + (size_t)max_batch * img : 0;
+        size_t bytes = qkv_bytes > expanded ? qkv_bytes : expanded;
+        bytes = bytes > crops ? bytes : crops;
+        TRY(vh_malloc((void **)&ctx->qkv, bytes));
     }
     {   /* patch geometries that need gathered rows (H/14) borrow the MLP hidden buffer, idle at that point */
         size_t ws = vh_patch_embed_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->patch_size, cfg->embed_dim);
@@ -733,6 +776,11 @@ static int alloc_arena(vit_hip_ctx *ctx)
             ws = ws > planes ? ws : planes;
         }
         const size_t hid_bytes = rows * F * act;
+        if (cfg->in_chans <= 4) {   /* the resize's coefficient tables at the largest downscale (more only for tiny configs) */
+            const size_t tables = (size_t)max_batch * resize_table_bytes(cfg->img_size, resize_max_taps(cfg->img_size),
+                                                                          resize_max_taps(cfg->img_size));
+            ws = ws > tables ? ws : tables;
+        }
         ctx->ws_bytes = ws > hid_bytes ? ws : hid_bytes;
         TRY(vh_malloc((void **)&ctx->hid, ctx->ws_bytes));
     }
@@ -750,6 +798,11 @@ static int alloc_arena(vit_hip_ctx *ctx)
         TRY(vh_event_create(&ctx->up_done[i]));
         TRY(vh_event_create(&ctx->comp_done[i]));
         TRY(vh_event_create(&ctx->out_done[i]));
+    }
+    for (int i = 0; i < DESC_RING; ++i) {
+        TRY(vh_malloc((void **)&ctx->d_desc[i], (size_t)max_batch * sizeof(vh_resize_desc)));
+        TRY(vh_host_alloc((void **)&ctx->h_desc[i], (size_t)max_batch * sizeof(vh_resize_desc)));
+        TRY(vh_event_create(&ctx->desc_done[i]));
     }
     TRY(vh_stream_sync(ctx->stream));
     return 0;
@@ -956,7 +1009,48 @@ struct pixel_src
     const unsigned char *u8;
     int layout;
     const vit_pixel_norm *norm;
+    const vit_image_u8 *resize;   /* or 8-bit images of any size in `layout` (device data), resized and cropped first */
+    const vit_resize_crop *rc;
 };
+
+/* Queue the resize + centre crop of n validated images (device data) into out, [n][img][img][C] bytes: the descriptors go
+ * up through the next ring slot, the coefficient tables into hid.  The slot's event is recorded behind the launches that
+ * read it. */
+static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const vit_image_u8 *images, int n, int layout,
+                              const vit_resize_crop *rc, unsigned char *out)
+{
+    int rc_ = 0;
+    const vit_config *c = &ctx->cfg;
+    const int S = c->img_size, C = c->in_chans, slot = ctx->desc_next;
+    ctx->desc_next = (slot + 1) % DESC_RING;
+    if (ctx->desc_live[slot] && (rc_ = vh_event_sync(ctx->desc_done[slot])) != 0)
+        return rc_;
+    ctx->desc_live[slot] = 0;
+    vh_resize_desc *d = ctx->h_desc[slot];
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const vit_image_u8 *im = &images[i];
+        vh_resize_desc *e = &d[i];
+        vit_resize_crop_geometry(im->height, im->width, rc, S, &e->resized_h, &e->resized_w, &e->top, &e->left);
+        e->data = im->data;
+        e->row_stride = im->row_stride;
+        e->plane_stride = (long)im->height * im->row_stride;
+        e->height = im->height;
+        e->width = im->width;
+        e->kx = resize_taps(im->width, e->resized_w, rc->filter);
+        e->ky = resize_taps(im->height, e->resized_h, rc->filter);
+        e->coef_offset = (long)off;
+        off += resize_table_bytes(S, e->kx, e->ky);
+    }
+    if (off > ctx->ws_bytes)   /* alloc_arena sized hid for max_batch tables at the steepest downscale */
+        return vh_set_error(1, "resize: coefficient tables exceed the scratch");
+    if ((rc_ = vh_h2d(ctx->d_desc[slot], d, (size_t)n * sizeof(*d), s)) != 0)
+        return rc_;
+    rc_ = vh_launch_resize_crop_u8(s, ctx->d_desc[slot], n, C, layout, rc->filter, S, ctx->hid, ctx->ws_bytes, out);
+    const int rec = vh_event_record(ctx->desc_done[slot], s);   /* behind the copy even if the launch was refused */
+    ctx->desc_live[slot] = rec == 0;
+    return rc_ ? rc_ : rec;
+}
 
 /* patch embedding + class token + position embedding (ViT_seq.c:437-443), in the form the mode's first layer reads.  8-bit
  * pixels: the planes paths' im2row producer normalises them as it gathers; the fp32-rows paths expand them first into the
@@ -1009,6 +1103,13 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
     const int E = c->embed_dim, T = ctx->tokens, NC = c->num_classes;
     vh_stream_t s = stream ? stream : ctx->stream;
 
+    struct pixel_src crops;
+    if (src->resize) {   /* resized crops into Q|K|V, then the u8 path on them; both count as the patch embedding */
+        unsigned char *out = (unsigned char *)ctx->qkv + ctx->crop_off;
+        OP(VIT_OP_PATCH_EMBED, resize_crop_launch(ctx, s, src->resize, n, src->layout, src->rc, out));
+        crops = (struct pixel_src){NULL, out, VIT_PIXELS_HWC, src->norm, NULL, NULL};
+        src = &crops;
+    }
     OP(VIT_OP_PATCH_EMBED, patch_embed_launches(ctx, s, src, n));
     int cls_rows = 0;   /* the last layer ran on the class-token rows only (opt-in, fp32 path on planes) */
     for (int l = 0; l < c->depth; ++l) {
@@ -1087,6 +1188,89 @@ int vit_hip_forward_device_u8(vit_hip_ctx *ctx, const unsigned char *d_images, i
     if (u8_args("vit_hip_forward_device_u8", ctx, d_images, n, layout, norm, 1))
         return 1;
     const struct pixel_src src = {NULL, d_images, layout, norm};
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream);
+}
+
+int vit_resize_crop_geometry(int height, int width, const vit_resize_crop *rc, int crop, int *resized_h, int *resized_w, int *top,
+                             int *left)
+{
+    char msg[200];
+    const char *why = !rc || !resized_h || !resized_w || !top || !left ? "NULL argument"
+                      : crop <= 0 ? "crop must be positive"
+                      : height < 1 || width < 1 || height > RESIZE_MAX_SIDE || width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
+                      : rc->filter != VIT_RESIZE_BILINEAR && rc->filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
+                      : rc->resize_short < crop || (long long)rc->resize_short > 4LL * crop ? "resize_short must be in crop..4 x crop"
+                      : NULL;
+    if (why) {
+        snprintf(msg, sizeof msg, "vit_resize_crop_geometry: %s", why);
+        return vh_set_error(1, msg);
+    }
+    /* torchvision's _compute_resized_output_size: the short side becomes resize_short, the long one
+     * int(resize_short * long / short); CenterCrop: int(round((size - crop) / 2.0)), Python's round (half to even) */
+    const long long rs = rc->resize_short;
+    const int nh = height <= width ? (int)rs : (int)((double)(rs * height) / width);
+    const int nw = height <= width ? (int)((double)(rs * width) / height) : (int)rs;
+    *resized_h = nh;
+    *resized_w = nw;
+    *top = (int)nearbyint((nh - crop) / 2.0);
+    *left = (int)nearbyint((nw - crop) / 2.0);
+    return 0;
+}
+
+/* The resize forms' checks that need no device.  norm_needed: the forwards; device: n <= max_batch; slot_bytes: the host
+ * form's limit on one image's packed bytes (0 = none) */
+static int resize_args(const char *who, const vit_hip_ctx *ctx, const vit_image_u8 *images, int n, int layout, const vit_resize_crop *rc,
+                       const vit_pixel_norm *norm, int norm_needed, const void *out, int out_needed, int device, size_t slot_bytes)
+{
+    char msg[240];
+    const char *why = !ctx || !images || !rc || (norm_needed && !norm) || (out_needed && !out) ? "NULL argument"
+                      : n <= 0 ? "n must be positive"
+                      : device && n > ctx->max_batch ? "n exceeds the context's max_batch"
+                      : layout != VIT_PIXELS_HWC && layout != VIT_PIXELS_CHW ? "layout must be VIT_PIXELS_HWC or VIT_PIXELS_CHW"
+                      : rc->filter != VIT_RESIZE_BILINEAR && rc->filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
+                      : ctx->cfg.in_chans > 4 ? "8-bit images take at most 4 channels"
+                      : rc->resize_short < ctx->cfg.img_size || rc->resize_short > 4 * ctx->cfg.img_size ? "resize_short must be in img_size..4 x img_size"
+                      : NULL;
+    int bad = -1;
+    if (!why) {
+        const long C = ctx->cfg.in_chans;
+        for (int i = 0; i < n && !why; ++i) {
+            const vit_image_u8 *im = &images[i];
+            const long row = layout == VIT_PIXELS_HWC ? (long)im->width * C : (long)im->width;
+            why = !im->data ? "NULL image data"
+                  : im->height < 1 || im->width < 1 || im->height > RESIZE_MAX_SIDE || im->width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
+                  : im->row_stride < row ? "row_stride below the row's bytes"
+                  : slot_bytes && (size_t)im->height * im->width * C > slot_bytes ? "image larger than a staging slot"
+                  : NULL;
+            bad = i;
+        }
+    }
+    if (!why)
+        return 0;
+    if (bad >= 0)
+        snprintf(msg, sizeof msg, "%s: image %d: %s", who, bad, why);
+    else
+        snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return vh_set_error(1, msg);
+}
+
+int vit_hip_resize_crop_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n, int layout, const vit_resize_crop *rc,
+                           unsigned char *d_out, vh_stream_t stream)
+{
+    int rc_ = 0;
+    if (resize_args("vit_hip_resize_crop_u8", ctx, d_images, n, layout, rc, NULL, 0, d_out, 1, 1, 0))
+        return 1;
+    if ((rc_ = vh_set_device(ctx->device)) != 0)
+        return rc_;
+    return resize_crop_launch(ctx, stream ? stream : ctx->stream, d_images, n, layout, rc, d_out);
+}
+
+int vit_hip_forward_device_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n, int layout, const vit_resize_crop *rc,
+                                      const vit_pixel_norm *norm, float *d_logits, float *d_probs, vh_stream_t stream)
+{
+    if (resize_args("vit_hip_forward_device_u8_resized", ctx, d_images, n, layout, rc, norm, 1, NULL, 0, 1, 0))
+        return 1;
+    const struct pixel_src src = {NULL, NULL, layout, norm, d_images, rc};
     return forward_device(ctx, &src, n, d_logits, d_probs, stream);
 }
 
@@ -1194,6 +1378,10 @@ struct host_src
     const unsigned char *u8;   /* or 8-bit, contiguous */
     int layout;
     const vit_pixel_norm *norm;
+    const vit_image_u8 *resize;   /* or 8-bit images of any size, packed into the slot without their row padding */
+    const vit_resize_crop *rc;
+    size_t *packed;               /* resize: the chunk's byte offsets in the slot, [max_batch + 1] */
+    vit_image_u8 *staged;         /* resize: the chunk's descriptors, data in the device slot, [max_batch] */
 };
 
 struct gather_job
@@ -1205,15 +1393,53 @@ struct gather_job
     size_t bytes;       /* per image */
 };
 
+/* one image of a resize chunk, its rows packed: HWC rows of width x C bytes, or C planes of height rows of width bytes */
+static void pack_image(char *dst, const vit_image_u8 *im, int layout, int chans)
+{
+    const size_t row = (size_t)im->width * (layout == VIT_PIXELS_HWC ? chans : 1);
+    const int rows = layout == VIT_PIXELS_HWC ? im->height : im->height * chans;
+    if ((size_t)im->row_stride == row) {
+        memcpy(dst, im->data, row * rows);
+        return;
+    }
+    for (int y = 0; y < rows; ++y)   /* CHW: plane p's row y is row p * height + y at the same stride */
+        memcpy(dst + (size_t)y * row, im->data + (size_t)y * im->row_stride, row);
+}
+
 static void *gather_worker(void *arg)
 {
     const struct gather_job *j = (const struct gather_job *)arg;
     for (int i = j->first; i < j->first + j->count; ++i) {
+        if (j->src->resize) {
+            pack_image(j->dst + j->src->packed[i], &j->src->resize[j->base + i], j->src->layout, (int)j->bytes);
+            continue;
+        }
         const void *from = j->src->images ? (const void *)j->src->images[j->base + i].data
                                           : (const void *)(j->src->u8 + (size_t)(j->base + i) * j->bytes);
         memcpy(j->dst + (size_t)i * j->bytes, from, j->bytes);
     }
     return NULL;
+}
+
+/* A resize chunk from image `first`: at most max_batch images whose packed bytes fit one staging slot (resize_args has
+ * refused any image larger than a slot); fills src->packed and src->staged (data pointers into d_slot) */
+static int resize_chunk(const vit_hip_ctx *ctx, const struct host_src *src, int first, int n, size_t slot_bytes, const unsigned char *d_slot)
+{
+    const size_t C = (size_t)ctx->cfg.in_chans;
+    size_t off = 0;
+    int m = 0;
+    for (; m < ctx->max_batch && first + m < n; ++m) {
+        const vit_image_u8 *im = &src->resize[first + m];
+        const size_t bytes = (size_t)im->height * im->width * C;
+        if (off + bytes > slot_bytes)
+            break;
+        src->packed[m] = off;
+        src->staged[m] = (vit_image_u8){d_slot + off, im->height, im->width,
+                                        (long)im->width * (src->layout == VIT_PIXELS_HWC ? (long)C : 1)};
+        off += bytes;
+    }
+    src->packed[m] = off;
+    return m;
 }
 
 static void gather_images(void *dst, const struct host_src *src, int base, int m, size_t bytes)
@@ -1253,21 +1479,31 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->u8 ? 1 : sizeof(float));
     const size_t NC = (size_t)c->num_classes;
+    const size_t slot_bytes = (size_t)ctx->max_batch * c->in_chans * c->img_size * c->img_size * sizeof(float);
 
     int prev_first = 0, prev_m = 0, k = 0;
-    for (int first = 0; first < n; first += ctx->max_batch, ++k) {
-        const int m = (n - first < ctx->max_batch) ? n - first : ctx->max_batch;
+    for (int first = 0, m = 0; first < n; first += m, ++k) {
         const int s = k & 1;
+        if (src->resize)   /* cut by count and by bytes; gather_images packs with per-image offsets (bytes carries C) */
+            m = resize_chunk(ctx, src, first, n, slot_bytes, (const unsigned char *)ctx->d_images[s]);
+        else
+            m = (n - first < ctx->max_batch) ? n - first : ctx->max_batch;
+        if (m <= 0) {
+            rc = vh_set_error(1, "forward: an image does not fit a staging slot");
+            goto fail;
+        }
+        const size_t up = src->resize ? src->packed[m] : (size_t)m * bytes;
         /* slot s was last used by chunk k-2, whose outputs were waited for below */
-        gather_images(ctx->h_images[s], src, first, m, bytes);
+        gather_images(ctx->h_images[s], src, first, m, src->resize ? (size_t)c->in_chans : bytes);
         if (k >= 2)
             TRY(vh_stream_wait_event(ctx->copy_stream, ctx->comp_done[s]));
-        TRY(vh_h2d(ctx->d_images[s], ctx->h_images[s], (size_t)m * bytes, ctx->copy_stream));
+        TRY(vh_h2d(ctx->d_images[s], ctx->h_images[s], up, ctx->copy_stream));
         TRY(vh_event_record(ctx->up_done[s], ctx->copy_stream));
 
         TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
-        const struct pixel_src dev = {src->u8 ? NULL : ctx->d_images[s], src->u8 ? (const unsigned char *)ctx->d_images[s] : NULL,
-                                      src->layout, src->norm};
+        const struct pixel_src dev = {src->u8 || src->resize ? NULL : ctx->d_images[s],
+                                      src->u8 ? (const unsigned char *)ctx->d_images[s] : NULL, src->layout, src->norm,
+                                      src->resize ? src->staged : NULL, src->rc};
         TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         if (logits)
@@ -1312,6 +1548,26 @@ int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int
         return 1;
     const struct host_src src = {NULL, images, layout, norm};
     return forward_pipelined(ctx, &src, n, logits, probs);
+}
+
+int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int n, int layout, const vit_resize_crop *rc,
+                               const vit_pixel_norm *norm, float *logits, float **probs)
+{
+    const size_t slot_bytes = ctx ? (size_t)ctx->max_batch * ctx->cfg.in_chans * ctx->cfg.img_size * ctx->cfg.img_size * sizeof(float) : 0;
+    if (resize_args("vit_hip_forward_u8_resized", ctx, images, n, layout, rc, norm, 1, NULL, 0, 0, slot_bytes))
+        return 1;
+    size_t *packed = malloc(((size_t)ctx->max_batch + 1) * sizeof(*packed));
+    vit_image_u8 *staged = malloc((size_t)ctx->max_batch * sizeof(*staged));
+    int rc_ = 1;
+    if (packed && staged) {
+        const struct host_src src = {NULL, NULL, layout, norm, images, rc, packed, staged};
+        rc_ = forward_pipelined(ctx, &src, n, logits, probs);
+    } else {
+        vh_set_error(1, "vit_hip_forward_u8_resized: out of host memory");
+    }
+    free(packed);
+    free(staged);
+    return rc_;
 }
 
 /* ---- several GPUs behind one call -------------------------------------------------

@@ -59,6 +59,8 @@ EXPORTS = [
     "vit_write_result_file", "vit_compare_rows",
     "vh_launch_patch_embed_planes_u8", "vh_launch_expand_u8", "vit_pixel_norm_from_mean_std", "vit_hip_forward_device_u8",
     "vit_hip_forward_u8",
+    "vh_launch_resize_crop_u8", "vit_resize_crop_geometry", "vit_hip_resize_crop_u8", "vit_hip_forward_device_u8_resized",
+    "vit_hip_forward_u8_resized",
 ]
 
 
@@ -79,6 +81,63 @@ class PixelNorm(C.Structure):
 
 
 PIXEL_LAYOUTS = {"hwc": 0, "chw": 1}
+
+
+class ImageU8(C.Structure):
+    """`vit_image_u8` (include/ViT_opencl.h): one 8-bit image of any size; data is a host or device pointer."""
+
+    _fields_ = [("data", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("row_stride", C.c_long)]
+
+
+class ResizeCrop(C.Structure):
+    """`vit_resize_crop` (include/ViT_opencl.h): shorter side resized to resize_short, then the centre crop."""
+
+    _fields_ = [("resize_short", C.c_int), ("filter", C.c_int)]
+
+
+RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}
+
+
+def resize_crop(resize_short: int, filter: str = "bilinear") -> ResizeCrop:
+    return ResizeCrop(int(resize_short), RESIZE_FILTERS[filter])
+
+
+def resize_crop_geometry(height: int, width: int, resize_short: int, crop: int, filter: str = "bilinear"):
+    """vit_resize_crop_geometry -> (resized_h, resized_w, top, left)"""
+    out = [C.c_int() for _ in range(4)]
+    rc = resize_crop(resize_short, filter)
+    check(lib().vit_resize_crop_geometry(height, width, C.byref(rc), crop, *[C.byref(o) for o in out]), "vit_resize_crop_geometry")
+    return tuple(o.value for o in out)
+
+
+def image_descs(images) -> C.Array:
+    """An array of vit_image_u8 from (data pointer, height, width, row_stride) tuples (device forms)."""
+    arr = (ImageU8 * len(images))()
+    for i, (ptr, h, w, stride) in enumerate(images):
+        arr[i] = ImageU8(int(ptr.value if isinstance(ptr, C.c_void_p) else ptr), h, w, stride)
+    return arr
+
+
+def host_image_descs(images, layout: str):
+    """vit_image_u8 for uint8 host arrays, [h][w][C] (hwc) or [C][h][w] (chw); padded rows are passed as they are, other
+    strides are made contiguous.  Returns (array, arrays kept alive)."""
+    keep = []
+    arr = (ImageU8 * len(images))()
+    for i, a in enumerate(images):
+        a = np.asarray(a)
+        if a.dtype != np.uint8 or a.ndim != 3:
+            raise ValueError(f"image {i}: need a 3-d uint8 array, got {a.dtype} {a.shape}")
+        if layout == "hwc":
+            h, w, ch = a.shape
+            ok = a.strides[2] == 1 and a.strides[1] == ch and a.strides[0] >= w * ch
+        else:
+            ch, h, w = a.shape
+            ok = a.strides[2] == 1 and a.strides[1] >= w and a.strides[0] == h * a.strides[1]
+        if not ok:
+            a = np.ascontiguousarray(a)
+        keep.append(a)
+        arr[i] = ImageU8(a.ctypes.data, h, w, a.strides[0] if layout == "hwc" else a.strides[1])
+    return arr, keep
 
 
 class CompareReport(C.Structure):
@@ -284,6 +343,12 @@ def lib() -> C.CDLL:
     L.vit_pixel_norm_from_mean_std.argtypes = [C.POINTER(PixelNorm), f32p, f32p, i]
     L.vit_hip_forward_device_u8.argtypes = [voidp, voidp, i, i, C.POINTER(PixelNorm), voidp, voidp, voidp]
     L.vit_hip_forward_u8.argtypes = [voidp, u8p, i, i, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
+    imgp, rcp, ip = C.POINTER(ImageU8), C.POINTER(ResizeCrop), C.POINTER(C.c_int)
+    L.vh_launch_resize_crop_u8.argtypes = [voidp, voidp, i, i, i, i, i, voidp, sz, voidp]
+    L.vit_resize_crop_geometry.argtypes = [i, i, rcp, i, ip, ip, ip, ip]
+    L.vit_hip_resize_crop_u8.argtypes = [voidp, imgp, i, i, rcp, voidp, voidp]
+    L.vit_hip_forward_device_u8_resized.argtypes = [voidp, imgp, i, i, rcp, C.POINTER(PixelNorm), voidp, voidp, voidp]
+    L.vit_hip_forward_u8_resized.argtypes = [voidp, imgp, i, i, rcp, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
     _lib = L
     return L
 
@@ -465,6 +530,37 @@ class ViTHip:
         """Device-resident 8-bit path (d_images: a uint8 DeviceBuffer's .ptr, or any device pointer)."""
         check(self.L.vit_hip_forward_device_u8(self.ctx, d_images, n, PIXEL_LAYOUTS[layout], C.byref(norm), d_logits, d_probs,
                                                stream), "vit_hip_forward_device_u8")
+
+    def forward_u8_resized(self, images, resize_short: int, filter: str = "bilinear", mean=None, std=None, layout: str = "hwc",
+                           logits: bool = True, probs: bool = True):
+        """Host 8-bit images of any size (a list of [h][w][C] or [C][h][w] uint8 arrays), resized (shorter side to
+        resize_short) and centre-cropped on the GPU exactly as Pillow + torchvision's CenterCrop, normalised with
+        pixel_norm(mean, std) (or a PixelNorm as `mean`) -> (logits, probs) as forward_u8."""
+        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
+        descs, keep = host_image_descs(images, layout)
+        n, nc = len(images), self.cfg.num_classes
+        out_l = np.empty((n, nc), dtype=np.float32) if logits else None
+        out_p = np.empty((n, nc), dtype=np.float32) if probs else None
+        rows = (f32p * n)(*[fptr(out_p[i]) for i in range(n)]) if probs else None
+        rc = resize_crop(resize_short, filter)
+        check(self.L.vit_hip_forward_u8_resized(self.ctx, descs, n, PIXEL_LAYOUTS[layout], C.byref(rc), C.byref(norm),
+                                                fptr(out_l) if logits else None, rows), "vit_hip_forward_u8_resized")
+        del keep
+        return out_l, out_p
+
+    def forward_device_u8_resized(self, d_images, resize_short: int, norm: PixelNorm, filter: str = "bilinear",
+                                  layout: str = "hwc", d_logits=None, d_probs=None, stream=None):
+        """Device-resident images of any size: d_images is a list of (device pointer, height, width, row_stride)."""
+        rc = resize_crop(resize_short, filter)
+        check(self.L.vit_hip_forward_device_u8_resized(self.ctx, image_descs(d_images), len(d_images), PIXEL_LAYOUTS[layout],
+                                                       C.byref(rc), C.byref(norm), d_logits, d_probs, stream),
+              "vit_hip_forward_device_u8_resized")
+
+    def resize_crop_u8(self, d_images, resize_short: int, d_out, filter: str = "bilinear", layout: str = "hwc", stream=None):
+        """The crops alone, [n][img][img][C] bytes into the device buffer d_out."""
+        rc = resize_crop(resize_short, filter)
+        check(self.L.vit_hip_resize_crop_u8(self.ctx, image_descs(d_images), len(d_images), PIXEL_LAYOUTS[layout], C.byref(rc),
+                                            d_out, stream), "vit_hip_resize_crop_u8")
 
     def forward_device(self, d_images, n: int, d_logits=None, d_probs=None, stream=None):
         """Device-resident path; pointers are ints / c_void_p / DeviceBuffer.ptr."""
