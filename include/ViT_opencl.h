@@ -243,7 +243,60 @@ const float *vit_hip_weight(const vit_hip_ctx *ctx, int idx);
  * -1 for a NULL context. */
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on);
 
-/* Copy the residual stream left by the last forward ([n*tokens][embed]) to the host. */
+/* ---- feature outputs: class, pooled and patch-token embeddings (the model as a backbone) ----
+ * A feature request is ARMED on a context.  While armed, every forward through the context also writes the requested
+ * embeddings, read from the fp32 residual stream behind the tapped encoder layers by one memory-bound kernel
+ * (csrc/features.hip) in every precision mode; logits and probabilities are bit-identical to an un-armed forward, and an
+ * un-armed context launches exactly what it launched before.
+ *   taps          encoder layers whose OUTPUT is read: 0-based, or negative from the end (-1 = the last layer); after
+ *                 resolution strictly ascending, each in [-depth, depth)
+ *   final_norm    1: the model's final LayerNorm (tensors 4 + 12 depth and + 1, cfg.eps) is applied to every tapped row,
+ *                 bit-identical to vh_launch_layer_norm on that row; 0: the rows of the residual stream as they are
+ *   l2_normalize  1: every class and pooled vector is scaled to unit L2 norm, per tap, before the taps are concatenated
+ *                 (a zero vector stays zero)
+ *   dtype         VIT_FEATURE_BF16 = the fp32 result rounded to nearest even; nothing else differs
+ * Layouts are image-major: cls and pooled are [n][n_taps][E] (per image the taps concatenated in ascending layer order:
+ * what a linear probe consumes); tokens is [n][n_taps][T-1][E] (VIT_TOKENS_NLC) or [n][n_taps][E][g][g] (VIT_TOKENS_NCHW,
+ * g = img / patch).  The class token is never part of tokens.  pooled = mean over the T-1 patch rows of the values
+ * tokens holds BEFORE any narrowing to bf16 (normalise, then pool, when final_norm is set).  Outputs depend on the image
+ * only: bit-identical wherever it sits in the batch and whatever n is (fixed-order sums, no floating-point atomics).
+ * Device form (vit_hip_set_features): device buffers, 16-byte aligned, for up to max_batch images; written asynchronously
+ * on the forward's stream like the logits, by vit_hip_forward_device, _device_u8 and _device_u8_resized.  Host form
+ * (vit_hip_set_features_host): host buffers for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized calls (each
+ * call writes from image 0), complete on return; cls and pooled only -- tokens is refused (308 MB per 512-image chunk
+ * through pinned staging).  The host form's staging is allocated when it is armed, not per call.
+ * spec == NULL disarms.  Arming one form disarms the other; a device-form forward while the host form is armed (and the
+ * reverse) is refused with code 1 and a message, no launch.  Code 1 with a message also for: NULL ctx, n_taps not in
+ * 1..4, a tap outside [-depth, depth), taps not ascending and distinct, an unknown dtype or token_layout, all three
+ * buffers NULL, a misaligned device buffer, T < 2 with pooled or tokens asked for.  A refused call leaves the previous
+ * request armed.
+ * vit_hip_set_last_layer_cls_only: a forward whose armed request needs patch rows of the last layer (pooled or tokens
+ * with the last layer among the taps) runs the last layer on all rows; one that needs only cls there uses the compacted
+ * class-token rows.  Logits are bit-identical either way.
+ * vit_hip_multi: a context from vit_hip_multi_ctx may be armed for the device forms like any other;
+ * vit_hip_forward_multi and vit_hip_forward_device_multi neither write features nor refuse. */
+enum { VIT_FEATURE_F32 = 0, VIT_FEATURE_BF16 = 1 };
+enum { VIT_TOKENS_NLC = 0, VIT_TOKENS_NCHW = 1 };
+typedef struct vit_feature_spec
+{
+    int n_taps;        /* 1..4 */
+    int taps[4];
+    int final_norm;
+    int l2_normalize;
+    int dtype;         /* VIT_FEATURE_*: element type of every feature output */
+    int token_layout;  /* VIT_TOKENS_* */
+} vit_feature_spec;
+typedef struct vit_feature_buffers { void *cls, *pooled, *tokens; } vit_feature_buffers;   /* each may be NULL, not all */
+/* host only, no device: validates spec against cfg; ELEMENTS PER IMAGE of each output (each pointer may be NULL;
+ * pooled and tokens are 0 when T < 2); 0, or 1 with a message */
+int vit_feature_sizes(const vit_config *cfg, const vit_feature_spec *spec, size_t *cls_elems, size_t *pooled_elems,
+                      size_t *tokens_elems);
+int vit_hip_set_features(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *d_bufs);
+int vit_hip_set_features_host(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *h_bufs);
+
+/* Debug hook: copy the residual stream left by the last forward ([n*tokens][embed], un-normalised; rows other than the
+ * class tokens are stale under vit_hip_set_last_layer_cls_only) to the host.  The supported interface to the encoder's
+ * output is vit_hip_set_features above. */
 int vit_hip_read_tokens(vit_hip_ctx *ctx, int n, float *host_out);
 
 /* Per-operator timing with HIP events recorded on the launch stream (the capability

@@ -383,6 +383,24 @@ typedef struct vh_resize_desc
 int vh_launch_resize_crop_u8(vh_stream_t s, const vh_resize_desc *desc, int n, int chans, int layout, int filter, int crop,
                              void *coef, size_t coef_bytes, unsigned char *out);
 
+/* Feature readout behind an encoder layer (csrc/features.hip; the kernel under vit_hip_set_features, include/ViT_opencl.h):
+ * from the fp32 residual stream x [n_images * tokens][embed_dim], tap `tap_index` of `n_taps` into
+ *   cls    [n_images][n_taps][embed_dim]            the class-token rows: row i * tokens of x, or row i of cls_rows at
+ *                                                    cls_row_stride floats when cls_rows != NULL (compacted class rows)
+ *   pooled [n_images][n_taps][embed_dim]            mean of the tokens - 1 patch rows, as tokens holds them before narrowing
+ *   tokens [n_images][n_taps][tokens - 1][embed_dim] (token_layout 0) or [n_images][n_taps][embed_dim][tokens - 1] (1)
+ * each may be NULL (not all).  final_norm: every row read goes through LayerNorm(gamma, beta, eps) first, bit-identical
+ * to vh_launch_layer_norm on that row; final_norm 0 hands the rows through unchanged.  l2_normalize: cls and pooled are
+ * scaled to unit L2 norm (a zero vector stays zero).  dtype 0 fp32, 1 bf16 (the fp32 result rounded to nearest even).
+ * x is read once (only the n class rows when cls alone is asked for); pooled is summed in a fixed order that depends on
+ * `tokens` alone (no atomics) through `scratch` (vh_feature_readout_scratch bytes).  embed_dim % 4 == 0, <= 2048;
+ * every pointer 16-byte aligned. */
+size_t vh_feature_readout_scratch(int n_images, int tokens, int embed_dim);
+int vh_launch_feature_readout(vh_stream_t s, const float *x, const float *cls_rows, long cls_row_stride, const float *gamma,
+                              const float *beta, double eps, int final_norm, int l2_normalize, int dtype, int token_layout,
+                              int n_images, int tokens, int embed_dim, int tap_index, int n_taps, void *cls, void *pooled,
+                              void *tokens_out, void *scratch, size_t scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,8 @@ enum { MAX_DEPTH = 256, MAX_TENSORS = 4 + 12 * MAX_DEPTH + 4 };
 /* resize + crop: descriptor slots in flight, and the largest source side */
 enum { DESC_RING = 8, RESIZE_MAX_SIDE = 16384 };
 
+enum { FEAT_NONE, FEAT_DEVICE, FEAT_HOST };
+
 struct vit_hip_ctx
 {
     vit_config cfg;
@@ -119,6 +121,20 @@ struct vit_hip_ctx
     vh_event_t desc_done[DESC_RING];
     int desc_live[DESC_RING];
     int desc_next;
+
+    /* feature request (vit_hip_set_features / _host): what is armed, the taps resolved to layer indices, and where the
+     * embeddings go.  The host form writes into device buffers of its own and carries them through two pinned slots. */
+    struct feature_req
+    {
+        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
+        vit_feature_spec spec;
+        int layer[4];                /* spec.taps resolved, ascending */
+        vit_feature_buffers out;     /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: d_stage */
+        vit_feature_buffers host;    /* FEAT_HOST: the caller's host buffers (cls, pooled) */
+        size_t per_image[2];         /* FEAT_HOST: bytes per image of cls, pooled */
+        void *d_stage[2];            /* FEAT_HOST: device cls, pooled for max_batch images */
+        void *h_stage[2][2];         /* FEAT_HOST: pinned [slot][cls, pooled] */
+    } feat;
 
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
@@ -187,6 +203,18 @@ const float *vit_hip_weight(const vit_hip_ctx *ctx, int idx)
     return (idx >= 0 && idx < ctx->n_tensors) ? ctx->w[idx] : NULL;
 }
 
+static void feature_stage_release(vit_hip_ctx *ctx)
+{
+    for (int k = 0; k < 2; ++k) {
+        if (ctx->feat.d_stage[k]) vh_free(ctx->feat.d_stage[k]);
+        ctx->feat.d_stage[k] = NULL;
+        for (int slot = 0; slot < 2; ++slot) {
+            if (ctx->feat.h_stage[slot][k]) vh_host_free(ctx->feat.h_stage[slot][k]);
+            ctx->feat.h_stage[slot][k] = NULL;
+        }
+    }
+}
+
 void vit_hip_destroy(vit_hip_ctx *ctx)
 {
     if (!ctx)
@@ -197,6 +225,7 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
         vh_stream_sync(ctx->stream);
     }
     prof_release(ctx);
+    feature_stage_release(ctx);
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
@@ -1095,9 +1124,29 @@ static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct pi
 }
 
 /* Everything after the argument checks of vit_hip_forward_device and vit_hip_forward_device_u8 */
-static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream)
+/* The readout behind layer l for tap k of the armed request: one pass over the residual stream (the class rows alone when
+ * only cls is asked for), timed with the LayerNorms.  Partial sums of pooled go through the MLP buffer, idle behind fc2.
+ * cls_rows: the last layer ran class-only, its class rows lie compacted at the start of Q|K|V. */
+static int feature_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct feature_req *fr, int k, int n, int cls_rows)
 {
     int rc = 0;
+    const vit_config *c = &ctx->cfg;
+    float **tw = ctx->w + 4 + 12 * c->depth;
+    OP(VIT_OP_LAYER_NORM, vh_launch_feature_readout(s, ctx->x, cls_rows ? (const float *)ctx->qkv : NULL, c->embed_dim, tw[0], tw[1],
+                                                    c->eps, fr->spec.final_norm, fr->spec.l2_normalize, fr->spec.dtype,
+                                                    fr->spec.token_layout, n, ctx->tokens, c->embed_dim, k, fr->spec.n_taps,
+                                                    fr->out.cls, fr->out.pooled, fr->out.tokens, ctx->hid, ctx->ws_bytes));
+    return 0;
+fail:
+    return rc;
+}
+
+/* Everything after the argument checks of the forwards.  fr: the armed feature request to serve, or NULL. */
+static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
+                          const struct feature_req *fr)
+{
+    int rc = 0;
+    const int cls_only_saved = ctx->cls_only_last;
     TRY(vh_set_device(ctx->device));   /* the current device is per host thread */
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, T = ctx->tokens, NC = c->num_classes;
@@ -1112,7 +1161,10 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
     }
     OP(VIT_OP_PATCH_EMBED, patch_embed_launches(ctx, s, src, n));
     int cls_rows = 0;   /* the last layer ran on the class-token rows only (opt-in, fp32 path on planes) */
-    for (int l = 0; l < c->depth; ++l) {
+    /* a request for patch rows of the last layer makes this forward run the last layer on all rows */
+    if (fr && fr->layer[fr->spec.n_taps - 1] == c->depth - 1 && (fr->out.pooled || fr->out.tokens))
+        ctx->cls_only_last = 0;
+    for (int l = 0, k = 0; l < c->depth; ++l) {
         switch (ctx->precision) {
         case VIT_PRECISION_FP8_GEMM: TRY(layer_fp8(ctx, s, n, l)); break;
         case VIT_PRECISION_BF16_GEMM: TRY(layer_bf16(ctx, s, n, l)); break;
@@ -1123,7 +1175,10 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
             else
                 TRY(layer_f32_rows(ctx, s, n, l));
         }
+        if (fr && k < fr->spec.n_taps && fr->layer[k] == l)
+            TRY(feature_tap(ctx, s, fr, k++, n, cls_rows));
     }
+    ctx->cls_only_last = cls_only_saved;
 
     /* final LayerNorm on the class-token rows -- row i * stride of the residual stream, or compacted at the start of the
      * Q|K|V buffer -- classifier, softmax (ViT_seq.c:506-515) */
@@ -1137,7 +1192,30 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
         OP(VIT_OP_SOFTMAX, vh_launch_softmax(s, logits, d_probs, n, NC));
     return 0;
 fail:
+    ctx->cls_only_last = cls_only_saved;
     return rc;
+}
+
+/* The armed request a device-form forward serves; *refused when the host form is armed */
+static const struct feature_req *device_features(vit_hip_ctx *ctx, const char *who, int *refused)
+{
+    *refused = 0;
+    if (ctx->feat.form == FEAT_HOST) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s: the context is armed for host feature buffers (vit_hip_set_features_host); disarm it or use the host forms", who);
+        vh_set_error(1, msg);
+        *refused = 1;
+    }
+    return ctx->feat.form == FEAT_DEVICE ? &ctx->feat : NULL;
+}
+
+/* vit_hip_forward_device with no feature output whatever is armed (vit_gather_rccl.c) */
+int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits, float *d_probs, vh_stream_t stream)
+{
+    if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
+        return 1;
+    const struct pixel_src src = {d_images, NULL, 0, NULL};
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL);
 }
 
 int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
@@ -1145,8 +1223,12 @@ int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float
 {
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
+    int refused;
+    const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device", &refused);
+    if (refused)
+        return 1;
     const struct pixel_src src = {d_images, NULL, 0, NULL};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr);
 }
 
 int vit_pixel_norm_from_mean_std(vit_pixel_norm *out, const float *mean, const float *std, int chans)
@@ -1187,8 +1269,12 @@ int vit_hip_forward_device_u8(vit_hip_ctx *ctx, const unsigned char *d_images, i
 {
     if (u8_args("vit_hip_forward_device_u8", ctx, d_images, n, layout, norm, 1))
         return 1;
+    int refused;
+    const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device_u8", &refused);
+    if (refused)
+        return 1;
     const struct pixel_src src = {NULL, d_images, layout, norm};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr);
 }
 
 int vit_resize_crop_geometry(int height, int width, const vit_resize_crop *rc, int crop, int *resized_h, int *resized_w, int *top,
@@ -1270,8 +1356,120 @@ int vit_hip_forward_device_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *d_im
 {
     if (resize_args("vit_hip_forward_device_u8_resized", ctx, d_images, n, layout, rc, norm, 1, NULL, 0, 1, 0))
         return 1;
+    int refused;
+    const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device_u8_resized", &refused);
+    if (refused)
+        return 1;
     const struct pixel_src src = {NULL, NULL, layout, norm, d_images, rc};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr);
+}
+
+/* spec against cfg; the taps resolved to ascending layer indices */
+static int feature_spec_check(const char *who, const vit_config *cfg, const vit_feature_spec *spec, int layer[4])
+{
+    char msg[200];
+    const char *why = !cfg || !spec ? "NULL argument"
+                      : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
+                      : spec->n_taps < 1 || spec->n_taps > 4 ? "n_taps must be in 1..4"
+                      : spec->dtype != VIT_FEATURE_F32 && spec->dtype != VIT_FEATURE_BF16 ? "dtype must be VIT_FEATURE_F32 or VIT_FEATURE_BF16"
+                      : spec->token_layout != VIT_TOKENS_NLC && spec->token_layout != VIT_TOKENS_NCHW ? "token_layout must be VIT_TOKENS_NLC or VIT_TOKENS_NCHW"
+                      : NULL;
+    for (int k = 0; !why && k < spec->n_taps; ++k) {
+        const int t = spec->taps[k];
+        if (t < -cfg->depth || t >= cfg->depth)
+            why = "a tap lies outside [-depth, depth)";
+        else if (k > 0 && (t < 0 ? t + cfg->depth : t) <= layer[k - 1])
+            why = "taps must be strictly ascending once resolved";
+        else
+            layer[k] = t < 0 ? t + cfg->depth : t;
+    }
+    if (!why)
+        return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return vh_set_error(1, msg);
+}
+
+int vit_feature_sizes(const vit_config *cfg, const vit_feature_spec *spec, size_t *cls_elems, size_t *pooled_elems, size_t *tokens_elems)
+{
+    int layer[4];
+    if (feature_spec_check("vit_feature_sizes", cfg, spec, layer))
+        return 1;
+    const size_t per = (size_t)spec->n_taps * (size_t)cfg->embed_dim, patches = (size_t)vit_config_tokens(cfg) - 1;
+    if (cls_elems)
+        *cls_elems = per;
+    if (pooled_elems)
+        *pooled_elems = patches ? per : 0;
+    if (tokens_elems)
+        *tokens_elems = per * patches;
+    return 0;
+}
+
+/* Both forms of arming; host: bufs are host memory, staged through device buffers and pinned slots made here */
+static int set_features(const char *who, vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *bufs, int host)
+{
+    int rc = 0;
+    char msg[200];
+    if (!ctx) {
+        snprintf(msg, sizeof msg, "%s: NULL context", who);
+        return vh_set_error(1, msg);
+    }
+    struct feature_req fr;
+    memset(&fr, 0, sizeof fr);
+    if (spec) {
+        if (feature_spec_check(who, &ctx->cfg, spec, fr.layer))
+            return 1;
+        const char *why = !bufs || (!bufs->cls && !bufs->pooled && !bufs->tokens) ? "no output buffer"
+                          : host && bufs->tokens ? "the host form takes cls and pooled only (tokens: use the device form)"
+                          : ctx->tokens < 2 && (bufs->pooled || bufs->tokens) ? "pooled and tokens need at least one patch token"
+                          : !host && (((uintptr_t)bufs->cls | (uintptr_t)bufs->pooled | (uintptr_t)bufs->tokens) & 15) ? "device buffers must be 16-byte aligned"
+                          : NULL;
+        if (why) {
+            snprintf(msg, sizeof msg, "%s: %s", who, why);
+            return vh_set_error(1, msg);
+        }
+        fr.form = host ? FEAT_HOST : FEAT_DEVICE;
+        fr.spec = *spec;
+        fr.out = *bufs;
+    }
+    TRY(vh_set_device(ctx->device));
+    /* the staging of an earlier host request may still be read by its last forward's copies */
+    TRY(vh_stream_sync(ctx->stream));
+    if (fr.form == FEAT_HOST) {
+        const size_t per = (size_t)spec->n_taps * ctx->cfg.embed_dim * (spec->dtype == VIT_FEATURE_BF16 ? 2 : 4);
+        const void *want[2] = {bufs->cls, bufs->pooled};
+        fr.host = *bufs;
+        for (int k = 0; k < 2 && rc == 0; ++k) {
+            if (!want[k])
+                continue;
+            fr.per_image[k] = per;
+            rc = vh_malloc(&fr.d_stage[k], (size_t)ctx->max_batch * per);
+            for (int slot = 0; slot < 2 && rc == 0; ++slot)
+                rc = vh_host_alloc(&fr.h_stage[slot][k], (size_t)ctx->max_batch * per);
+        }
+        fr.out = (vit_feature_buffers){fr.d_stage[0], fr.d_stage[1], NULL};
+        if (rc != 0) {   /* the previous request stays armed */
+            struct feature_req keep = ctx->feat;
+            ctx->feat = fr;
+            feature_stage_release(ctx);
+            ctx->feat = keep;
+            return rc;
+        }
+    }
+    feature_stage_release(ctx);
+    ctx->feat = fr;
+    return 0;
+fail:
+    return rc;
+}
+
+int vit_hip_set_features(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *d_bufs)
+{
+    return set_features("vit_hip_set_features", ctx, spec, d_bufs, 0);
+}
+
+int vit_hip_set_features_host(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *h_bufs)
+{
+    return set_features("vit_hip_set_features_host", ctx, spec, h_bufs, 1);
 }
 
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
@@ -1283,7 +1481,8 @@ int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
     return before;
 }
 
-/* Debug/test hook: copy the residual stream ([n*tokens][E]) to the host. */
+/* Debug/test hook: copy the residual stream ([n*tokens][E], un-normalised) to the host.  The supported interface to the
+ * encoder's output is vit_hip_set_features. */
 int vit_hip_read_tokens(vit_hip_ctx *ctx, int n, float *host_out)
 {
     int rc = vh_set_device(ctx->device);
@@ -1304,7 +1503,7 @@ int vit_hip_profile_enable(vit_hip_ctx *ctx, int max_forwards)
     prof_release(ctx);
     if (max_forwards <= 0)
         return 0;
-    const int per_forward = 1 + 7 * ctx->cfg.depth + 3;
+    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4;   /* + the readouts of an armed feature request */
     ctx->prof_cap = per_forward * max_forwards;
     ctx->prof_ev = (vh_event_t *)calloc((size_t)2 * ctx->prof_cap, sizeof(vh_event_t));
     ctx->prof_class = (int *)calloc((size_t)ctx->prof_cap, sizeof(int));
@@ -1359,9 +1558,14 @@ fail:
  *   compute  : forward chunk k, D2H its logits/probs  (after the H2D)
  * so PCIe and the gather of the separately malloc'd images (Network.c:90) hide under
  * the previous chunk's kernels. */
-static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, float *logits, float **probs)
+static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, float *logits, float **probs, const struct feature_req *fr)
 {
     const size_t NC = (size_t)ctx->cfg.num_classes;
+    for (int k = 0; fr && k < 2; ++k) {   /* cls, pooled of the armed host request */
+        char *to = (char *)(k == 0 ? fr->host.cls : fr->host.pooled);
+        if (to)
+            memcpy(to + (size_t)first * fr->per_image[k], fr->h_stage[slot][k], (size_t)m * fr->per_image[k]);
+    }
     if (logits)
         memcpy(logits + (size_t)first * NC, ctx->h_logits[slot], (size_t)m * NC * sizeof(float));
     if (probs)
@@ -1472,9 +1676,12 @@ static void gather_images(void *dst, const struct host_src *src, int base, int m
 }
 
 /* The pipeline of vit_hip_forward and vit_hip_forward_u8: a u8 chunk fills a quarter of a staging slot */
-static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n, float *logits, float **probs)
+static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n, float *logits, float **probs, int features)
 {
     int rc = 0;
+    if (features && ctx->feat.form == FEAT_DEVICE)
+        return vh_set_error(1, "forward: the context is armed for device feature buffers (vit_hip_set_features); disarm it or use the device forms");
+    const struct feature_req *fr = features && ctx->feat.form == FEAT_HOST ? &ctx->feat : NULL;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->u8 ? 1 : sizeof(float));
@@ -1504,23 +1711,26 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
         const struct pixel_src dev = {src->u8 || src->resize ? NULL : ctx->d_images[s],
                                       src->u8 ? (const unsigned char *)ctx->d_images[s] : NULL, src->layout, src->norm,
                                       src->resize ? src->staged : NULL, src->rc};
-        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream));
+        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         if (logits)
             TRY(vh_d2h(ctx->h_logits[s], ctx->d_logits, (size_t)m * NC * sizeof(float), ctx->stream));
         if (probs)
             TRY(vh_d2h(ctx->h_probs[s], ctx->d_probs, (size_t)m * NC * sizeof(float), ctx->stream));
+        for (int f = 0; fr && f < 2; ++f)
+            if (fr->d_stage[f])
+                TRY(vh_d2h(fr->h_stage[s][f], fr->d_stage[f], (size_t)m * fr->per_image[f], ctx->stream));
         TRY(vh_event_record(ctx->out_done[s], ctx->stream));
 
         if (k >= 1) { /* finish chunk k-1 while chunk k runs */
             TRY(vh_event_sync(ctx->out_done[s ^ 1]));
-            scatter_outputs(ctx, s ^ 1, prev_first, prev_m, logits, probs);
+            scatter_outputs(ctx, s ^ 1, prev_first, prev_m, logits, probs, fr);
         }
         prev_first = first;
         prev_m = m;
     }
     TRY(vh_event_sync(ctx->out_done[(k - 1) & 1]));
-    scatter_outputs(ctx, (k - 1) & 1, prev_first, prev_m, logits, probs);
+    scatter_outputs(ctx, (k - 1) & 1, prev_first, prev_m, logits, probs, fr);
     return 0;
 fail:
     vh_stream_sync(ctx->copy_stream);
@@ -1528,7 +1738,7 @@ fail:
     return rc;
 }
 
-int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs)
+static int forward_host_images(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs, int features)
 {
     if (!ctx || !images || n <= 0)
         return 1;
@@ -1538,7 +1748,12 @@ int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *log
             images[i].w != c->img_size)
             return 5;
     const struct host_src src = {images, NULL, 0, NULL};
-    return forward_pipelined(ctx, &src, n, logits, probs);
+    return forward_pipelined(ctx, &src, n, logits, probs, features);
+}
+
+int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs)
+{
+    return forward_host_images(ctx, images, n, logits, probs, 1);
 }
 
 int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int layout,
@@ -1547,7 +1762,7 @@ int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int
     if (u8_args("vit_hip_forward_u8", ctx, images, n, layout, norm, 0))
         return 1;
     const struct host_src src = {NULL, images, layout, norm};
-    return forward_pipelined(ctx, &src, n, logits, probs);
+    return forward_pipelined(ctx, &src, n, logits, probs, 1);
 }
 
 int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int n, int layout, const vit_resize_crop *rc,
@@ -1561,7 +1776,7 @@ int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int
     int rc_ = 1;
     if (packed && staged) {
         const struct host_src src = {NULL, NULL, layout, norm, images, rc, packed, staged};
-        rc_ = forward_pipelined(ctx, &src, n, logits, probs);
+        rc_ = forward_pipelined(ctx, &src, n, logits, probs, 1);
     } else {
         vh_set_error(1, "vit_hip_forward_u8_resized: out of host memory");
     }
@@ -1748,8 +1963,9 @@ static int multi_forward_one(void *arg, int shard, int lo, int hi)
 {
     vit_hip_multi *m = (vit_hip_multi *)arg;
     const size_t NC = (size_t)vit_hip_config(m->ctx[shard])->num_classes;
-    return vit_hip_forward(m->ctx[shard], m->images + lo, hi - lo, m->logits ? m->logits + (size_t)lo * NC : NULL,
-                           m->probs ? m->probs + lo : NULL);
+    /* no feature output, whatever a caller armed on the shard's context */
+    return forward_host_images(m->ctx[shard], m->images + lo, hi - lo, m->logits ? m->logits + (size_t)lo * NC : NULL,
+                               m->probs ? m->probs + lo : NULL, 0);
 }
 
 /* Not re-entrant on one vit_hip_multi (like vit_hip_forward on one context). */

@@ -41,6 +41,7 @@ struct vit_gather_state
 void **vit_hip_multi_gather_slot(vit_hip_multi *m);
 float *vit_hip_logits_buffer(vit_hip_ctx *ctx);
 int vit_hip_device(const vit_hip_ctx *ctx);
+int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits, float *d_probs, vh_stream_t stream);
 double *vit_hip_multi_enqueue_ms_slot(vit_hip_multi *m);
 
 static int fail(int code, const char *what, const char *detail)
@@ -148,8 +149,8 @@ static int enqueue_shard(void *arg, int g, int lo, int hi)
         return 0;
     vit_hip_ctx *ctx = vit_hip_multi_ctx(j->m, g);
     /* shard 0 writes straight into the gathered buffer */
-    return vit_hip_forward_device(ctx, j->d_images[g], j->counts[g], g == 0 ? j->d_logits_root : vit_hip_logits_buffer(ctx), NULL,
-                                  vit_hip_stream(ctx));
+    return vit_hip_forward_device_plain(ctx, j->d_images[g], j->counts[g], g == 0 ? j->d_logits_root : vit_hip_logits_buffer(ctx), NULL,
+                                        vit_hip_stream(ctx));
 }
 
 /* Wait for everything this call may have put on any device's stream.  Every return path behind the first enqueue goes

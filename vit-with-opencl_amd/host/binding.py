@@ -61,6 +61,8 @@ EXPORTS = [
     "vit_hip_forward_u8",
     "vh_launch_resize_crop_u8", "vit_resize_crop_geometry", "vit_hip_resize_crop_u8", "vit_hip_forward_device_u8_resized",
     "vit_hip_forward_u8_resized",
+    "vh_feature_readout_scratch", "vh_launch_feature_readout", "vit_feature_sizes", "vit_hip_set_features",
+    "vit_hip_set_features_host",
 ]
 
 
@@ -96,6 +98,51 @@ class ResizeCrop(C.Structure):
 
 
 RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}
+
+
+class FeatureSpecC(C.Structure):
+    """`vit_feature_spec` (include/ViT_opencl.h)."""
+
+    _fields_ = [("n_taps", C.c_int), ("taps", C.c_int * 4), ("final_norm", C.c_int), ("l2_normalize", C.c_int),
+                ("dtype", C.c_int), ("token_layout", C.c_int)]
+
+
+class FeatureBuffers(C.Structure):
+    """`vit_feature_buffers` (include/ViT_opencl.h): device or host pointers, each may be NULL."""
+
+    _fields_ = [("cls", C.c_void_p), ("pooled", C.c_void_p), ("tokens", C.c_void_p)]
+
+
+FEATURE_DTYPES = {"f32": 0, "bf16": 1}
+TOKEN_LAYOUTS = {"nlc": 0, "nchw": 1}
+
+
+class FeatureSpec:
+    """A feature request: taps (encoder layers whose output is read, negative from the end), the final LayerNorm, unit L2
+    norm of cls / pooled, the element type ("f32" | "bf16"; bf16 arrives as uint16 bit patterns) and the token layout
+    ("nlc" | "nchw")."""
+
+    def __init__(self, taps=(-1,), final_norm: bool = True, l2_normalize: bool = False, dtype: str = "f32",
+                 token_layout: str = "nlc"):
+        self.taps, self.final_norm, self.l2_normalize = tuple(int(t) for t in taps), bool(final_norm), bool(l2_normalize)
+        self.dtype, self.token_layout = dtype, token_layout
+
+    @property
+    def np_dtype(self):
+        return np.dtype(np.float32 if self.dtype == "f32" else np.uint16)
+
+    def c_struct(self) -> FeatureSpecC:
+        taps = list(self.taps[:4]) + [0] * (4 - min(len(self.taps), 4))
+        return FeatureSpecC(len(self.taps), (C.c_int * 4)(*taps), int(self.final_norm), int(self.l2_normalize),
+                            FEATURE_DTYPES[self.dtype], TOKEN_LAYOUTS[self.token_layout])
+
+
+def feature_sizes(cfg: "VitConfig", spec: FeatureSpec):
+    """vit_feature_sizes -> (cls, pooled, tokens) elements per image"""
+    out = [C.c_size_t() for _ in range(3)]
+    cs = spec.c_struct()
+    check(lib().vit_feature_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_feature_sizes")
+    return tuple(o.value for o in out)
 
 
 def resize_crop(resize_short: int, filter: str = "bilinear") -> ResizeCrop:
@@ -349,6 +396,13 @@ def lib() -> C.CDLL:
     L.vit_hip_resize_crop_u8.argtypes = [voidp, imgp, i, i, rcp, voidp, voidp]
     L.vit_hip_forward_device_u8_resized.argtypes = [voidp, imgp, i, i, rcp, C.POINTER(PixelNorm), voidp, voidp, voidp]
     L.vit_hip_forward_u8_resized.argtypes = [voidp, imgp, i, i, rcp, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
+    L.vh_feature_readout_scratch.argtypes = [i, i, i]
+    L.vh_feature_readout_scratch.restype = sz
+    L.vh_launch_feature_readout.argtypes = [voidp, voidp, voidp, C.c_long, voidp, voidp, C.c_double] + [i] * 9 + [voidp] * 4 + [sz]
+    specp, bufp, szp = C.POINTER(FeatureSpecC), C.POINTER(FeatureBuffers), C.POINTER(sz)
+    L.vit_feature_sizes.argtypes = [C.POINTER(VitConfig), specp, szp, szp, szp]
+    L.vit_hip_set_features.argtypes = [voidp, specp, bufp]
+    L.vit_hip_set_features_host.argtypes = [voidp, specp, bufp]
     _lib = L
     return L
 
@@ -569,6 +623,46 @@ class ViTHip:
 
     def sync(self):
         check(self.L.vh_stream_sync(self.stream), "vh_stream_sync")
+
+    def set_features(self, spec, cls=None, pooled=None, tokens=None):
+        """Arm (spec=None: disarm) the device forms: cls / pooled / tokens are DeviceBuffers (or device pointers) for up to
+        max_batch images, written by every forward_device* until disarmed."""
+        if spec is None:
+            check(self.L.vit_hip_set_features(self.ctx, None, None), "vit_hip_set_features")
+            self._feature_keep = None
+            return
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        cs, bufs = spec.c_struct(), FeatureBuffers(ptr(cls), ptr(pooled), ptr(tokens))
+        check(self.L.vit_hip_set_features(self.ctx, C.byref(cs), C.byref(bufs)), "vit_hip_set_features")
+        self._feature_keep = (cls, pooled, tokens)
+
+    def set_features_host(self, spec, cls=None, pooled=None, tokens=None):
+        """Arm (spec=None: disarm) the host forms: cls / pooled are C-contiguous NumPy arrays of spec.np_dtype for all n
+        images of the coming forward / forward_u8 / forward_u8_resized calls."""
+        if spec is None:
+            check(self.L.vit_hip_set_features_host(self.ctx, None, None), "vit_hip_set_features_host")
+            self._feature_keep = None
+            return
+        for a in (cls, pooled, tokens):
+            if a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == spec.np_dtype):
+                raise ValueError(f"set_features_host: need C-contiguous arrays of {spec.np_dtype}")
+        ptr = lambda a: None if a is None else a.ctypes.data
+        cs, bufs = spec.c_struct(), FeatureBuffers(ptr(cls), ptr(pooled), ptr(tokens))
+        check(self.L.vit_hip_set_features_host(self.ctx, C.byref(cs), C.byref(bufs)), "vit_hip_set_features_host")
+        self._feature_keep = (cls, pooled, tokens)
+
+    def embed(self, images: np.ndarray, spec):
+        """fp32 images [n][C][H][W] -> (logits, cls, pooled): the host form armed for this one call."""
+        n = np.asarray(images).shape[0]
+        c_el, p_el, _ = feature_sizes(self.cfg, spec)
+        cls = np.empty((n, c_el), dtype=spec.np_dtype)
+        pooled = np.empty((n, p_el), dtype=spec.np_dtype)
+        self.set_features_host(spec, cls=cls, pooled=pooled)
+        try:
+            logits, _ = self.forward(images)
+        finally:
+            self.set_features_host(None)
+        return logits, cls, pooled
 
     def read_tokens(self, n: int) -> np.ndarray:
         out = np.empty((n * self.tokens, self.cfg.embed_dim), dtype=np.float32)
