@@ -380,6 +380,7 @@ typedef struct vh_resize_desc
 /* desc: n descriptors in device memory; filter 0 bilinear, 1 bicubic; layout 0 HWC, 1 CHW; chans 1..4; out: [n][crop][crop]
  * [chans] bytes (HWC).  One setup launch writes every image's tables into coef (coef_bytes long), then one launch per
  * (image, band of output rows) runs the horizontal pass into LDS and the vertical pass in int32 registers. */
+#define VH_RESIZE_MAX_ROW_BYTES 3072   /* crop x chans at most: 12 crop bytes per thread and row */
 int vh_launch_resize_crop_u8(vh_stream_t s, const vh_resize_desc *desc, int n, int chans, int layout, int filter, int crop,
                              void *coef, size_t coef_bytes, unsigned char *out);
 

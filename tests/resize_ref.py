@@ -68,14 +68,18 @@ def resize_crop(img: np.ndarray, resize_short: int, crop: int, f: int) -> np.nda
     xmin, _, kx = coefficients(w, nw, f, left, crop)
     ymin, ycnt, ky = coefficients(h, nh, f, top, crop)
     y0, y1 = int(ymin.min()), int((ymin + ycnt).max())
-    src = img[y0:y1].astype(np.int64)
-    acc = np.full((y1 - y0, crop, img.shape[2]), 1 << (PRECISION_BITS - 1), dtype=np.int64)
+    # int32 as in Resample.c: |sum u k| <= 255 x sum |k| < 2^31 for both filters (sum |k| stays below 1.3 x 2^22)
+    src = img[y0:y1].astype(np.int32)
+    kx, ky = kx.astype(np.int32), ky.astype(np.int32)
+    acc = np.full((y1 - y0, crop, img.shape[2]), 1 << (PRECISION_BITS - 1), dtype=np.int32)
     for t in range(kx.shape[1]):   # taps beyond a column's count have weight 0; clamp their index into the row
-        acc += src[:, np.minimum(xmin + t, w - 1), :] * kx[:, t][None, :, None]
-    hrow = _clip8(acc).astype(np.int64)
-    out = np.full((crop, crop, img.shape[2]), 1 << (PRECISION_BITS - 1), dtype=np.int64)
+        if kx[:, t].any():
+            acc += src[:, np.minimum(xmin + t, w - 1), :] * kx[:, t][None, :, None]
+    hrow = _clip8(acc).astype(np.int32)
+    out = np.full((crop, crop, img.shape[2]), 1 << (PRECISION_BITS - 1), dtype=np.int32)
     for t in range(ky.shape[1]):
-        out += hrow[np.minimum(ymin + t, y1 - 1) - y0] * ky[:, t][:, None, None]
+        if ky[:, t].any():
+            out += hrow[np.minimum(ymin + t, y1 - 1) - y0] * ky[:, t][:, None, None]
     return _clip8(out)
 
 
@@ -112,20 +116,29 @@ def sha256(a: np.ndarray) -> str:
 
 
 def pil_resize_crop(img: np.ndarray, resize_short: int, crop: int, f: int) -> np.ndarray:
-    """Pillow's Image.resize((nw, nh), BILINEAR | BICUBIC) then [top:top+crop, left:left+crop] (needs Pillow)"""
+    """Pillow's Image.resize((nw, nh), BILINEAR | BICUBIC) then [top:top+crop, left:left+crop] (needs Pillow).
+
+    1 channel is an "L" image and 3 channels an "RGB" image.  2 and 4 channels are INDEPENDENT BANDS: every channel is
+    resized as an "L" image of its own and the results are stacked.  Channel 4 (or 2) is not treated as alpha: Pillow's own
+    "RGBA" / "LA" resize premultiplies the colour bands by alpha and divides again, the library resizes every channel of a
+    pixel alike ("Image ingest")."""
     from PIL import Image
-    h, w = img.shape[:2]
+    h, w, c = img.shape
     nh, nw, top, left = geometry(h, w, resize_short, crop)
-    mode = {1: "L", 3: "RGB"}[img.shape[2]]
-    pim = Image.fromarray(img[:, :, 0] if mode == "L" else img, mode)
-    out = np.asarray(pim.resize((nw, nh), Image.Resampling.BICUBIC if f == BICUBIC else Image.Resampling.BILINEAR))
-    out = out.reshape(nh, nw, img.shape[2])
+    how = Image.Resampling.BICUBIC if f == BICUBIC else Image.Resampling.BILINEAR
+    if c == 3:
+        out = np.asarray(Image.fromarray(img, "RGB").resize((nw, nh), how))
+    else:
+        out = np.stack([np.asarray(Image.fromarray(np.ascontiguousarray(img[:, :, ch]), "L").resize((nw, nh), how))
+                        for ch in range(c)], axis=2)
+    out = out.reshape(nh, nw, c)
     return np.ascontiguousarray(out[top:top + crop, left:left + crop])
 
 
 # The cases the committed Pillow hashes (tests/golden/resize_crop_pil_sha256.json) were made from: (seed, h, w, channels,
 # resize_short, crop, filter).  Portrait, landscape, square, h == resize_short, upscales, 1 x N and N x 1, 4000 x 3000 and a
-# downscale beyond 16x.
+# downscale beyond 16x; then 1, 2 and 4 channels at the crops whose row length crop x channels selects each instantiation
+# of the resize kernel (40 to 768 px; 2 and 4 channels are independent bands, see pil_resize_crop).
 GOLDEN_CASES = [
     (1, 375, 500, 3, 256, 224, "bilinear"), (2, 500, 375, 3, 256, 224, "bicubic"), (3, 256, 256, 3, 256, 224, "bilinear"),
     (4, 224, 224, 3, 224, 224, "bicubic"), (5, 100, 150, 3, 224, 224, "bilinear"), (6, 150, 100, 3, 248, 224, "bicubic"),
@@ -134,4 +147,10 @@ GOLDEN_CASES = [
     (13, 257, 300, 3, 248, 224, "bicubic"), (14, 481, 257, 3, 256, 224, "bilinear"), (15, 6000, 4000, 3, 224, 224, "bicubic"),
     (16, 999, 256, 3, 256, 224, "bilinear"), (17, 300, 400, 1, 256, 224, "bicubic"), (18, 512, 683, 3, 384, 384, "bicubic"),
     (19, 384, 600, 3, 384, 384, "bilinear"), (20, 90, 60, 3, 224, 224, "bicubic"),
+    (21, 60, 45, 1, 48, 40, "bilinear"), (22, 200, 13, 1, 40, 40, "bicubic"), (23, 300, 400, 2, 192, 168, "bicubic"),
+    (24, 90, 120, 2, 168, 168, "bilinear"), (25, 168, 168, 4, 168, 168, "bicubic"), (26, 800, 700, 4, 176, 168, "bilinear"),
+    (27, 250, 333, 4, 256, 224, "bicubic"), (28, 100, 80, 4, 350, 350, "bilinear"), (29, 500, 400, 4, 400, 392, "bicubic"),
+    (30, 1, 300, 4, 476, 476, "bilinear"), (31, 64, 64, 4, 518, 518, "bicubic"), (32, 2500, 2500, 4, 602, 602, "bilinear"),
+    (33, 120, 90, 4, 700, 658, "bicubic"), (34, 300, 1, 4, 714, 714, "bilinear"), (35, 200, 260, 4, 768, 768, "bicubic"),
+    (36, 333, 500, 1, 400, 384, "bilinear"),
 ]

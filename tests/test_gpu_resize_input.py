@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import resize_ref as R
+from ingest_common import Staged
 
 pytestmark = pytest.mark.gpu
 
@@ -24,31 +25,6 @@ RAGGED = [(500, 375), (375, 500), (256, 256), (256, 300), (100, 150), (4000, 300
 def _clean_env(monkeypatch):
     for var in ENV:
         monkeypatch.delenv(var, raising=False)
-
-
-class Staged:
-    """Images uploaded into one device buffer at odd byte offsets, with padded rows: descriptors for the device forms."""
-
-    def __init__(self, pkg, images_hwc, layout):
-        self.descs, blobs, off = [], [], 0
-        for i, img in enumerate(images_hwc):
-            h, w, c = img.shape
-            a = img if layout == "hwc" else np.ascontiguousarray(img.transpose(2, 0, 1))
-            pad = 3 + 5 * (i % 3)   # bytes of padding per row
-            row = w * c if layout == "hwc" else w
-            rows = h if layout == "hwc" else c * h
-            buf = np.zeros((rows, row + pad), dtype=np.uint8)
-            buf[:, :row] = a.reshape(rows, row)
-            off += 1 + 2 * (i % 4)   # odd offsets
-            blobs.append((off, buf))
-            self.descs.append((off, h, w, row + pad))
-            off += buf.nbytes
-        host = np.zeros(off + 16, dtype=np.uint8)
-        for o, buf in blobs:
-            host[o:o + buf.nbytes] = buf.reshape(-1)
-        self.buf = pkg.DeviceBuffer.from_numpy(host, dtype=np.uint8)
-        base = self.buf.ptr.value
-        self.descs = [(base + o, h, w, s) for o, h, w, s in self.descs]
 
 
 def _crops_gpu(pkg, m, images, rs, f, layout):
@@ -103,20 +79,34 @@ def test_crop_bytes_equal_the_reference_on_a_ragged_batch(pkg, b16, f, layout):
 
 
 def test_crop_bytes_equal_pillows_committed_hashes(pkg, b16):
-    """every 3-channel 224 px case of the Pillow fixture, grouped into one call per (resize_short, filter)"""
-    cases = [c for c in json.loads(GOLDEN.read_text())["cases"] if c["channels"] == 3 and c["crop"] == 224]
-    groups = {}
+    """every case of the Pillow fixture that a 3-channel 224 px context or one of ingest_common's tiny contexts serves,
+    grouped by (channels, crop) for the context and into one call per (resize_short, filter)"""
+    from ingest_common import RESIZE_CASES, tiny_resize_context
+    cases = json.loads(GOLDEN.read_text())["cases"]
+    by_context = {}
     for c in cases:
-        groups.setdefault((c["resize_short"], c["filter"]), []).append(c)
-    checked = 0
-    for (rs, f), group in groups.items():
-        images = [R.source_image(c["seed"], c["height"], c["width"], 3) for c in group]
-        for layout in ("hwc", "chw"):
-            got = _crops_gpu(pkg, b16, images, rs, f, layout)
-            for c, crop in zip(group, got):
-                assert R.sha256(crop) == c["sha256"], f"{c} {layout}"
-                checked += 1
-    assert checked >= 30
+        by_context.setdefault((c["channels"], c["crop"]), []).append(c)
+    served = [key for key in by_context if key == (3, 224) or key in RESIZE_CASES]
+    assert (3, 224) in served and len(served) >= 12 and {1, 2, 3, 4} <= {ch for ch, _ in served}
+    checked = {}
+    for chans, crop in served:
+        m = b16 if (chans, crop) == (3, 224) else tiny_resize_context(pkg, chans, crop)
+        try:
+            groups = {}
+            for c in by_context[(chans, crop)]:
+                groups.setdefault((c["resize_short"], c["filter"]), []).append(c)
+            for (rs, f), group in groups.items():
+                images = [R.source_image(c["seed"], c["height"], c["width"], chans) for c in group]
+                for layout in ("hwc", "chw"):
+                    got = _crops_gpu(pkg, m, images, rs, f, layout)
+                    for c, crop_bytes in zip(group, got):
+                        assert R.sha256(crop_bytes) == c["sha256"], f"{c} {layout}"
+                        checked[(chans, crop)] = checked.get((chans, crop), 0) + 1
+        finally:
+            if m is not b16:
+                m.close()
+    assert checked[(3, 224)] >= 30
+    assert sum(checked.values()) == 2 * sum(len(by_context[key]) for key in served)
 
 
 MODES = {

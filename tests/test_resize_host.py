@@ -102,6 +102,11 @@ def _pil_cases():
             seed += 1
             cases.append((seed, h, w, 3, rs, 224, f))
     cases += [(seed + 1, 300, 400, 1, 256, 224, "bicubic"), (seed + 2, 384, 512, 3, 384, 384, "bilinear")]
+    # 1, 2 and 4 channels (independent bands) at other crops, up- and downscaled
+    for k, (h, w, c, rs, crop) in enumerate(((70, 50, 1, 44, 40), (130, 170, 2, 168, 168), (500, 640, 2, 180, 168),
+                                             (90, 120, 4, 350, 350), (700, 900, 4, 224, 224), (33, 300, 4, 96, 96))):
+        for f in ("bilinear", "bicubic"):
+            cases.append((seed + 10 + 2 * k + (f == "bicubic"), h, w, c, rs, crop, f))
     return cases
 
 
@@ -115,6 +120,26 @@ def test_reference_equals_pillow_byte_for_byte():
         want = R.pil_resize_crop(img, rs, crop, R.FILTERS[f])
         assert got.shape == (crop, crop, c)
         assert np.array_equal(got, want), (seed, h, w, c, rs, crop, f, int((got != want).sum()))
+
+
+def test_two_and_four_channels_are_independent_bands_not_alpha():
+    """2 and 4 channels: every channel is resized as an image of its own, in the reference and in the Pillow statement the
+    committed hashes come from.  Pillow's RGBA resize premultiplies by the fourth channel: on a source whose fourth channel
+    varies it gives other colour bytes, which is not what the library computes."""
+    for c in (2, 4):
+        img = R.source_image(77 + c, 90, 130, c)
+        got = R.resize_crop(img, 48, 40, R.BICUBIC)
+        for ch in range(c):
+            alone = R.resize_crop(np.ascontiguousarray(img[:, :, ch:ch + 1]), 48, 40, R.BICUBIC)
+            assert np.array_equal(got[:, :, ch], alone[:, :, 0]), (c, ch)
+    Image = pytest.importorskip("PIL.Image")
+    img = R.source_image(81, 90, 130, 4)
+    assert len(np.unique(img[:, :, 3])) > 16
+    ours = R.pil_resize_crop(img, 48, 40, R.BILINEAR)
+    assert np.array_equal(ours, R.resize_crop(img, 48, 40, R.BILINEAR))
+    nh, nw, top, left = R.geometry(90, 130, 48, 40)
+    rgba = np.asarray(Image.fromarray(img, "RGBA").resize((nw, nh), Image.Resampling.BILINEAR))[top:top + 40, left:left + 40]
+    assert np.array_equal(rgba[:, :, 3], ours[:, :, 3]) and not np.array_equal(rgba[:, :, :3], ours[:, :, :3])
 
 
 def test_sources_saturate_and_bicubic_clips():

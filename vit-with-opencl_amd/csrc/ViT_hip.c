@@ -1315,6 +1315,7 @@ static int resize_args(const char *who, const vit_hip_ctx *ctx, const vit_image_
                       : layout != VIT_PIXELS_HWC && layout != VIT_PIXELS_CHW ? "layout must be VIT_PIXELS_HWC or VIT_PIXELS_CHW"
                       : rc->filter != VIT_RESIZE_BILINEAR && rc->filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
                       : ctx->cfg.in_chans > 4 ? "8-bit images take at most 4 channels"
+                      : (long)ctx->cfg.img_size * ctx->cfg.in_chans > VH_RESIZE_MAX_ROW_BYTES ? "img_size x in_chans above 3072 bytes per crop row"
                       : rc->resize_short < ctx->cfg.img_size || rc->resize_short > 4 * ctx->cfg.img_size ? "resize_short must be in img_size..4 x img_size"
                       : NULL;
     int bad = -1;

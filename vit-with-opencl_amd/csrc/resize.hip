@@ -28,6 +28,7 @@ namespace {
 
 enum { LAYOUT_HWC = 0, LAYOUT_CHW = 1 };   /* VIT_PIXELS_* */
 enum { THREADS = 256, HBUF_BYTES = 32768, ACC_REGS = 48, MAX_JN = 12 };
+static_assert(MAX_JN * THREADS == VH_RESIZE_MAX_ROW_BYTES, "the callers' limit on crop x chans");
 
 /* Pillow's filters (Resample.c), a = -0.5 for bicubic */
 __device__ __forceinline__ double bilinear_filter(double x)
