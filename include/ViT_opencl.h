@@ -55,8 +55,23 @@ typedef struct vit_config
  *                                        BF16_GEMM, FP8_GEMM
  * Above 512 tokens F32_FP16X2, the fp32-rows path ($VIT_HIP_P3=0,
  * $VIT_HIP_GEMM_FP32=native, embed_dim or mlp_hidden not multiples of 128) and
- * other head dims are refused at creation (code 2).  $VIT_HIP_ATTN=long selects
- * attention_long.hip at any T on the planes paths with head_dim 64 or 80. */
+ * other head dims are refused at creation (code 2).
+ *
+ * The $VIT_HIP_* switches are read when a context is created and at no other
+ * time: they are part of that context's plan, and two contexts of one process
+ * may differ in them.  Which plans each one reaches:
+ *   $VIT_HIP_P3=0              F32: fp32 activation rows, operands split inside
+ *                              the GEMM loop (the fp32-rows path)
+ *   $VIT_HIP_GEMM_FP32=native  F32: the fp32-rows path with the fp32 matrix
+ *                              instruction in the patch embedding, the attention
+ *                              and every projection without pre-split weights
+ *   $VIT_HIP_ATTN=long         the planes paths with head_dim 64 or 80:
+ *                              attention_long.hip at any T
+ *   $VIT_HIP_ATTN=tiled        plans whose attention reads fp32 rows -- the
+ *                              fp32-rows path, F32_FP16X2 and the "otherwise"
+ *                              line above: attention_tiled.hip at every shape.
+ *                              The resident planes kernels (the default ViT-B/16
+ *                              plan among them) are not affected. */
 int vit_config_preset(vit_config *cfg, const char *name);
 
 /* Derived sizes. */

@@ -142,6 +142,16 @@ int vh_launch_layer_norm(vh_stream_t s, const float *input, const float *weight,
 int vh_launch_linear(vh_stream_t s, float *output, const float *weight, const float *input,
                      const float *bias, int rowA, int colA, int colB, int doGelu,
                      const float *residual);
+/* ... and vh_launch_patch_embed_ws, with the arithmetic of the fp32 products named: the exact three-part bf16 split on the
+ * bf16 matrix cores (what the two entries above run), or the native fp32 matrix instruction.  Ragged colB (% 128 != 0) and
+ * pointers that are not 16-byte aligned run natively under either. */
+enum { VH_FP32_SPLIT3 = 0, VH_FP32_NATIVE = 1 };
+int vh_launch_linear_math(vh_stream_t s, float *output, const float *weight, const float *input, const float *bias,
+                          int rowA, int colA, int colB, int doGelu, const float *residual, int fp32_math);
+int vh_launch_patch_embed_ws_math(vh_stream_t s, const float *images, const float *conv_w, const float *conv_b,
+                                  const float *cls_token, const float *pos_embed, float *tokens, int n_images, int in_chans,
+                                  int img_size, int patch_size, int embed_dim, void *workspace, size_t workspace_bytes,
+                                  int fp32_math);
 
 /* The same product with the weight pre-split: `weight_planes` holds the exact three-way split
  * w = p0 + p1 + p2 as bfloat16, laid out [colA/32][3][colB][32] (K step, part, row, element: what one K
@@ -241,6 +251,18 @@ int vh_launch_attention_h2(vh_stream_t s, const float *qkv, float *output, int n
  *   qkv    [n_images*tokens][3*embed],  output [n_images*tokens][embed] */
 int vh_launch_attention(vh_stream_t s, const float *qkv, float *output, int n_images,
                         int tokens, int embed_dim, int num_heads);
+/* Every attention on fp32 Q|K|V rows is this launcher with its choices named (vh_launch_attention = rows out, SPLIT3, AUTO).
+ *   arith     how Q.K^T and P.V reach the matrix cores: the exact three-part bf16 split, the fp32 matrix instruction, two
+ *             fp16 parts (vh_launch_attention_h2), operands rounded to fp16 (vh_launch_attention_f16)
+ *   kernel    AUTO: K and V of a head resident in LDS where head_dim is 64 and tokens <= 208, else streamed through it
+ *             (head_dim 64, 80 or 128, tokens <= 512); STREAMING: streamed at any shape.  The streaming kernel
+ *             has fp32 products (SPLIT3, NATIVE, FP16X2) or fp16 operands (FP16)
+ *   out_kind  0 fp32 rows; 3 three-part planes (vh_launch_attention_p3: SPLIT3) and 4 one-part bf16 planes
+ *             (vh_launch_attention_planes_bf16: FP16) are written by the resident kernel only: AUTO on its shapes */
+enum { VH_ATTN_NATIVE = 0, VH_ATTN_FP16 = 1, VH_ATTN_FP16X2 = 2, VH_ATTN_SPLIT3 = 3 };
+enum { VH_ATTN_AUTO = 0, VH_ATTN_STREAMING = 1 };
+int vh_launch_attention_rows(vh_stream_t s, const float *qkv, void *output, int out_kind, int arith, int kernel, int n_images,
+                             int tokens, int embed_dim, int num_heads);
 
 /* Every row_stride-th row compacted: dst[p][i][:] = src[p][i * row_stride][:] over n_planes planes of src_rows rows of
  * row_bytes bytes (a row-major fp32 matrix: n_planes 1, row_bytes 4 * cols; a planes tensor: row_bytes 64).  Used to

@@ -745,14 +745,12 @@ def test_model_fp32_emulated_with_fp16_pairs_meets_the_fp32_tolerance(pkg, devic
 # ---- tuning / fallback paths behind environment switches ---------------------------------
 
 
-@pytest.mark.parametrize("env", [
-    {"VIT_HIP_GEMM_FP32": "native"},                                # fp32 matrix instruction everywhere (GEMMs and attention)
-    {"VIT_HIP_P3": "0"},                                            # activations split inside the GEMM loop (gemm_mfma.hip)
-    {"VIT_HIP_ATTN": "tiled"},                                      # streaming attention kernel on the B/16 shape
-])
-def test_switchable_paths_meet_the_fp32_parity(env, tmp_path):
-    """Every switch is read once per process, so each combination runs in a child process: two
-    images through the whole model against the reference's goldens at the fp32 tolerance."""
+SWITCHES = ("VIT_HIP_GEMM_FP32", "VIT_HIP_P3", "VIT_HIP_ATTN")
+
+
+def _child_logits(env, out_path):
+    """Two images through ViT-B/16 in a child process whose only switches are `env`: the child asserts the fp32
+    parity against the reference's goldens and saves its logits to out_path."""
     import os
     import subprocess
     import sys
@@ -763,14 +761,112 @@ def test_switchable_paths_meet_the_fp32_parity(env, tmp_path):
         "pkg = g.load_package(); cfg = pkg.preset('vit_b_16')\n"
         "m = pkg.ViTHip(cfg, pkg.synth_weights(cfg, 0), device=0, max_batch=2)\n"
         "logits, probs = m.forward(pkg.synth_images(cfg, 0, 2)); m.close()\n"
+        "np.save(%r, logits)\n"
         "gold = np.load(%r)\n"
         "err = float(np.abs(logits - gold['logits'][:2]).max())\n"
         "print('max |dlogit|', err)\n"
         "assert err <= 1e-4 and (logits.argmax(1) == gold['logits'][:2].argmax(1)).all()\n"
-    ) % (str(root), str(root / "tests" / "golden" / "b16_full.npz"))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True,
-                       timeout=300)
+    ) % (str(root), str(out_path), str(root / "tests" / "golden" / "b16_full.npz"))
+    base = {k: v for k, v in os.environ.items() if k not in SWITCHES}
+    r = subprocess.run([sys.executable, "-c", code], env=dict(base, **env), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"{env}: {r.stdout[-300:]} {r.stderr[-800:]}"
+    return np.load(out_path)
+
+
+@pytest.mark.parametrize("env", [
+    {"VIT_HIP_GEMM_FP32": "native"},                                # fp32 matrix instruction: patch embedding and attention
+    {"VIT_HIP_P3": "0"},                                            # activations split inside the GEMM loop (gemm_mfma.hip)
+    {"VIT_HIP_P3": "0", "VIT_HIP_ATTN": "tiled"},                   # streaming attention kernel on the B/16 shape
+])
+def test_switchable_paths_meet_the_fp32_parity(env, tmp_path):
+    """Each combination in a child process of its own: two images through the whole model against the reference's
+    goldens at the fp32 tolerance.  VIT_HIP_ATTN=tiled goes with VIT_HIP_P3=0: the switch reaches only plans whose
+    attention reads fp32 rows, and the default ViT-B/16 plan runs the planes attention (vh_launch_attention_planes),
+    where `tiled` alone selects nothing."""
+    _child_logits(env, tmp_path / "logits.npy")
+
+
+def test_switches_are_read_at_context_creation_and_nowhere_else(pkg, device, weights, golden_full, monkeypatch, tmp_path):
+    """Contexts made one after the other in ONE process under different switches: each meets the fp32 parity, and each
+    gives, bit for bit, the logits of a process that has only ever seen that environment -- a switch that a launcher
+    kept from its first use would make every context after the first run the first one's kernels."""
+    cfg = pkg.preset("vit_b_16")
+    images = pkg.synth_images(cfg, 0, 2)
+    settings = [{"VIT_HIP_GEMM_FP32": "native"}, {}, {"VIT_HIP_P3": "0"}, {"VIT_HIP_P3": "0", "VIT_HIP_ATTN": "tiled"}, {}]
+    got = []
+    for env in settings:
+        for k in SWITCHES:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        m = pkg.ViTHip(cfg, weights, device=0, max_batch=2)
+        logits, _ = m.forward(images)
+        m.close()
+        err = float(np.abs(logits - golden_full["logits"][:2]).max())
+        print(env, "max |dlogit|", err)
+        assert err <= LOGIT_TOL and np.array_equal(logits.argmax(1), golden_full["logits"][:2].argmax(1)), env
+        got.append(logits)
+    alone = {}
+    for env, logits in zip(settings, got):
+        key = tuple(sorted(env.items()))
+        if key not in alone:
+            alone[key] = _child_logits(env, tmp_path / f"alone{len(alone)}.npy")
+        assert np.array_equal(logits, alone[key]), f"{env}: differs from a process with this environment alone"
+
+
+def test_linear_with_explicit_fp32_math(pkg, device, oracle):
+    """vh_launch_linear_math: one ragged M tile at the smallest N the split kernel takes, both arithmetics against the
+    oracle; at a ragged N both run the guarded native tile and equal vh_launch_linear bit for bit."""
+    M, K = 40, 64
+    for N in (128, 72):
+        x = oracle.synth_fill(M * K, 100 + M, 1.0, 0.1).reshape(M, K)
+        w = oracle.synth_fill(N * K, 200 + N, 0.04, 0.0)
+        b = oracle.synth_fill(N, 300 + N, 0.1, 0.0)
+        want = oracle.linear(x, w, b, N)
+        d_x, d_w, d_b, d_o = _dev(pkg, x), _dev(pkg, w), _dev(pkg, b), pkg.DeviceBuffer(M * N)
+        got = {}
+        for math, code in pkg.binding.FP32_MATH.items():
+            _launch(pkg, "vh_launch_linear_math", None, d_o.ptr, d_w.ptr, d_x.ptr, d_b.ptr, M, K, N, 0, None, code)
+            got[math] = d_o.to_numpy((M, N))
+            assert np.abs(got[math] - want).max() <= OP_TOL, (N, math)
+        if N == 72:
+            _launch(pkg, "vh_launch_linear", None, d_o.ptr, d_w.ptr, d_x.ptr, d_b.ptr, M, K, N, 0, None)
+            assert np.array_equal(got["split3"], got["native"]) and np.array_equal(got["split3"], d_o.to_numpy((M, N)))
+    L = pkg.lib()
+    assert L.vh_launch_linear_math(None, d_o.ptr, d_w.ptr, d_x.ptr, d_b.ptr, M, K, 72, 0, None, 2) != 0
+    assert b"fp32_math" in L.vh_last_error()
+
+
+def test_rows_attention_with_the_kernel_named(pkg, device):
+    """vh_launch_attention_rows: the streaming kernel asked for at a shape the resident kernel would take (head_dim 64,
+    one partial 32-key tile) against the oracle; where auto already streams (head_dim 80) both give the same bits; bad
+    choices are refused."""
+    from oracle.oracle import Oracle
+    A, KN = pkg.binding.ATTN_ARITH, pkg.binding.ATTN_KERNEL
+    orc = Oracle("vit_b_16")
+    n, T, E, H = 2, 50, 128, 2
+    orc.cfg.embed_dim, orc.cfg.num_heads = E, H
+    qkv = orc.synth_fill(n * T * 3 * E, 31 + T, 1.5, 0.0).reshape(n * T, 3 * E)
+    d_q, d_o = _dev(pkg, qkv), pkg.DeviceBuffer(n * T * E)
+    _launch(pkg, "vh_launch_attention_rows", None, d_q.ptr, d_o.ptr, 0, A["split3"], KN["streaming"], n, T, E, H)
+    got = d_o.to_numpy((n * T, E))
+    for i in range(n):
+        assert np.abs(got[i * T:(i + 1) * T] - orc.attention(qkv[i * T:(i + 1) * T])).max() <= OP_TOL, f"image {i}"
+
+    n, T, E, H = 1, 50, 160, 2
+    qkv = orc.synth_fill(n * T * 3 * E, 32 + T, 1.5, 0.0)
+    d_q, d_a, d_b = _dev(pkg, qkv), pkg.DeviceBuffer(n * T * E), pkg.DeviceBuffer(n * T * E)
+    _launch(pkg, "vh_launch_attention_rows", None, d_q.ptr, d_a.ptr, 0, A["split3"], KN["auto"], n, T, E, H)
+    _launch(pkg, "vh_launch_attention_rows", None, d_q.ptr, d_b.ptr, 0, A["split3"], KN["streaming"], n, T, E, H)
+    assert np.array_equal(d_a.to_numpy(), d_b.to_numpy()) and np.isfinite(d_a.to_numpy()).all()
+
+    L = pkg.lib()
+    assert L.vh_launch_attention_rows(None, d_q.ptr, d_a.ptr, 0, 7, KN["auto"], 1, 50, 128, 2) != 0
+    assert b"arith" in L.vh_last_error()
+    assert L.vh_launch_attention_rows(None, d_q.ptr, d_a.ptr, 0, A["split3"], 5, 1, 50, 128, 2) != 0
+    assert b"kernel" in L.vh_last_error()
+    assert L.vh_launch_attention_rows(None, d_q.ptr, d_a.ptr, 3, A["split3"], KN["streaming"], 1, 50, 128, 2) != 0
+    assert b"planes" in L.vh_last_error()
 
 
 @pytest.mark.parametrize("n_images,tokens,E,H", [(2, 257, 1280, 16), (1, 50, 1280, 16), (3, 300, 256, 2)])

@@ -122,15 +122,18 @@ def main():
     pkg.binding.check(lib.vh_launch_split_rows(stream, w.ptr, w16.ptr, N, K, 1), "planes")
     print(f"power sources: {sysfs_sources() or 'rocm-smi'}", flush=True)
 
+    math = "native" if os.environ.get("VIT_HIP_GEMM_FP32", "").startswith("n") else "split3"
+
     def f32():
-        pkg.binding.check(lib.vh_launch_linear(stream, out.ptr, w.ptr, a.ptr, b.ptr, M, K, N, 1, None), "linear")
+        pkg.binding.check(lib.vh_launch_linear_math(stream, out.ptr, w.ptr, a.ptr, b.ptr, M, K, N, 1, None,
+                                                    pkg.binding.FP32_MATH[math]), "linear")
 
     def b16():
         pkg.binding.check(lib.vh_launch_linear_planes(stream, out.ptr, 0, w16.ptr, a16.ptr, 1, b.ptr, M, K, N, 1, None),
                   "linear_planes")
 
     leg("idle", lambda: time.sleep(0.01), lib, stream)
-    leg("fp32 (" + os.environ.get("VIT_HIP_GEMM_FP32", "split3") + ", split in the K loop)", f32, lib, stream)
+    leg("fp32 (" + math + ", operands as fp32 rows)", f32, lib, stream)
     leg("bf16 operands", b16, lib, stream)
 
 

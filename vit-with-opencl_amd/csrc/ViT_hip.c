@@ -84,6 +84,9 @@ struct vit_hip_ctx
     int use_p3;         /* F32: GEMM inputs travel as three-part bf16 planes (y, attn, hid hold 6 bytes per value) */
     int cls_only_last;  /* use_p3: the last layer's output projection and MLP run on the class-token rows only */
     int attn_form;      /* ATTN_*, for the planes paths */
+    int fp32_native;    /* $VIT_HIP_GEMM_FP32=native: F32 on fp32 rows, with the fp32 matrix instruction in the patch embedding, the
+                         * attention and every projection without pre-split weights (VH_FP32_NATIVE, VH_ATTN_NATIVE) */
+    int attn_rows_streaming;   /* $VIT_HIP_ATTN=tiled: attention that reads fp32 rows takes the streaming kernel at every shape */
 
     void *slab[N_SLABS];
     size_t slab_bytes[N_SLABS];
@@ -451,9 +454,10 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
     const int reduced = precision == VIT_PRECISION_BF16_GEMM || precision == VIT_PRECISION_FP8_GEMM;
     /* F32 by default writes every GEMM input as the exact three-part bf16 split (csrc/gemm_p3.hip), 6 bytes per value;
      * $VIT_HIP_P3=0 keeps fp32 activations and the in-loop split (csrc/gemm_mfma.hip), $VIT_HIP_GEMM_FP32=native the fp32
-     * matrix instruction (read again by the kernels) */
+     * matrix instruction */
     const char *env_p3 = getenv("VIT_HIP_P3"), *env_native = getenv("VIT_HIP_GEMM_FP32");
-    const int planes_wanted = !(env_p3 && env_p3[0] == '0') && !(env_native && env_native[0] == 'n');
+    const int fp32_native = env_native && env_native[0] == 'n';
+    const int planes_wanted = !(env_p3 && env_p3[0] == '0') && !fp32_native;
     const int use_p3 = precision == VIT_PRECISION_F32 && E % 128 == 0 && F % 128 == 0 && planes_wanted &&
                        (size_t)max_batch * (size_t)T * 64 <= 0xffffffffull;
     /* the fold's row terms take at most 16 partial sums per row (row_norm_terms); on F32 it needs the planes path */
@@ -471,8 +475,9 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
                                "needs the planes path)");
     const char *env_ll = getenv("VIT_HIP_LAST_LAYER");
     /* attention: ATTN_LONG is the only kernel past STREAMING_MAX_TOKENS, and it reads the planes paths' Q|K|V with head_dim
-     * 64 or 80; $VIT_HIP_ATTN=long forces it at any T (tests, A/B).  Shapes no kernel runs are refused here, not at every
-     * forward. */
+     * 64 or 80; $VIT_HIP_ATTN=long forces it at any T (tests, A/B), $VIT_HIP_ATTN=tiled the streaming kernel wherever
+     * attention reads fp32 rows (the planes paths' resident kernels are not rows kernels and stay).  Shapes no kernel runs are
+     * refused here, not at every forward. */
     const char *env_attn = getenv("VIT_HIP_ATTN");
     const int long_hd = E == 64 * H || E == 80 * H;
     const int long_wanted = T > STREAMING_MAX_TOKENS || (env_attn && strcmp(env_attn, "long") == 0);
@@ -501,6 +506,8 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
               : (long_wanted && long_hd) ? ATTN_LONG
               : (E == 64 * H && T <= 208) ? ATTN_HD64
               : (reduced && E == 80 * H && T <= 272) ? ATTN_HD80 : ATTN_STREAMING;
+    ctx->fp32_native = fp32_native;
+    ctx->attn_rows_streaming = env_attn && env_attn[0] == 't';
     ctx->w = (float **)calloc((size_t)n_tensors, sizeof(float *));
     ctx->op = (struct operand *)calloc((size_t)4 * cfg->depth, sizeof(struct operand));
     if (!ctx->w || !ctx->op) {
@@ -845,6 +852,16 @@ fail:
  * ctx->ln_fold the two LayerNorms are not launched: whoever wrote x also left it as the projection's operand in ctx->y
  * with the rows' partial sums in ctx->stats, and the QKV / fc1 launches apply the row terms (csrc/norm_fold.h). */
 
+/* The plan's arithmetic for fp32 products on fp32 rows (kernelHandler.h) */
+static int fp32_math(const vit_hip_ctx *ctx) { return ctx->fp32_native ? VH_FP32_NATIVE : VH_FP32_SPLIT3; }
+
+/* Attention on fp32 Q|K|V rows into fp32 rows at out, in the plan's kernel */
+static int attention_rows(const vit_hip_ctx *ctx, vh_stream_t s, float *out, int arith, int n)
+{
+    return vh_launch_attention_rows(s, ctx->qkv, out, 0, arith, ctx->attn_rows_streaming ? VH_ATTN_STREAMING : VH_ATTN_AUTO, n,
+                                    ctx->tokens, ctx->cfg.embed_dim, ctx->cfg.num_heads);
+}
+
 /* The reduced modes' attention on fp16-rounded operands, writing the output projection's operand: one-part bf16 planes
  * (attn_scales NULL) or an MX tensor.  The resident kernels write it themselves; the streaming kernel leaves fp32 rows in
  * the idle MLP buffer, which are then rounded / quantised (one timed operator). */
@@ -863,7 +880,7 @@ static int attention_reduced(vit_hip_ctx *ctx, vh_stream_t s, int n, char *attn_
                              attn_scales ? vh_launch_quantize_mx_act(s, ctx->hid, ctx->attn, attn_scales, rows, E)
                                          : vh_launch_split_rows(s, ctx->hid, ctx->attn, rows, E, 1));
     else
-        OP(VIT_OP_ATTENTION, (rc = vh_launch_attention_f16(s, ctx->qkv, ctx->hid, n, T, E, H)) != 0 ? rc :
+        OP(VIT_OP_ATTENTION, (rc = attention_rows(ctx, s, ctx->hid, VH_ATTN_FP16, n)) != 0 ? rc :
                              attn_scales ? vh_launch_quantize_mx_act(s, ctx->hid, ctx->attn, attn_scales, rows, E)
                                          : vh_launch_split_rows(s, ctx->hid, ctx->attn, rows, E, 1));
     return 0;
@@ -940,7 +957,7 @@ static int layer_fp16x2(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     const struct operand *op = ctx->op + 4 * l;
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, E, c->eps));
     OP(VIT_OP_QKV, vh_launch_linear_h2(s, ctx->qkv, op[0].w, op[0].pair_scale, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
-    OP(VIT_OP_ATTENTION, vh_launch_attention_h2(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads));
+    OP(VIT_OP_ATTENTION, attention_rows(ctx, s, ctx->attn, VH_ATTN_FP16X2, n));
     OP(VIT_OP_OUT_PROJ, vh_launch_linear_h2(s, ctx->x, op[1].w, op[1].pair_scale, ctx->attn, lw[5], rows, E, E, 0, ctx->x));
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, E, c->eps));
     OP(VIT_OP_FC1, vh_launch_linear_h2(s, ctx->hid, op[2].w, op[2].pair_scale, ctx->y, lw[9], rows, E, F, 1, NULL));
@@ -971,7 +988,7 @@ static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int *
                         : vh_launch_linear_p3(s, ctx->qkv, planes_attn, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
     OP(VIT_OP_ATTENTION, ctx->attn_form == ATTN_HD64 ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
                          : (rc = ctx->attn_form == ATTN_LONG ? vh_launch_attention_long(s, ctx->qkv, 3, ctx->hid, n, T, E, c->num_heads)
-                                                             : vh_launch_attention(s, ctx->qkv, ctx->hid, n, T, E, c->num_heads)) != 0 ? rc
+                                                             : attention_rows(ctx, s, ctx->hid, VH_ATTN_SPLIT3, n)) != 0 ? rc
                          : vh_launch_split3_rows(s, ctx->hid, ctx->attn, rows, E));
     if (last && ctx->cls_only_last && T >= 4) {
         /* Opt-in (vit_hip_set_last_layer_cls_only / $VIT_HIP_LAST_LAYER=cls).  The classifier reads row 0 of every
@@ -1015,17 +1032,18 @@ static int layer_f32_rows(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->tokens, rows = n * T;
     float **lw = layer_tensors(ctx, l);
     const struct operand *op = ctx->op + 4 * l;   /* pre-split weight planes, when built */
+    const int math = fp32_math(ctx);
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, E, c->eps));
     OP(VIT_OP_QKV, op[0].w ? vh_launch_linear_w3(s, ctx->qkv, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL)
-                         : vh_launch_linear(s, ctx->qkv, lw[2], ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
-    OP(VIT_OP_ATTENTION, vh_launch_attention(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads));
+                         : vh_launch_linear_math(s, ctx->qkv, lw[2], ctx->y, lw[3], rows, E, 3 * E, 0, NULL, math));
+    OP(VIT_OP_ATTENTION, attention_rows(ctx, s, ctx->attn, ctx->fp32_native ? VH_ATTN_NATIVE : VH_ATTN_SPLIT3, n));
     OP(VIT_OP_OUT_PROJ, op[1].w ? vh_launch_linear_w3(s, ctx->x, op[1].w, ctx->attn, lw[5], rows, E, E, 0, ctx->x)
-                              : vh_launch_linear(s, ctx->x, lw[4], ctx->attn, lw[5], rows, E, E, 0, ctx->x));
+                              : vh_launch_linear_math(s, ctx->x, lw[4], ctx->attn, lw[5], rows, E, E, 0, ctx->x, math));
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, E, c->eps));
     OP(VIT_OP_FC1, op[2].w ? vh_launch_linear_w3(s, ctx->hid, op[2].w, ctx->y, lw[9], rows, E, F, 1, NULL)
-                         : vh_launch_linear(s, ctx->hid, lw[8], ctx->y, lw[9], rows, E, F, 1, NULL));
+                         : vh_launch_linear_math(s, ctx->hid, lw[8], ctx->y, lw[9], rows, E, F, 1, NULL, math));
     OP(VIT_OP_FC2, op[3].w ? vh_launch_linear_w3(s, ctx->x, op[3].w, ctx->hid, lw[11], rows, F, E, 0, ctx->x)
-                          : vh_launch_linear(s, ctx->x, lw[10], ctx->hid, lw[11], rows, F, E, 0, ctx->x));
+                          : vh_launch_linear_math(s, ctx->x, lw[10], ctx->hid, lw[11], rows, F, E, 0, ctx->x, math));
     return 0;
 fail:
     return rc;
@@ -1119,8 +1137,8 @@ static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct pi
     if (ctx->use_p3)   /* the fp32 path on planes: im2row writes the exact three-part split, six products per block */
         return vh_launch_patch_embed_planes3(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size,
                                              E, ctx->hid, ctx->ws_bytes);
-    return vh_launch_patch_embed_ws(s, images, w[1], w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size, E,
-                                    ctx->hid, ctx->ws_bytes);
+    return vh_launch_patch_embed_ws_math(s, images, w[1], w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size, E,
+                                         ctx->hid, ctx->ws_bytes, fp32_math(ctx));
 }
 
 /* Everything after the argument checks of vit_hip_forward_device and vit_hip_forward_device_u8 */
@@ -1187,7 +1205,8 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
     const float *final_x = cls_rows ? (const float *)ctx->qkv : ctx->x;
     const long final_stride = cls_rows ? (long)E : (long)T * E;
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, final_x, tw[0], tw[1], ctx->cls, n, E, final_stride, E, c->eps));
-    OP(VIT_OP_HEAD, vh_launch_linear(s, logits, tw[2], ctx->cls, tw[3], n, E, NC, 0, NULL));
+    /* ragged class counts (1000) run on the fp32 matrix instruction either way; a multiple of 128 follows the plan */
+    OP(VIT_OP_HEAD, vh_launch_linear_math(s, logits, tw[2], ctx->cls, tw[3], n, E, NC, 0, NULL, fp32_math(ctx)));
     if (d_probs)
         OP(VIT_OP_SOFTMAX, vh_launch_softmax(s, logits, d_probs, n, NC));
     return 0;

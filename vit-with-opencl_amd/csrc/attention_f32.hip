@@ -25,7 +25,7 @@
  *  - Both products are fp32 products; by default they run like the GEMMs' (gemm_mfma.hip):
  *    every operand fragment is split exactly into three bf16 parts in registers and the
  *    six partial products of weight >= 2^-16 go through v_mfma_f32_32x32x16_bf16 (template
- *    NPL = 3) -- the same accuracy as v_mfma_f32_32x32x2_f32 (NPL = 0, VIT_HIP_ATTN_MFMA=fp32)
+ *    NPL = 3) -- the same accuracy as v_mfma_f32_32x32x2_f32 (NPL = 0, VH_ATTN_NATIVE)
  *    at 2.67x its rate, which turns the kernel from MFMA-bound to VALU-bound.
  *  - The normalised P never leaves registers: an S^T accumulator register is exactly
  *    the B operand (k = key pair {klo, klo+4}, column = query) of the next product
@@ -42,8 +42,6 @@
 #include "kernelHandler.h"
 #include "vit_kernels.h"
 #include "fp32_split.h"
-
-#include <cstdlib>
 
 namespace {
 
@@ -421,9 +419,8 @@ int launch_k(hipStream_t st, const float *qkv, void *out, int n_images, int T, i
     return 0;
 }
 
-/* arith: 0 = fp32 MFMA, 3 = exact three-part bf16 split (default), 2 = two fp16 parts (emulation mode),
- * 1 = operands rounded to fp16 (the bf16 / fp8 GEMM modes).  out_kind: 0 = fp32 rows, 3 = three-part planes
- * (exact split), 4 = one-part (bf16) planes. */
+/* out_kind: 0 = fp32 rows, 3 = three-part planes (exact split; VH_ATTN_SPLIT3 only), 4 = one-part (bf16) planes
+ * (VH_ATTN_FP16 only); arith = the kernel's NPL. */
 template <int NKT>
 int launch(hipStream_t st, const float *qkv, void *out, int out_kind, int arith, int n_images, int T, int E, int H)
 {
@@ -432,55 +429,51 @@ int launch(hipStream_t st, const float *qkv, void *out, int out_kind, int arith,
     if (out_kind == 4)
         return launch_k<NKT, 4, 1>(st, qkv, out, n_images, T, E, H);
     switch (arith) {
-    case 0: return launch_k<NKT, 0, 0>(st, qkv, out, n_images, T, E, H);
-    case 1: return launch_k<NKT, 0, 1>(st, qkv, out, n_images, T, E, H);
-    case 2: return launch_k<NKT, 0, 2>(st, qkv, out, n_images, T, E, H);
+    case VH_ATTN_NATIVE: return launch_k<NKT, 0, 0>(st, qkv, out, n_images, T, E, H);
+    case VH_ATTN_FP16: return launch_k<NKT, 0, 1>(st, qkv, out, n_images, T, E, H);
+    case VH_ATTN_FP16X2: return launch_k<NKT, 0, 2>(st, qkv, out, n_images, T, E, H);
     default: return launch_k<NKT, 0, 3>(st, qkv, out, n_images, T, E, H);
     }
 }
 
 } // namespace
 
-static int launch_attention(vh_stream_t s, const float *qkv, void *output, int out_bf16, int arith, int n_images,
-                            int tokens, int embed_dim, int num_heads)
+extern "C" int vh_launch_attention_rows(vh_stream_t s, const float *qkv, void *output, int out_kind, int arith, int kernel,
+                                        int n_images, int tokens, int embed_dim, int num_heads)
 {
     if (!qkv || !output)
         return vh_fail(1, "vh_launch_attention: null pointer argument");
     if (n_images <= 0 || tokens <= 0 || num_heads <= 0 || embed_dim <= 0)
         return vh_fail(1, "vh_launch_attention: non-positive dimension (n=%d tokens=%d embed=%d heads=%d)",
                        n_images, tokens, embed_dim, num_heads);
-    /* Resident K/V (this file) where one head's K and V fit the LDS three times over;
-     * otherwise the streaming kernel (VIT_HIP_ATTN=tiled forces it, for tests). */
-    static int force_tiled = -1;
-    if (force_tiled < 0) {
-        const char *env = getenv("VIT_HIP_ATTN");
-        force_tiled = (env && env[0] == 't') ? 1 : 0;
-    }
-    if (embed_dim != num_heads * HD || tokens > MAX_ROWS || (force_tiled && out_bf16 < 3))   /* arith 1: fp16 operands there too */
-        return vh_attention_tiled(s, qkv, output, out_bf16, arith == 1 && out_bf16 == 0, n_images, tokens, embed_dim, num_heads);
-    static int native = -1;
-    if (native < 0) {
-        const char *env = getenv("VIT_HIP_GEMM_FP32");   /* "native": the fp32 matrix instruction here too */
-        native = (env && env[0] == 'n') ? 1 : 0;
-    }
-    if (native && arith == 3 && out_bf16 == 0)
-        arith = 0;
+    if (arith < VH_ATTN_NATIVE || arith > VH_ATTN_SPLIT3 || (kernel != VH_ATTN_AUTO && kernel != VH_ATTN_STREAMING))
+        return vh_fail(1, "vh_launch_attention: unknown arith %d or kernel %d", arith, kernel);
+    const bool resident = embed_dim == num_heads * HD && tokens <= MAX_ROWS;
+    if (out_kind != 0 && !(resident && kernel == VH_ATTN_AUTO && ((out_kind == 3 && arith == VH_ATTN_SPLIT3) ||
+                                                                  (out_kind == 4 && arith == VH_ATTN_FP16))))
+        return vh_fail(1, "vh_launch_attention: planes output (out_kind %d, arith %d) needs the resident kernel: head_dim 64, "
+                          "tokens <= %d, not streaming; three parts with the split, one part with fp16 operands",
+                       out_kind, arith, MAX_ROWS);
+    /* Resident K/V (this file) where one head's K and V fit the LDS three times over; otherwise, or when asked for,
+     * the streaming kernel (fp16 operands there too) */
+    if (!resident || kernel == VH_ATTN_STREAMING)
+        return vh_attention_tiled(s, qkv, output, 0, arith == VH_ATTN_FP16, n_images, tokens, embed_dim, num_heads);
     hipStream_t st = (hipStream_t)s;
     switch ((tokens + 31) / 32) {
-    case 1: return launch<1>(st, qkv, output, out_bf16, arith, n_images, tokens, embed_dim, num_heads);
-    case 2: return launch<2>(st, qkv, output, out_bf16, arith, n_images, tokens, embed_dim, num_heads);
-    case 3: return launch<3>(st, qkv, output, out_bf16, arith, n_images, tokens, embed_dim, num_heads);
-    case 4: return launch<4>(st, qkv, output, out_bf16, arith, n_images, tokens, embed_dim, num_heads);
-    case 5: return launch<5>(st, qkv, output, out_bf16, arith, n_images, tokens, embed_dim, num_heads);
-    case 6: return launch<6>(st, qkv, output, out_bf16, arith, n_images, tokens, embed_dim, num_heads);
-    default: return launch<7>(st, qkv, output, out_bf16, arith, n_images, tokens, embed_dim, num_heads);
+    case 1: return launch<1>(st, qkv, output, out_kind, arith, n_images, tokens, embed_dim, num_heads);
+    case 2: return launch<2>(st, qkv, output, out_kind, arith, n_images, tokens, embed_dim, num_heads);
+    case 3: return launch<3>(st, qkv, output, out_kind, arith, n_images, tokens, embed_dim, num_heads);
+    case 4: return launch<4>(st, qkv, output, out_kind, arith, n_images, tokens, embed_dim, num_heads);
+    case 5: return launch<5>(st, qkv, output, out_kind, arith, n_images, tokens, embed_dim, num_heads);
+    case 6: return launch<6>(st, qkv, output, out_kind, arith, n_images, tokens, embed_dim, num_heads);
+    default: return launch<7>(st, qkv, output, out_kind, arith, n_images, tokens, embed_dim, num_heads);
     }
 }
 
 extern "C" int vh_launch_attention(vh_stream_t s, const float *qkv, float *output, int n_images,
                                    int tokens, int embed_dim, int num_heads)
 {
-    return launch_attention(s, qkv, output, 0, 3, n_images, tokens, embed_dim, num_heads);
+    return vh_launch_attention_rows(s, qkv, output, 0, VH_ATTN_SPLIT3, VH_ATTN_AUTO, n_images, tokens, embed_dim, num_heads);
 }
 
 /* The fp32 attention writing its output as the three-part split planes [E/32][3][n_images*tokens][32] that
@@ -488,9 +481,7 @@ extern "C" int vh_launch_attention(vh_stream_t s, const float *qkv, float *outpu
 extern "C" int vh_launch_attention_p3(vh_stream_t s, const float *qkv, void *out_planes, int n_images,
                                       int tokens, int embed_dim, int num_heads)
 {
-    if (embed_dim != num_heads * HD || tokens > MAX_ROWS)
-        return vh_fail(1, "vh_launch_attention_p3: needs head_dim 64 and tokens <= %d", MAX_ROWS);
-    return launch_attention(s, qkv, out_planes, 3, 3, n_images, tokens, embed_dim, num_heads);
+    return vh_launch_attention_rows(s, qkv, out_planes, 3, VH_ATTN_SPLIT3, VH_ATTN_AUTO, n_images, tokens, embed_dim, num_heads);
 }
 
 /* The bf16-operand mode's attention writing one-part planes [E/32][1][n_images*tokens][32] (bf16) for
@@ -499,9 +490,7 @@ extern "C" int vh_launch_attention_p3(vh_stream_t s, const float *qkv, void *out
 extern "C" int vh_launch_attention_planes_bf16(vh_stream_t s, const float *qkv, void *out_planes, int n_images,
                                                int tokens, int embed_dim, int num_heads)
 {
-    if (embed_dim != num_heads * HD || tokens > MAX_ROWS)
-        return vh_fail(1, "vh_launch_attention_planes_bf16: needs head_dim 64 and tokens <= %d", MAX_ROWS);
-    return launch_attention(s, qkv, out_planes, 4, 1, n_images, tokens, embed_dim, num_heads);
+    return vh_launch_attention_rows(s, qkv, out_planes, 4, VH_ATTN_FP16, VH_ATTN_AUTO, n_images, tokens, embed_dim, num_heads);
 }
 
 /* The emulation mode's attention: Q.K^T and P.V on two fp16 parts / three products (kernelHandler.h,
@@ -509,12 +498,12 @@ extern "C" int vh_launch_attention_planes_bf16(vh_stream_t s, const float *qkv, 
 extern "C" int vh_launch_attention_h2(vh_stream_t s, const float *qkv, float *output, int n_images,
                                       int tokens, int embed_dim, int num_heads)
 {
-    return launch_attention(s, qkv, output, 0, 2, n_images, tokens, embed_dim, num_heads);
+    return vh_launch_attention_rows(s, qkv, output, 0, VH_ATTN_FP16X2, VH_ATTN_AUTO, n_images, tokens, embed_dim, num_heads);
 }
 
 /* fp32 in, fp32 out, Q / K / V / P rounded to fp16 for the two products: the fp8-operand GEMM mode. */
 extern "C" int vh_launch_attention_f16(vh_stream_t s, const float *qkv, float *output, int n_images,
                                        int tokens, int embed_dim, int num_heads)
 {
-    return launch_attention(s, qkv, output, 0, 1, n_images, tokens, embed_dim, num_heads);
+    return vh_launch_attention_rows(s, qkv, output, 0, VH_ATTN_FP16, VH_ATTN_AUTO, n_images, tokens, embed_dim, num_heads);
 }

@@ -37,30 +37,17 @@
  */
 #include "kernelHandler.h"
 #include "vit_kernels.h"
+#include "fp32_split.h"
 #include "gemm_common.h"
 
 namespace {
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int MAX_LDS = 160 * 1024;
-
-__device__ __forceinline__ half4 to_half4(const f32x4 &v)
-{
-    half4 h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float x = v[e];
-        asm("" : "+v"(x));   /* no multiply + convert fusion: rounded twice everywhere (fp32_split.h, split_parts) */
-        h[e] = (_Float16)x;
-    }
-    return h;
-}
 
 template <int HD, int NJ, int NW, int OUTK> /* NJ 16-key tiles (T <= 16 NJ), NW waves; two rounds of NW 16-query tiles cover T <= 32 NW */
 __global__ __launch_bounds__(64 * NW) void attention_h16_kernel(const char *__restrict__ qkvh, float *__restrict__ out,

@@ -38,7 +38,6 @@ namespace {
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
@@ -48,18 +47,6 @@ constexpr int MAX_LDS = 160 * 1024;
 
 template <int HD> constexpr int planes_staged() { return HD % 32 == 0 ? HD / 32 : (HD + 16 + 31) / 32; }
 template <int HD, int NPL> constexpr size_t lds_bytes() { return (size_t)2 * 2 * planes_staged<HD>() * NPL * KC * 64; }
-
-__device__ __forceinline__ half4 to_half4(const f32x4 &v)
-{
-    half4 h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float x = v[e];
-        asm("" : "+v"(x));   /* no multiply + convert fusion (fp32_split.h, split_parts): rounded twice everywhere */
-        h[e] = (_Float16)x;
-    }
-    return h;
-}
 
 template <int HD, int NPL>
 __global__ __launch_bounds__(64 * NW) void attention_long_kernel(const char *__restrict__ qkv, float *__restrict__ out,

@@ -27,35 +27,13 @@
  */
 #include "kernelHandler.h"
 #include "vit_kernels.h"
+#include "fp32_split.h"
 
 namespace {
 
 constexpr int KC = 64;   /* keys per LDS chunk (four 16-key MFMA tiles) */
 constexpr int TPC = KC / 16;
 constexpr int QB_MIN = 64;   /* queries per workgroup = 16 x NW waves, NW = 4 or 6 (whichever leaves fewer idle waves in the last block) */
-
-/* Workgroup barrier for LDS hand-overs only: this wave's LDS operations have completed (lgkmcnt), global loads stay
- * in flight.  __syncthreads() is a full workgroup fence -- it also drains vmcnt, i.e. it waits at every chunk step
- * for the prefetch issued a few hundred cycles earlier, which put the whole load latency into each of the 18 steps. */
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ half4 to_half4(const f32x4 &v)
-{
-    half4 h;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float x = v[e];
-        asm("" : "+v"(x));   /* no multiply + convert fusion (fp32_split.h, split_parts): rounded twice everywhere */
-        h[e] = (_Float16)x;
-    }
-    return h;
-}
 
 /* LOWP (the reduced-precision GEMM modes only): Q, K, V and the probabilities are rounded to fp16 in registers and
  * the four contraction steps of a lane group become ONE v_mfma_f32_16x16x16_f16 -- its lane layout (row l & 15,

@@ -26,14 +26,6 @@ constexpr int RD_WAVES = 16;              /* waves per workgroup of readout_rows
 constexpr int RD_ROWS = 2 * RD_WAVES;     /* patch rows per workgroup */
 constexpr int RD_TILE_STRIDE = 257;       /* dwords per row of the transposition tile: 256 columns + 1 */
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        v += __shfl_xor(v, m);
-    return v;
-}
-
 /* The row in x[], normalised in place: the arithmetic and summation order of layernorm_kernel (rowops.hip) */
 template <int NV, bool FULL>
 __device__ __forceinline__ void normalise_row(f32x4 (&x)[NV], const float *__restrict__ gamma, const float *__restrict__ beta,

@@ -87,6 +87,19 @@ __device__ __forceinline__ void split_parts(const f32x4 &u, const f32x4 &v, half
         o[0][e] = (_Float16)x;
     }
 }
+/* Four values rounded to fp16 (the fp16-operand attention kernels), rounded twice like split_parts above */
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ half4 to_half4(const f32x4 &v)
+{
+    half4 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float x = v[e];
+        asm("" : "+v"(x));   /* no multiply + convert fusion */
+        h[e] = (_Float16)x;
+    }
+    return h;
+}
 __device__ __forceinline__ f32x4 mfma_part(bf16x8 w, bf16x8 a, f32x4 c)
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, a, c, 0, 0, 0);

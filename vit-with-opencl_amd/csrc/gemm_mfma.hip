@@ -13,7 +13,7 @@
  *   fp32, default   exact 3-way bf16 split of both operands in registers, six v_mfma_f32_16x16x32_bf16 per
  *                   product block: vh_launch_linear on raw fp32 weights and the patch embedding (im2row on load);
  *                   with the weights pre-split into planes (vh_launch_linear_w3) only the activations are split
- *   fp32, native    v_mfma_f32_32x32x2_f32: the ragged-N classifier, and everything under VIT_HIP_GEMM_FP32=native
+ *   fp32, native    v_mfma_f32_32x32x2_f32: the ragged-N classifier, and everything asked for with VH_FP32_NATIVE
  *   fp16 pairs      vh_launch_linear_h2 (opt-in emulation mode: two fp16 parts, three products)
  * Two kernel templates share one staging scheme: gemm_mf16_kernel (the 16x16x32 shapes) and
  * gemm_f32_kernel (native fp32, ragged N).
@@ -46,16 +46,14 @@
 #include "gemm_common.h"
 
 #include <cstdint>
-#include <cstdlib>
 
 namespace {
 
 constexpr int BK = 32;   /* 32-bit words per LDS row: 32 fp32 or 64 bf16 K elements per K step */
-
+constexpr int ES = 4;    /* bytes per operand element */
 
 enum { A_ROWS = 0, A_PATCH = 1 };
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_PATCH = 3 };
-enum { K_F32 = 0 };   /* element kind of GEMM operands / output */
 #define SGB_M 1   /* scheduled split loop: SGB_M MFMAs, then SGB_V VALU instructions, repeated (measured best of 1:1 .. 3:6) */
 #define SGB_V 2
 
@@ -97,12 +95,11 @@ struct GemmParams {
 };
 
 /* The native fp32 matrix instruction (v_mfma_f32_32x32x2_f32: exact fp32, 1/16 of the bf16 rate): the
- * classifier head (ragged N), and every projection under VIT_HIP_GEMM_FP32=native. */
+ * classifier head (ragged N), and every projection launched with VH_FP32_NATIVE. */
 template <class T, int AMODE, int EPI, bool NGUARD>
 __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_f32_kernel(const GemmParams p)
 {
     constexpr int BM = T::BM, BN = T::BN, IT = T::IT, JT = T::JT;
-    constexpr int ES = 4;                /* operand element size */
     constexpr int KE = 128 / ES;         /* K elements per step (one 128-byte LDS row) */
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -266,7 +263,7 @@ __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_f32_kernel(
 /* Operand staging shared by the 16x16x32 kernel below: per-lane source addresses of the
  * 8-row LDS-DMA pieces (same LDS image as gemm_f32_kernel: 128-byte rows, chunk c of row r
  * at c ^ ((r >> 1) & 7)). */
-template <class T, int AMODE, int ES, int NPL = 0>
+template <class T, int AMODE, int NPL = 0>
 struct Staging {
     static constexpr int NWP = T::chw(NPL);               /* W pieces per wave */
     static constexpr int STAGE = T::stage_f(NPL);
@@ -349,15 +346,14 @@ struct Staging {
  * row: lane l holds out[m = i*16 + (l & 15)][n = j*16 + 4*(l >> 4) + r], r = 0..3, and the
  * bias, residual, position-embedding reads and the store are one 16-byte access each.
  * Operand fragment: lane l holds k = 8*(l >> 4) .. +7 of row (l & 15), natural k order. */
-template <class T, int AMODE, int EPI, int INK, int OUTK, bool SCHED = false, int NPL = 0>
+template <class T, int AMODE, int EPI, int NPL = 0>
 __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_mf16_kernel(const GemmParams p)
 {
     constexpr int BM = T::BM, BN = T::BN;
     constexpr int IT = BM / T::WM / 16, JT = BN / T::WN / 16;   /* 16x16 blocks per wave */
     constexpr int IC = IT < 4 ? IT : 4;                          /* A fragments split at a time */
-    constexpr int ES = 4;
     constexpr int KE = 128 / ES;
-        static_assert(IT % IC == 0, "row blocks per wave");
+    static_assert(IT % IC == 0, "row blocks per wave");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
@@ -368,9 +364,9 @@ __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_mf16_kernel
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / T::WN, wn = wave % T::WN, l15 = lane & 15, q = lane >> 4;
 
-    static_assert(NPL == 0 || (SCHED && INK == K_F32 && IT < JT), "pre-split weight planes: scheduled fp32 loop, wave tile wider along N");
+    static_assert(NPL == 0 || IT < JT, "pre-split weight planes: wave tile wider along N");
     constexpr int STG = T::stage_f(NPL);   /* floats per LDS stage */
-    Staging<T, AMODE, ES, NPL> stg;
+    Staging<T, AMODE, NPL> stg;
     stg.init(p, m0, n0, wave, lane);
 
     f32x4 acc[IT][JT];
@@ -389,66 +385,61 @@ __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_mf16_kernel
     const float *a_lane = smem + (wm * 16 * IT + l15) * BK;
     const float *w_lane = smem + BM * BK + (wn * 16 * JT + l15) * BK;
 
-
     auto compute = [&](int stage) {
         const float *ab = a_lane + stage * STG, *wb = w_lane + stage * STG;
-        if constexpr (SCHED) {
-            /* Fragment-grained pipeline inside the K step: group i issues the LDS reads of A
-             * fragment i+2, splits fragment i+1 and runs the 6*JT MFMAs of fragment i, the
-             * MFMA / VALU interleave pinned with sched_group_barrier (left alone, the compiler
-             * emits the splits of several fragments, then their MFMAs, and the matrix pipe
-             * idles during the former).  The W splits and the first A split stay exposed
-             * (hiding them too -- a per-W-fragment ramp, or carrying the next step's W across
-             * the barrier -- measured slower). */
-            static_assert(IT >= 2, "pipeline depth");
-            const int k0 = 4 * ((2 * q) ^ swz), k1 = 4 * ((2 * q + 1) ^ swz);
-            bf16x8 w0[JT], w1[JT], w2[JT], c0, c1, c2;
-            f32x4 ra[2][2];
-            ra[0][0] = *reinterpret_cast<const f32x4 *>(ab + k0);
-            ra[0][1] = *reinterpret_cast<const f32x4 *>(ab + k1);
-            ra[1][0] = *reinterpret_cast<const f32x4 *>(ab + 16 * BK + k0);
-            ra[1][1] = *reinterpret_cast<const f32x4 *>(ab + 16 * BK + k1);
+        /* Fragment-grained pipeline inside the K step: group i issues the LDS reads of A
+         * fragment i+2, splits fragment i+1 and runs the 6*JT MFMAs of fragment i, the
+         * MFMA / VALU interleave pinned with sched_group_barrier (left alone, the compiler
+         * emits the splits of several fragments, then their MFMAs, and the matrix pipe
+         * idles during the former).  The W splits and the first A split stay exposed
+         * (hiding them too -- a per-W-fragment ramp, or carrying the next step's W across
+         * the barrier -- measured slower). */
+        static_assert(IT >= 2, "pipeline depth");
+        const int k0 = 4 * ((2 * q) ^ swz), k1 = 4 * ((2 * q + 1) ^ swz);
+        bf16x8 w0[JT], w1[JT], w2[JT], c0, c1, c2;
+        f32x4 ra[2][2];
+        ra[0][0] = *reinterpret_cast<const f32x4 *>(ab + k0);
+        ra[0][1] = *reinterpret_cast<const f32x4 *>(ab + k1);
+        ra[1][0] = *reinterpret_cast<const f32x4 *>(ab + 16 * BK + k0);
+        ra[1][1] = *reinterpret_cast<const f32x4 *>(ab + 16 * BK + k1);
 #pragma unroll
-            for (int j = 0; j < JT; ++j)
-                split8(*reinterpret_cast<const f32x4 *>(wb + j * 16 * BK + k0),
-                       *reinterpret_cast<const f32x4 *>(wb + j * 16 * BK + k1), w0[j], w1[j], w2[j]);
-            split8(ra[0][0], ra[0][1], c0, c1, c2);
-            __builtin_amdgcn_sched_barrier(0);
+        for (int j = 0; j < JT; ++j)
+            split8(*reinterpret_cast<const f32x4 *>(wb + j * 16 * BK + k0),
+                   *reinterpret_cast<const f32x4 *>(wb + j * 16 * BK + k1), w0[j], w1[j], w2[j]);
+        split8(ra[0][0], ra[0][1], c0, c1, c2);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < IT; ++i) {
-                bf16x8 n0, n1, n2;
-                if (i + 1 < IT)
-                    split8(ra[(i + 1) & 1][0], ra[(i + 1) & 1][1], n0, n1, n2);
-                if (i + 2 < IT) {
-                    ra[i & 1][0] = *reinterpret_cast<const f32x4 *>(ab + (i + 2) * 16 * BK + k0);
-                    ra[i & 1][1] = *reinterpret_cast<const f32x4 *>(ab + (i + 2) * 16 * BK + k1);
-                }
-#pragma unroll
-                for (int t = 0; t < 6; ++t)
-#pragma unroll
-                    for (int j = 0; j < JT; ++j) { /* per accumulator: smallest terms first */
-                        const bf16x8 wp = (t == 0 || t == 3 || t == 5) ? w0[j] : (t == 1) ? w2[j] : w1[j];
-                        const bf16x8 ap = (t == 0) ? c2 : (t == 2 || t == 3) ? c1 : c0;
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp, ap, acc[i][j], 0, 0, 0);
-                    }
-                if (i + 1 < IT) {
-                    if (i + 2 < IT)
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    constexpr int VPM = JT >= 8 ? 1 : SGB_V;   /* ~44 split instructions over the group's MFMAs */
-#pragma unroll
-                    for (int r = 0; r < (6 * JT - 2) / SGB_M; ++r) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, SGB_M, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 6 * JT - (6 * JT - 2) / SGB_M * SGB_M, 0);
-                    c0 = n0;
-                    c1 = n1;
-                    c2 = n2;
-                }
-                __builtin_amdgcn_sched_barrier(0);
+        for (int i = 0; i < IT; ++i) {
+            bf16x8 n0, n1, n2;
+            if (i + 1 < IT)
+                split8(ra[(i + 1) & 1][0], ra[(i + 1) & 1][1], n0, n1, n2);
+            if (i + 2 < IT) {
+                ra[i & 1][0] = *reinterpret_cast<const f32x4 *>(ab + (i + 2) * 16 * BK + k0);
+                ra[i & 1][1] = *reinterpret_cast<const f32x4 *>(ab + (i + 2) * 16 * BK + k1);
             }
-        } else {
-            static_assert(SCHED, "fp32 operands use the scheduled loop");
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int j = 0; j < JT; ++j) { /* per accumulator: smallest terms first */
+                    const bf16x8 wp = (t == 0 || t == 3 || t == 5) ? w0[j] : (t == 1) ? w2[j] : w1[j];
+                    const bf16x8 ap = (t == 0) ? c2 : (t == 2 || t == 3) ? c1 : c0;
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp, ap, acc[i][j], 0, 0, 0);
+                }
+            if (i + 1 < IT) {
+                if (i + 2 < IT)
+                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                constexpr int VPM = JT >= 8 ? 1 : SGB_V;   /* ~44 split instructions over the group's MFMAs */
+#pragma unroll
+                for (int r = 0; r < (6 * JT - 2) / SGB_M; ++r) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, SGB_M, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, 6 * JT - (6 * JT - 2) / SGB_M * SGB_M, 0);
+                c0 = n0;
+                c1 = n1;
+                c2 = n2;
+            }
+            __builtin_amdgcn_sched_barrier(0);
         }
     };
 
@@ -612,13 +603,13 @@ __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_mf16_kernel
     }
 }
 
-template <class T, int AMODE, int EPI, int INK, int OUTK, bool SCHED = false, int NPL = 0>
+template <class T, int AMODE, int EPI, int NPL = 0>
 int launch_mf16(hipStream_t st, GemmParams p)
 {
-    VH_SET_LDS_ONCE((gemm_mf16_kernel<T, AMODE, EPI, INK, OUTK, SCHED, NPL>), T::lds(NPL));
+    VH_SET_LDS_ONCE((gemm_mf16_kernel<T, AMODE, EPI, NPL>), T::lds(NPL));
     p.mtiles = (p.M + T::BM - 1) / T::BM;
     p.ntiles = p.N / T::BN;
-    hipLaunchKernelGGL((gemm_mf16_kernel<T, AMODE, EPI, INK, OUTK, SCHED, NPL>), dim3(p.mtiles * p.ntiles),
+    hipLaunchKernelGGL((gemm_mf16_kernel<T, AMODE, EPI, NPL>), dim3(p.mtiles * p.ntiles),
                        dim3(T::NT), T::lds(NPL), st, p);
     VH_LAUNCH_CHECK("gemm_mf16_kernel");
     return 0;
@@ -656,28 +647,17 @@ using Tile8 = Tile<256, 256, 4, 2>; /*  8 waves of 64x128 (pre-split weights: fe
 using Tile9 = Tile<128, 128, 4, 1>; /*  4 waves of 32x128, 2 workgroups per CU */
 using TileS = Tile<32, 64, 1, 2>;   /*  2 waves of 32x32: skinny problems (the classifier at batch <= 512) */
 
-/* fp32 products: the exact 3-way bf16 split on the bf16 cores (default), or the native
- * fp32 MFMA (VIT_HIP_GEMM_FP32=native).  Both give fp32-level results (same measured
- * logit parity); the split is ~1.4x faster end to end. */
-bool use_split3()
-{
-    static int v = -1;
-    if (v < 0) {
-        const char *env = getenv("VIT_HIP_GEMM_FP32");
-        v = (env && env[0] == 'n') ? 0 : 1;
-    }
-    return v == 1;
-}
-
 bool aligned16(const GemmParams &p)
 {
     return (((uintptr_t)p.C | (uintptr_t)p.bias | (uintptr_t)p.R | (uintptr_t)p.pos) & 15) == 0;
 }
 
 /* fp32 operands, both split inside the K loop (vh_launch_linear on raw fp32 weights, and the patch
- * embedding): 256x256 tiles where N allows and there is enough work, else 128x128. */
+ * embedding): 256x256 tiles where N allows and there is enough work, else 128x128.  fp32_math: the exact
+ * 3-way bf16 split on the bf16 cores (VH_FP32_SPLIT3), or the native fp32 MFMA (VH_FP32_NATIVE).  Both give
+ * fp32-level results (same measured logit parity); the split is ~1.4x faster end to end. */
 template <int AMODE, int EPI>
-int launch(hipStream_t st, const GemmParams &p)
+int launch(hipStream_t st, const GemmParams &p, int fp32_math)
 {
     const bool big = p.N % 256 == 0 && p.M >= 4096 && !(EPI == EPI_RESID && p.K < 2048);
     if (p.N % 128 != 0) {                    /* ragged N (the classifier): the guarded tiles on the native fp32 MFMA */
@@ -688,36 +668,56 @@ int launch(hipStream_t st, const GemmParams &p)
             return launch_tile<TileS, AMODE, EPI, true>(st, p);
         return launch_tile<Tile0, AMODE, EPI, true>(st, p);
     }
-    if (use_split3() && aligned16(p))
-        return big ? launch_mf16<Tile3, AMODE, EPI, K_F32, K_F32, true>(st, p)
-                   : launch_mf16<Tile1, AMODE, EPI, K_F32, K_F32, true>(st, p);
+    if (fp32_math == VH_FP32_SPLIT3 && aligned16(p))
+        return big ? launch_mf16<Tile3, AMODE, EPI>(st, p) : launch_mf16<Tile1, AMODE, EPI>(st, p);
     return big ? launch_tile<Tile4, AMODE, EPI, false>(st, p) : launch_tile<Tile0, AMODE, EPI, false>(st, p);
+}
+
+/* Argument checks and GemmParams shared by the rows launchers.  planes: the weights come pre-split
+ * (vh_launch_linear_w3 / _h2), which takes whole 128-column tiles and 16-byte aligned pointers. */
+int linear_params(GemmParams &p, const char *who, bool planes, float *output, const void *weight, const float *input,
+                  const float *bias, int rowA, int colA, int colB, int doGelu, const float *residual)
+{
+    if (!output || !weight || !input || !bias)
+        return vh_fail(1, "%s: null pointer argument", who);
+    if (rowA <= 0 || colA <= 0 || colB <= 0)
+        return vh_fail(1, "%s: non-positive dimension (%d,%d,%d)", who, rowA, colA, colB);
+    if (colA % BK != 0)
+        return vh_fail(1, "%s: colA=%d must be a multiple of %d", who, colA, BK);
+    if (planes && colB % 128 != 0)
+        return vh_fail(1, "%s: colB=%d must be a multiple of 128", who, colB);
+    if (doGelu && residual)
+        return vh_fail(1, "%s: GELU and residual together are not a model op", who);
+    p = GemmParams{};
+    p.A = input; p.W = weight; p.bias = bias; p.R = residual; p.C = output;
+    p.M = rowA; p.N = colB; p.K = colA;
+    if (planes && (!aligned16(p) || (((uintptr_t)weight | (uintptr_t)input) & 15) != 0))
+        return vh_fail(1, "%s: pointers must be 16-byte aligned", who);
+    return 0;
 }
 
 } // namespace
 
-extern "C" int vh_launch_linear(vh_stream_t s, float *output, const float *weight,
-                                const float *input, const float *bias, int rowA, int colA,
-                                int colB, int doGelu, const float *residual)
+extern "C" int vh_launch_linear_math(vh_stream_t s, float *output, const float *weight, const float *input, const float *bias,
+                                     int rowA, int colA, int colB, int doGelu, const float *residual, int fp32_math)
 {
-    if (!output || !weight || !input || !bias)
-        return vh_fail(1, "vh_launch_linear: null pointer argument");
-    if (rowA <= 0 || colA <= 0 || colB <= 0)
-        return vh_fail(1, "vh_launch_linear: non-positive dimension (%d,%d,%d)", rowA, colA, colB);
-    if (colA % BK != 0)
-        return vh_fail(1, "vh_launch_linear: colA=%d must be a multiple of %d", colA, BK);
-    if (doGelu && residual)
-        return vh_fail(1, "vh_launch_linear: GELU and residual together are not a model op");
-
-    GemmParams p = {};
-    p.A = input; p.W = weight; p.bias = bias; p.R = residual; p.C = output;
-    p.M = rowA; p.N = colB; p.K = colA;
+    if (fp32_math != VH_FP32_SPLIT3 && fp32_math != VH_FP32_NATIVE)
+        return vh_fail(1, "vh_launch_linear: unknown fp32_math %d", fp32_math);
+    GemmParams p;
+    if (int rc = linear_params(p, "vh_launch_linear", false, output, weight, input, bias, rowA, colA, colB, doGelu, residual))
+        return rc;
     hipStream_t st = (hipStream_t)s;
     if (doGelu)
-        return launch<A_ROWS, EPI_GELU>(st, p);
+        return launch<A_ROWS, EPI_GELU>(st, p, fp32_math);
     if (residual)
-        return launch<A_ROWS, EPI_RESID>(st, p);
-    return launch<A_ROWS, EPI_NONE>(st, p);
+        return launch<A_ROWS, EPI_RESID>(st, p, fp32_math);
+    return launch<A_ROWS, EPI_NONE>(st, p, fp32_math);
+}
+
+extern "C" int vh_launch_linear(vh_stream_t s, float *output, const float *weight, const float *input,
+                                const float *bias, int rowA, int colA, int colB, int doGelu, const float *residual)
+{
+    return vh_launch_linear_math(s, output, weight, input, bias, rowA, colA, colB, doGelu, residual, VH_FP32_SPLIT3);
 }
 
 namespace {
@@ -751,10 +751,6 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ i
         atomicMax(reinterpret_cast<unsigned *>(amax), __builtin_bit_cast(unsigned, mx));
 }
 
-} // namespace
-
-namespace {
-
 /* fp32 [n] -> three bf16 planes [3][n]: x = p0 + p1 + p2 exactly (the SPLIT3 parts), done once
  * for the weights so that the GEMM's inner loop splits only the activations. */
 __global__ void split3_planes_kernel(const float *__restrict__ in, __bf16 *__restrict__ out, int N, int K)
@@ -775,10 +771,6 @@ __global__ void split3_planes_kernel(const float *__restrict__ in, __bf16 *__res
     out[o + 2 * plane] = (__bf16)r2;
 }
 
-} // namespace
-
-namespace {
-
 /* Pre-split-weight GEMM on the tile the shape wants, with the last, partly filled scheduling round
  * of 256x256 tiles handed to 128x128 tiles instead: with one
  * workgroup per CU a grid of r.f rounds costs ceil(r.f) rounds; the remainder rows as quarter-size
@@ -787,13 +779,13 @@ template <int EPI, int NPL>
 int launch_planes(hipStream_t st, GemmParams p, bool prefer_small)
 {
     if (!(p.N % 256 == 0 && p.M >= 4096 && !prefer_small))
-        return launch_mf16<Tile9, A_ROWS, EPI, K_F32, K_F32, true, NPL>(st, p);
+        return launch_mf16<Tile9, A_ROWS, EPI, NPL>(st, p);
     const int num_cus = vh_device_cus(vh_current_device());
     const int ntiles = p.N / 256, mtiles = (p.M + 255) / 256;
     const long tiles = (long)mtiles * ntiles, full = tiles / num_cus, rem = tiles % num_cus;
     const int rows_big = (int)(full * num_cus / ntiles) * 256;
     if (full < 1 || rem == 0 || 4 * rem > 3 * num_cus || rows_big <= 0 || rows_big >= p.M)
-        return launch_mf16<Tile8, A_ROWS, EPI, K_F32, K_F32, true, NPL>(st, p);
+        return launch_mf16<Tile8, A_ROWS, EPI, NPL>(st, p);
     GemmParams big = p, rest = p;
     big.M = rows_big;
     rest.M = p.M - rows_big;
@@ -801,8 +793,21 @@ int launch_planes(hipStream_t st, GemmParams p, bool prefer_small)
     rest.C = static_cast<float *>(p.C) + (size_t)rows_big * p.N;
     if (p.R)
         rest.R = p.R + (size_t)rows_big * p.N;
-    const int rc = launch_mf16<Tile8, A_ROWS, EPI, K_F32, K_F32, true, NPL>(st, big);
-    return rc ? rc : launch_mf16<Tile9, A_ROWS, EPI, K_F32, K_F32, true, NPL>(st, rest);
+    const int rc = launch_mf16<Tile8, A_ROWS, EPI, NPL>(st, big);
+    return rc ? rc : launch_mf16<Tile9, A_ROWS, EPI, NPL>(st, rest);
+}
+
+/* vh_launch_linear_w3 (NPL 3) and _h2 (NPL 2) behind their checks */
+template <int NPL>
+int launch_planes_epi(vh_stream_t s, const GemmParams &p, int doGelu)
+{
+    hipStream_t st = (hipStream_t)s;
+    const bool prefer_small = p.R && p.K < 2048;   /* measured: the N = 768, K = 768 out-projection */
+    if (doGelu)
+        return launch_planes<EPI_GELU, NPL>(st, p, prefer_small);
+    if (p.R)
+        return launch_planes<EPI_RESID, NPL>(st, p, prefer_small);
+    return launch_planes<EPI_NONE, NPL>(st, p, prefer_small);
 }
 
 } // namespace
@@ -851,48 +856,22 @@ extern "C" int vh_launch_linear_h2(vh_stream_t s, float *output, const void *wei
                                    const float *input, const float *bias, int rowA, int colA, int colB, int doGelu,
                                    const float *residual)
 {
-    if (!output || !weight_planes || !input || !bias)
-        return vh_fail(1, "vh_launch_linear_h2: null pointer argument");
-    if (rowA <= 0 || colA <= 0 || colB <= 0 || colA % BK != 0 || colB % 128 != 0 || !(weight_scale > 0.0f))
-        return vh_fail(1, "vh_launch_linear_h2: needs colA %% 32 == 0, colB %% 128 == 0, scale > 0 (%d,%d,%d)", rowA, colA, colB);
-    if (doGelu && residual)
-        return vh_fail(1, "vh_launch_linear_h2: GELU and residual together are not a model op");
-    GemmParams p = {};
-    p.A = input; p.W = weight_planes; p.bias = bias; p.R = residual; p.C = output;
-    p.M = rowA; p.N = colB; p.K = colA;
+    if (!(weight_scale > 0.0f))
+        return vh_fail(1, "vh_launch_linear_h2: weight_scale must be positive");
+    GemmParams p;
+    if (int rc = linear_params(p, "vh_launch_linear_h2", true, output, weight_planes, input, bias, rowA, colA, colB, doGelu, residual))
+        return rc;
     p.w_scale = weight_scale; p.inv_w_scale = 1.0f / weight_scale;
-    if (!aligned16(p) || (((uintptr_t)weight_planes | (uintptr_t)input) & 15) != 0)
-        return vh_fail(1, "vh_launch_linear_h2: pointers must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)s;
-    const bool prefer_small = residual && colA < 2048;
-    if (doGelu)
-        return launch_planes<EPI_GELU, 2>(st, p, prefer_small);
-    if (residual)
-        return launch_planes<EPI_RESID, 2>(st, p, prefer_small);
-    return launch_planes<EPI_NONE, 2>(st, p, prefer_small);
+    return launch_planes_epi<2>(s, p, doGelu);
 }
 
 extern "C" int vh_launch_linear_w3(vh_stream_t s, float *output, const void *weight_planes, const float *input,
                                    const float *bias, int rowA, int colA, int colB, int doGelu, const float *residual)
 {
-    if (!output || !weight_planes || !input || !bias)
-        return vh_fail(1, "vh_launch_linear_w3: null pointer argument");
-    if (rowA <= 0 || colA <= 0 || colB <= 0 || colA % BK != 0 || colB % 128 != 0)
-        return vh_fail(1, "vh_launch_linear_w3: needs colA %% 32 == 0 and colB %% 128 == 0 (%d,%d,%d)", rowA, colA, colB);
-    if (doGelu && residual)
-        return vh_fail(1, "vh_launch_linear_w3: GELU and residual together are not a model op");
-    GemmParams p = {};
-    p.A = input; p.W = weight_planes; p.bias = bias; p.R = residual; p.C = output;
-    p.M = rowA; p.N = colB; p.K = colA;
-    if (!aligned16(p) || (((uintptr_t)weight_planes | (uintptr_t)input) & 15) != 0)
-        return vh_fail(1, "vh_launch_linear_w3: pointers must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)s;
-    const bool prefer_small = residual && colA < 2048;   /* measured: the N = 768, K = 768 out-projection */
-    if (doGelu)
-        return launch_planes<EPI_GELU, 3>(st, p, prefer_small);
-    if (residual)
-        return launch_planes<EPI_RESID, 3>(st, p, prefer_small);
-    return launch_planes<EPI_NONE, 3>(st, p, prefer_small);
+    GemmParams p;
+    if (int rc = linear_params(p, "vh_launch_linear_w3", true, output, weight_planes, input, bias, rowA, colA, colB, doGelu, residual))
+        return rc;
+    return launch_planes_epi<3>(s, p, doGelu);
 }
 
 extern "C" int vh_launch_absmax(vh_stream_t s, const float *input, size_t count, float *amax)
@@ -966,12 +945,13 @@ extern "C" size_t vh_patch_embed_workspace(int n_images, int in_chans, int img_s
     return ((size_t)n_images * grid * grid + (size_t)embed_dim) * Kp * sizeof(float);
 }
 
-extern "C" int vh_launch_patch_embed_ws(vh_stream_t s, const float *images, const float *conv_w,
-                                        const float *conv_b, const float *cls_token,
-                                        const float *pos_embed, float *tokens, int n_images,
-                                        int in_chans, int img_size, int patch_size, int embed_dim,
-                                        void *workspace, size_t workspace_bytes)
+extern "C" int vh_launch_patch_embed_ws_math(vh_stream_t s, const float *images, const float *conv_w, const float *conv_b,
+                                             const float *cls_token, const float *pos_embed, float *tokens, int n_images,
+                                             int in_chans, int img_size, int patch_size, int embed_dim, void *workspace,
+                                             size_t workspace_bytes, int fp32_math)
 {
+    if (fp32_math != VH_FP32_SPLIT3 && fp32_math != VH_FP32_NATIVE)
+        return vh_fail(1, "vh_launch_patch_embed: unknown fp32_math %d", fp32_math);
     if (!images || !conv_w || !conv_b || !cls_token || !pos_embed || !tokens)
         return vh_fail(1, "vh_launch_patch_embed: null pointer argument");
     if (n_images <= 0 || in_chans <= 0 || img_size <= 0 || patch_size <= 0 || embed_dim <= 0 ||
@@ -995,7 +975,7 @@ extern "C" int vh_launch_patch_embed_ws(vh_stream_t s, const float *images, cons
     if (int rc = vh_cls_rows(st, cls_token, pos_embed, tokens, n_images, p.tokens, embed_dim))
         return rc;
     if (direct)
-        return launch<A_PATCH, EPI_PATCH>(st, p);
+        return launch<A_PATCH, EPI_PATCH>(st, p, fp32_math);
 
     const int Kp = (K + BK - 1) / BK * BK;
     float *rows = static_cast<float *>(workspace), *wpad = rows + (size_t)p.M * Kp;
@@ -1007,7 +987,16 @@ extern "C" int vh_launch_patch_embed_ws(vh_stream_t s, const float *images, cons
                        embed_dim, K, Kp);
     VH_LAUNCH_CHECK("pad_rows_kernel");
     p.A = rows; p.W = wpad; p.K = Kp;
-    return launch<A_ROWS, EPI_PATCH>(st, p);
+    return launch<A_ROWS, EPI_PATCH>(st, p, fp32_math);
+}
+
+extern "C" int vh_launch_patch_embed_ws(vh_stream_t s, const float *images, const float *conv_w, const float *conv_b,
+                                        const float *cls_token, const float *pos_embed, float *tokens, int n_images,
+                                        int in_chans, int img_size, int patch_size, int embed_dim, void *workspace,
+                                        size_t workspace_bytes)
+{
+    return vh_launch_patch_embed_ws_math(s, images, conv_w, conv_b, cls_token, pos_embed, tokens, n_images, in_chans,
+                                         img_size, patch_size, embed_dim, workspace, workspace_bytes, VH_FP32_SPLIT3);
 }
 
 extern "C" int vh_launch_patch_embed(vh_stream_t s, const float *images, const float *conv_w,

@@ -19,14 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-        v += __shfl_xor(v, m);
-    return v;
-}
-
 __device__ __forceinline__ float wave_max(float v)
 {
 #pragma unroll
@@ -93,15 +85,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
  * planes' own order, [K step][part][16 rows][64 B], so that every global store instruction writes one
  * contiguous, aligned KiB (16 rows x 64 B of one K step and part) instead of eight 64-byte pieces 19 MB apart. */
 constexpr int LN3_ROWS = 16;
-
-/* Workgroup barrier for LDS hand-overs only (lgkmcnt): global loads stay in flight across it.  __syncthreads() is a
- * full fence and drains vmcnt, i.e. it would wait for the NEXT row group's loads issued a moment earlier. */
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 /* Persistent: a workgroup walks row groups blockIdx.x, blockIdx.x + gridDim.x, ... and loads the rows of the next
  * group before it normalises, stages and stores the current one -- with one group per workgroup the loads of a

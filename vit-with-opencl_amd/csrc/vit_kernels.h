@@ -49,6 +49,25 @@ __device__ __forceinline__ size_t mx_act_scale_index(int ks, int blk, size_t row
     return ((((size_t)(ks >> 2) * 4 + (2 * (blk & 1) + (blk >> 1))) * (size_t)rows + row) << 2) + (size_t)(ks & 3);
 }
 
+/* Sum over the 64 lanes of a wave, in every lane (xor butterfly: the same order in every lane) */
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+        v += __shfl_xor(v, m);
+    return v;
+}
+
+/* Workgroup barrier for LDS hand-overs only: this wave's LDS operations have completed (lgkmcnt), global loads stay
+ * in flight.  __syncthreads() is a full workgroup fence -- it also drains vmcnt, i.e. it waits for prefetches issued a
+ * few hundred cycles earlier and puts the whole load latency into every step of a pipelined loop. */
+__device__ __forceinline__ void lds_barrier()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
 /* Records `msg` as the calling thread's last error and returns `code`. */
 int vh_fail(int code, const char *fmt, ...);
 /* Converts a hipError_t into the launcher return convention, recording text. */

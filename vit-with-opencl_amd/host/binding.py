@@ -63,7 +63,14 @@ EXPORTS = [
     "vit_hip_forward_u8_resized",
     "vh_feature_readout_scratch", "vh_launch_feature_readout", "vit_feature_sizes", "vit_hip_set_features",
     "vit_hip_set_features_host",
+    "vh_launch_linear_math", "vh_launch_patch_embed_ws_math", "vh_launch_attention_rows",
 ]
+
+# include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
+# vh_launch_attention_rows
+FP32_MATH = {"split3": 0, "native": 1}
+ATTN_ARITH = {"native": 0, "fp16": 1, "fp16x2": 2, "split3": 3}
+ATTN_KERNEL = {"auto": 0, "streaming": 1}
 
 
 class VitConfig(C.Structure):
@@ -270,6 +277,7 @@ def lib() -> C.CDLL:
     L.vh_d2d.argtypes = [voidp, voidp, sz, voidp]
     L.vh_launch_patch_embed.argtypes = [voidp] + [voidp] * 6 + [i] * 5
     L.vh_launch_patch_embed_ws.argtypes = [voidp] + [voidp] * 6 + [i] * 5 + [voidp, sz]
+    L.vh_launch_patch_embed_ws_math.argtypes = [voidp] + [voidp] * 6 + [i] * 5 + [voidp, sz, i]
     L.vh_patch_embed_workspace.argtypes = [i] * 5
     L.vh_patch_planes_k.argtypes = [i, i]
     L.vh_launch_conv_weight_planes.argtypes = [voidp, voidp, voidp, i, i, i]
@@ -277,7 +285,9 @@ def lib() -> C.CDLL:
     L.vh_patch_embed_workspace.restype = sz
     L.vh_launch_layer_norm.argtypes = [voidp] + [voidp] * 4 + [i, i, C.c_long, C.c_long, C.c_double]
     L.vh_launch_linear.argtypes = [voidp] + [voidp] * 4 + [i, i, i, i, voidp]
+    L.vh_launch_linear_math.argtypes = [voidp] + [voidp] * 4 + [i, i, i, i, voidp, i]
     L.vh_launch_attention.argtypes = [voidp, voidp, voidp, i, i, i, i]
+    L.vh_launch_attention_rows.argtypes = [voidp, voidp, voidp, i, i, i, i, i, i, i]
     L.vh_launch_attention_h2.argtypes = [voidp, voidp, voidp, i, i, i, i]
     L.vh_launch_attention_f16.argtypes = [voidp, voidp, voidp, i, i, i, i]
     L.vh_launch_split3_planes.argtypes = [voidp, voidp, voidp, i, i]
