@@ -5,8 +5,12 @@
  * oracle/_ref/ref_main (oracle/Makefile); this driver exists because those two hard-code 100
  * images and their file names (Main.c:20,43; comparator.c:9,30-31).
  *
- *   vit_main [image_file] [network_dir] [result_file] [planes_file]
+ *   vit_main [--topk K] [image_file] [network_dir] [result_file] [planes_file]
  *   defaults: ./Data/input-100.bin ./Network ./Data/opencl_result.txt (no planes file)
+ *
+ * --topk K (1..32): the K best labels of every image with their probabilities, selected on the GPU (vit_hip_set_topk_host):
+ * only the K pairs per image come back over PCIe, no probability rows.  The pairs are printed, and the result file is
+ * written from their first column (vit_write_result_file_topk: the same bytes as without the option).
  *
  * With a fourth argument the driver shows the offline half of the weight tooling: if `planes_file` exists the context
  * is built from it (vit_hip_create_from_planes: ONE file of already repacked operands, the 152 fp32 files of
@@ -50,8 +54,61 @@ static int requested_precision(void)
     return VIT_PRECISION_F32;
 }
 
+/* The --topk path: a context of its own, the host form of the top-k request armed, no logits or probabilities asked for */
+static int run_topk(const ImageData *images, int n, const char *network_dir, const char *result_file, int k)
+{
+    Network network[NUM_TENSORS];
+    vit_config cfg;
+    vit_hip_ctx *ctx = NULL;
+    const int device = getenv("VIT_HIP_DEVICE") ? atoi(getenv("VIT_HIP_DEVICE")) : 0;
+    const vit_topk_spec spec = {k, VIT_TOPK_PROBS};
+    vit_config_preset(&cfg, "vit_b_16");
+    if (vit_topk_check(&cfg, &spec) != 0) {
+        fprintf(stderr, "vit_main: %s\n", vh_last_error());
+        return 100;
+    }
+    int *labels = (int *)malloc(sizeof(int) * (size_t)n * (size_t)k);
+    float *scores = (float *)malloc(sizeof(float) * (size_t)n * (size_t)k);
+    if (labels == NULL || scores == NULL) {
+        fprintf(stderr, "vit_main: out of memory (%d x %d result pairs)\n", n, k);
+        return 101;
+    }
+    const vit_topk_buffers bufs = {labels, scores};
+    const double t0 = wall();
+    load_weights(network_dir, network, NUM_TENSORS);
+    VH_CHECK(vit_hip_create_ex(&ctx, &cfg, network, NUM_TENSORS, device, n < 512 ? n : 512, requested_precision()));
+    VH_CHECK(vit_hip_set_topk_host(ctx, &spec, &bufs));
+    VH_CHECK(vit_hip_forward(ctx, images, n, NULL, NULL));
+    vit_hip_destroy(ctx);
+    printf("Elapsed time: %.4f sec\n", wall() - t0);
+    for (int i = 0; i < n; ++i) {
+        printf("[%d]", i);
+        for (int j = 0; j < k; ++j)
+            printf(" %d:%.6f", labels[(size_t)i * k + j], scores[(size_t)i * k + j]);
+        printf("\n");
+    }
+    if (vit_write_result_file_topk(result_file, labels, scores, n, k) != 0) {
+        fprintf(stderr, "cannot write %s\n", result_file);
+        return 100;
+    }
+    printf("wrote %d result line(s) to %s\n", n, result_file);
+    free(labels);
+    free(scores);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    int topk = 0;
+    if (argc > 2 && strcmp(argv[1], "--topk") == 0) {
+        topk = atoi(argv[2]);
+        if (topk < 1) {
+            fprintf(stderr, "vit_main: --topk takes a count in 1..32\n");
+            return 100;
+        }
+        argv += 2;
+        argc -= 2;
+    }
     const char *image_file = argc > 1 ? argv[1] : "./Data/input-100.bin";
     const char *network_dir = argc > 2 ? argv[2] : "./Network";
     const char *result_file = argc > 3 ? argv[3] : "./Data/opencl_result.txt";
@@ -62,6 +119,10 @@ int main(int argc, char **argv)
     if (images == NULL)
         return 100;
     const int n = images->n;
+    if (topk > 0 && n > 0) {
+        printf("=====================Start========================\n");
+        return run_topk(images, n, network_dir, result_file, topk);
+    }
     float **probabilities = (float **)malloc(sizeof(float *) * (size_t)(n > 0 ? n : 1));
     if (probabilities == NULL) {
         fprintf(stderr, "vit_main: out of memory (%d result rows)\n", n);

@@ -309,6 +309,40 @@ int vit_feature_sizes(const vit_config *cfg, const vit_feature_spec *spec, size_
 int vit_hip_set_features(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *d_bufs);
 int vit_hip_set_features_host(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *h_bufs);
 
+/* ---- top-k predictions: the k best labels of every image with their scores, selected on the GPU ----
+ * A top-k request is ARMED on a context like a feature request, and independently of it (both may be armed at once).
+ * While armed, every forward through the context also writes labels[i][j] (class index of image i's j-th best logit) and,
+ * unless scores is NULL, scores[i][j]: its probability (VIT_TOPK_PROBS) or its logit (VIT_TOPK_LOGITS), by one extra launch
+ * behind the classifier (vh_launch_topk, csrc/topk.hip; timed under VIT_OP_SOFTMAX).  It reads the fp32 logits only, so it
+ * is the same in every precision mode; logits, probabilities and features are bit-identical to an un-armed forward, and an
+ * un-armed context launches exactly what it launched before.
+ * Ranking (the library's one definition; Main.c:59-72's strict `>` is its k = 1 case): by logit, descending; equal logits
+ * by ascending class index -- the lowest index wins; -0.0f and +0.0f are equal; NaN ranks below -inf, NaNs among themselves
+ * by ascending index.  The labels of an image are distinct.  1 <= k <= 32, k <= num_classes <= 65536.
+ * Scores: VIT_TOPK_LOGITS are the logits' own bits.  VIT_TOPK_PROBS with num_classes <= 2048 are the bits the
+ * probabilities output holds at those positions; with more classes they are exp(x - max) / sum over the whole row in a
+ * fixed summation order (relative error <= (ceil(num_classes / 256) + 32) * 2^-24).  The full probabilities output itself
+ * stays limited to 2048 classes: a forward with probs / d_probs != NULL on a wider head is refused as before (a long-row
+ * full softmax is not part of this interface); top-k is the way to read such a head.
+ * An image's labels and scores depend on that image only: bit-identical wherever it sits in the batch.
+ * Device form (vit_hip_set_topk): device buffers [max_batch][k], 16-byte aligned, written asynchronously on the forward's
+ * stream by vit_hip_forward_device, _device_u8 and _device_u8_resized, whether d_logits and d_probs are NULL or not.
+ * Host form (vit_hip_set_topk_host): host buffers [n][k] for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized
+ * calls (each call writes from image 0), complete on return; two pinned slots of max_batch * k pairs are allocated when it
+ * is armed.  With logits == NULL and probs == NULL a chunk's device-to-host traffic is its k pairs per image only.
+ * spec == NULL disarms.  Arming one form disarms the other; a device-form forward while the host form is armed (and the
+ * reverse) is refused with code 1 and a message, no launch.  Code 1 with a message also for a NULL ctx, a spec
+ * vit_topk_check refuses, NULL buffers or labels, a misaligned device buffer.  A refused call leaves the previous request
+ * armed.
+ * vit_hip_multi: a context from vit_hip_multi_ctx may be armed for the device forms like any other; vit_hip_forward_multi
+ * and vit_hip_forward_device_multi neither write top-k outputs nor refuse. */
+typedef struct vit_topk_spec { int k; int score_kind; } vit_topk_spec;              /* score_kind: VIT_TOPK_PROBS | VIT_TOPK_LOGITS (kernelHandler.h) */
+typedef struct vit_topk_buffers { int *labels; float *scores; } vit_topk_buffers;   /* scores may be NULL */
+/* host only, no device: validates spec against cfg; 0, or 1 with a message */
+int vit_topk_check(const vit_config *cfg, const vit_topk_spec *spec);
+int vit_hip_set_topk(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *d_bufs);
+int vit_hip_set_topk_host(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *h_bufs);
+
 /* Debug hook: copy the residual stream left by the last forward ([n*tokens][embed], un-normalised; rows other than the
  * class tokens are stale under vit_hip_set_last_layer_cls_only) to the host.  The supported interface to the encoder's
  * output is vit_hip_set_features above. */
@@ -352,6 +386,9 @@ typedef struct {
     int nonfinite;
 } vit_compare_report;
 int vit_write_result_file(const char *path, float *const *probabilities, int n, int classes);
+/* The same file from top-k outputs ([n][k], k >= 1): line i holds labels[i][0] and scores[i][0].  Byte-identical to
+ * vit_write_result_file on the full rows the columns were selected from (the lowest index wins a tie in both). */
+int vit_write_result_file_topk(const char *path, const int *labels, const float *scores, int n, int k);
 int vit_compare_rows(const float *got, const float *want, int n, int classes, double tolerance,
                      vit_compare_report *rep);
 

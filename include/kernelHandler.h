@@ -275,6 +275,17 @@ int vh_launch_gather_rows(vh_stream_t s, const void *src, void *dst, int n_plane
  * ViT_seq.c:372. */
 int vh_launch_softmax(vh_stream_t s, const float *input, float *output, int rows, int length);
 
+/* The k best entries of every row of `logits` ([rows][length] fp32): labels[r][j] = index of the j-th best, scores[r][j] its
+ * logit (VIT_TOPK_LOGITS: the input's own bits) or its probability (VIT_TOPK_PROBS: exp(x - max) / sum over the whole row;
+ * for length <= 2048 the bits vh_launch_softmax writes at that position, for longer rows -- which the softmax does not
+ * take -- the same formula with each thread's strided elements summed in ascending index order).  Ranking: by logit,
+ * descending; equal logits (-0.0f and +0.0f are equal) by ascending index; NaN below -inf, NaNs among themselves by
+ * ascending index.  The labels of a row are distinct and lie in [0, length).  One workgroup per row, no atomics: a row's
+ * output depends on that row only.  1 <= k <= 32, k <= length, 1 <= length <= 65536; `scores` may be NULL.  Anything
+ * else: code 1 with a message, no launch.  (csrc/topk.hip; replaces the host arg-max of Main.c:59-72.) */
+enum { VIT_TOPK_PROBS = 0, VIT_TOPK_LOGITS = 1 };
+int vh_launch_topk(vh_stream_t s, const float *logits, int rows, int length, int k, int score_kind, int *labels, float *scores);
+
 /* ---- reduced-precision attention (the bf16- and fp8-operand modes, BASELINE configs 3 and 5) ----
  * fp32 in, fp32 out; Q, K, V and P rounded to fp16 for the two products (11-bit operands, fp32 accumulation and
  * softmax): far inside those modes' tolerances.  The bf16-operand mode itself runs on one-part planes:

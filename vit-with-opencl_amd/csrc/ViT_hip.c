@@ -139,6 +139,18 @@ struct vit_hip_ctx
         void *h_stage[2][2];         /* FEAT_HOST: pinned [slot][cls, pooled] */
     } feat;
 
+    /* top-k request (vit_hip_set_topk / _host), armed independently of the feature request.  The host form selects into
+     * device buffers of its own and carries the pairs through two pinned slots. */
+    struct topk_req
+    {
+        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
+        vit_topk_spec spec;
+        vit_topk_buffers out;        /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: d_stage */
+        vit_topk_buffers host;       /* FEAT_HOST: the caller's host buffers */
+        vit_topk_buffers d_stage;    /* FEAT_HOST: device labels, scores for max_batch images */
+        vit_topk_buffers h_stage[2]; /* FEAT_HOST: pinned, per slot */
+    } topk;
+
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
     int *prof_class;       /* operator class per recorded launch */
@@ -218,6 +230,18 @@ static void feature_stage_release(vit_hip_ctx *ctx)
     }
 }
 
+static void topk_stage_release(struct topk_req *tk)
+{
+    if (tk->d_stage.labels) vh_free(tk->d_stage.labels);
+    if (tk->d_stage.scores) vh_free(tk->d_stage.scores);
+    tk->d_stage = (vit_topk_buffers){NULL, NULL};
+    for (int slot = 0; slot < 2; ++slot) {
+        if (tk->h_stage[slot].labels) vh_host_free(tk->h_stage[slot].labels);
+        if (tk->h_stage[slot].scores) vh_host_free(tk->h_stage[slot].scores);
+        tk->h_stage[slot] = (vit_topk_buffers){NULL, NULL};
+    }
+}
+
 void vit_hip_destroy(vit_hip_ctx *ctx)
 {
     if (!ctx)
@@ -229,6 +253,7 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     }
     prof_release(ctx);
     feature_stage_release(ctx);
+    topk_stage_release(&ctx->topk);
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
@@ -1159,9 +1184,9 @@ fail:
     return rc;
 }
 
-/* Everything after the argument checks of the forwards.  fr: the armed feature request to serve, or NULL. */
+/* Everything after the argument checks of the forwards.  fr, tk: the armed feature / top-k request to serve, or NULL. */
 static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
-                          const struct feature_req *fr)
+                          const struct feature_req *fr, const struct topk_req *tk)
 {
     int rc = 0;
     const int cls_only_saved = ctx->cls_only_last;
@@ -1209,6 +1234,8 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
     OP(VIT_OP_HEAD, vh_launch_linear_math(s, logits, tw[2], ctx->cls, tw[3], n, E, NC, 0, NULL, fp32_math(ctx)));
     if (d_probs)
         OP(VIT_OP_SOFTMAX, vh_launch_softmax(s, logits, d_probs, n, NC));
+    if (tk)   /* the k best of every row of the fp32 logits: one launch, whatever the precision mode */
+        OP(VIT_OP_SOFTMAX, vh_launch_topk(s, logits, n, NC, tk->spec.k, tk->spec.score_kind, tk->out.labels, tk->out.scores));
     return 0;
 fail:
     ctx->cls_only_last = cls_only_saved;
@@ -1228,13 +1255,25 @@ static const struct feature_req *device_features(vit_hip_ctx *ctx, const char *w
     return ctx->feat.form == FEAT_DEVICE ? &ctx->feat : NULL;
 }
 
+/* The same for the top-k request; called only when device_features did not refuse */
+static const struct topk_req *device_topk(vit_hip_ctx *ctx, const char *who, int *refused)
+{
+    if (ctx->topk.form == FEAT_HOST) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s: the context is armed for host top-k buffers (vit_hip_set_topk_host); disarm it or use the host forms", who);
+        vh_set_error(1, msg);
+        *refused = 1;
+    }
+    return ctx->topk.form == FEAT_DEVICE ? &ctx->topk : NULL;
+}
+
 /* vit_hip_forward_device with no feature output whatever is armed (vit_gather_rccl.c) */
 int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits, float *d_probs, vh_stream_t stream)
 {
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
     const struct pixel_src src = {d_images, NULL, 0, NULL};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL);
 }
 
 int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
@@ -1244,10 +1283,11 @@ int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float
         return 1;
     int refused;
     const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device", &refused);
+    const struct topk_req *tk = refused ? NULL : device_topk(ctx, "vit_hip_forward_device", &refused);
     if (refused)
         return 1;
     const struct pixel_src src = {d_images, NULL, 0, NULL};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr, tk);
 }
 
 int vit_pixel_norm_from_mean_std(vit_pixel_norm *out, const float *mean, const float *std, int chans)
@@ -1290,10 +1330,11 @@ int vit_hip_forward_device_u8(vit_hip_ctx *ctx, const unsigned char *d_images, i
         return 1;
     int refused;
     const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device_u8", &refused);
+    const struct topk_req *tk = refused ? NULL : device_topk(ctx, "vit_hip_forward_device_u8", &refused);
     if (refused)
         return 1;
     const struct pixel_src src = {NULL, d_images, layout, norm};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr, tk);
 }
 
 int vit_resize_crop_geometry(int height, int width, const vit_resize_crop *rc, int crop, int *resized_h, int *resized_w, int *top,
@@ -1378,10 +1419,11 @@ int vit_hip_forward_device_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *d_im
         return 1;
     int refused;
     const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device_u8_resized", &refused);
+    const struct topk_req *tk = refused ? NULL : device_topk(ctx, "vit_hip_forward_device_u8_resized", &refused);
     if (refused)
         return 1;
     const struct pixel_src src = {NULL, NULL, layout, norm, d_images, rc};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr, tk);
 }
 
 /* spec against cfg; the taps resolved to ascending layer indices */
@@ -1492,6 +1534,88 @@ int vit_hip_set_features_host(vit_hip_ctx *ctx, const vit_feature_spec *spec, co
     return set_features("vit_hip_set_features_host", ctx, spec, h_bufs, 1);
 }
 
+static int topk_spec_check(const char *who, const vit_config *cfg, const vit_topk_spec *spec)
+{
+    char msg[200];
+    const char *why = !cfg || !spec ? "NULL argument"
+                      : cfg->num_classes < 1 || cfg->num_classes > 65536 ? "num_classes must be in 1..65536"
+                      : spec->k < 1 || spec->k > 32 ? "k must be in 1..32"
+                      : spec->k > cfg->num_classes ? "k exceeds num_classes"
+                      : spec->score_kind != VIT_TOPK_PROBS && spec->score_kind != VIT_TOPK_LOGITS ? "score_kind must be VIT_TOPK_PROBS or VIT_TOPK_LOGITS"
+                      : NULL;
+    if (!why)
+        return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return vh_set_error(1, msg);
+}
+
+int vit_topk_check(const vit_config *cfg, const vit_topk_spec *spec)
+{
+    return topk_spec_check("vit_topk_check", cfg, spec);
+}
+
+/* Both forms of arming; host: bufs are host memory, staged through device buffers and pinned slots made here */
+static int set_topk(const char *who, vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *bufs, int host)
+{
+    int rc = 0;
+    char msg[200];
+    if (!ctx) {
+        snprintf(msg, sizeof msg, "%s: NULL context", who);
+        return vh_set_error(1, msg);
+    }
+    struct topk_req tk;
+    memset(&tk, 0, sizeof tk);
+    if (spec) {
+        if (topk_spec_check(who, &ctx->cfg, spec))
+            return 1;
+        const char *why = !bufs || !bufs->labels ? "no labels buffer"
+                          : !host && (((uintptr_t)bufs->labels | (uintptr_t)bufs->scores) & 15) ? "device buffers must be 16-byte aligned"
+                          : NULL;
+        if (why) {
+            snprintf(msg, sizeof msg, "%s: %s", who, why);
+            return vh_set_error(1, msg);
+        }
+        tk.form = host ? FEAT_HOST : FEAT_DEVICE;
+        tk.spec = *spec;
+        tk.out = *bufs;
+    }
+    TRY(vh_set_device(ctx->device));
+    /* the staging of an earlier host request may still be read by its last forward's copies */
+    TRY(vh_stream_sync(ctx->stream));
+    if (tk.form == FEAT_HOST) {
+        const size_t pairs = (size_t)ctx->max_batch * spec->k;
+        tk.host = *bufs;
+        rc = vh_malloc((void **)&tk.d_stage.labels, pairs * sizeof(int));
+        if (rc == 0 && bufs->scores)
+            rc = vh_malloc((void **)&tk.d_stage.scores, pairs * sizeof(float));
+        for (int slot = 0; slot < 2 && rc == 0; ++slot) {
+            rc = vh_host_alloc((void **)&tk.h_stage[slot].labels, pairs * sizeof(int));
+            if (rc == 0 && bufs->scores)
+                rc = vh_host_alloc((void **)&tk.h_stage[slot].scores, pairs * sizeof(float));
+        }
+        tk.out = tk.d_stage;
+        if (rc != 0) {   /* the previous request stays armed */
+            topk_stage_release(&tk);
+            return rc;
+        }
+    }
+    topk_stage_release(&ctx->topk);
+    ctx->topk = tk;
+    return 0;
+fail:
+    return rc;
+}
+
+int vit_hip_set_topk(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *d_bufs)
+{
+    return set_topk("vit_hip_set_topk", ctx, spec, d_bufs, 0);
+}
+
+int vit_hip_set_topk_host(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *h_bufs)
+{
+    return set_topk("vit_hip_set_topk_host", ctx, spec, h_bufs, 1);
+}
+
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
 {
     if (!ctx)
@@ -1523,7 +1647,7 @@ int vit_hip_profile_enable(vit_hip_ctx *ctx, int max_forwards)
     prof_release(ctx);
     if (max_forwards <= 0)
         return 0;
-    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4;   /* + the readouts of an armed feature request */
+    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1;   /* + the readouts of an armed feature request + top-k */
     ctx->prof_cap = per_forward * max_forwards;
     ctx->prof_ev = (vh_event_t *)calloc((size_t)2 * ctx->prof_cap, sizeof(vh_event_t));
     ctx->prof_class = (int *)calloc((size_t)ctx->prof_cap, sizeof(int));
@@ -1578,9 +1702,16 @@ fail:
  *   compute  : forward chunk k, D2H its logits/probs  (after the H2D)
  * so PCIe and the gather of the separately malloc'd images (Network.c:90) hide under
  * the previous chunk's kernels. */
-static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, float *logits, float **probs, const struct feature_req *fr)
+static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, float *logits, float **probs, const struct feature_req *fr,
+                            const struct topk_req *tk)
 {
     const size_t NC = (size_t)ctx->cfg.num_classes;
+    if (tk) {   /* the k pairs per image of the armed host request */
+        const size_t k = (size_t)tk->spec.k;
+        memcpy(tk->host.labels + (size_t)first * k, tk->h_stage[slot].labels, (size_t)m * k * sizeof(int));
+        if (tk->host.scores)
+            memcpy(tk->host.scores + (size_t)first * k, tk->h_stage[slot].scores, (size_t)m * k * sizeof(float));
+    }
     for (int k = 0; fr && k < 2; ++k) {   /* cls, pooled of the armed host request */
         char *to = (char *)(k == 0 ? fr->host.cls : fr->host.pooled);
         if (to)
@@ -1701,7 +1832,10 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
     int rc = 0;
     if (features && ctx->feat.form == FEAT_DEVICE)
         return vh_set_error(1, "forward: the context is armed for device feature buffers (vit_hip_set_features); disarm it or use the device forms");
+    if (features && ctx->topk.form == FEAT_DEVICE)
+        return vh_set_error(1, "forward: the context is armed for device top-k buffers (vit_hip_set_topk); disarm it or use the device forms");
     const struct feature_req *fr = features && ctx->feat.form == FEAT_HOST ? &ctx->feat : NULL;
+    const struct topk_req *tk = features && ctx->topk.form == FEAT_HOST ? &ctx->topk : NULL;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->u8 ? 1 : sizeof(float));
@@ -1731,8 +1865,9 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
         const struct pixel_src dev = {src->u8 || src->resize ? NULL : ctx->d_images[s],
                                       src->u8 ? (const unsigned char *)ctx->d_images[s] : NULL, src->layout, src->norm,
                                       src->resize ? src->staged : NULL, src->rc};
-        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr));
+        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
+        /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
         if (logits)
             TRY(vh_d2h(ctx->h_logits[s], ctx->d_logits, (size_t)m * NC * sizeof(float), ctx->stream));
         if (probs)
@@ -1740,17 +1875,22 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
         for (int f = 0; fr && f < 2; ++f)
             if (fr->d_stage[f])
                 TRY(vh_d2h(fr->h_stage[s][f], fr->d_stage[f], (size_t)m * fr->per_image[f], ctx->stream));
+        if (tk) {
+            TRY(vh_d2h(tk->h_stage[s].labels, tk->d_stage.labels, (size_t)m * tk->spec.k * sizeof(int), ctx->stream));
+            if (tk->d_stage.scores)
+                TRY(vh_d2h(tk->h_stage[s].scores, tk->d_stage.scores, (size_t)m * tk->spec.k * sizeof(float), ctx->stream));
+        }
         TRY(vh_event_record(ctx->out_done[s], ctx->stream));
 
         if (k >= 1) { /* finish chunk k-1 while chunk k runs */
             TRY(vh_event_sync(ctx->out_done[s ^ 1]));
-            scatter_outputs(ctx, s ^ 1, prev_first, prev_m, logits, probs, fr);
+            scatter_outputs(ctx, s ^ 1, prev_first, prev_m, logits, probs, fr, tk);
         }
         prev_first = first;
         prev_m = m;
     }
     TRY(vh_event_sync(ctx->out_done[(k - 1) & 1]));
-    scatter_outputs(ctx, (k - 1) & 1, prev_first, prev_m, logits, probs, fr);
+    scatter_outputs(ctx, (k - 1) & 1, prev_first, prev_m, logits, probs, fr, tk);
     return 0;
 fail:
     vh_stream_sync(ctx->copy_stream);
@@ -1983,7 +2123,7 @@ static int multi_forward_one(void *arg, int shard, int lo, int hi)
 {
     vit_hip_multi *m = (vit_hip_multi *)arg;
     const size_t NC = (size_t)vit_hip_config(m->ctx[shard])->num_classes;
-    /* no feature output, whatever a caller armed on the shard's context */
+    /* no feature or top-k output, whatever a caller armed on the shard's context */
     return forward_host_images(m->ctx[shard], m->images + lo, hi - lo, m->logits ? m->logits + (size_t)lo * NC : NULL,
                                m->probs ? m->probs + lo : NULL, 0);
 }

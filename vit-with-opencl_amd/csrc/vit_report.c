@@ -38,6 +38,18 @@ int vit_write_result_file(const char *path, float *const *probabilities, int n, 
     return fclose(f) == 0 ? 0 : 2;
 }
 
+int vit_write_result_file_topk(const char *path, const int *labels, const float *scores, int n, int k)
+{
+    if (!path || !labels || !scores || n < 0 || k <= 0)
+        return 1;
+    FILE *f = fopen(path, "w");
+    if (!f)
+        return 2;
+    for (int i = 0; i < n; ++i)
+        fprintf(f, "[%d] label: %d / prob: %.6f\n", i, labels[(size_t)i * k], scores[(size_t)i * k]);
+    return fclose(f) == 0 ? 0 : 2;
+}
+
 static void top5(const float *row, int classes, int out[5])
 {
     for (int k = 0; k < 5; ++k)

@@ -64,6 +64,7 @@ EXPORTS = [
     "vh_feature_readout_scratch", "vh_launch_feature_readout", "vit_feature_sizes", "vit_hip_set_features",
     "vit_hip_set_features_host",
     "vh_launch_linear_math", "vh_launch_patch_embed_ws_math", "vh_launch_attention_rows",
+    "vh_launch_topk", "vit_topk_check", "vit_hip_set_topk", "vit_hip_set_topk_host", "vit_write_result_file_topk",
 ]
 
 # include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
@@ -142,6 +143,37 @@ class FeatureSpec:
         taps = list(self.taps[:4]) + [0] * (4 - min(len(self.taps), 4))
         return FeatureSpecC(len(self.taps), (C.c_int * 4)(*taps), int(self.final_norm), int(self.l2_normalize),
                             FEATURE_DTYPES[self.dtype], TOKEN_LAYOUTS[self.token_layout])
+
+
+class TopKSpecC(C.Structure):
+    """`vit_topk_spec` (include/ViT_opencl.h)."""
+
+    _fields_ = [("k", C.c_int), ("score_kind", C.c_int)]
+
+
+class TopKBuffers(C.Structure):
+    """`vit_topk_buffers` (include/ViT_opencl.h): device or host pointers; scores may be NULL."""
+
+    _fields_ = [("labels", C.c_void_p), ("scores", C.c_void_p)]
+
+
+TOPK_SCORES = {"probs": 0, "logits": 1}
+
+
+class TopKSpec:
+    """A top-k request: the k best classes per image (1..32) with their scores ("probs" | "logits")."""
+
+    def __init__(self, k: int = 5, scores: str = "probs"):
+        self.k, self.scores = int(k), scores
+
+    def c_struct(self) -> TopKSpecC:
+        return TopKSpecC(self.k, TOPK_SCORES[self.scores])
+
+
+def topk_check(cfg: "VitConfig", spec: TopKSpec) -> None:
+    """vit_topk_check: raises VitHipError with the library's message when cfg does not take spec"""
+    cs = spec.c_struct()
+    check(lib().vit_topk_check(C.byref(cfg), C.byref(cs)), "vit_topk_check")
 
 
 def feature_sizes(cfg: "VitConfig", spec: FeatureSpec):
@@ -413,6 +445,13 @@ def lib() -> C.CDLL:
     L.vit_feature_sizes.argtypes = [C.POINTER(VitConfig), specp, szp, szp, szp]
     L.vit_hip_set_features.argtypes = [voidp, specp, bufp]
     L.vit_hip_set_features_host.argtypes = [voidp, specp, bufp]
+    ip32 = C.POINTER(C.c_int)
+    L.vh_launch_topk.argtypes = [voidp, voidp, i, i, i, i, voidp, voidp]
+    tkp, tbp = C.POINTER(TopKSpecC), C.POINTER(TopKBuffers)
+    L.vit_topk_check.argtypes = [C.POINTER(VitConfig), tkp]
+    L.vit_hip_set_topk.argtypes = [voidp, tkp, tbp]
+    L.vit_hip_set_topk_host.argtypes = [voidp, tkp, tbp]
+    L.vit_write_result_file_topk.argtypes = [C.c_char_p, ip32, f32p, i, i]
     _lib = L
     return L
 
@@ -673,6 +712,46 @@ class ViTHip:
         finally:
             self.set_features_host(None)
         return logits, cls, pooled
+
+    def set_topk(self, spec, labels=None, scores=None):
+        """Arm (spec=None: disarm) the device forms: labels (int32) / scores (float32, may be None) are DeviceBuffers (or
+        device pointers) of [max_batch][k], written by every forward_device* until disarmed."""
+        if spec is None:
+            check(self.L.vit_hip_set_topk(self.ctx, None, None), "vit_hip_set_topk")
+            self._topk_keep = None
+            return
+        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
+        cs, bufs = spec.c_struct(), TopKBuffers(ptr(labels), ptr(scores))
+        check(self.L.vit_hip_set_topk(self.ctx, C.byref(cs), C.byref(bufs)), "vit_hip_set_topk")
+        self._topk_keep = (labels, scores)
+
+    def set_topk_host(self, spec, labels=None, scores=None):
+        """Arm (spec=None: disarm) the host forms: labels (int32 [n][k]) / scores (float32 [n][k], may be None) are
+        C-contiguous NumPy arrays for all n images of the coming forward / forward_u8 / forward_u8_resized calls."""
+        if spec is None:
+            check(self.L.vit_hip_set_topk_host(self.ctx, None, None), "vit_hip_set_topk_host")
+            self._topk_keep = None
+            return
+        for a, dt in ((labels, np.int32), (scores, np.float32)):
+            if a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == dt):
+                raise ValueError("set_topk_host: need C-contiguous int32 labels and float32 scores")
+        ptr = lambda a: None if a is None else a.ctypes.data
+        cs, bufs = spec.c_struct(), TopKBuffers(ptr(labels), ptr(scores))
+        check(self.L.vit_hip_set_topk_host(self.ctx, C.byref(cs), C.byref(bufs)), "vit_hip_set_topk_host")
+        self._topk_keep = (labels, scores)
+
+    def classify(self, images: np.ndarray, k: int = 5, scores: str = "probs"):
+        """fp32 images [n][C][H][W] -> (labels[n][k] int32, scores[n][k] float32): the host form armed for this one call;
+        neither logits nor probabilities cross PCIe."""
+        images = np.ascontiguousarray(images, dtype=np.float32)
+        n = images.shape[0]
+        labels, out = np.empty((n, k), dtype=np.int32), np.empty((n, k), dtype=np.float32)
+        self.set_topk_host(TopKSpec(k, scores), labels=labels, scores=out)
+        try:
+            check(self.L.vit_hip_forward(self.ctx, image_array(images), n, None, None), "vit_hip_forward")
+        finally:
+            self.set_topk_host(None)
+        return labels, out
 
     def read_tokens(self, n: int) -> np.ndarray:
         out = np.empty((n * self.tokens, self.cfg.embed_dim), dtype=np.float32)
