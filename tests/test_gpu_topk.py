@@ -285,6 +285,96 @@ def test_u8_entry_points_with_features_armed_too(pkg, models, cfg):
         assert np.abs(dev[2]).max() > 0 and (dev[1] > 0).all() and all(len(set(r)) == k for r in dev[0].tolist())
 
 
+def test_every_staged_array_over_three_ragged_chunks(pkg, device):
+    """Logits, probabilities, cls, pooled, labels and scores of the host forms at once, on the 17-token config of
+    tests/test_gpu_configs.py with max_batch 2 and 5 images: chunks of 2, 2 and 1, the third in the first one's pinned slot.
+    Every array has the bits of the device forms armed the same way on images [0:2], [2:4], [4:5]; again with bf16 features
+    (2-byte elements), with labels only, and with neither logits nor probabilities; then a re-arm of the top-k request
+    without a disarm (new stages), and the plain forward once both are disarmed."""
+    b, L = pkg.binding, pkg.lib()
+    cfg = pkg.preset("vit_b_16")
+    cfg.img_size, cfg.patch_size, cfg.in_chans, cfg.num_classes = 64, 16, 3, 10
+    cfg.embed_dim, cfg.depth, cfg.num_heads, cfg.mlp_hidden = 256, 2, 4, 512
+    n, nc, mb = 5, 10, 2
+    imgs = pkg.synth_images(cfg, 0, n)
+    model = pkg.ViTHip(cfg, pkg.synth_weights(cfg, 21), device=0, max_batch=mb)
+
+    def device_form(fspec, k):
+        """-> logits, probs, cls, pooled, labels, scores of the chunks, concatenated"""
+        c_el, p_el, _ = b.feature_sizes(cfg, fspec)
+        d_cls, d_pool = pkg.DeviceBuffer(mb * c_el, dtype=fspec.np_dtype), pkg.DeviceBuffer(mb * p_el, dtype=fspec.np_dtype)
+        d_lab, d_sc = pkg.DeviceBuffer(mb * k, np.int32), pkg.DeviceBuffer(mb * k)
+        d_l, d_p = pkg.DeviceBuffer(mb * nc), pkg.DeviceBuffer(mb * nc)
+        model.set_features(fspec, cls=d_cls, pooled=d_pool)
+        model.set_topk(b.TopKSpec(k, "probs"), labels=d_lab, scores=d_sc)
+        chunks = []
+        try:
+            for first in range(0, n, mb):
+                m = min(mb, n - first)
+                d_img = pkg.DeviceBuffer.from_numpy(imgs[first:first + m])
+                model.forward_device(d_img.ptr, m, d_l.ptr, d_p.ptr)
+                model.sync()
+                chunks.append([d.to_numpy()[: m * per].reshape(m, per) for d, per in
+                               ((d_l, nc), (d_p, nc), (d_cls, c_el), (d_pool, p_el), (d_lab, k), (d_sc, k))])
+        finally:
+            model.set_features(None)
+            model.set_topk(None)
+        return [np.concatenate(parts) for parts in zip(*chunks)]
+
+    def host_arrays(fspec, k, scores=True):
+        c_el, p_el, _ = b.feature_sizes(cfg, fspec)
+        return (np.zeros((n, c_el), fspec.np_dtype), np.zeros((n, p_el), fspec.np_dtype), np.full((n, k), -1, np.int32),
+                np.full((n, k), -1.0, np.float32) if scores else None)
+
+    def host_form(fspec, k, scores=True, outputs=True):
+        """-> the same six of one host forward; None for what was not asked for"""
+        cls, pooled, labels, sc = host_arrays(fspec, k, scores)
+        model.set_features_host(fspec, cls=cls, pooled=pooled)
+        model.set_topk_host(b.TopKSpec(k, "probs"), labels=labels, scores=sc)
+        try:
+            if outputs:
+                logits, probs = model.forward(imgs)
+            else:
+                b.check(L.vit_hip_forward(model.ctx, b.image_array(imgs), n, None, None), "vit_hip_forward")
+                logits = probs = None
+        finally:
+            model.set_features_host(None)
+            model.set_topk_host(None)
+        return [logits, probs, cls, pooled, labels, sc]
+
+    try:
+        l0, p0 = model.forward(imgs)
+        f32, bf16 = b.FeatureSpec(taps=(0, -1)), b.FeatureSpec(taps=(0, -1), dtype="bf16")
+        want = device_form(f32, 3)
+        assert same(want[0], l0) and same(want[1], p0) and np.abs(want[2]).max() > 0 and np.abs(want[3]).max() > 0
+        assert np.array_equal(want[4], tr.topk(l0, 3)) and same(want[5], np.take_along_axis(p0, want[4], axis=1))
+        got = host_form(f32, 3)
+        assert all(same(g, w) for g, w in zip(got, want))
+        want16 = device_form(bf16, 3)
+        assert want16[2].dtype == np.uint16 and want16[2].any() and want16[3].any()
+        got = host_form(bf16, 3)
+        assert all(same(g, w) for g, w in zip(got, want16))
+        got = host_form(f32, 3, scores=False)
+        assert got[5] is None and all(same(g, w) for g, w in zip(got[:5], want[:5]))
+        got = host_form(f32, 3, outputs=False)
+        assert got[0] is None and got[1] is None and all(same(g, w) for g, w in zip(got[2:], want[2:]))
+        # k = 5 over the armed k = 3, no disarm between: the stages are made anew
+        want5 = device_form(f32, 5)
+        cls, pooled, labels, sc = host_arrays(f32, 3)
+        model.set_features_host(f32, cls=cls, pooled=pooled)
+        model.set_topk_host(b.TopKSpec(3, "probs"), labels=labels, scores=sc)
+        labels5, sc5 = host_arrays(f32, 5)[2:]
+        model.set_topk_host(b.TopKSpec(5, "probs"), labels=labels5, scores=sc5)
+        got = list(model.forward(imgs)) + [cls, pooled, labels5, sc5]
+        assert all(same(g, w) for g, w in zip(got, want5)) and (labels == -1).all() and (sc == -1.0).all()
+        model.set_features_host(None)
+        model.set_topk_host(None)
+        l1, p1 = model.forward(imgs)
+        assert same(l1, l0) and same(p1, p0)
+    finally:
+        model.close()
+
+
 def test_arming_rules_and_launch_counts(pkg, models, images19):
     model, b, L = models("f32"), pkg.binding, pkg.lib()
     n, nc, k = 5, 1000, 5

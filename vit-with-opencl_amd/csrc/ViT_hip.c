@@ -22,6 +22,7 @@
 
 #include <math.h>
 #include <pthread.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -68,6 +69,15 @@ enum { MAX_DEPTH = 256, MAX_TENSORS = 4 + 12 * MAX_DEPTH + 4 };
 enum { DESC_RING = 8, RESIZE_MAX_SIDE = 16384 };
 
 enum { FEAT_NONE, FEAT_DEVICE, FEAT_HOST };
+
+/* One array of a host-form forward: written on the device for a chunk, copied into the chunk's pinned slot, scattered into
+ * the caller's memory at image `first`.  dev NULL: the array is not asked for. */
+struct staged
+{
+    void *dev, *pinned[2];   /* for max_batch images: the device buffer, and a pinned one per slot */
+    char *host;              /* the caller's memory, for all n images of a call */
+    size_t per_image;        /* bytes */
+};
 
 struct vit_hip_ctx
 {
@@ -132,11 +142,8 @@ struct vit_hip_ctx
         int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
         vit_feature_spec spec;
         int layer[4];                /* spec.taps resolved, ascending */
-        vit_feature_buffers out;     /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: d_stage */
-        vit_feature_buffers host;    /* FEAT_HOST: the caller's host buffers (cls, pooled) */
-        size_t per_image[2];         /* FEAT_HOST: bytes per image of cls, pooled */
-        void *d_stage[2];            /* FEAT_HOST: device cls, pooled for max_batch images */
-        void *h_stage[2][2];         /* FEAT_HOST: pinned [slot][cls, pooled] */
+        vit_feature_buffers out;     /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: st[].dev */
+        struct staged st[2];         /* FEAT_HOST: cls, pooled */
     } feat;
 
     /* top-k request (vit_hip_set_topk / _host), armed independently of the feature request.  The host form selects into
@@ -145,10 +152,8 @@ struct vit_hip_ctx
     {
         int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
         vit_topk_spec spec;
-        vit_topk_buffers out;        /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: d_stage */
-        vit_topk_buffers host;       /* FEAT_HOST: the caller's host buffers */
-        vit_topk_buffers d_stage;    /* FEAT_HOST: device labels, scores for max_batch images */
-        vit_topk_buffers h_stage[2]; /* FEAT_HOST: pinned, per slot */
+        vit_topk_buffers out;        /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: st[].dev */
+        struct staged st[2];         /* FEAT_HOST: labels, scores */
     } topk;
 
     /* optional per-operator timing with HIP events on the launch stream */
@@ -218,28 +223,44 @@ const float *vit_hip_weight(const vit_hip_ctx *ctx, int idx)
     return (idx >= 0 && idx < ctx->n_tensors) ? ctx->w[idx] : NULL;
 }
 
-static void feature_stage_release(vit_hip_ctx *ctx)
+/* The device buffer for max_batch images of st->per_image bytes and the two pinned slots; what a failure leaves behind,
+ * staged_release frees */
+static int staged_alloc(const vit_hip_ctx *ctx, struct staged *st)
 {
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->feat.d_stage[k]) vh_free(ctx->feat.d_stage[k]);
-        ctx->feat.d_stage[k] = NULL;
-        for (int slot = 0; slot < 2; ++slot) {
-            if (ctx->feat.h_stage[slot][k]) vh_host_free(ctx->feat.h_stage[slot][k]);
-            ctx->feat.h_stage[slot][k] = NULL;
-        }
+    const size_t bytes = (size_t)ctx->max_batch * st->per_image;
+    int rc = vh_malloc(&st->dev, bytes);
+    for (int slot = 0; slot < 2 && rc == 0; ++slot)
+        rc = vh_host_alloc(&st->pinned[slot], bytes);
+    return rc;
+}
+
+static void staged_release(struct staged *st)
+{
+    if (st->dev) vh_free(st->dev);
+    st->dev = NULL;
+    for (int slot = 0; slot < 2; ++slot) {
+        if (st->pinned[slot]) vh_host_free(st->pinned[slot]);
+        st->pinned[slot] = NULL;
     }
 }
 
-static void topk_stage_release(struct topk_req *tk)
+/* Queue the copy of a chunk of m images into its pinned slot */
+static int staged_d2h(const vit_hip_ctx *ctx, const struct staged *st, int slot, int m)
 {
-    if (tk->d_stage.labels) vh_free(tk->d_stage.labels);
-    if (tk->d_stage.scores) vh_free(tk->d_stage.scores);
-    tk->d_stage = (vit_topk_buffers){NULL, NULL};
-    for (int slot = 0; slot < 2; ++slot) {
-        if (tk->h_stage[slot].labels) vh_host_free(tk->h_stage[slot].labels);
-        if (tk->h_stage[slot].scores) vh_host_free(tk->h_stage[slot].scores);
-        tk->h_stage[slot] = (vit_topk_buffers){NULL, NULL};
-    }
+    return vh_d2h(st->pinned[slot], st->dev, (size_t)m * st->per_image, ctx->stream);
+}
+
+/* A chunk of m images from its pinned slot into the caller's memory, at image `first` */
+static void staged_scatter(const struct staged *st, int slot, int first, int m)
+{
+    memcpy(st->host + (size_t)first * st->per_image, st->pinned[slot], (size_t)m * st->per_image);
+}
+
+/* The staging of a host-form request, feature (cls, pooled) or top-k (labels, scores) */
+static void request_release(struct staged st[2])
+{
+    staged_release(&st[0]);
+    staged_release(&st[1]);
 }
 
 void vit_hip_destroy(vit_hip_ctx *ctx)
@@ -252,8 +273,8 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
         vh_stream_sync(ctx->stream);
     }
     prof_release(ctx);
-    feature_stage_release(ctx);
-    topk_stage_release(&ctx->topk);
+    request_release(ctx->feat.st);
+    request_release(ctx->topk.st);
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
@@ -1242,29 +1263,38 @@ fail:
     return rc;
 }
 
-/* The armed request a device-form forward serves; *refused when the host form is armed */
-static const struct feature_req *device_features(vit_hip_ctx *ctx, const char *who, int *refused)
+/* The armed requests a forward of the function `who` serves.  form: what that call can serve -- FEAT_DEVICE, FEAT_HOST, or
+ * FEAT_NONE for a call that serves nothing, whatever is armed.  A request armed in the other form refuses the call, the
+ * feature request first. */
+static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const struct feature_req **fr, const struct topk_req **tk)
 {
-    *refused = 0;
-    if (ctx->feat.form == FEAT_HOST) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: the context is armed for host feature buffers (vit_hip_set_features_host); disarm it or use the host forms", who);
-        vh_set_error(1, msg);
-        *refused = 1;
-    }
-    return ctx->feat.form == FEAT_DEVICE ? &ctx->feat : NULL;
+    const int armed[2] = {ctx->feat.form, ctx->topk.form};
+    *fr = NULL;
+    *tk = NULL;
+    if (form == FEAT_NONE)
+        return 0;
+    for (int r = 0; r < 2; ++r)
+        if (armed[r] != FEAT_NONE && armed[r] != form) {
+            char msg[200];
+            const char *const is = armed[r] == FEAT_HOST ? "host" : "device";
+            snprintf(msg, sizeof msg, "%s: the context is armed for %s %s buffers (vit_hip_set_%s%s); disarm it or use the %s forms", who, is,
+                     r ? "top-k" : "feature", r ? "topk" : "features", armed[r] == FEAT_HOST ? "_host" : "", is);
+            return vh_set_error(1, msg);
+        }
+    *fr = armed[0] == form ? &ctx->feat : NULL;
+    *tk = armed[1] == form ? &ctx->topk : NULL;
+    return 0;
 }
 
-/* The same for the top-k request; called only when device_features did not refuse */
-static const struct topk_req *device_topk(vit_hip_ctx *ctx, const char *who, int *refused)
+/* A public device-form forward, behind its argument checks */
+static int forward_device_armed(vit_hip_ctx *ctx, const char *who, const struct pixel_src *src, int n, float *d_logits, float *d_probs,
+                                vh_stream_t stream)
 {
-    if (ctx->topk.form == FEAT_HOST) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: the context is armed for host top-k buffers (vit_hip_set_topk_host); disarm it or use the host forms", who);
-        vh_set_error(1, msg);
-        *refused = 1;
-    }
-    return ctx->topk.form == FEAT_DEVICE ? &ctx->topk : NULL;
+    const struct feature_req *fr;
+    const struct topk_req *tk;
+    if (armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk))
+        return 1;
+    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk);
 }
 
 /* vit_hip_forward_device with no feature output whatever is armed (vit_gather_rccl.c) */
@@ -1281,13 +1311,8 @@ int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float
 {
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
-    int refused;
-    const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device", &refused);
-    const struct topk_req *tk = refused ? NULL : device_topk(ctx, "vit_hip_forward_device", &refused);
-    if (refused)
-        return 1;
     const struct pixel_src src = {d_images, NULL, 0, NULL};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr, tk);
+    return forward_device_armed(ctx, "vit_hip_forward_device", &src, n, d_logits, d_probs, stream);
 }
 
 int vit_pixel_norm_from_mean_std(vit_pixel_norm *out, const float *mean, const float *std, int chans)
@@ -1328,13 +1353,8 @@ int vit_hip_forward_device_u8(vit_hip_ctx *ctx, const unsigned char *d_images, i
 {
     if (u8_args("vit_hip_forward_device_u8", ctx, d_images, n, layout, norm, 1))
         return 1;
-    int refused;
-    const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device_u8", &refused);
-    const struct topk_req *tk = refused ? NULL : device_topk(ctx, "vit_hip_forward_device_u8", &refused);
-    if (refused)
-        return 1;
     const struct pixel_src src = {NULL, d_images, layout, norm};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr, tk);
+    return forward_device_armed(ctx, "vit_hip_forward_device_u8", &src, n, d_logits, d_probs, stream);
 }
 
 int vit_resize_crop_geometry(int height, int width, const vit_resize_crop *rc, int crop, int *resized_h, int *resized_w, int *top,
@@ -1417,19 +1437,21 @@ int vit_hip_forward_device_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *d_im
 {
     if (resize_args("vit_hip_forward_device_u8_resized", ctx, d_images, n, layout, rc, norm, 1, NULL, 0, 1, 0))
         return 1;
-    int refused;
-    const struct feature_req *fr = device_features(ctx, "vit_hip_forward_device_u8_resized", &refused);
-    const struct topk_req *tk = refused ? NULL : device_topk(ctx, "vit_hip_forward_device_u8_resized", &refused);
-    if (refused)
-        return 1;
     const struct pixel_src src = {NULL, NULL, layout, norm, d_images, rc};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, fr, tk);
+    return forward_device_armed(ctx, "vit_hip_forward_device_u8_resized", &src, n, d_logits, d_probs, stream);
+}
+
+/* "who: why" as the thread's error text; returns 1 */
+static int refuse(const char *who, const char *why)
+{
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return vh_set_error(1, msg);
 }
 
 /* spec against cfg; the taps resolved to ascending layer indices */
 static int feature_spec_check(const char *who, const vit_config *cfg, const vit_feature_spec *spec, int layer[4])
 {
-    char msg[200];
     const char *why = !cfg || !spec ? "NULL argument"
                       : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
                       : spec->n_taps < 1 || spec->n_taps > 4 ? "n_taps must be in 1..4"
@@ -1445,10 +1467,7 @@ static int feature_spec_check(const char *who, const vit_config *cfg, const vit_
         else
             layer[k] = t < 0 ? t + cfg->depth : t;
     }
-    if (!why)
-        return 0;
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return vh_set_error(1, msg);
+    return why ? refuse(who, why) : 0;
 }
 
 int vit_feature_sizes(const vit_config *cfg, const vit_feature_spec *spec, size_t *cls_elems, size_t *pooled_elems, size_t *tokens_elems)
@@ -1466,18 +1485,35 @@ int vit_feature_sizes(const vit_config *cfg, const vit_feature_spec *spec, size_
     return 0;
 }
 
-/* Both forms of arming; host: bufs are host memory, staged through device buffers and pinned slots made here */
-static int set_features(const char *who, vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *bufs, int host)
+/* What arming a feature and a top-k request share, behind their own spec and buffer checks (skipped without a context, which
+ * is refused here).  req: the new request's staged arrays; the host form has named the caller's memory and the bytes per
+ * image of those it wants, and their stages are made here.  armed: where the context keeps the request's staged arrays.
+ * Returns 0 with the old request's staging released, for the caller to store the new request; on failure the previous
+ * request stays armed and nothing leaks. */
+static int arm(const char *who, vit_hip_ctx *ctx, size_t armed, struct staged req[2])
 {
     int rc = 0;
-    char msg[200];
-    if (!ctx) {
-        snprintf(msg, sizeof msg, "%s: NULL context", who);
-        return vh_set_error(1, msg);
-    }
+    if (!ctx)
+        return refuse(who, "NULL context");
+    TRY(vh_set_device(ctx->device));
+    /* the staging of an earlier host request may still be read by its last forward's copies */
+    TRY(vh_stream_sync(ctx->stream));
+    for (int k = 0; k < 2; ++k)
+        if (req[k].host)
+            TRY(staged_alloc(ctx, &req[k]));
+    request_release((struct staged *)((char *)ctx + armed));
+    return 0;
+fail:
+    request_release(req);
+    return rc;
+}
+
+/* Both forms of arming; host: bufs are host memory, staged through device buffers and pinned slots made by arm() */
+static int set_features(const char *who, vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *bufs, int host)
+{
     struct feature_req fr;
     memset(&fr, 0, sizeof fr);
-    if (spec) {
+    if (ctx && spec) {
         if (feature_spec_check(who, &ctx->cfg, spec, fr.layer))
             return 1;
         const char *why = !bufs || (!bufs->cls && !bufs->pooled && !bufs->tokens) ? "no output buffer"
@@ -1485,43 +1521,24 @@ static int set_features(const char *who, vit_hip_ctx *ctx, const vit_feature_spe
                           : ctx->tokens < 2 && (bufs->pooled || bufs->tokens) ? "pooled and tokens need at least one patch token"
                           : !host && (((uintptr_t)bufs->cls | (uintptr_t)bufs->pooled | (uintptr_t)bufs->tokens) & 15) ? "device buffers must be 16-byte aligned"
                           : NULL;
-        if (why) {
-            snprintf(msg, sizeof msg, "%s: %s", who, why);
-            return vh_set_error(1, msg);
-        }
+        if (why)
+            return refuse(who, why);
         fr.form = host ? FEAT_HOST : FEAT_DEVICE;
         fr.spec = *spec;
         fr.out = *bufs;
-    }
-    TRY(vh_set_device(ctx->device));
-    /* the staging of an earlier host request may still be read by its last forward's copies */
-    TRY(vh_stream_sync(ctx->stream));
-    if (fr.form == FEAT_HOST) {
-        const size_t per = (size_t)spec->n_taps * ctx->cfg.embed_dim * (spec->dtype == VIT_FEATURE_BF16 ? 2 : 4);
-        const void *want[2] = {bufs->cls, bufs->pooled};
-        fr.host = *bufs;
-        for (int k = 0; k < 2 && rc == 0; ++k) {
-            if (!want[k])
-                continue;
-            fr.per_image[k] = per;
-            rc = vh_malloc(&fr.d_stage[k], (size_t)ctx->max_batch * per);
-            for (int slot = 0; slot < 2 && rc == 0; ++slot)
-                rc = vh_host_alloc(&fr.h_stage[slot][k], (size_t)ctx->max_batch * per);
-        }
-        fr.out = (vit_feature_buffers){fr.d_stage[0], fr.d_stage[1], NULL};
-        if (rc != 0) {   /* the previous request stays armed */
-            struct feature_req keep = ctx->feat;
-            ctx->feat = fr;
-            feature_stage_release(ctx);
-            ctx->feat = keep;
-            return rc;
+        if (host) {
+            const size_t per = (size_t)spec->n_taps * ctx->cfg.embed_dim * (spec->dtype == VIT_FEATURE_BF16 ? 2 : 4);
+            fr.st[0] = (struct staged){.host = (char *)bufs->cls, .per_image = per};
+            fr.st[1] = (struct staged){.host = (char *)bufs->pooled, .per_image = per};
         }
     }
-    feature_stage_release(ctx);
+    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, feat.st), fr.st);
+    if (rc != 0)
+        return rc;
+    if (fr.form == FEAT_HOST)
+        fr.out = (vit_feature_buffers){fr.st[0].dev, fr.st[1].dev, NULL};
     ctx->feat = fr;
     return 0;
-fail:
-    return rc;
 }
 
 int vit_hip_set_features(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *d_bufs)
@@ -1536,17 +1553,13 @@ int vit_hip_set_features_host(vit_hip_ctx *ctx, const vit_feature_spec *spec, co
 
 static int topk_spec_check(const char *who, const vit_config *cfg, const vit_topk_spec *spec)
 {
-    char msg[200];
     const char *why = !cfg || !spec ? "NULL argument"
                       : cfg->num_classes < 1 || cfg->num_classes > 65536 ? "num_classes must be in 1..65536"
                       : spec->k < 1 || spec->k > 32 ? "k must be in 1..32"
                       : spec->k > cfg->num_classes ? "k exceeds num_classes"
                       : spec->score_kind != VIT_TOPK_PROBS && spec->score_kind != VIT_TOPK_LOGITS ? "score_kind must be VIT_TOPK_PROBS or VIT_TOPK_LOGITS"
                       : NULL;
-    if (!why)
-        return 0;
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return vh_set_error(1, msg);
+    return why ? refuse(who, why) : 0;
 }
 
 int vit_topk_check(const vit_config *cfg, const vit_topk_spec *spec)
@@ -1554,56 +1567,34 @@ int vit_topk_check(const vit_config *cfg, const vit_topk_spec *spec)
     return topk_spec_check("vit_topk_check", cfg, spec);
 }
 
-/* Both forms of arming; host: bufs are host memory, staged through device buffers and pinned slots made here */
+/* Both forms of arming, as set_features */
 static int set_topk(const char *who, vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *bufs, int host)
 {
-    int rc = 0;
-    char msg[200];
-    if (!ctx) {
-        snprintf(msg, sizeof msg, "%s: NULL context", who);
-        return vh_set_error(1, msg);
-    }
     struct topk_req tk;
     memset(&tk, 0, sizeof tk);
-    if (spec) {
+    if (ctx && spec) {
         if (topk_spec_check(who, &ctx->cfg, spec))
             return 1;
         const char *why = !bufs || !bufs->labels ? "no labels buffer"
                           : !host && (((uintptr_t)bufs->labels | (uintptr_t)bufs->scores) & 15) ? "device buffers must be 16-byte aligned"
                           : NULL;
-        if (why) {
-            snprintf(msg, sizeof msg, "%s: %s", who, why);
-            return vh_set_error(1, msg);
-        }
+        if (why)
+            return refuse(who, why);
         tk.form = host ? FEAT_HOST : FEAT_DEVICE;
         tk.spec = *spec;
         tk.out = *bufs;
-    }
-    TRY(vh_set_device(ctx->device));
-    /* the staging of an earlier host request may still be read by its last forward's copies */
-    TRY(vh_stream_sync(ctx->stream));
-    if (tk.form == FEAT_HOST) {
-        const size_t pairs = (size_t)ctx->max_batch * spec->k;
-        tk.host = *bufs;
-        rc = vh_malloc((void **)&tk.d_stage.labels, pairs * sizeof(int));
-        if (rc == 0 && bufs->scores)
-            rc = vh_malloc((void **)&tk.d_stage.scores, pairs * sizeof(float));
-        for (int slot = 0; slot < 2 && rc == 0; ++slot) {
-            rc = vh_host_alloc((void **)&tk.h_stage[slot].labels, pairs * sizeof(int));
-            if (rc == 0 && bufs->scores)
-                rc = vh_host_alloc((void **)&tk.h_stage[slot].scores, pairs * sizeof(float));
-        }
-        tk.out = tk.d_stage;
-        if (rc != 0) {   /* the previous request stays armed */
-            topk_stage_release(&tk);
-            return rc;
+        if (host) {
+            tk.st[0] = (struct staged){.host = (char *)bufs->labels, .per_image = (size_t)spec->k * sizeof(int)};
+            tk.st[1] = (struct staged){.host = (char *)bufs->scores, .per_image = (size_t)spec->k * sizeof(float)};
         }
     }
-    topk_stage_release(&ctx->topk);
+    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, topk.st), tk.st);
+    if (rc != 0)
+        return rc;
+    if (tk.form == FEAT_HOST)
+        tk.out = (vit_topk_buffers){tk.st[0].dev, tk.st[1].dev};
     ctx->topk = tk;
     return 0;
-fail:
-    return rc;
 }
 
 int vit_hip_set_topk(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *d_bufs)
@@ -1696,29 +1687,13 @@ fail:
     return rc;
 }
 
-/* Host-pointer forward, software-pipelined over chunks of max_batch images:
- *   host     : gather chunk k into pinned slot k&1   | scatter outputs of chunk k-1
- *   copy strm: H2D chunk k                            (after compute of chunk k-2 released the slot)
- *   compute  : forward chunk k, D2H its logits/probs  (after the H2D)
- * so PCIe and the gather of the separately malloc'd images (Network.c:90) hide under
- * the previous chunk's kernels. */
-static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, float *logits, float **probs, const struct feature_req *fr,
-                            const struct topk_req *tk)
+/* The outputs of one finished chunk from its pinned slot into the caller's memory.  The probabilities keep a scatter of
+ * their own: the ABI hands them over as float **, one allocation per image (Network.c:90), which no struct staged describes. */
+static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, const struct staged *const *arrays, int n_arrays, float **probs)
 {
     const size_t NC = (size_t)ctx->cfg.num_classes;
-    if (tk) {   /* the k pairs per image of the armed host request */
-        const size_t k = (size_t)tk->spec.k;
-        memcpy(tk->host.labels + (size_t)first * k, tk->h_stage[slot].labels, (size_t)m * k * sizeof(int));
-        if (tk->host.scores)
-            memcpy(tk->host.scores + (size_t)first * k, tk->h_stage[slot].scores, (size_t)m * k * sizeof(float));
-    }
-    for (int k = 0; fr && k < 2; ++k) {   /* cls, pooled of the armed host request */
-        char *to = (char *)(k == 0 ? fr->host.cls : fr->host.pooled);
-        if (to)
-            memcpy(to + (size_t)first * fr->per_image[k], fr->h_stage[slot][k], (size_t)m * fr->per_image[k]);
-    }
-    if (logits)
-        memcpy(logits + (size_t)first * NC, ctx->h_logits[slot], (size_t)m * NC * sizeof(float));
+    for (int a = 0; a < n_arrays; ++a)
+        staged_scatter(arrays[a], slot, first, m);
     if (probs)
         for (int i = 0; i < m; ++i)
             memcpy(probs[first + i], ctx->h_probs[slot] + (size_t)i * NC, NC * sizeof(float));
@@ -1826,21 +1801,42 @@ static void gather_images(void *dst, const struct host_src *src, int base, int m
         pthread_join(tid[t], NULL);
 }
 
-/* The pipeline of vit_hip_forward and vit_hip_forward_u8: a u8 chunk fills a quarter of a staging slot */
-static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n, float *logits, float **probs, int features)
+/* The bytes of one staging slot of images: max_batch fp32 images */
+static size_t image_slot_bytes(const vit_hip_ctx *ctx)
+{
+    return (size_t)ctx->max_batch * ctx->cfg.in_chans * ctx->cfg.img_size * ctx->cfg.img_size * sizeof(float);
+}
+
+/* Host-pointer forward, software-pipelined over chunks of max_batch images:
+ *   host     : gather chunk k into pinned slot k&1   | scatter outputs of chunk k-1
+ *   copy strm: H2D chunk k                            (after compute of chunk k-2 released the slot)
+ *   compute  : forward chunk k, D2H its logits/probs  (after the H2D)
+ * so PCIe and the gather of the separately malloc'd images (Network.c:90) hide under
+ * the previous chunk's kernels.  A u8 chunk fills a quarter of a staging slot.  form: FEAT_HOST to serve the armed host
+ * requests, FEAT_NONE to serve none. */
+static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n, float *logits, float **probs, int form)
 {
     int rc = 0;
-    if (features && ctx->feat.form == FEAT_DEVICE)
-        return vh_set_error(1, "forward: the context is armed for device feature buffers (vit_hip_set_features); disarm it or use the device forms");
-    if (features && ctx->topk.form == FEAT_DEVICE)
-        return vh_set_error(1, "forward: the context is armed for device top-k buffers (vit_hip_set_topk); disarm it or use the device forms");
-    const struct feature_req *fr = features && ctx->feat.form == FEAT_HOST ? &ctx->feat : NULL;
-    const struct topk_req *tk = features && ctx->topk.form == FEAT_HOST ? &ctx->topk : NULL;
+    const struct feature_req *fr;
+    const struct topk_req *tk;
+    if (armed_requests(ctx, "forward", form, &fr, &tk))
+        return 1;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->u8 ? 1 : sizeof(float));
     const size_t NC = (size_t)c->num_classes;
-    const size_t slot_bytes = (size_t)ctx->max_batch * c->in_chans * c->img_size * c->img_size * sizeof(float);
+    const size_t slot_bytes = image_slot_bytes(ctx);
+    /* what comes back per chunk besides the probabilities, in the order it is queued: logits, cls, pooled, labels, scores */
+    const struct staged logits_st = {ctx->d_logits, {ctx->h_logits[0], ctx->h_logits[1]}, (char *)logits, NC * sizeof(float)};
+    const struct staged *arrays[5];
+    int n_arrays = 0;
+    if (logits)
+        arrays[n_arrays++] = &logits_st;
+    for (int a = 0; a < 4; ++a) {
+        const struct staged *st = a < 2 ? (fr ? &fr->st[a] : NULL) : (tk ? &tk->st[a - 2] : NULL);
+        if (st && st->dev)
+            arrays[n_arrays++] = st;
+    }
 
     int prev_first = 0, prev_m = 0, k = 0;
     for (int first = 0, m = 0; first < n; first += m, ++k) {
@@ -1868,29 +1864,24 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
         TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
+        int a = 0;
         if (logits)
-            TRY(vh_d2h(ctx->h_logits[s], ctx->d_logits, (size_t)m * NC * sizeof(float), ctx->stream));
-        if (probs)
+            TRY(staged_d2h(ctx, arrays[a++], s, m));
+        if (probs)   /* queued between the logits and the armed requests' arrays */
             TRY(vh_d2h(ctx->h_probs[s], ctx->d_probs, (size_t)m * NC * sizeof(float), ctx->stream));
-        for (int f = 0; fr && f < 2; ++f)
-            if (fr->d_stage[f])
-                TRY(vh_d2h(fr->h_stage[s][f], fr->d_stage[f], (size_t)m * fr->per_image[f], ctx->stream));
-        if (tk) {
-            TRY(vh_d2h(tk->h_stage[s].labels, tk->d_stage.labels, (size_t)m * tk->spec.k * sizeof(int), ctx->stream));
-            if (tk->d_stage.scores)
-                TRY(vh_d2h(tk->h_stage[s].scores, tk->d_stage.scores, (size_t)m * tk->spec.k * sizeof(float), ctx->stream));
-        }
+        for (; a < n_arrays; ++a)
+            TRY(staged_d2h(ctx, arrays[a], s, m));
         TRY(vh_event_record(ctx->out_done[s], ctx->stream));
 
         if (k >= 1) { /* finish chunk k-1 while chunk k runs */
             TRY(vh_event_sync(ctx->out_done[s ^ 1]));
-            scatter_outputs(ctx, s ^ 1, prev_first, prev_m, logits, probs, fr, tk);
+            scatter_outputs(ctx, s ^ 1, prev_first, prev_m, arrays, n_arrays, probs);
         }
         prev_first = first;
         prev_m = m;
     }
     TRY(vh_event_sync(ctx->out_done[(k - 1) & 1]));
-    scatter_outputs(ctx, (k - 1) & 1, prev_first, prev_m, logits, probs, fr, tk);
+    scatter_outputs(ctx, (k - 1) & 1, prev_first, prev_m, arrays, n_arrays, probs);
     return 0;
 fail:
     vh_stream_sync(ctx->copy_stream);
@@ -1898,7 +1889,7 @@ fail:
     return rc;
 }
 
-static int forward_host_images(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs, int features)
+static int forward_host_images(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs, int form)
 {
     if (!ctx || !images || n <= 0)
         return 1;
@@ -1908,12 +1899,12 @@ static int forward_host_images(vit_hip_ctx *ctx, const ImageData *images, int n,
             images[i].w != c->img_size)
             return 5;
     const struct host_src src = {images, NULL, 0, NULL};
-    return forward_pipelined(ctx, &src, n, logits, probs, features);
+    return forward_pipelined(ctx, &src, n, logits, probs, form);
 }
 
 int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs)
 {
-    return forward_host_images(ctx, images, n, logits, probs, 1);
+    return forward_host_images(ctx, images, n, logits, probs, FEAT_HOST);
 }
 
 int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int layout,
@@ -1922,13 +1913,13 @@ int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int
     if (u8_args("vit_hip_forward_u8", ctx, images, n, layout, norm, 0))
         return 1;
     const struct host_src src = {NULL, images, layout, norm};
-    return forward_pipelined(ctx, &src, n, logits, probs, 1);
+    return forward_pipelined(ctx, &src, n, logits, probs, FEAT_HOST);
 }
 
 int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int n, int layout, const vit_resize_crop *rc,
                                const vit_pixel_norm *norm, float *logits, float **probs)
 {
-    const size_t slot_bytes = ctx ? (size_t)ctx->max_batch * ctx->cfg.in_chans * ctx->cfg.img_size * ctx->cfg.img_size * sizeof(float) : 0;
+    const size_t slot_bytes = ctx ? image_slot_bytes(ctx) : 0;
     if (resize_args("vit_hip_forward_u8_resized", ctx, images, n, layout, rc, norm, 1, NULL, 0, 0, slot_bytes))
         return 1;
     size_t *packed = malloc(((size_t)ctx->max_batch + 1) * sizeof(*packed));
@@ -1936,7 +1927,7 @@ int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int
     int rc_ = 1;
     if (packed && staged) {
         const struct host_src src = {NULL, NULL, layout, norm, images, rc, packed, staged};
-        rc_ = forward_pipelined(ctx, &src, n, logits, probs, 1);
+        rc_ = forward_pipelined(ctx, &src, n, logits, probs, FEAT_HOST);
     } else {
         vh_set_error(1, "vit_hip_forward_u8_resized: out of host memory");
     }
@@ -2125,7 +2116,7 @@ static int multi_forward_one(void *arg, int shard, int lo, int hi)
     const size_t NC = (size_t)vit_hip_config(m->ctx[shard])->num_classes;
     /* no feature or top-k output, whatever a caller armed on the shard's context */
     return forward_host_images(m->ctx[shard], m->images + lo, hi - lo, m->logits ? m->logits + (size_t)lo * NC : NULL,
-                               m->probs ? m->probs + lo : NULL, 0);
+                               m->probs ? m->probs + lo : NULL, FEAT_NONE);
 }
 
 /* Not re-entrant on one vit_hip_multi (like vit_hip_forward on one context). */

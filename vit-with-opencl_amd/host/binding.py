@@ -560,6 +560,14 @@ class DeviceBuffer:
             pass
 
 
+def _device_ptr(b):
+    return b.ptr if isinstance(b, DeviceBuffer) else b
+
+
+def _host_ptr(a):
+    return a.ctypes.data
+
+
 class ViTHip:
     """Resident-weights context (vit_hip_create / forward / destroy)."""
 
@@ -673,32 +681,28 @@ class ViTHip:
     def sync(self):
         check(self.L.vh_stream_sync(self.stream), "vh_stream_sync")
 
+    def _arm(self, entry, spec, buffers, arrays, ptr, keep):
+        """What the four setters share: the C entry point `entry` gets spec's C struct and the `buffers` struct of
+        ptr(array) per array, and the attribute `keep` holds the arrays alive; spec=None disarms."""
+        if spec is None:
+            cs = bufs = None
+        else:
+            cs, bufs = C.byref(spec.c_struct()), C.byref(buffers(*[None if a is None else ptr(a) for a in arrays]))
+        check(getattr(self.L, entry)(self.ctx, cs, bufs), entry)
+        setattr(self, keep, None if spec is None else tuple(arrays))
+
     def set_features(self, spec, cls=None, pooled=None, tokens=None):
         """Arm (spec=None: disarm) the device forms: cls / pooled / tokens are DeviceBuffers (or device pointers) for up to
         max_batch images, written by every forward_device* until disarmed."""
-        if spec is None:
-            check(self.L.vit_hip_set_features(self.ctx, None, None), "vit_hip_set_features")
-            self._feature_keep = None
-            return
-        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
-        cs, bufs = spec.c_struct(), FeatureBuffers(ptr(cls), ptr(pooled), ptr(tokens))
-        check(self.L.vit_hip_set_features(self.ctx, C.byref(cs), C.byref(bufs)), "vit_hip_set_features")
-        self._feature_keep = (cls, pooled, tokens)
+        self._arm("vit_hip_set_features", spec, FeatureBuffers, (cls, pooled, tokens), _device_ptr, "_feature_keep")
 
     def set_features_host(self, spec, cls=None, pooled=None, tokens=None):
         """Arm (spec=None: disarm) the host forms: cls / pooled are C-contiguous NumPy arrays of spec.np_dtype for all n
         images of the coming forward / forward_u8 / forward_u8_resized calls."""
-        if spec is None:
-            check(self.L.vit_hip_set_features_host(self.ctx, None, None), "vit_hip_set_features_host")
-            self._feature_keep = None
-            return
         for a in (cls, pooled, tokens):
-            if a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == spec.np_dtype):
+            if spec is not None and a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == spec.np_dtype):
                 raise ValueError(f"set_features_host: need C-contiguous arrays of {spec.np_dtype}")
-        ptr = lambda a: None if a is None else a.ctypes.data
-        cs, bufs = spec.c_struct(), FeatureBuffers(ptr(cls), ptr(pooled), ptr(tokens))
-        check(self.L.vit_hip_set_features_host(self.ctx, C.byref(cs), C.byref(bufs)), "vit_hip_set_features_host")
-        self._feature_keep = (cls, pooled, tokens)
+        self._arm("vit_hip_set_features_host", spec, FeatureBuffers, (cls, pooled, tokens), _host_ptr, "_feature_keep")
 
     def embed(self, images: np.ndarray, spec):
         """fp32 images [n][C][H][W] -> (logits, cls, pooled): the host form armed for this one call."""
@@ -716,29 +720,15 @@ class ViTHip:
     def set_topk(self, spec, labels=None, scores=None):
         """Arm (spec=None: disarm) the device forms: labels (int32) / scores (float32, may be None) are DeviceBuffers (or
         device pointers) of [max_batch][k], written by every forward_device* until disarmed."""
-        if spec is None:
-            check(self.L.vit_hip_set_topk(self.ctx, None, None), "vit_hip_set_topk")
-            self._topk_keep = None
-            return
-        ptr = lambda b: None if b is None else (b.ptr if isinstance(b, DeviceBuffer) else b)
-        cs, bufs = spec.c_struct(), TopKBuffers(ptr(labels), ptr(scores))
-        check(self.L.vit_hip_set_topk(self.ctx, C.byref(cs), C.byref(bufs)), "vit_hip_set_topk")
-        self._topk_keep = (labels, scores)
+        self._arm("vit_hip_set_topk", spec, TopKBuffers, (labels, scores), _device_ptr, "_topk_keep")
 
     def set_topk_host(self, spec, labels=None, scores=None):
         """Arm (spec=None: disarm) the host forms: labels (int32 [n][k]) / scores (float32 [n][k], may be None) are
         C-contiguous NumPy arrays for all n images of the coming forward / forward_u8 / forward_u8_resized calls."""
-        if spec is None:
-            check(self.L.vit_hip_set_topk_host(self.ctx, None, None), "vit_hip_set_topk_host")
-            self._topk_keep = None
-            return
         for a, dt in ((labels, np.int32), (scores, np.float32)):
-            if a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == dt):
+            if spec is not None and a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == dt):
                 raise ValueError("set_topk_host: need C-contiguous int32 labels and float32 scores")
-        ptr = lambda a: None if a is None else a.ctypes.data
-        cs, bufs = spec.c_struct(), TopKBuffers(ptr(labels), ptr(scores))
-        check(self.L.vit_hip_set_topk_host(self.ctx, C.byref(cs), C.byref(bufs)), "vit_hip_set_topk_host")
-        self._topk_keep = (labels, scores)
+        self._arm("vit_hip_set_topk_host", spec, TopKBuffers, (labels, scores), _host_ptr, "_topk_keep")
 
     def classify(self, images: np.ndarray, k: int = 5, scores: str = "probs"):
         """fp32 images [n][C][H][W] -> (labels[n][k] int32, scores[n][k] float32): the host form armed for this one call;
