@@ -179,6 +179,10 @@ int vh_launch_merge3_rows(vh_stream_t s, const void *planes, float *output, int 
  * the bf16-operand mode, BASELINE config 3), planes[cols/32][1][rows][32]: the same GEMM kernel takes both. */
 int vh_launch_split_rows(vh_stream_t s, const float *input, void *planes, int rows, int cols, int parts);
 int vh_launch_merge_rows(vh_stream_t s, const void *planes, float *output, int rows, int cols, int parts);
+/* vh_launch_layer_norm writing planes [embed_dim/32][parts][rows][32]: embed_dim % 32 == 0 and at most
+ * vh_layer_norm_planes_max_embed(parts) -- 2048 with one part, 1696 with three: the kernel stages 16 rows of every part
+ * in LDS, 32 * parts * embed_dim bytes of a CU's 160 KiB.  Wider rows are refused before any launch. */
+int vh_layer_norm_planes_max_embed(int parts);   /* 0 for parts other than 1 and 3 */
 int vh_launch_layer_norm_planes(vh_stream_t s, const float *input, const float *weight, const float *bias,
                                 void *out_planes, int parts, int rows, int embed_dim, long in_row_stride, double eps);
 int vh_launch_attention_planes_bf16(vh_stream_t s, const float *qkv, void *out_planes, int n_images, int tokens,
@@ -189,7 +193,7 @@ int vh_launch_attention_planes_bf16(vh_stream_t s, const float *qkv, void *out_p
 int vh_launch_linear_planes(vh_stream_t s, void *output, int output_planes, const void *weight_planes,
                             const void *input_planes, int parts, const float *bias, int rowA, int colA, int colB,
                             int doGelu, const float *residual);
-/* vh_launch_layer_norm writing planes [embed_dim/32][3][rows][32] */
+/* vh_launch_layer_norm writing planes [embed_dim/32][3][rows][32]: vh_launch_layer_norm_planes with parts = 3, embed_dim <= 1696 */
 int vh_launch_layer_norm_p3(vh_stream_t s, const float *input, const float *weight, const float *bias,
                             void *out_planes, int rows, int embed_dim, long in_row_stride, double eps);
 /* vh_launch_attention writing planes [embed_dim/32][3][n_images*tokens][32] (head_dim 64, tokens <= 208) */

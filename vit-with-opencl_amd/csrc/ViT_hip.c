@@ -519,6 +519,15 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
     if (ln_fold && (!fold_fits || (precision == VIT_PRECISION_F32 && !use_p3)))
         return vh_set_error(2, "vit_hip_create: this shape, precision and batch cannot fold the LayerNorms (the fp32 path "
                                "needs the planes path)");
+    /* the planes path's LayerNorms write three parts per value through an LDS image that ends at embed_dim 1696
+     * (vh_layer_norm_planes_max_embed, csrc/rowops.hip); the lab fold launches none of them */
+    if (use_p3 && !ln_fold && E > vh_layer_norm_planes_max_embed(3)) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "vit_hip_create: embed_dim=%d: the fp32 planes path's LayerNorm (three-part planes, 96 bytes of "
+                 "LDS per column) takes a LayerNorm width of at most %d",
+                 E, vh_layer_norm_planes_max_embed(3));
+        return vh_set_error(2, msg);
+    }
     const char *env_ll = getenv("VIT_HIP_LAST_LAYER");
     /* attention: ATTN_LONG is the only kernel past STREAMING_MAX_TOKENS, and it reads the planes paths' Q|K|V with head_dim
      * 64 or 80; $VIT_HIP_ATTN=long forces it at any T (tests, A/B), $VIT_HIP_ATTN=tiled the streaming kernel wherever

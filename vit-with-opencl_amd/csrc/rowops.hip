@@ -391,6 +391,18 @@ extern "C" int vh_launch_layer_norm(vh_stream_t s, const float *input, const flo
                              out_row_stride, eps);
 }
 
+/* The planes kernel stages 16 rows of every part in LDS, 32 * parts * embed_dim bytes, and a CU has LN3_LDS_LIMIT of it:
+ * the registers hold rows of up to 2048 values, the LDS image with three parts only 1696 (162 816 of 163 840 bytes). */
+constexpr int LN3_LDS_LIMIT = 160 * 1024;
+
+extern "C" int vh_layer_norm_planes_max_embed(int parts)
+{
+    if (parts != 1 && parts != 3)
+        return 0;
+    const int by_lds = LN3_LDS_LIMIT / (parts * LN3_ROWS * 64) * 32;
+    return by_lds < 2048 ? by_lds : 2048;
+}
+
 extern "C" int vh_launch_layer_norm_planes(vh_stream_t s, const float *input, const float *weight, const float *bias,
                                            void *out_planes, int parts, int rows, int embed_dim, long in_row_stride,
                                            double eps)
@@ -399,20 +411,24 @@ extern "C" int vh_launch_layer_norm_planes(vh_stream_t s, const float *input, co
         return vh_fail(1, "vh_launch_layer_norm_planes: null pointer argument");
     if (rows <= 0 || embed_dim <= 0 || embed_dim % 32 != 0 || embed_dim > 2048 || ((uintptr_t)out_planes & 15) ||
         (parts != 1 && parts != 3))
-        return vh_fail(1, "vh_launch_layer_norm_planes: embed_dim=%d must be a multiple of 32, <= 2048, planes 16-byte "
-                          "aligned, parts 1 or 3", embed_dim);
+        return vh_fail(1, "vh_launch_layer_norm_planes: embed_dim=%d must be a multiple of 32, <= 2048 with one part and "
+                          "<= 1696 with three, planes 16-byte aligned, parts 1 or 3", embed_dim);
+    if (embed_dim > vh_layer_norm_planes_max_embed(parts))
+        return vh_fail(1, "vh_launch_layer_norm_planes: embed_dim=%d with %d parts needs %d bytes of LDS for its 16-row image, "
+                          "a CU has %d: the largest embed_dim with %d parts is %d", embed_dim, parts,
+                       32 * parts * embed_dim, LN3_LDS_LIMIT, parts, vh_layer_norm_planes_max_embed(parts));
     if (in_row_stride % 4 != 0 || in_row_stride < embed_dim)
         return vh_fail(1, "vh_launch_layer_norm_planes: row stride must be a multiple of 4 floats and >= embed_dim");
     const int nv = (embed_dim / 4 + 63) / 64;
     const size_t lds = (size_t)(embed_dim / 32) * parts * LN3_ROWS * 64;
     const int ngroups = (rows + LN3_ROWS - 1) / LN3_ROWS;
-    const int resident = (160 * 1024) / (int)lds < 2 ? 1 : 2;            /* workgroups of 1024 threads per CU */
+    const int resident = LN3_LDS_LIMIT / (int)lds < 2 ? 1 : 2;           /* workgroups of 1024 threads per CU */
     const int cap = resident * vh_device_cus(vh_current_device());
     const dim3 grid(ngroups < cap ? ngroups : cap), block(64 * LN3_ROWS);
     hipStream_t st = (hipStream_t)s;
 #define VH_LN3_F(NV, NPL, FULL)                                                                           \
     do {                                                                                                  \
-        VH_SET_LDS_ONCE((layernorm_p3_kernel<NV, NPL, FULL>), 160 * 1024);                                \
+        VH_SET_LDS_ONCE((layernorm_p3_kernel<NV, NPL, FULL>), LN3_LDS_LIMIT);                             \
         hipLaunchKernelGGL((layernorm_p3_kernel<NV, NPL, FULL>), grid, block, lds, st, input, weight, bias, \
                            static_cast<char *>(out_planes), rows, embed_dim, in_row_stride, eps);         \
     } while (0)

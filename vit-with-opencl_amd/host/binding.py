@@ -40,7 +40,7 @@ EXPORTS = [
     "vh_launch_split2h_planes", "vh_launch_linear_h2", "vh_launch_attention_h2", "vh_launch_attention_f16",
     "vh_launch_absmax",
     "vh_launch_split3_rows", "vh_launch_merge3_rows", "vh_launch_layer_norm_p3", "vh_launch_attention_p3",
-    "vh_launch_linear_p3", "vh_launch_split_rows", "vh_launch_merge_rows", "vh_launch_layer_norm_planes",
+    "vh_launch_linear_p3", "vh_launch_split_rows", "vh_launch_merge_rows", "vh_launch_layer_norm_planes", "vh_layer_norm_planes_max_embed",
     "vh_launch_attention_planes_bf16", "vh_launch_linear_planes", "vh_launch_attention_planes",
     "vh_launch_quantize_mx_rows", "vh_launch_quantize_mx_act", "vh_mx_act_scale_bytes", "vh_launch_linear_mx", "vh_launch_layer_norm_mx",
     "vh_launch_attention_planes_f16", "vh_launch_linear_mx_planes_f16", "vh_launch_attention_planes_f16_mx",
@@ -335,6 +335,7 @@ def lib() -> C.CDLL:
     L.vh_launch_split_rows.argtypes = [voidp, voidp, voidp, i, i, i]
     L.vh_launch_merge_rows.argtypes = [voidp, voidp, voidp, i, i, i]
     L.vh_launch_layer_norm_planes.argtypes = [voidp] + [voidp] * 4 + [i, i, i, C.c_long, C.c_double]
+    L.vh_layer_norm_planes_max_embed.argtypes = [i]
     L.vh_launch_attention_planes_bf16.argtypes = [voidp, voidp, voidp, i, i, i, i]
     L.vh_launch_attention_planes.argtypes = [voidp, voidp, voidp, i, i, i, i]
     L.vh_launch_gather_rows.argtypes = [voidp, voidp, voidp, i, i, i, i, i]
