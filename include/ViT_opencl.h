@@ -343,6 +343,52 @@ int vit_topk_check(const vit_config *cfg, const vit_topk_spec *spec);
 int vit_hip_set_topk(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *d_bufs);
 int vit_hip_set_topk_host(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *h_bufs);
 
+/* ---- class-token attention maps: which patches the class token looked at, per head, in any layer ----
+ * An attention request is ARMED on a context like a feature or a top-k request, and independently of both (all three may
+ * be armed at once).  While armed, every forward through the context also writes, for every tapped layer, the class
+ * token's row of that layer's attention matrix, by one extra memory-bound launch (two when both outputs are asked for)
+ * between the layer's QKV projection and its attention (vh_launch_cls_attention, csrc/attn_map.hip; timed under
+ * VIT_OP_ATTENTION).  It reads the Q|K|V buffer the projection has just completed; no attention kernel is involved, and
+ * logits, probabilities, features and top-k outputs are bit-identical to an un-armed forward.  An un-armed context
+ * launches exactly what it launched before.
+ * Definition.  For image i, tap k (layer l), head h and key t in [0, T), with D = embed_dim / num_heads:
+ *     s[t]              = (1/sqrt(D)) * sum_d Q[i*T + 0][h*D + d] * K[i*T + t][h*D + d]
+ *     heads[i][k][h][t] = exp(s[t] - max_t s) / sum_t exp(s[t] - max_t s)
+ *     mean [i][k][t]    = (sum over h ascending of heads[i][k][h][t], in fp32) / (float)H
+ * Q and K are THE VALUES LAYER l'S Q|K|V BUFFER HOLDS IN THIS CONTEXT'S PLAN, decoded exactly to fp32: fp32 rows on the
+ * fp32-rows paths and wherever attention streams, the exact three-part split (so again the fp32 values) on the fp32 planes
+ * path, values rounded to fp16 in the BF16_GEMM and FP8_GEMM modes' resident and long-sequence plans.  Arithmetic is fp32;
+ * the sum over d runs in an order fixed per (D, stored form), the sums over t and h in orders fixed by (T, H) alone.  The
+ * output is NOT the probability matrix an attention kernel forms internally (those differ per kernel: exp2 with a folded
+ * scale, P rounded to fp16, online softmax); against the definition evaluated in double on the same Q and K a value p
+ * errs by at most (4 (D + 2) S + T + 64) 2^-24 p, S = max_t sum_d |q_d k_d| / sqrt(D).
+ * Key 0 is the class token itself, so every row of heads (and of mean) sums to 1; keys 1 .. T-1, viewed as [g][g]
+ * (g = img / patch), are the map.  taps are those of vit_feature_spec: layers, 0-based or negative from the end, strictly
+ * ascending once resolved; here the layer's own attention is read, not its output.
+ * Both outputs are fp32 and image-major: heads [n][n_taps][H][T], mean [n][n_taps][T]; either may be NULL, not both, and
+ * mean has the same bits whether heads is asked for or not.  No floating-point atomics: an image's output is
+ * bit-identical wherever it sits in the batch and whatever n is.  Any T; head_dim a multiple of 16, at most 128 -- anything
+ * else is refused when the request is armed, not at the first forward.
+ * Device form (vit_hip_set_attention): device buffers for up to max_batch images, 16-byte aligned, written asynchronously
+ * on the forward's stream by vit_hip_forward_device, _device_u8 and _device_u8_resized.  Host form
+ * (vit_hip_set_attention_host): host buffers for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized calls (each
+ * call writes from image 0), complete on return; its staging (a device buffer and two pinned slots of max_batch images per
+ * output) is allocated when it is armed.
+ * spec == NULL disarms.  Arming one form disarms the other; a device-form forward while the host form is armed (and the
+ * reverse) is refused with code 1 and a message, no launch.  Code 1 with a message also for: NULL ctx, n_taps not in
+ * 1..4, a tap outside [-depth, depth), taps not ascending and distinct, both buffers NULL, a misaligned device buffer, a
+ * head_dim the kernel does not take.  A refused call leaves the previous request armed.
+ * vit_hip_set_last_layer_cls_only does not matter here: the last layer's Q|K|V is complete either way.
+ * vit_hip_multi: a context from vit_hip_multi_ctx may be armed for the device forms like any other; vit_hip_forward_multi
+ * and vit_hip_forward_device_multi neither write attention maps nor refuse. */
+typedef struct vit_attn_spec { int n_taps; int taps[4]; } vit_attn_spec;        /* taps as in vit_feature_spec */
+typedef struct vit_attn_buffers { float *heads, *mean; } vit_attn_buffers;      /* each may be NULL, not both */
+/* host only, no device: validates spec against cfg; ELEMENTS PER IMAGE of each output (each pointer may be NULL):
+ * n_taps * H * T and n_taps * T; 0, or 1 with a message */
+int vit_attn_sizes(const vit_config *cfg, const vit_attn_spec *spec, size_t *heads_elems, size_t *mean_elems);
+int vit_hip_set_attention(vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *d_bufs);
+int vit_hip_set_attention_host(vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *h_bufs);
+
 /* Debug hook: copy the residual stream left by the last forward ([n*tokens][embed], un-normalised; rows other than the
  * class tokens are stale under vit_hip_set_last_layer_cls_only) to the host.  The supported interface to the encoder's
  * output is vit_hip_set_features above. */

@@ -290,6 +290,26 @@ int vh_launch_softmax(vh_stream_t s, const float *input, float *output, int rows
 enum { VIT_TOPK_PROBS = 0, VIT_TOPK_LOGITS = 1 };
 int vh_launch_topk(vh_stream_t s, const float *logits, int rows, int length, int k, int score_kind, int *labels, float *scores);
 
+/* The class token's attention row of every (image, head), from one layer's Q|K|V (csrc/attn_map.hip; the kernel under
+ * vit_hip_set_attention, include/ViT_opencl.h, which states the definition): tap `tap_index` of `n_taps` into
+ *   heads [n_images][n_taps][num_heads][tokens]   softmax over the keys t of (q_cls . k_t) / sqrt(head_dim), fp32
+ *   mean  [n_images][n_taps][tokens]              (sum over heads ascending of heads) / (float)num_heads, bit for bit
+ * Either may be NULL, not both; `mean` has the same bits whether `heads` is asked for or not.  qkv as its producer left
+ * it, rows = n_images * tokens, decoded exactly to fp32:
+ *   VH_QKV_ROWS_F32    fp32 rows [rows][3E]
+ *   VH_QKV_PLANES3     exact three-part bf16 planes [3E/32][3][rows][32], (p0 + p1) + p2 (vh_launch_merge3_rows)
+ *   VH_QKV_PLANES_F16  one-part fp16 planes [3E/32][rows][32]
+ * fp32 arithmetic; the sums over keys and over heads run in an order that depends on (tokens, num_heads) alone, the dot
+ * products in one that depends on (head_dim, form); no atomics: an image's output is the same bits wherever it sits in
+ * the batch.  Any tokens >= 1 (nothing is sized by it); head_dim a multiple of 16, at
+ * most 128 (vh_cls_attention_head_dim_ok); embed_dim % 32 == 0 for the planes forms; pointers 16-byte aligned;
+ * 0 <= tap_index < n_taps <= 4.  Anything else: code 1 with a message, no launch.  No reference counterpart
+ * (multihead.cl:3 keeps its probabilities to itself). */
+enum { VH_QKV_ROWS_F32 = 0, VH_QKV_PLANES3 = 1, VH_QKV_PLANES_F16 = 2 };
+int vh_cls_attention_head_dim_ok(int head_dim);
+int vh_launch_cls_attention(vh_stream_t s, const void *qkv, int qkv_form, int n_images, int tokens, int embed_dim,
+                            int num_heads, int tap_index, int n_taps, float *heads, float *mean);
+
 /* ---- reduced-precision attention (the bf16- and fp8-operand modes, BASELINE configs 3 and 5) ----
  * fp32 in, fp32 out; Q, K, V and P rounded to fp16 for the two products (11-bit operands, fp32 accumulation and
  * softmax): far inside those modes' tolerances.  The bf16-operand mode itself runs on one-part planes:

@@ -156,6 +156,18 @@ struct vit_hip_ctx
         struct staged st[2];         /* FEAT_HOST: labels, scores */
     } topk;
 
+    /* attention-map request (vit_hip_set_attention / _host), armed independently of the other two.  `attn_serving` is the
+     * request the running forward serves: forward_device sets it for its layer functions and clears it on both exits. */
+    struct attn_req
+    {
+        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
+        vit_attn_spec spec;
+        int layer[4];                /* spec.taps resolved, ascending */
+        vit_attn_buffers out;        /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: st[].dev */
+        struct staged st[2];         /* FEAT_HOST: heads, mean */
+    } amap;
+    const struct attn_req *attn_serving;
+
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
     int *prof_class;       /* operator class per recorded launch */
@@ -256,7 +268,7 @@ static void staged_scatter(const struct staged *st, int slot, int first, int m)
     memcpy(st->host + (size_t)first * st->per_image, st->pinned[slot], (size_t)m * st->per_image);
 }
 
-/* The staging of a host-form request, feature (cls, pooled) or top-k (labels, scores) */
+/* The staging of a host-form request: feature (cls, pooled), top-k (labels, scores) or attention maps (heads, mean) */
 static void request_release(struct staged st[2])
 {
     staged_release(&st[0]);
@@ -275,6 +287,7 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     prof_release(ctx);
     request_release(ctx->feat.st);
     request_release(ctx->topk.st);
+    request_release(ctx->amap.st);
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
@@ -917,6 +930,31 @@ static int attention_rows(const vit_hip_ctx *ctx, vh_stream_t s, float *out, int
                                     ctx->tokens, ctx->cfg.embed_dim, ctx->cfg.num_heads);
 }
 
+/* The class-token attention maps of layer l when the forward's armed request taps it: one pass over q_cls and the K
+ * columns of the Q|K|V the projection has just completed, in the form the plan made it write (csrc/attn_map.hip), timed
+ * with the attention.  Called between the QKV and the attention launch: nothing that reuses the buffer -- the attention's
+ * output, the class-only last layer's scratch, the next layer's projection -- is earlier in stream order. */
+static int attention_tap(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
+{
+    int rc = 0;
+    const struct attn_req *ar = ctx->attn_serving;
+    if (!ar)
+        return 0;
+    const vit_config *c = &ctx->cfg;
+    const int reduced = ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
+    /* layer_f32_planes' planes_attn, the reduced layers' kind; everything else writes fp32 rows */
+    const int form = reduced ? (ctx->attn_form == ATTN_STREAMING ? VH_QKV_ROWS_F32 : VH_QKV_PLANES_F16)
+                   : ctx->precision == VIT_PRECISION_F32 && ctx->use_p3 && (ctx->attn_form == ATTN_HD64 || ctx->attn_form == ATTN_LONG)
+                       ? VH_QKV_PLANES3 : VH_QKV_ROWS_F32;
+    for (int k = 0; k < ar->spec.n_taps; ++k)
+        if (ar->layer[k] == l)
+            OP(VIT_OP_ATTENTION, vh_launch_cls_attention(s, ctx->qkv, form, n, ctx->tokens, c->embed_dim, c->num_heads, k,
+                                                         ar->spec.n_taps, ar->out.heads, ar->out.mean));
+    return 0;
+fail:
+    return rc;
+}
+
 /* The reduced modes' attention on fp16-rounded operands, writing the output projection's operand: one-part bf16 planes
  * (attn_scales NULL) or an MX tensor.  The resident kernels write it themselves; the streaming kernel leaves fp32 rows in
  * the idle MLP buffer, which are then rounded / quantised (one timed operator). */
@@ -959,6 +997,7 @@ static int layer_fp8(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     OP(VIT_OP_QKV, fold ? vh_launch_linear_mx_norm(s, ctx->qkv, NULL, kind, op[0].w, op[0].scales, ctx->y, ys, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
                  : kind ? vh_launch_linear_mx_planes_f16(s, ctx->qkv, op[0].w, op[0].scales, ctx->y, ys, lw[3], rows, E, 3 * E)
                         : vh_launch_linear_mx(s, ctx->qkv, NULL, op[0].w, op[0].scales, ctx->y, ys, lw[3], rows, E, 3 * E, 0, NULL));
+    TRY(attention_tap(ctx, s, n, l));
     TRY(attention_reduced(ctx, s, n, as_));
     OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_mx_resid_norm(s, ctx->x, op[1].w, op[1].scales, ctx->attn, as_, lw[5], ctx->x, rows, E, E, ctx->y, ys, ctx->stats)
                              : vh_launch_linear_mx(s, ctx->x, NULL, op[1].w, op[1].scales, ctx->attn, as_, lw[5], rows, E, E, 0, ctx->x));
@@ -988,6 +1027,7 @@ static int layer_bf16(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_planes(s, ctx->x, lw[0], lw[1], ctx->y, 1, rows, E, E, c->eps));
     OP(VIT_OP_QKV, fold ? vh_launch_linear_planes_norm(s, ctx->qkv, kind, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
                         : vh_launch_linear_planes(s, ctx->qkv, kind, op[0].w, ctx->y, 1, lw[3], rows, E, 3 * E, 0, NULL));
+    TRY(attention_tap(ctx, s, n, l));
     TRY(attention_reduced(ctx, s, n, NULL));
     OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_planes_resid_norm(s, ctx->x, op[1].w, ctx->attn, lw[5], ctx->x, rows, E, E, ctx->y, NULL, ctx->stats)
                              : vh_launch_linear_planes(s, ctx->x, 0, op[1].w, ctx->attn, 1, lw[5], rows, E, E, 0, ctx->x));
@@ -1012,6 +1052,7 @@ static int layer_fp16x2(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     const struct operand *op = ctx->op + 4 * l;
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, E, c->eps));
     OP(VIT_OP_QKV, vh_launch_linear_h2(s, ctx->qkv, op[0].w, op[0].pair_scale, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
+    TRY(attention_tap(ctx, s, n, l));
     OP(VIT_OP_ATTENTION, attention_rows(ctx, s, ctx->attn, VH_ATTN_FP16X2, n));
     OP(VIT_OP_OUT_PROJ, vh_launch_linear_h2(s, ctx->x, op[1].w, op[1].pair_scale, ctx->attn, lw[5], rows, E, E, 0, ctx->x));
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, E, c->eps));
@@ -1041,6 +1082,7 @@ static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int *
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, c->eps));
     OP(VIT_OP_QKV, fold ? vh_launch_linear_p3_norm(s, ctx->qkv, planes_attn, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
                         : vh_launch_linear_p3(s, ctx->qkv, planes_attn, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
+    TRY(attention_tap(ctx, s, n, l));
     OP(VIT_OP_ATTENTION, ctx->attn_form == ATTN_HD64 ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
                          : (rc = ctx->attn_form == ATTN_LONG ? vh_launch_attention_long(s, ctx->qkv, 3, ctx->hid, n, T, E, c->num_heads)
                                                              : attention_rows(ctx, s, ctx->hid, VH_ATTN_SPLIT3, n)) != 0 ? rc
@@ -1091,6 +1133,7 @@ static int layer_f32_rows(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, E, c->eps));
     OP(VIT_OP_QKV, op[0].w ? vh_launch_linear_w3(s, ctx->qkv, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL)
                          : vh_launch_linear_math(s, ctx->qkv, lw[2], ctx->y, lw[3], rows, E, 3 * E, 0, NULL, math));
+    TRY(attention_tap(ctx, s, n, l));
     OP(VIT_OP_ATTENTION, attention_rows(ctx, s, ctx->attn, ctx->fp32_native ? VH_ATTN_NATIVE : VH_ATTN_SPLIT3, n));
     OP(VIT_OP_OUT_PROJ, op[1].w ? vh_launch_linear_w3(s, ctx->x, op[1].w, ctx->attn, lw[5], rows, E, E, 0, ctx->x)
                               : vh_launch_linear_math(s, ctx->x, lw[4], ctx->attn, lw[5], rows, E, E, 0, ctx->x, math));
@@ -1214,12 +1257,14 @@ fail:
     return rc;
 }
 
-/* Everything after the argument checks of the forwards.  fr, tk: the armed feature / top-k request to serve, or NULL. */
+/* Everything after the argument checks of the forwards.  fr, tk, ar: the armed feature / top-k / attention-map request to
+ * serve, or NULL. */
 static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
-                          const struct feature_req *fr, const struct topk_req *tk)
+                          const struct feature_req *fr, const struct topk_req *tk, const struct attn_req *ar)
 {
     int rc = 0;
     const int cls_only_saved = ctx->cls_only_last;
+    ctx->attn_serving = ar;   /* read by the layer functions (attention_tap) */
     TRY(vh_set_device(ctx->device));   /* the current device is per host thread */
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, T = ctx->tokens, NC = c->num_classes;
@@ -1252,6 +1297,7 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
             TRY(feature_tap(ctx, s, fr, k++, n, cls_rows));
     }
     ctx->cls_only_last = cls_only_saved;
+    ctx->attn_serving = NULL;
 
     /* final LayerNorm on the class-token rows -- row i * stride of the residual stream, or compacted at the start of the
      * Q|K|V buffer -- classifier, softmax (ViT_seq.c:506-515) */
@@ -1269,29 +1315,34 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
     return 0;
 fail:
     ctx->cls_only_last = cls_only_saved;
+    ctx->attn_serving = NULL;
     return rc;
 }
 
 /* The armed requests a forward of the function `who` serves.  form: what that call can serve -- FEAT_DEVICE, FEAT_HOST, or
  * FEAT_NONE for a call that serves nothing, whatever is armed.  A request armed in the other form refuses the call, the
  * feature request first. */
-static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const struct feature_req **fr, const struct topk_req **tk)
+static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const struct feature_req **fr, const struct topk_req **tk,
+                          const struct attn_req **ar)
 {
-    const int armed[2] = {ctx->feat.form, ctx->topk.form};
+    static const char *const what[3] = {"feature", "top-k", "attention"}, *const setter[3] = {"features", "topk", "attention"};
+    const int armed[3] = {ctx->feat.form, ctx->topk.form, ctx->amap.form};
     *fr = NULL;
     *tk = NULL;
+    *ar = NULL;
     if (form == FEAT_NONE)
         return 0;
-    for (int r = 0; r < 2; ++r)
+    for (int r = 0; r < 3; ++r)
         if (armed[r] != FEAT_NONE && armed[r] != form) {
             char msg[200];
             const char *const is = armed[r] == FEAT_HOST ? "host" : "device";
             snprintf(msg, sizeof msg, "%s: the context is armed for %s %s buffers (vit_hip_set_%s%s); disarm it or use the %s forms", who, is,
-                     r ? "top-k" : "feature", r ? "topk" : "features", armed[r] == FEAT_HOST ? "_host" : "", is);
+                     what[r], setter[r], armed[r] == FEAT_HOST ? "_host" : "", is);
             return vh_set_error(1, msg);
         }
     *fr = armed[0] == form ? &ctx->feat : NULL;
     *tk = armed[1] == form ? &ctx->topk : NULL;
+    *ar = armed[2] == form ? &ctx->amap : NULL;
     return 0;
 }
 
@@ -1301,9 +1352,10 @@ static int forward_device_armed(vit_hip_ctx *ctx, const char *who, const struct 
 {
     const struct feature_req *fr;
     const struct topk_req *tk;
-    if (armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk))
+    const struct attn_req *ar;
+    if (armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar))
         return 1;
-    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk);
+    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar);
 }
 
 /* vit_hip_forward_device with no feature output whatever is armed (vit_gather_rccl.c) */
@@ -1312,7 +1364,7 @@ int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n,
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
     const struct pixel_src src = {d_images, NULL, 0, NULL};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL);
 }
 
 int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
@@ -1458,24 +1510,36 @@ static int refuse(const char *who, const char *why)
     return vh_set_error(1, msg);
 }
 
+/* What the spec checks of a feature and of an attention-map request share; NULL, or why not: the config and the count of taps ... */
+static const char *taps_count_check(const vit_config *cfg, int n_taps)
+{
+    return cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
+           : n_taps < 1 || n_taps > 4 ? "n_taps must be in 1..4"
+           : NULL;
+}
+
+/* ... and the taps themselves (1 <= n_taps <= 4), resolved to ascending layer indices */
+static const char *resolve_taps(const vit_config *cfg, int n_taps, const int taps[4], int layer[4])
+{
+    for (int k = 0; k < n_taps; ++k) {
+        const int t = taps[k];
+        if (t < -cfg->depth || t >= cfg->depth)
+            return "a tap lies outside [-depth, depth)";
+        if (k > 0 && (t < 0 ? t + cfg->depth : t) <= layer[k - 1])
+            return "taps must be strictly ascending once resolved";
+        layer[k] = t < 0 ? t + cfg->depth : t;
+    }
+    return NULL;
+}
+
 /* spec against cfg; the taps resolved to ascending layer indices */
 static int feature_spec_check(const char *who, const vit_config *cfg, const vit_feature_spec *spec, int layer[4])
 {
-    const char *why = !cfg || !spec ? "NULL argument"
-                      : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
-                      : spec->n_taps < 1 || spec->n_taps > 4 ? "n_taps must be in 1..4"
-                      : spec->dtype != VIT_FEATURE_F32 && spec->dtype != VIT_FEATURE_BF16 ? "dtype must be VIT_FEATURE_F32 or VIT_FEATURE_BF16"
-                      : spec->token_layout != VIT_TOKENS_NLC && spec->token_layout != VIT_TOKENS_NCHW ? "token_layout must be VIT_TOKENS_NLC or VIT_TOKENS_NCHW"
-                      : NULL;
-    for (int k = 0; !why && k < spec->n_taps; ++k) {
-        const int t = spec->taps[k];
-        if (t < -cfg->depth || t >= cfg->depth)
-            why = "a tap lies outside [-depth, depth)";
-        else if (k > 0 && (t < 0 ? t + cfg->depth : t) <= layer[k - 1])
-            why = "taps must be strictly ascending once resolved";
-        else
-            layer[k] = t < 0 ? t + cfg->depth : t;
-    }
+    const char *why = !cfg || !spec ? "NULL argument" : taps_count_check(cfg, spec->n_taps);
+    why = why ? why
+          : spec->dtype != VIT_FEATURE_F32 && spec->dtype != VIT_FEATURE_BF16 ? "dtype must be VIT_FEATURE_F32 or VIT_FEATURE_BF16"
+          : spec->token_layout != VIT_TOKENS_NLC && spec->token_layout != VIT_TOKENS_NCHW ? "token_layout must be VIT_TOKENS_NLC or VIT_TOKENS_NCHW"
+          : resolve_taps(cfg, spec->n_taps, spec->taps, layer);
     return why ? refuse(who, why) : 0;
 }
 
@@ -1494,8 +1558,8 @@ int vit_feature_sizes(const vit_config *cfg, const vit_feature_spec *spec, size_
     return 0;
 }
 
-/* What arming a feature and a top-k request share, behind their own spec and buffer checks (skipped without a context, which
- * is refused here).  req: the new request's staged arrays; the host form has named the caller's memory and the bytes per
+/* What arming a feature, a top-k and an attention-map request share, behind their own spec and buffer checks (skipped
+ * without a context, which is refused here).  req: the new request's staged arrays; the host form has named the caller's memory and the bytes per
  * image of those it wants, and their stages are made here.  armed: where the context keeps the request's staged arrays.
  * Returns 0 with the old request's staging released, for the caller to store the new request; on failure the previous
  * request stays armed and nothing leaks. */
@@ -1616,6 +1680,71 @@ int vit_hip_set_topk_host(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit
     return set_topk("vit_hip_set_topk_host", ctx, spec, h_bufs, 1);
 }
 
+static int attn_spec_check(const char *who, const vit_config *cfg, const vit_attn_spec *spec, int layer[4])
+{
+    const char *why = !cfg || !spec ? "NULL argument" : taps_count_check(cfg, spec->n_taps);
+    why = why ? why
+          : cfg->num_heads <= 0 || cfg->embed_dim % cfg->num_heads != 0 ? "bad model config"
+          : resolve_taps(cfg, spec->n_taps, spec->taps, layer);
+    return why ? refuse(who, why) : 0;
+}
+
+int vit_attn_sizes(const vit_config *cfg, const vit_attn_spec *spec, size_t *heads_elems, size_t *mean_elems)
+{
+    int layer[4];
+    if (attn_spec_check("vit_attn_sizes", cfg, spec, layer))
+        return 1;
+    const size_t per = (size_t)spec->n_taps * (size_t)vit_config_tokens(cfg);
+    if (heads_elems)
+        *heads_elems = per * (size_t)cfg->num_heads;
+    if (mean_elems)
+        *mean_elems = per;
+    return 0;
+}
+
+/* Both forms of arming, as set_features */
+static int set_attention(const char *who, vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *bufs, int host)
+{
+    struct attn_req ar;
+    memset(&ar, 0, sizeof ar);
+    if (ctx && spec) {
+        if (attn_spec_check(who, &ctx->cfg, spec, ar.layer))
+            return 1;
+        const vit_config *c = &ctx->cfg;
+        const char *why = !bufs || (!bufs->heads && !bufs->mean) ? "no output buffer"
+                          : !vh_cls_attention_head_dim_ok(c->embed_dim / c->num_heads) ? "head_dim must be a multiple of 16, at most 128"
+                          : !host && (((uintptr_t)bufs->heads | (uintptr_t)bufs->mean) & 15) ? "device buffers must be 16-byte aligned"
+                          : NULL;
+        if (why)
+            return refuse(who, why);
+        ar.form = host ? FEAT_HOST : FEAT_DEVICE;
+        ar.spec = *spec;
+        ar.out = *bufs;
+        if (host) {
+            const size_t per = (size_t)spec->n_taps * ctx->tokens * sizeof(float);
+            ar.st[0] = (struct staged){.host = (char *)bufs->heads, .per_image = per * c->num_heads};
+            ar.st[1] = (struct staged){.host = (char *)bufs->mean, .per_image = per};
+        }
+    }
+    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, amap.st), ar.st);
+    if (rc != 0)
+        return rc;
+    if (ar.form == FEAT_HOST)
+        ar.out = (vit_attn_buffers){ar.st[0].dev, ar.st[1].dev};
+    ctx->amap = ar;
+    return 0;
+}
+
+int vit_hip_set_attention(vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *d_bufs)
+{
+    return set_attention("vit_hip_set_attention", ctx, spec, d_bufs, 0);
+}
+
+int vit_hip_set_attention_host(vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *h_bufs)
+{
+    return set_attention("vit_hip_set_attention_host", ctx, spec, h_bufs, 1);
+}
+
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
 {
     if (!ctx)
@@ -1647,7 +1776,7 @@ int vit_hip_profile_enable(vit_hip_ctx *ctx, int max_forwards)
     prof_release(ctx);
     if (max_forwards <= 0)
         return 0;
-    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1;   /* + the readouts of an armed feature request + top-k */
+    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4;   /* + the readouts of an armed feature request + top-k + attention maps */
     ctx->prof_cap = per_forward * max_forwards;
     ctx->prof_ev = (vh_event_t *)calloc((size_t)2 * ctx->prof_cap, sizeof(vh_event_t));
     ctx->prof_class = (int *)calloc((size_t)ctx->prof_cap, sizeof(int));
@@ -1828,21 +1957,23 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
     int rc = 0;
     const struct feature_req *fr;
     const struct topk_req *tk;
-    if (armed_requests(ctx, "forward", form, &fr, &tk))
+    const struct attn_req *ar;
+    if (armed_requests(ctx, "forward", form, &fr, &tk, &ar))
         return 1;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->u8 ? 1 : sizeof(float));
     const size_t NC = (size_t)c->num_classes;
     const size_t slot_bytes = image_slot_bytes(ctx);
-    /* what comes back per chunk besides the probabilities, in the order it is queued: logits, cls, pooled, labels, scores */
+    /* what comes back per chunk besides the probabilities, in the order it is queued: logits, cls, pooled, labels, scores,
+     * heads, mean */
     const struct staged logits_st = {ctx->d_logits, {ctx->h_logits[0], ctx->h_logits[1]}, (char *)logits, NC * sizeof(float)};
-    const struct staged *arrays[5];
+    const struct staged *arrays[7];
     int n_arrays = 0;
     if (logits)
         arrays[n_arrays++] = &logits_st;
-    for (int a = 0; a < 4; ++a) {
-        const struct staged *st = a < 2 ? (fr ? &fr->st[a] : NULL) : (tk ? &tk->st[a - 2] : NULL);
+    for (int a = 0; a < 6; ++a) {
+        const struct staged *st = a < 2 ? (fr ? &fr->st[a] : NULL) : a < 4 ? (tk ? &tk->st[a - 2] : NULL) : (ar ? &ar->st[a - 4] : NULL);
         if (st && st->dev)
             arrays[n_arrays++] = st;
     }
@@ -1870,7 +2001,7 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
         const struct pixel_src dev = {src->u8 || src->resize ? NULL : ctx->d_images[s],
                                       src->u8 ? (const unsigned char *)ctx->d_images[s] : NULL, src->layout, src->norm,
                                       src->resize ? src->staged : NULL, src->rc};
-        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk));
+        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
         int a = 0;
@@ -2123,7 +2254,7 @@ static int multi_forward_one(void *arg, int shard, int lo, int hi)
 {
     vit_hip_multi *m = (vit_hip_multi *)arg;
     const size_t NC = (size_t)vit_hip_config(m->ctx[shard])->num_classes;
-    /* no feature or top-k output, whatever a caller armed on the shard's context */
+    /* no feature, top-k or attention-map output, whatever a caller armed on the shard's context */
     return forward_host_images(m->ctx[shard], m->images + lo, hi - lo, m->logits ? m->logits + (size_t)lo * NC : NULL,
                                m->probs ? m->probs + lo : NULL, FEAT_NONE);
 }

@@ -65,6 +65,8 @@ EXPORTS = [
     "vit_hip_set_features_host",
     "vh_launch_linear_math", "vh_launch_patch_embed_ws_math", "vh_launch_attention_rows",
     "vh_launch_topk", "vit_topk_check", "vit_hip_set_topk", "vit_hip_set_topk_host", "vit_write_result_file_topk",
+    "vh_cls_attention_head_dim_ok", "vh_launch_cls_attention", "vit_attn_sizes", "vit_hip_set_attention",
+    "vit_hip_set_attention_host",
 ]
 
 # include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
@@ -168,6 +170,41 @@ class TopKSpec:
 
     def c_struct(self) -> TopKSpecC:
         return TopKSpecC(self.k, TOPK_SCORES[self.scores])
+
+
+class AttnSpecC(C.Structure):
+    """`vit_attn_spec` (include/ViT_opencl.h)."""
+
+    _fields_ = [("n_taps", C.c_int), ("taps", C.c_int * 4)]
+
+
+class AttnBuffers(C.Structure):
+    """`vit_attn_buffers` (include/ViT_opencl.h): device or host pointers; each may be NULL, not both."""
+
+    _fields_ = [("heads", C.c_void_p), ("mean", C.c_void_p)]
+
+
+# include/kernelHandler.h: qkv_form of vh_launch_cls_attention
+QKV_FORMS = {"rows_f32": 0, "planes3": 1, "planes_f16": 2}
+
+
+class AttentionSpec:
+    """An attention-map request: taps (encoder layers whose class-token attention is read, negative from the end)."""
+
+    def __init__(self, taps=(-1,)):
+        self.taps = tuple(int(t) for t in taps)
+
+    def c_struct(self) -> AttnSpecC:
+        taps = list(self.taps[:4]) + [0] * (4 - min(len(self.taps), 4))
+        return AttnSpecC(len(self.taps), (C.c_int * 4)(*taps))
+
+
+def attention_sizes(cfg: "VitConfig", spec: AttentionSpec):
+    """vit_attn_sizes -> (heads, mean) elements per image"""
+    out = [C.c_size_t() for _ in range(2)]
+    cs = spec.c_struct()
+    check(lib().vit_attn_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_attn_sizes")
+    return tuple(o.value for o in out)
 
 
 def topk_check(cfg: "VitConfig", spec: TopKSpec) -> None:
@@ -453,6 +490,12 @@ def lib() -> C.CDLL:
     L.vit_hip_set_topk.argtypes = [voidp, tkp, tbp]
     L.vit_hip_set_topk_host.argtypes = [voidp, tkp, tbp]
     L.vit_write_result_file_topk.argtypes = [C.c_char_p, ip32, f32p, i, i]
+    L.vh_cls_attention_head_dim_ok.argtypes = [i]
+    L.vh_launch_cls_attention.argtypes = [voidp, voidp] + [i] * 7 + [voidp, voidp]
+    asp, abp = C.POINTER(AttnSpecC), C.POINTER(AttnBuffers)
+    L.vit_attn_sizes.argtypes = [C.POINTER(VitConfig), asp, szp, szp]
+    L.vit_hip_set_attention.argtypes = [voidp, asp, abp]
+    L.vit_hip_set_attention_host.argtypes = [voidp, asp, abp]
     _lib = L
     return L
 
@@ -743,6 +786,33 @@ class ViTHip:
         finally:
             self.set_topk_host(None)
         return labels, out
+
+    def set_attention(self, spec, heads=None, mean=None):
+        """Arm (spec=None: disarm) the device forms: heads [max_batch][taps][H][T] / mean [max_batch][taps][T] are float32
+        DeviceBuffers (or device pointers), either may be None; written by every forward_device* until disarmed."""
+        self._arm("vit_hip_set_attention", spec, AttnBuffers, (heads, mean), _device_ptr, "_attention_keep")
+
+    def set_attention_host(self, spec, heads=None, mean=None):
+        """Arm (spec=None: disarm) the host forms: heads [n][taps][H][T] / mean [n][taps][T] are C-contiguous float32 NumPy
+        arrays for all n images of the coming forward / forward_u8 / forward_u8_resized calls."""
+        for a in (heads, mean):
+            if spec is not None and a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == np.float32):
+                raise ValueError("set_attention_host: need C-contiguous float32 arrays")
+        self._arm("vit_hip_set_attention_host", spec, AttnBuffers, (heads, mean), _host_ptr, "_attention_keep")
+
+    def attention(self, images: np.ndarray, taps=(-1,)):
+        """fp32 images [n][C][H][W] -> (logits, heads [n][taps][H][T], mean [n][taps][T]): the class token's attention in
+        the tapped layers, the host form armed for this one call."""
+        images = np.ascontiguousarray(images, dtype=np.float32)
+        n, spec = images.shape[0], AttentionSpec(taps)
+        heads = np.empty((n, len(spec.taps), self.cfg.num_heads, self.tokens), dtype=np.float32)
+        mean = np.empty((n, len(spec.taps), self.tokens), dtype=np.float32)
+        self.set_attention_host(spec, heads=heads, mean=mean)
+        try:
+            logits, _ = self.forward(images)
+        finally:
+            self.set_attention_host(None)
+        return logits, heads, mean
 
     def read_tokens(self, n: int) -> np.ndarray:
         out = np.empty((n * self.tokens, self.cfg.embed_dim), dtype=np.float32)
