@@ -209,6 +209,44 @@ int vit_hip_forward_device_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *d_im
 int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int n, int layout,
                                const vit_resize_crop *rc, const vit_pixel_norm *norm, float *logits, float **probs);
 
+/* ---- regions of 8-bit images: boxes resized on the GPU, bit-exact with Pillow's Image.resize(size, resample, box=) ----
+ * Detector boxes, the tiles of a slide or satellite frame, five-crop: n boxes of n_images source images (vit_image_u8, as
+ * above), each resized to img x img -- a non-square box is squashed, as resize(box=) does -- with the pixels of Pillow's
+ * Image.resize((img, img), BILINEAR | BICUBIC, box=(left, top, right, bottom)) on 8-bit channels (2 and 4 channels are
+ * independent bands), then normalised and run exactly as the u8 path.  A box: the index of its source in the images array
+ * and left, top, right, bottom in source pixel coordinates as C floats (Pillow converts a box to float first); every value
+ * finite, 0 <= left, right <= width, 0 <= top, bottom <= height, right - left >= 1 and bottom - top >= 1 (the differences
+ * taken in float).  Boxes may repeat a source and name the sources in any order.  Code 1 (with a message, no launch) for a
+ * NULL argument, n out of range, n_images < 1, an unknown filter or layout, an image outside vit_image_u8's limits, a
+ * row_stride that is too small, a box outside this domain or an image index outside 0 .. n_images - 1: every image and box
+ * is checked before anything is queued. */
+typedef struct vit_box_u8 { int image; float box[4]; } vit_box_u8;  /* index into the images array; left, top, right, bottom */
+int vit_box_check(int height, int width, const float box[4]);        /* host only; 0, or 1 with a message */
+/* host only: the source rows [first, first + count) that the `out` output rows of this box read -- the kernel's own bounds */
+int vit_box_rows(int height, float top, float bottom, int out, int filter, int *first, int *count);
+/* host only: row-major tiling, tile x tile boxes every `stride` px; the last row / column of tiles is moved flush to the
+ * bottom / right edge when the stride does not land there, so the image is covered; tile <= min(height, width), 1 <= stride
+ * <= tile; returns the number of boxes (written up to `capacity`), -1 with a message on a bad argument */
+int vit_tile_boxes(int height, int width, int tile, int stride, int image, vit_box_u8 *out, int capacity);
+/* The crops alone: [n][img][img][in_chans] bytes (HWC) into d_out; n <= max_batch boxes; asynchronous on `stream` (0 = the
+ * context's); the coefficient tables go into the context's MLP buffer, as vit_hip_resize_crop_u8's. */
+int vit_hip_crop_boxes_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n_images, const vit_box_u8 *boxes, int n,
+                          int layout, int filter, unsigned char *d_out, vh_stream_t stream);
+/* crops + vit_hip_forward_device_u8's forward; n <= max_batch boxes; asynchronous, the descriptors through the pinned ring
+ * like vit_hip_forward_device_u8_resized; armed feature, top-k and attention outputs are written for boxes like for any
+ * other image. */
+int vit_hip_forward_device_u8_boxes(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n_images, const vit_box_u8 *boxes,
+                                    int n, int layout, int filter, const vit_pixel_norm *norm, float *d_logits,
+                                    float *d_probs, vh_stream_t stream);
+/* Host form: any n; outputs in box order.  Chunks are consecutive runs of boxes; per chunk every distinct source that its
+ * boxes name is packed into the staging slot once, and of it only the rows that the chunk's boxes read (the union of their
+ * vit_box_rows spans, at full width; per plane for CHW), so an overlapping tiling uploads every row about once per chunk and
+ * a source larger than a slot works.  A chunk is cut at max_batch boxes or when the next box would push the packed bytes
+ * past the slot (max_batch x in_chans x img^2 x 4 bytes); a box whose own rows do not fit a slot is refused up front (code
+ * 1).  Synchronous; logits and probs as vit_hip_forward, each may be NULL; armed host outputs are served. */
+int vit_hip_forward_u8_boxes(vit_hip_ctx *ctx, const vit_image_u8 *images, int n_images, const vit_box_u8 *boxes, int n,
+                             int layout, int filter, const vit_pixel_norm *norm, float *logits, float **probs);
+
 /* ---- several GPUs behind one call (the reference takes exactly one device, ViT_opencl.c:803) ----
  * Batch shards only: images never interact (ViT_opencl.c:926), so n images are cut into n_devices
  * contiguous shards (shard s = images [s*ceil(n/G), ...)); every device holds a full replica of the weights
@@ -276,8 +314,8 @@ int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on);
  * tokens holds BEFORE any narrowing to bf16 (normalise, then pool, when final_norm is set).  Outputs depend on the image
  * only: bit-identical wherever it sits in the batch and whatever n is (fixed-order sums, no floating-point atomics).
  * Device form (vit_hip_set_features): device buffers, 16-byte aligned, for up to max_batch images; written asynchronously
- * on the forward's stream like the logits, by vit_hip_forward_device, _device_u8 and _device_u8_resized.  Host form
- * (vit_hip_set_features_host): host buffers for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized calls (each
+ * on the forward's stream like the logits, by vit_hip_forward_device, _device_u8, _device_u8_resized and _device_u8_boxes.  Host form
+ * (vit_hip_set_features_host): host buffers for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized / _u8_boxes calls (each
  * call writes from image 0), complete on return; cls and pooled only -- tokens is refused (308 MB per 512-image chunk
  * through pinned staging).  The host form's staging is allocated when it is armed, not per call.
  * spec == NULL disarms.  Arming one form disarms the other; a device-form forward while the host form is armed (and the
@@ -326,7 +364,7 @@ int vit_hip_set_features_host(vit_hip_ctx *ctx, const vit_feature_spec *spec, co
  * full softmax is not part of this interface); top-k is the way to read such a head.
  * An image's labels and scores depend on that image only: bit-identical wherever it sits in the batch.
  * Device form (vit_hip_set_topk): device buffers [max_batch][k], 16-byte aligned, written asynchronously on the forward's
- * stream by vit_hip_forward_device, _device_u8 and _device_u8_resized, whether d_logits and d_probs are NULL or not.
+ * stream by vit_hip_forward_device, _device_u8, _device_u8_resized and _device_u8_boxes, whether d_logits and d_probs are NULL or not.
  * Host form (vit_hip_set_topk_host): host buffers [n][k] for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized
  * calls (each call writes from image 0), complete on return; two pinned slots of max_batch * k pairs are allocated when it
  * is armed.  With logits == NULL and probs == NULL a chunk's device-to-host traffic is its k pairs per image only.
@@ -370,8 +408,8 @@ int vit_hip_set_topk_host(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit
  * bit-identical wherever it sits in the batch and whatever n is.  Any T; head_dim a multiple of 16, at most 128 -- anything
  * else is refused when the request is armed, not at the first forward.
  * Device form (vit_hip_set_attention): device buffers for up to max_batch images, 16-byte aligned, written asynchronously
- * on the forward's stream by vit_hip_forward_device, _device_u8 and _device_u8_resized.  Host form
- * (vit_hip_set_attention_host): host buffers for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized calls (each
+ * on the forward's stream by vit_hip_forward_device, _device_u8, _device_u8_resized and _device_u8_boxes.  Host form
+ * (vit_hip_set_attention_host): host buffers for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized / _u8_boxes calls (each
  * call writes from image 0), complete on return; its staging (a device buffer and two pinned slots of max_batch images per
  * output) is allocated when it is armed.
  * spec == NULL disarms.  Arming one form disarms the other; a device-form forward while the host form is armed (and the

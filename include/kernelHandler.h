@@ -420,17 +420,24 @@ int vh_launch_patch_embed_planes_u8(vh_stream_t s, const unsigned char *images, 
 int vh_launch_expand_u8(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias, float *out,
                         int n_images, int in_chans, int img_size);
 
-/* ---- Pillow-exact resize + centre crop of 8-bit images (csrc/resize.hip; vit_hip_resize_crop_u8) ----
- * One source image, its resized size and crop offsets (vit_resize_crop_geometry) and where its coefficient tables lie in
- * the scratch.  Tables of one image, at coef + coef_offset (16-byte aligned): x bounds int2 [crop] (first tap, taps), y
- * bounds int2 [crop], x weights int32 [kx][crop] (tap-major), y weights int32 [crop][ky]; weights in 22 fractional bits. */
+/* ---- Pillow-exact resize + crop of 8-bit images (csrc/resize.hip; vit_hip_resize_crop_u8, vit_hip_crop_boxes_u8) ----
+ * One output image: its source, and per axis Pillow's precompute_coeffs(in, in0, in1, out) -- the source span [in0, in1)
+ * (C floats, as Pillow takes a box) resized to `out` samples, of which the crop indices first .. first + crop - 1 are
+ * computed -- and where its coefficient tables lie in the scratch.  Resize + centre crop (vit_resize_crop_geometry) is
+ * in0 = 0, in1 = (float)in, out = the resized size, first = the crop offset; a box (Image.resize(box=)) is in0 / in1 = the
+ * box ends, out = crop, first = 0.  Tables of one image, at coef + coef_offset (16-byte aligned): x bounds int2 [crop]
+ * (first tap, taps), y bounds int2 [crop], x weights int32 [kx][crop] (tap-major), y weights int32 [crop][ky]; weights in
+ * 22 fractional bits. */
 typedef struct vh_resize_desc
 {
-    const unsigned char *data;  /* device; any alignment */
+    const unsigned char *data;  /* device; any alignment; column 0 of source row `row0` */
     long row_stride;            /* bytes between rows */
     long plane_stride;          /* CHW: bytes between channel planes */
-    int height, width;
-    int resized_h, resized_w, top, left;
+    int height, width;          /* of the whole source: the bounds are clamped to them */
+    int row0;                   /* the first source row in memory: at most the first row any crop row reads */
+    float x0, x1, y0, y1;       /* in0, in1 along x and y */
+    int out_w, out_h;           /* out along x and y */
+    int left, top;              /* first along x and y */
     int kx, ky;                 /* Pillow's ksize along x and y */
     long coef_offset;
 } vh_resize_desc;

@@ -8,5 +8,5 @@ Python identifier; load it with `__graft_entry__.load_package()`.
 from .host import binding  # noqa: F401
 from .host.binding import (  # noqa: F401
     DeviceBuffer, PixelNorm, ViTHip, ViTHipMulti, VitConfig, VitHipError, build_library, lib, pixel_norm, preset, shard_range,
-    synth_images, synth_weights,
+    synth_images, synth_weights, tile_boxes,
 )

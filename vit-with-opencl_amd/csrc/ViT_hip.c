@@ -828,12 +828,18 @@ static int planes_patch_embed(const vit_hip_ctx *ctx)
     return ctx->ln_fold || ctx->use_p3 || ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
 }
 
-/* Pillow's ksize: taps per output index of one axis (in -> out) */
-static int resize_taps(int in, int out, int filter)
+/* Pillow's ksize: taps per output index of one axis, the span [in0, in1) -> out (the subtraction in float, as in Pillow) */
+static int span_taps(float in0, float in1, int out, int filter)
 {
-    const double scale = (double)(float)in / out;
+    const double scale = (double)(in1 - in0) / out;
     const double support = (filter == VIT_RESIZE_BICUBIC ? 2.0 : 1.0) * (scale < 1.0 ? 1.0 : scale);
     return (int)ceil(support) * 2 + 1;
+}
+
+/* a whole axis (in -> out) */
+static int resize_taps(int in, int out, int filter)
+{
+    return span_taps(0.0f, (float)in, out, filter);
 }
 
 /* bicubic taps at the steepest downscale a crop x crop crop can see: the short side 16384 -> resize_short >= crop, the
@@ -1147,6 +1153,13 @@ fail:
     return rc;
 }
 
+/* An image of which only some rows are in memory: data is column 0 of row row0, planes (CHW) plane_stride bytes apart */
+struct row_origin
+{
+    int row0;
+    long plane_stride;
+};
+
 /* What a forward reads: fp32 [n][C][H][W], or 8-bit pixels in `layout` with their normalisation (vit_hip_forward_device_u8) */
 struct pixel_src
 {
@@ -1156,16 +1169,19 @@ struct pixel_src
     const vit_pixel_norm *norm;
     const vit_image_u8 *resize;   /* or 8-bit images of any size in `layout` (device data), resized and cropped first */
     const vit_resize_crop *rc;
+    const vit_box_u8 *boxes;      /* or n boxes of the images `resize` (then rc is NULL), each resized to img x img */
+    int filter;                   /* boxes: VIT_RESIZE_* */
+    const struct row_origin *origin;   /* boxes, host form: per image of `resize`, where its `data` starts; NULL = whole images */
 };
 
-/* Queue the resize + centre crop of n validated images (device data) into out, [n][img][img][C] bytes: the descriptors go
- * up through the next ring slot, the coefficient tables into hid.  The slot's event is recorded behind the launches that
- * read it. */
-static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const vit_image_u8 *images, int n, int layout,
-                              const vit_resize_crop *rc, unsigned char *out)
+/* Queue the resize + centre crop of n validated images (device data) -- or, with src->boxes, the resize of n validated
+ * boxes of them -- into out, [n][img][img][C] bytes: the descriptors go up through the next ring slot, the coefficient
+ * tables into hid.  The slot's event is recorded behind the launches that read it. */
+static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct pixel_src *src, int n, unsigned char *out)
 {
     int rc_ = 0;
     const vit_config *c = &ctx->cfg;
+    const int layout = src->layout, filter = src->boxes ? src->filter : src->rc->filter;
     const int S = c->img_size, C = c->in_chans, slot = ctx->desc_next;
     ctx->desc_next = (slot + 1) % DESC_RING;
     if (ctx->desc_live[slot] && (rc_ = vh_event_sync(ctx->desc_done[slot])) != 0)
@@ -1174,16 +1190,27 @@ static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const vit_image_u
     vh_resize_desc *d = ctx->h_desc[slot];
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
-        const vit_image_u8 *im = &images[i];
+        const int which = src->boxes ? src->boxes[i].image : i;
+        const vit_image_u8 *im = &src->resize[which];
         vh_resize_desc *e = &d[i];
-        vit_resize_crop_geometry(im->height, im->width, rc, S, &e->resized_h, &e->resized_w, &e->top, &e->left);
         e->data = im->data;
         e->row_stride = im->row_stride;
-        e->plane_stride = (long)im->height * im->row_stride;
+        e->plane_stride = src->origin ? src->origin[which].plane_stride : (long)im->height * im->row_stride;
         e->height = im->height;
         e->width = im->width;
-        e->kx = resize_taps(im->width, e->resized_w, rc->filter);
-        e->ky = resize_taps(im->height, e->resized_h, rc->filter);
+        e->row0 = src->origin ? src->origin[which].row0 : 0;
+        if (src->boxes) {   /* Image.resize((img, img), box=): every output index, from 0 */
+            const float *b = src->boxes[i].box;
+            e->x0 = b[0], e->y0 = b[1], e->x1 = b[2], e->y1 = b[3];
+            e->out_w = e->out_h = S;
+            e->left = e->top = 0;
+        } else {            /* the whole image to the resized size, of which the centre crop's indices */
+            vit_resize_crop_geometry(im->height, im->width, src->rc, S, &e->out_h, &e->out_w, &e->top, &e->left);
+            e->x0 = e->y0 = 0.0f;
+            e->x1 = (float)im->width, e->y1 = (float)im->height;
+        }
+        e->kx = span_taps(e->x0, e->x1, e->out_w, filter);
+        e->ky = span_taps(e->y0, e->y1, e->out_h, filter);
         e->coef_offset = (long)off;
         off += resize_table_bytes(S, e->kx, e->ky);
     }
@@ -1191,7 +1218,7 @@ static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const vit_image_u
         return vh_set_error(1, "resize: coefficient tables exceed the scratch");
     if ((rc_ = vh_h2d(ctx->d_desc[slot], d, (size_t)n * sizeof(*d), s)) != 0)
         return rc_;
-    rc_ = vh_launch_resize_crop_u8(s, ctx->d_desc[slot], n, C, layout, rc->filter, S, ctx->hid, ctx->ws_bytes, out);
+    rc_ = vh_launch_resize_crop_u8(s, ctx->d_desc[slot], n, C, layout, filter, S, ctx->hid, ctx->ws_bytes, out);
     const int rec = vh_event_record(ctx->desc_done[slot], s);   /* behind the copy even if the launch was refused */
     ctx->desc_live[slot] = rec == 0;
     return rc_ ? rc_ : rec;
@@ -1273,7 +1300,7 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
     struct pixel_src crops;
     if (src->resize) {   /* resized crops into Q|K|V, then the u8 path on them; both count as the patch embedding */
         unsigned char *out = (unsigned char *)ctx->qkv + ctx->crop_off;
-        OP(VIT_OP_PATCH_EMBED, resize_crop_launch(ctx, s, src->resize, n, src->layout, src->rc, out));
+        OP(VIT_OP_PATCH_EMBED, resize_crop_launch(ctx, s, src, n, out));
         crops = (struct pixel_src){NULL, out, VIT_PIXELS_HWC, src->norm, NULL, NULL};
         src = &crops;
     }
@@ -1490,7 +1517,8 @@ int vit_hip_resize_crop_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n
         return 1;
     if ((rc_ = vh_set_device(ctx->device)) != 0)
         return rc_;
-    return resize_crop_launch(ctx, stream ? stream : ctx->stream, d_images, n, layout, rc, d_out);
+    const struct pixel_src src = {NULL, NULL, layout, NULL, d_images, rc};
+    return resize_crop_launch(ctx, stream ? stream : ctx->stream, &src, n, d_out);
 }
 
 int vit_hip_forward_device_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n, int layout, const vit_resize_crop *rc,
@@ -1508,6 +1536,177 @@ static int refuse(const char *who, const char *why)
     char msg[200];
     snprintf(msg, sizeof msg, "%s: %s", who, why);
     return vh_set_error(1, msg);
+}
+
+/* ---- boxes: regions of 8-bit images, each resized to img x img as Pillow's Image.resize(size, resample, box=) ---- */
+
+/* NULL, or why `box` is not a box of a height x width image.  Written so that a NaN fails its comparison. */
+static const char *box_why(int height, int width, const float box[4])
+{
+    return !box ? "NULL box"
+           : height < 1 || width < 1 || height > RESIZE_MAX_SIDE || width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
+           : !isfinite(box[0]) || !isfinite(box[1]) || !isfinite(box[2]) || !isfinite(box[3]) ? "box values must be finite"
+           : !(box[0] >= 0.0f) || !(box[1] >= 0.0f) || !(box[2] <= (float)width) || !(box[3] <= (float)height) ? "box outside the image"
+           : !(box[2] - box[0] >= 1.0f) || !(box[3] - box[1] >= 1.0f) ? "box narrower or lower than 1 px"
+           : NULL;
+}
+
+int vit_box_check(int height, int width, const float box[4])
+{
+    const char *why = box_why(height, width, box);
+    return why ? refuse("vit_box_check", why) : 0;
+}
+
+/* Pillow's bounds of output index xx of one axis: the first source index read and how many (resize_coef_kernel's own
+ * arithmetic, csrc/resize.hip; this file too is built without fused multiply-adds) */
+static void span_bounds(int in, float in0, float in1, int out, int filter, int xx, int *first, int *taps)
+{
+    const double scale = (double)(in1 - in0) / out;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = (filter == VIT_RESIZE_BICUBIC ? 2.0 : 1.0) * filterscale;
+    const double center = (double)in0 + (xx + 0.5) * scale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0)
+        xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in)
+        xmax = in;
+    *first = xmin;
+    *taps = xmax - xmin;
+}
+
+/* the rows [first, first + count) that the `out` output rows of a validated span read */
+static void box_rows(int height, float top, float bottom, int out, int filter, int *first, int *count)
+{
+    int lo = height, hi = 0;
+    for (int yy = 0; yy < out; ++yy) {
+        int ymin, taps;
+        span_bounds(height, top, bottom, out, filter, yy, &ymin, &taps);
+        lo = ymin < lo ? ymin : lo;
+        hi = ymin + taps > hi ? ymin + taps : hi;
+    }
+    *first = lo;
+    *count = hi - lo;
+}
+
+int vit_box_rows(int height, float top, float bottom, int out, int filter, int *first, int *count)
+{
+    const float box[4] = {0.0f, top, 1.0f, bottom};
+    const char *why = !first || !count ? "NULL argument"
+                      : out < 1 ? "out must be positive"
+                      : filter != VIT_RESIZE_BILINEAR && filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
+                      : box_why(height, 1, box);
+    if (why)
+        return refuse("vit_box_rows", why);
+    box_rows(height, top, bottom, out, filter, first, count);
+    return 0;
+}
+
+int vit_tile_boxes(int height, int width, int tile, int stride, int image, vit_box_u8 *out, int capacity)
+{
+    const char *why = height < 1 || width < 1 || height > RESIZE_MAX_SIDE || width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
+                      : tile < 1 || tile > height || tile > width ? "tile must be in 1..min(height, width)"
+                      : stride < 1 || stride > tile ? "stride must be in 1..tile"
+                      : image < 0 ? "image must not be negative"
+                      : capacity < 0 || (capacity > 0 && !out) ? "NULL out, or a negative capacity"
+                      : NULL;
+    if (why) {
+        refuse("vit_tile_boxes", why);
+        return -1;
+    }
+    /* tiles at 0, stride, ... while they fit; one more, flush to the far edge, when the last of those stops short of it */
+    const int ny = (height - tile) / stride + 1 + ((height - tile) % stride != 0);
+    const int nx = (width - tile) / stride + 1 + ((width - tile) % stride != 0);
+    for (int ty = 0, k = 0; ty < ny; ++ty)
+        for (int tx = 0; tx < nx; ++tx, ++k) {
+            if (k >= capacity)
+                continue;
+            const int y = ty * stride + tile > height ? height - tile : ty * stride;
+            const int x = tx * stride + tile > width ? width - tile : tx * stride;
+            out[k].image = image;
+            out[k].box[0] = (float)x, out[k].box[1] = (float)y;
+            out[k].box[2] = (float)(x + tile), out[k].box[3] = (float)(y + tile);
+        }
+    return ny * nx;
+}
+
+/* The box forms' checks that need no device: every image and every box, before anything is queued.  norm_needed: the
+ * forwards; device: n <= max_batch; slot_bytes: the host form's limit on the rows one box reads (0 = none) */
+static int box_args(const char *who, const vit_hip_ctx *ctx, const vit_image_u8 *images, int n_images, const vit_box_u8 *boxes, int n,
+                    int layout, int filter, const vit_pixel_norm *norm, int norm_needed, const void *out, int out_needed, int device,
+                    size_t slot_bytes)
+{
+    char msg[240];
+    const char *why = !ctx || !images || !boxes || (norm_needed && !norm) || (out_needed && !out) ? "NULL argument"
+                      : n <= 0 ? "n must be positive"
+                      : n_images <= 0 ? "n_images must be positive"
+                      : device && n > ctx->max_batch ? "n exceeds the context's max_batch"
+                      : layout != VIT_PIXELS_HWC && layout != VIT_PIXELS_CHW ? "layout must be VIT_PIXELS_HWC or VIT_PIXELS_CHW"
+                      : filter != VIT_RESIZE_BILINEAR && filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
+                      : ctx->cfg.in_chans > 4 ? "8-bit images take at most 4 channels"
+                      : (long)ctx->cfg.img_size * ctx->cfg.in_chans > VH_RESIZE_MAX_ROW_BYTES ? "img_size x in_chans above 3072 bytes per crop row"
+                      : NULL;
+    const char *what = NULL;
+    int bad = -1;
+    if (!why) {
+        const long C = ctx->cfg.in_chans;
+        for (int i = 0; i < n_images && !why; ++i) {
+            const vit_image_u8 *im = &images[i];
+            const long row = layout == VIT_PIXELS_HWC ? (long)im->width * C : (long)im->width;
+            why = !im->data ? "NULL image data"
+                  : im->height < 1 || im->width < 1 || im->height > RESIZE_MAX_SIDE || im->width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
+                  : im->row_stride < row ? "row_stride below the row's bytes"
+                  : NULL;
+            what = "image";
+            bad = i;
+        }
+        for (int i = 0; i < n && !why; ++i) {
+            const vit_box_u8 *b = &boxes[i];
+            what = "box";
+            bad = i;
+            if (b->image < 0 || b->image >= n_images) {
+                why = "image index outside 0..n_images - 1";
+                break;
+            }
+            const vit_image_u8 *im = &images[b->image];
+            why = box_why(im->height, im->width, b->box);
+            if (!why && slot_bytes) {
+                int first, count;
+                box_rows(im->height, b->box[1], b->box[3], ctx->cfg.img_size, filter, &first, &count);
+                if ((size_t)count * im->width * C > slot_bytes)
+                    why = "the rows it reads are larger than a staging slot";
+            }
+        }
+    }
+    if (!why)
+        return 0;
+    if (bad >= 0)
+        snprintf(msg, sizeof msg, "%s: %s %d: %s", who, what, bad, why);
+    else
+        snprintf(msg, sizeof msg, "%s: %s", who, why);
+    return vh_set_error(1, msg);
+}
+
+int vit_hip_crop_boxes_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n_images, const vit_box_u8 *boxes, int n, int layout,
+                          int filter, unsigned char *d_out, vh_stream_t stream)
+{
+    int rc_ = 0;
+    if (box_args("vit_hip_crop_boxes_u8", ctx, d_images, n_images, boxes, n, layout, filter, NULL, 0, d_out, 1, 1, 0))
+        return 1;
+    if ((rc_ = vh_set_device(ctx->device)) != 0)
+        return rc_;
+    const struct pixel_src src = {NULL, NULL, layout, NULL, d_images, NULL, boxes, filter, NULL};
+    return resize_crop_launch(ctx, stream ? stream : ctx->stream, &src, n, d_out);
+}
+
+int vit_hip_forward_device_u8_boxes(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n_images, const vit_box_u8 *boxes, int n,
+                                    int layout, int filter, const vit_pixel_norm *norm, float *d_logits, float *d_probs,
+                                    vh_stream_t stream)
+{
+    if (box_args("vit_hip_forward_device_u8_boxes", ctx, d_images, n_images, boxes, n, layout, filter, norm, 1, NULL, 0, 1, 0))
+        return 1;
+    const struct pixel_src src = {NULL, NULL, layout, norm, d_images, NULL, boxes, filter, NULL};
+    return forward_device_armed(ctx, "vit_hip_forward_device_u8_boxes", &src, n, d_logits, d_probs, stream);
 }
 
 /* What the spec checks of a feature and of an attention-map request share; NULL, or why not: the config and the count of taps ... */
@@ -1850,6 +2049,26 @@ struct host_src
     const vit_resize_crop *rc;
     size_t *packed;               /* resize: the chunk's byte offsets in the slot, [max_batch + 1] */
     vit_image_u8 *staged;         /* resize: the chunk's descriptors, data in the device slot, [max_batch] */
+    const vit_box_u8 *boxes;      /* or boxes of the images `resize` (rc NULL): only the rows a chunk's boxes read are packed */
+    int filter;
+    struct box_chunk *chunk;      /* boxes: the chunk being staged */
+};
+
+/* A chunk of the box host form.  Its distinct sources lie in the slot one behind the other, each as the rows its boxes read
+ * (a bit per source row), in row order, at full width: HWC rows, or per plane for CHW.  The rows of one box are consecutive
+ * there, so every box gets an image descriptor of its own that starts at its first row. */
+enum { ROWMAP_BYTES = RESIZE_MAX_SIDE / 8 };
+struct box_chunk
+{
+    int n_src;                   /* distinct sources */
+    int *src_image;              /* [max_batch] their indices into the caller's images */
+    int *src_rows;               /* [max_batch] rows packed of each */
+    size_t *src_off;             /* [max_batch] where each starts in the slot */
+    unsigned char *rowmap;       /* [max_batch][ROWMAP_BYTES] */
+    size_t bytes;                /* of the whole chunk */
+    vit_image_u8 *staged;        /* [max_batch] per box: data in the device slot */
+    struct row_origin *origin;   /* [max_batch] per box */
+    vit_box_u8 *boxes;           /* [max_batch] per box: image = its own index */
 };
 
 struct gather_job
@@ -1874,10 +2093,31 @@ static void pack_image(char *dst, const vit_image_u8 *im, int layout, int chans)
         memcpy(dst + (size_t)y * row, im->data + (size_t)y * im->row_stride, row);
 }
 
+/* source k of a box chunk: the rows of its map, in order, HWC rows or plane after plane */
+static void pack_rows(char *dst, const struct host_src *src, int k, int chans)
+{
+    const struct box_chunk *ch = src->chunk;
+    const vit_image_u8 *im = &src->resize[ch->src_image[k]];
+    const unsigned char *map = ch->rowmap + (size_t)k * ROWMAP_BYTES;
+    const size_t row = (size_t)im->width * (src->layout == VIT_PIXELS_HWC ? chans : 1);
+    const int planes = src->layout == VIT_PIXELS_HWC ? 1 : chans;
+    dst += ch->src_off[k];
+    for (int p = 0; p < planes; ++p)
+        for (int y = 0; y < im->height; ++y)
+            if (map[y >> 3] >> (y & 7) & 1) {
+                memcpy(dst, im->data + ((size_t)p * im->height + y) * im->row_stride, row);
+                dst += row;
+            }
+}
+
 static void *gather_worker(void *arg)
 {
     const struct gather_job *j = (const struct gather_job *)arg;
     for (int i = j->first; i < j->first + j->count; ++i) {
+        if (j->src->boxes) {
+            pack_rows(j->dst, j->src, i, (int)j->bytes);
+            continue;
+        }
         if (j->src->resize) {
             pack_image(j->dst + j->src->packed[i], &j->src->resize[j->base + i], j->src->layout, (int)j->bytes);
             continue;
@@ -1907,6 +2147,62 @@ static int resize_chunk(const vit_hip_ctx *ctx, const struct host_src *src, int 
         off += bytes;
     }
     src->packed[m] = off;
+    return m;
+}
+
+/* A box chunk from box `first`: at most max_batch boxes whose sources' rows, each packed once, fit one staging slot
+ * (box_args has refused any box whose own rows do not); fills src->chunk */
+static int box_chunk_build(const vit_hip_ctx *ctx, const struct host_src *src, int first, int n, size_t slot_bytes,
+                           const unsigned char *d_slot)
+{
+    struct box_chunk *ch = src->chunk;
+    const size_t C = (size_t)ctx->cfg.in_chans;
+    const int S = ctx->cfg.img_size, hwc = src->layout == VIT_PIXELS_HWC;
+    int m = 0;
+    ch->n_src = 0;
+    ch->bytes = 0;
+    for (; m < ctx->max_batch && first + m < n; ++m) {
+        const vit_box_u8 *b = &src->boxes[first + m];
+        const vit_image_u8 *im = &src->resize[b->image];
+        int k = 0, row0, count, fresh = 0;
+        while (k < ch->n_src && ch->src_image[k] != b->image)
+            ++k;
+        unsigned char *map = ch->rowmap + (size_t)k * ROWMAP_BYTES;
+        box_rows(im->height, b->box[1], b->box[3], S, src->filter, &row0, &count);
+        for (int y = row0; y < row0 + count; ++y)
+            fresh += k == ch->n_src || !(map[y >> 3] >> (y & 7) & 1);
+        if (ch->bytes + (size_t)fresh * im->width * C > slot_bytes)
+            break;
+        if (k == ch->n_src) {
+            ch->src_image[ch->n_src++] = b->image;
+            ch->src_rows[k] = 0;
+            memset(map, 0, ROWMAP_BYTES);
+        }
+        for (int y = row0; y < row0 + count; ++y)
+            map[y >> 3] |= (unsigned char)(1 << (y & 7));
+        ch->src_rows[k] += fresh;
+        ch->bytes += (size_t)fresh * im->width * C;
+        ch->origin[m].row0 = row0;       /* completed below, once the sources' row counts are final */
+        ch->boxes[m] = *b;
+    }
+    size_t off = 0;
+    for (int k = 0; k < ch->n_src; ++k) {
+        ch->src_off[k] = off;
+        off += (size_t)ch->src_rows[k] * src->resize[ch->src_image[k]].width * C;
+    }
+    for (int i = 0; i < m; ++i) {
+        const vit_image_u8 *im = &src->resize[ch->boxes[i].image];
+        int k = 0, rank = 0;
+        while (ch->src_image[k] != ch->boxes[i].image)
+            ++k;
+        const unsigned char *map = ch->rowmap + (size_t)k * ROWMAP_BYTES;
+        for (int y = 0; y < ch->origin[i].row0; ++y)   /* packed rows of the source ahead of the box's first */
+            rank += map[y >> 3] >> (y & 7) & 1;
+        const long row = (long)im->width * (hwc ? (long)C : 1);
+        ch->staged[i] = (vit_image_u8){d_slot + ch->src_off[k] + (size_t)rank * row, im->height, im->width, row};
+        ch->origin[i].plane_stride = (long)ch->src_rows[k] * row;
+        ch->boxes[i].image = i;
+    }
     return m;
 }
 
@@ -1981,7 +2277,9 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
     int prev_first = 0, prev_m = 0, k = 0;
     for (int first = 0, m = 0; first < n; first += m, ++k) {
         const int s = k & 1;
-        if (src->resize)   /* cut by count and by bytes; gather_images packs with per-image offsets (bytes carries C) */
+        if (src->boxes)    /* cut by count and by bytes; gather_images packs every distinct source's rows (bytes carries C) */
+            m = box_chunk_build(ctx, src, first, n, slot_bytes, (const unsigned char *)ctx->d_images[s]);
+        else if (src->resize)   /* cut by count and by bytes; gather_images packs with per-image offsets (bytes carries C) */
             m = resize_chunk(ctx, src, first, n, slot_bytes, (const unsigned char *)ctx->d_images[s]);
         else
             m = (n - first < ctx->max_batch) ? n - first : ctx->max_batch;
@@ -1989,9 +2287,9 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
             rc = vh_set_error(1, "forward: an image does not fit a staging slot");
             goto fail;
         }
-        const size_t up = src->resize ? src->packed[m] : (size_t)m * bytes;
+        const size_t up = src->boxes ? src->chunk->bytes : src->resize ? src->packed[m] : (size_t)m * bytes;
         /* slot s was last used by chunk k-2, whose outputs were waited for below */
-        gather_images(ctx->h_images[s], src, first, m, src->resize ? (size_t)c->in_chans : bytes);
+        gather_images(ctx->h_images[s], src, first, src->boxes ? src->chunk->n_src : m, src->resize ? (size_t)c->in_chans : bytes);
         if (k >= 2)
             TRY(vh_stream_wait_event(ctx->copy_stream, ctx->comp_done[s]));
         TRY(vh_h2d(ctx->d_images[s], ctx->h_images[s], up, ctx->copy_stream));
@@ -2000,7 +2298,8 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
         TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
         const struct pixel_src dev = {src->u8 || src->resize ? NULL : ctx->d_images[s],
                                       src->u8 ? (const unsigned char *)ctx->d_images[s] : NULL, src->layout, src->norm,
-                                      src->resize ? src->staged : NULL, src->rc};
+                                      src->boxes ? src->chunk->staged : src->resize ? src->staged : NULL, src->rc,
+                                      src->boxes ? src->chunk->boxes : NULL, src->filter, src->boxes ? src->chunk->origin : NULL};
         TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
@@ -2073,6 +2372,38 @@ int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int
     }
     free(packed);
     free(staged);
+    return rc_;
+}
+
+int vit_hip_forward_u8_boxes(vit_hip_ctx *ctx, const vit_image_u8 *images, int n_images, const vit_box_u8 *boxes, int n, int layout,
+                             int filter, const vit_pixel_norm *norm, float *logits, float **probs)
+{
+    const size_t slot_bytes = ctx ? image_slot_bytes(ctx) : 0;
+    if (box_args("vit_hip_forward_u8_boxes", ctx, images, n_images, boxes, n, layout, filter, norm, 1, NULL, 0, 0, slot_bytes))
+        return 1;
+    const size_t mb = (size_t)ctx->max_batch;
+    struct box_chunk ch = {0};
+    ch.src_image = malloc(mb * sizeof(*ch.src_image));
+    ch.src_rows = malloc(mb * sizeof(*ch.src_rows));
+    ch.src_off = malloc(mb * sizeof(*ch.src_off));
+    ch.rowmap = malloc(mb * ROWMAP_BYTES);
+    ch.staged = malloc(mb * sizeof(*ch.staged));
+    ch.origin = malloc(mb * sizeof(*ch.origin));
+    ch.boxes = malloc(mb * sizeof(*ch.boxes));
+    int rc_ = 1;
+    if (ch.src_image && ch.src_rows && ch.src_off && ch.rowmap && ch.staged && ch.origin && ch.boxes) {
+        const struct host_src src = {NULL, NULL, layout, norm, images, NULL, NULL, NULL, boxes, filter, &ch};
+        rc_ = forward_pipelined(ctx, &src, n, logits, probs, FEAT_HOST);
+    } else {
+        vh_set_error(1, "vit_hip_forward_u8_boxes: out of host memory");
+    }
+    free(ch.src_image);
+    free(ch.src_rows);
+    free(ch.src_off);
+    free(ch.rowmap);
+    free(ch.staged);
+    free(ch.origin);
+    free(ch.boxes);
     return rc_;
 }
 

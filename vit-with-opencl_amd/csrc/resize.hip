@@ -12,7 +12,8 @@
  *    scratch (the MLP hidden buffer inside a forward).  Double precision, in Pillow's operation order; the file is built
  *    with -ffp-contract=off, so no multiply-add is fused (one would change the bicubic weights in the last bit).
  *  - resize_crop_kernel<JN, R, LAYOUT>: one 256-thread workgroup per (image, band of R output rows).  The band's input rows
- *    [ymin of its first row, ymax of its last) are streamed in chunks: each chunk's horizontal pass (crop columns only)
+ *    [ymin of its first row, ymax of its last) are streamed in chunks (source row y lies at row y - row0 of the
+ *    descriptor's data: a caller may hold only the rows that the crop reads): each chunk's horizontal pass (crop columns only)
  *    lands as uint8 rows in LDS, and the vertical pass adds the chunk's taps into int32 registers -- thread t owns crop
  *    bytes t, t + 256, ... (JN of them) of each of the R rows.  Chunks add into the same accumulators, so an extreme
  *    downscale (16384 -> 224 bicubic: 293 taps) takes as many chunks as it needs with the LDS fixed at 32 KiB.
@@ -77,8 +78,9 @@ __device__ __forceinline__ Tables tables(const char *coef, const vh_resize_desc 
     return t;
 }
 
-/* One thread per (image, axis, crop index): Pillow's precompute_coeffs + normalize_coeffs_8bpc for output index
- * left + o (x) or top + o (y) */
+/* One thread per (image, axis, crop index): Pillow's precompute_coeffs(in, in0, in1, out) + normalize_coeffs_8bpc for
+ * output index left + o (x) or top + o (y).  in1 - in0 is a float subtraction, as in Pillow; a whole image (in0 = 0, in1 =
+ * (float)in) gives scale = (double)(float)in / out and center = 0.0 + x = x. */
 __global__ void resize_coef_kernel(const vh_resize_desc *__restrict__ desc, char *__restrict__ coef, int n, int crop, int filter)
 {
     const int per_image = (2 * crop + THREADS - 1) / THREADS;
@@ -88,17 +90,18 @@ __global__ void resize_coef_kernel(const vh_resize_desc *__restrict__ desc, char
         return;
     const vh_resize_desc d = desc[img];
     const int axis = o >= crop, i = axis ? o - crop : o;
-    const int in = axis ? d.height : d.width, out = axis ? d.resized_h : d.resized_w;
+    const int in = axis ? d.height : d.width, out = axis ? d.out_h : d.out_w;
+    const float in0 = axis ? d.y0 : d.x0, in1 = axis ? d.y1 : d.x1;
     const int xx = i + (axis ? d.top : d.left), ksize = axis ? d.ky : d.kx;
     char *base = coef + d.coef_offset;
     int2 *bounds = reinterpret_cast<int2 *>(base) + (axis ? crop : 0);
     int *wx = reinterpret_cast<int *>(reinterpret_cast<int2 *>(base) + 2 * crop);
     int *wy = wx + (size_t)d.kx * crop;
 
-    const double scale = (double)(float)in / out;
+    const double scale = (double)(in1 - in0) / out;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
     const double support = (filter ? 2.0 : 1.0) * filterscale;
-    const double center = (xx + 0.5) * scale;
+    const double center = (double)in0 + (xx + 0.5) * scale;
     const double ss = 1.0 / filterscale;
     int xmin = (int)(center - support + 0.5);
     if (xmin < 0)
@@ -163,8 +166,8 @@ __global__ __launch_bounds__(THREADS) void resize_crop_kernel(const vh_resize_de
             const int col = j / chans, c = j - col * chans;
             const int2 b = t.xb[col];
             const unsigned char *src = LAYOUT == LAYOUT_CHW
-                                           ? d.data + (size_t)c * d.plane_stride + (size_t)(y0 + rr) * d.row_stride + b.x
-                                           : d.data + (size_t)(y0 + rr) * d.row_stride + (size_t)b.x * chans + c;
+                                           ? d.data + (size_t)c * d.plane_stride + (size_t)(y0 + rr - d.row0) * d.row_stride + b.x
+                                           : d.data + (size_t)(y0 + rr - d.row0) * d.row_stride + (size_t)b.x * chans + c;
             const int *w = t.wx + col;
             int ss = 1 << 21;
             for (int k = 0; k < b.y; ++k)

@@ -61,6 +61,8 @@ EXPORTS = [
     "vit_hip_forward_u8",
     "vh_launch_resize_crop_u8", "vit_resize_crop_geometry", "vit_hip_resize_crop_u8", "vit_hip_forward_device_u8_resized",
     "vit_hip_forward_u8_resized",
+    "vit_box_check", "vit_box_rows", "vit_tile_boxes", "vit_hip_crop_boxes_u8", "vit_hip_forward_device_u8_boxes",
+    "vit_hip_forward_u8_boxes",
     "vh_feature_readout_scratch", "vh_launch_feature_readout", "vit_feature_sizes", "vit_hip_set_features",
     "vit_hip_set_features_host",
     "vh_launch_linear_math", "vh_launch_patch_embed_ws_math", "vh_launch_attention_rows",
@@ -108,6 +110,12 @@ class ResizeCrop(C.Structure):
 
 
 RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}
+
+
+class Box(C.Structure):
+    """`vit_box_u8` (include/ViT_opencl.h): a region (left, top, right, bottom) of image `image` of an images array."""
+
+    _fields_ = [("image", C.c_int), ("box", C.c_float * 4)]
 
 
 class FeatureSpecC(C.Structure):
@@ -231,6 +239,38 @@ def resize_crop_geometry(height: int, width: int, resize_short: int, crop: int, 
     rc = resize_crop(resize_short, filter)
     check(lib().vit_resize_crop_geometry(height, width, C.byref(rc), crop, *[C.byref(o) for o in out]), "vit_resize_crop_geometry")
     return tuple(o.value for o in out)
+
+
+def box_array(boxes) -> C.Array:
+    """An array of vit_box_u8 from (image, (left, top, right, bottom)) pairs, or from Box structures."""
+    arr = (Box * len(boxes))()
+    for i, b in enumerate(boxes):
+        arr[i] = b if isinstance(b, Box) else Box(int(b[0]), (C.c_float * 4)(*[float(v) for v in b[1]]))
+    return arr
+
+
+def box_check(height: int, width: int, box) -> None:
+    """vit_box_check: raises VitHipError unless (left, top, right, bottom) is a box of a height x width image"""
+    check(lib().vit_box_check(height, width, (C.c_float * 4)(*[float(v) for v in box])), "vit_box_check")
+
+
+def box_rows(height: int, top: float, bottom: float, out: int, filter: str = "bilinear"):
+    """vit_box_rows -> (first, count): the source rows that the `out` output rows of a box from top to bottom read"""
+    first, count = C.c_int(), C.c_int()
+    check(lib().vit_box_rows(height, top, bottom, out, RESIZE_FILTERS[filter], C.byref(first), C.byref(count)), "vit_box_rows")
+    return first.value, count.value
+
+
+def tile_boxes(h: int, w: int, tile: int, stride: int, image: int = 0):
+    """vit_tile_boxes -> [(image, (left, top, right, bottom)), ...]: row-major tile x tile boxes every `stride` px, the last
+    row and column flush to the bottom and right edges"""
+    n = lib().vit_tile_boxes(h, w, tile, stride, image, None, 0)
+    if n < 0:
+        check(1, "vit_tile_boxes")
+    arr = (Box * n)()
+    if lib().vit_tile_boxes(h, w, tile, stride, image, arr, n) != n:
+        check(1, "vit_tile_boxes")
+    return [(b.image, tuple(b.box)) for b in arr]
 
 
 def image_descs(images) -> C.Array:
@@ -476,6 +516,13 @@ def lib() -> C.CDLL:
     L.vit_hip_resize_crop_u8.argtypes = [voidp, imgp, i, i, rcp, voidp, voidp]
     L.vit_hip_forward_device_u8_resized.argtypes = [voidp, imgp, i, i, rcp, C.POINTER(PixelNorm), voidp, voidp, voidp]
     L.vit_hip_forward_u8_resized.argtypes = [voidp, imgp, i, i, rcp, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
+    boxp = C.POINTER(Box)
+    L.vit_box_check.argtypes = [i, i, C.POINTER(C.c_float)]
+    L.vit_box_rows.argtypes = [i, C.c_float, C.c_float, i, i, ip, ip]
+    L.vit_tile_boxes.argtypes = [i, i, i, i, i, boxp, i]
+    L.vit_hip_crop_boxes_u8.argtypes = [voidp, imgp, i, boxp, i, i, i, voidp, voidp]
+    L.vit_hip_forward_device_u8_boxes.argtypes = [voidp, imgp, i, boxp, i, i, i, C.POINTER(PixelNorm), voidp, voidp, voidp]
+    L.vit_hip_forward_u8_boxes.argtypes = [voidp, imgp, i, boxp, i, i, i, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
     L.vh_feature_readout_scratch.argtypes = [i, i, i]
     L.vh_feature_readout_scratch.restype = sz
     L.vh_launch_feature_readout.argtypes = [voidp, voidp, voidp, C.c_long, voidp, voidp, C.c_double] + [i] * 9 + [voidp] * 4 + [sz]
@@ -716,6 +763,36 @@ class ViTHip:
         rc = resize_crop(resize_short, filter)
         check(self.L.vit_hip_resize_crop_u8(self.ctx, image_descs(d_images), len(d_images), PIXEL_LAYOUTS[layout], C.byref(rc),
                                             d_out, stream), "vit_hip_resize_crop_u8")
+
+    def forward_u8_boxes(self, images, boxes, filter: str = "bilinear", mean=None, std=None, layout: str = "hwc",
+                         logits: bool = True, probs: bool = True):
+        """Regions of host 8-bit images: images as forward_u8_resized takes them, boxes a list of (image index, (left, top,
+        right, bottom)); every box is resized to img x img on the GPU exactly as Pillow's Image.resize(box=), normalised
+        with pixel_norm(mean, std) (or a PixelNorm as `mean`) -> (logits, probs) in box order, as forward_u8."""
+        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
+        descs, keep = host_image_descs(images, layout)
+        n, nc = len(boxes), self.cfg.num_classes
+        out_l = np.empty((n, nc), dtype=np.float32) if logits else None
+        out_p = np.empty((n, nc), dtype=np.float32) if probs else None
+        rows = (f32p * n)(*[fptr(out_p[i]) for i in range(n)]) if probs else None
+        check(self.L.vit_hip_forward_u8_boxes(self.ctx, descs, len(images), box_array(boxes), n, PIXEL_LAYOUTS[layout],
+                                              RESIZE_FILTERS[filter], C.byref(norm), fptr(out_l) if logits else None, rows),
+              "vit_hip_forward_u8_boxes")
+        del keep
+        return out_l, out_p
+
+    def forward_device_u8_boxes(self, d_images, boxes, norm: PixelNorm, filter: str = "bilinear", layout: str = "hwc",
+                                d_logits=None, d_probs=None, stream=None):
+        """Regions of device-resident images: d_images is a list of (device pointer, height, width, row_stride), boxes a
+        list of (image index, (left, top, right, bottom)), at most max_batch of them."""
+        check(self.L.vit_hip_forward_device_u8_boxes(self.ctx, image_descs(d_images), len(d_images), box_array(boxes), len(boxes),
+                                                     PIXEL_LAYOUTS[layout], RESIZE_FILTERS[filter], C.byref(norm), d_logits,
+                                                     d_probs, stream), "vit_hip_forward_device_u8_boxes")
+
+    def crop_boxes_u8(self, d_images, boxes, d_out, filter: str = "bilinear", layout: str = "hwc", stream=None):
+        """The boxes' crops alone, [n][img][img][C] bytes into the device buffer d_out."""
+        check(self.L.vit_hip_crop_boxes_u8(self.ctx, image_descs(d_images), len(d_images), box_array(boxes), len(boxes),
+                                           PIXEL_LAYOUTS[layout], RESIZE_FILTERS[filter], d_out, stream), "vit_hip_crop_boxes_u8")
 
     def forward_device(self, d_images, n: int, d_logits=None, d_probs=None, stream=None):
         """Device-resident path; pointers are ints / c_void_p / DeviceBuffer.ptr."""
