@@ -14,11 +14,17 @@
  *    LayerNorm runs on the class-token rows only (the reference normalises all
  *    197 rows and uses one, ViT_opencl.c:951-955 / ViT_seq.c:506-511).
  *
+ * What a forward reads -- fp32 or 8-bit pixels, of the model's size or resized / cropped from boxes first, in device or in
+ * host memory -- is one struct ingest_src (csrc/vit_ingest.h).  Everything about 8-bit sources that needs no device lives in
+ * csrc/vit_ingest.c: the argument checks, the fill of the resize kernel's descriptors, and the planner and packer of the host
+ * forms' staging slots.  This file keeps the descriptor ring, the launches and the pipeline over the staging slots.
+ *
  * Operator order per layer (ViT_seq.c:330-370):
  *   y = LN1(x); qkv = y Win^T + bin; a = attention(qkv); x = x + (a Wout^T + bout);
  *   y = LN2(x); h = gelu(y W1^T + b1); x = x + (h W2^T + b2)
  */
 #include "ViT_opencl.h"
+#include "vit_ingest.h"
 
 #include <math.h>
 #include <pthread.h>
@@ -65,8 +71,8 @@ enum { STREAMING_MAX_TOKENS = 512 };
 
 enum { MAX_DEPTH = 256, MAX_TENSORS = 4 + 12 * MAX_DEPTH + 4 };
 
-/* resize + crop: descriptor slots in flight, and the largest source side */
-enum { DESC_RING = 8, RESIZE_MAX_SIDE = 16384 };
+/* resize + crop: descriptor slots in flight */
+enum { DESC_RING = 8 };
 
 enum { FEAT_NONE, FEAT_DEVICE, FEAT_HOST };
 
@@ -222,8 +228,6 @@ static double wall_seconds(void)
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 const vit_config *vit_hip_config(const vit_hip_ctx *ctx) { return &ctx->cfg; }
 int vit_hip_device(const vit_hip_ctx *ctx) { return ctx->device; }
@@ -828,33 +832,6 @@ static int planes_patch_embed(const vit_hip_ctx *ctx)
     return ctx->ln_fold || ctx->use_p3 || ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
 }
 
-/* Pillow's ksize: taps per output index of one axis, the span [in0, in1) -> out (the subtraction in float, as in Pillow) */
-static int span_taps(float in0, float in1, int out, int filter)
-{
-    const double scale = (double)(in1 - in0) / out;
-    const double support = (filter == VIT_RESIZE_BICUBIC ? 2.0 : 1.0) * (scale < 1.0 ? 1.0 : scale);
-    return (int)ceil(support) * 2 + 1;
-}
-
-/* a whole axis (in -> out) */
-static int resize_taps(int in, int out, int filter)
-{
-    return span_taps(0.0f, (float)in, out, filter);
-}
-
-/* bicubic taps at the steepest downscale a crop x crop crop can see: the short side 16384 -> resize_short >= crop, the
- * long side's truncated size makes its scale at most 16384 / (crop - 1) */
-static int resize_max_taps(int crop)
-{
-    return resize_taps(RESIZE_MAX_SIDE, crop > 1 ? crop - 1 : 1, VIT_RESIZE_BICUBIC);
-}
-
-/* one image's coefficient tables (include/kernelHandler.h, vh_resize_desc) */
-static size_t resize_table_bytes(int crop, int kx, int ky)
-{
-    return align_up((size_t)crop * 16 + ((size_t)kx + ky) * crop * 4, 16);
-}
-
 /* The activation arena and the host-pointer path's staging, sized for max_batch images. */
 static int alloc_arena(vit_hip_ctx *ctx)
 {
@@ -887,8 +864,7 @@ static int alloc_arena(vit_hip_ctx *ctx)
         }
         const size_t hid_bytes = rows * F * act;
         if (cfg->in_chans <= 4) {   /* the resize's coefficient tables at the largest downscale (more only for tiny configs) */
-            const size_t tables = (size_t)max_batch * resize_table_bytes(cfg->img_size, resize_max_taps(cfg->img_size),
-                                                                          resize_max_taps(cfg->img_size));
+            const size_t tables = (size_t)max_batch * ingest_max_table_bytes(cfg->img_size);
             ws = ws > tables ? ws : tables;
         }
         ctx->ws_bytes = ws > hid_bytes ? ws : hid_bytes;
@@ -1153,35 +1129,14 @@ fail:
     return rc;
 }
 
-/* An image of which only some rows are in memory: data is column 0 of row row0, planes (CHW) plane_stride bytes apart */
-struct row_origin
-{
-    int row0;
-    long plane_stride;
-};
-
-/* What a forward reads: fp32 [n][C][H][W], or 8-bit pixels in `layout` with their normalisation (vit_hip_forward_device_u8) */
-struct pixel_src
-{
-    const float *f32;
-    const unsigned char *u8;
-    int layout;
-    const vit_pixel_norm *norm;
-    const vit_image_u8 *resize;   /* or 8-bit images of any size in `layout` (device data), resized and cropped first */
-    const vit_resize_crop *rc;
-    const vit_box_u8 *boxes;      /* or n boxes of the images `resize` (then rc is NULL), each resized to img x img */
-    int filter;                   /* boxes: VIT_RESIZE_* */
-    const struct row_origin *origin;   /* boxes, host form: per image of `resize`, where its `data` starts; NULL = whole images */
-};
-
-/* Queue the resize + centre crop of n validated images (device data) -- or, with src->boxes, the resize of n validated
- * boxes of them -- into out, [n][img][img][C] bytes: the descriptors go up through the next ring slot, the coefficient
- * tables into hid.  The slot's event is recorded behind the launches that read it. */
-static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct pixel_src *src, int n, unsigned char *out)
+/* Queue the resize of the n validated crops of src (device data: its images where they lie whole, or the items of a staged
+ * chunk) into out, [n][img][img][C] bytes: the descriptors go up through the next ring slot, the coefficient tables into
+ * hid.  The slot's event is recorded behind the launches that read it. */
+static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct ingest_src *src, int n, unsigned char *out)
 {
     int rc_ = 0;
     const vit_config *c = &ctx->cfg;
-    const int layout = src->layout, filter = src->boxes ? src->filter : src->rc->filter;
+    const int filter = ingest_filter(src);
     const int S = c->img_size, C = c->in_chans, slot = ctx->desc_next;
     ctx->desc_next = (slot + 1) % DESC_RING;
     if (ctx->desc_live[slot] && (rc_ = vh_event_sync(ctx->desc_done[slot])) != 0)
@@ -1190,35 +1145,14 @@ static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct pixe
     vh_resize_desc *d = ctx->h_desc[slot];
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
-        const int which = src->boxes ? src->boxes[i].image : i;
-        const vit_image_u8 *im = &src->resize[which];
-        vh_resize_desc *e = &d[i];
-        e->data = im->data;
-        e->row_stride = im->row_stride;
-        e->plane_stride = src->origin ? src->origin[which].plane_stride : (long)im->height * im->row_stride;
-        e->height = im->height;
-        e->width = im->width;
-        e->row0 = src->origin ? src->origin[which].row0 : 0;
-        if (src->boxes) {   /* Image.resize((img, img), box=): every output index, from 0 */
-            const float *b = src->boxes[i].box;
-            e->x0 = b[0], e->y0 = b[1], e->x1 = b[2], e->y1 = b[3];
-            e->out_w = e->out_h = S;
-            e->left = e->top = 0;
-        } else {            /* the whole image to the resized size, of which the centre crop's indices */
-            vit_resize_crop_geometry(im->height, im->width, src->rc, S, &e->out_h, &e->out_w, &e->top, &e->left);
-            e->x0 = e->y0 = 0.0f;
-            e->x1 = (float)im->width, e->y1 = (float)im->height;
-        }
-        e->kx = span_taps(e->x0, e->x1, e->out_w, filter);
-        e->ky = span_taps(e->y0, e->y1, e->out_h, filter);
-        e->coef_offset = (long)off;
-        off += resize_table_bytes(S, e->kx, e->ky);
+        const struct ingest_item item = src->items ? src->items[i] : ingest_whole_item(src, i);
+        off += ingest_fill_desc(&d[i], &item, S, filter, off);
     }
     if (off > ctx->ws_bytes)   /* alloc_arena sized hid for max_batch tables at the steepest downscale */
         return vh_set_error(1, "resize: coefficient tables exceed the scratch");
     if ((rc_ = vh_h2d(ctx->d_desc[slot], d, (size_t)n * sizeof(*d), s)) != 0)
         return rc_;
-    rc_ = vh_launch_resize_crop_u8(s, ctx->d_desc[slot], n, C, layout, filter, S, ctx->hid, ctx->ws_bytes, out);
+    rc_ = vh_launch_resize_crop_u8(s, ctx->d_desc[slot], n, C, src->layout, filter, S, ctx->hid, ctx->ws_bytes, out);
     const int rec = vh_event_record(ctx->desc_done[slot], s);   /* behind the copy even if the launch was refused */
     ctx->desc_live[slot] = rec == 0;
     return rc_ ? rc_ : rec;
@@ -1227,7 +1161,7 @@ static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct pixe
 /* patch embedding + class token + position embedding (ViT_seq.c:437-443), in the form the mode's first layer reads.  8-bit
  * pixels: the planes paths' im2row producer normalises them as it gathers; the fp32-rows paths expand them first into the
  * Q|K|V buffer (idle here; alloc_arena makes it hold max_batch fp32 images).  All of it is one VIT_OP_PATCH_EMBED. */
-static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct pixel_src *src, int n)
+static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct ingest_src *src, int n)
 {
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim;
@@ -1266,7 +1200,6 @@ static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct pi
                                          ctx->hid, ctx->ws_bytes, fp32_math(ctx));
 }
 
-/* Everything after the argument checks of vit_hip_forward_device and vit_hip_forward_device_u8 */
 /* The readout behind layer l for tap k of the armed request: one pass over the residual stream (the class rows alone when
  * only cls is asked for), timed with the LayerNorms.  Partial sums of pooled go through the MLP buffer, idle behind fc2.
  * cls_rows: the last layer ran class-only, its class rows lie compacted at the start of Q|K|V. */
@@ -1286,7 +1219,7 @@ fail:
 
 /* Everything after the argument checks of the forwards.  fr, tk, ar: the armed feature / top-k / attention-map request to
  * serve, or NULL. */
-static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
+static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
                           const struct feature_req *fr, const struct topk_req *tk, const struct attn_req *ar)
 {
     int rc = 0;
@@ -1297,11 +1230,11 @@ static int forward_device(vit_hip_ctx *ctx, const struct pixel_src *src, int n, 
     const int E = c->embed_dim, T = ctx->tokens, NC = c->num_classes;
     vh_stream_t s = stream ? stream : ctx->stream;
 
-    struct pixel_src crops;
-    if (src->resize) {   /* resized crops into Q|K|V, then the u8 path on them; both count as the patch embedding */
+    struct ingest_src crops;
+    if (src->kind == INGEST_U8_RESIZED || src->kind == INGEST_U8_BOXES) {   /* crops into Q|K|V, then the u8 path on them; both count as the patch embedding */
         unsigned char *out = (unsigned char *)ctx->qkv + ctx->crop_off;
         OP(VIT_OP_PATCH_EMBED, resize_crop_launch(ctx, s, src, n, out));
-        crops = (struct pixel_src){NULL, out, VIT_PIXELS_HWC, src->norm, NULL, NULL};
+        crops = (struct ingest_src){.kind = INGEST_U8, .on_device = 1, .u8 = out, .layout = VIT_PIXELS_HWC, .norm = src->norm};
         src = &crops;
     }
     OP(VIT_OP_PATCH_EMBED, patch_embed_launches(ctx, s, src, n));
@@ -1373,14 +1306,30 @@ static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const str
     return 0;
 }
 
-/* A public device-form forward, behind its argument checks */
-static int forward_device_armed(vit_hip_ctx *ctx, const char *who, const struct pixel_src *src, int n, float *d_logits, float *d_probs,
+/* What the ingest path needs of a context; a staging slot of images holds max_batch fp32 images */
+static struct ingest_model model_of(const vit_hip_ctx *ctx)
+{
+    const vit_config *c = &ctx->cfg;
+    return (struct ingest_model){.max_batch = ctx->max_batch, .in_chans = c->in_chans, .img_size = c->img_size,
+                                 .slot_bytes = (size_t)ctx->max_batch * c->in_chans * c->img_size * c->img_size * sizeof(float)};
+}
+
+/* The argument checks of an 8-bit form (ingest_check); a NULL context is refused there, not read here */
+static int source_check(const char *who, const vit_hip_ctx *ctx, const struct ingest_src *src, int n)
+{
+    const struct ingest_model model = ctx ? model_of(ctx) : (struct ingest_model){0};
+    return ingest_check(who, ctx ? &model : NULL, src, n);
+}
+
+/* A public device-form forward: the argument checks of the 8-bit kinds (fp32 callers have made their own), then the armed
+ * requests */
+static int forward_device_armed(vit_hip_ctx *ctx, const char *who, const struct ingest_src *src, int n, float *d_logits, float *d_probs,
                                 vh_stream_t stream)
 {
     const struct feature_req *fr;
     const struct topk_req *tk;
     const struct attn_req *ar;
-    if (armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar))
+    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar))
         return 1;
     return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar);
 }
@@ -1390,7 +1339,7 @@ int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n,
 {
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
-    const struct pixel_src src = {d_images, NULL, 0, NULL};
+    const struct ingest_src src = {.kind = INGEST_F32, .on_device = 1, .f32 = d_images};
     return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL);
 }
 
@@ -1399,313 +1348,58 @@ int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float
 {
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
-    const struct pixel_src src = {d_images, NULL, 0, NULL};
+    const struct ingest_src src = {.kind = INGEST_F32, .on_device = 1, .f32 = d_images};
     return forward_device_armed(ctx, "vit_hip_forward_device", &src, n, d_logits, d_probs, stream);
 }
 
-int vit_pixel_norm_from_mean_std(vit_pixel_norm *out, const float *mean, const float *std, int chans)
+/* A public call for the crops alone, into src->crops */
+static int crops_launch(vit_hip_ctx *ctx, const char *who, const struct ingest_src *src, int n, vh_stream_t stream)
 {
-    if (!out || !mean || !std || chans < 1 || chans > 4)
-        return vh_set_error(1, "vit_pixel_norm_from_mean_std: NULL argument, or chans not in 1..4");
-    for (int ch = 0; ch < chans; ++ch)
-        if (!(std[ch] > 0.0f) || !isfinite(std[ch]) || !isfinite(mean[ch]))
-            return vh_set_error(1, "vit_pixel_norm_from_mean_std: std must be positive and finite, mean finite");
-    memset(out, 0, sizeof(*out));
-    for (int ch = 0; ch < chans; ++ch) {
-        out->scale[ch] = (float)(1.0 / (255.0 * (double)std[ch]));
-        out->bias[ch] = (float)(-(double)mean[ch] / (double)std[ch]);
-    }
-    return 0;
-}
-
-/* The u8 forms' checks that need no device; device_ptr: the pointer is in HBM and must be 16-byte aligned */
-static int u8_args(const char *who, const vit_hip_ctx *ctx, const unsigned char *images, int n, int layout, const vit_pixel_norm *norm,
-                   int device_ptr)
-{
-    char msg[200];
-    const char *why = !ctx || !images || !norm ? "NULL context, images or norm"
-                      : n <= 0 ? "n must be positive"
-                      : device_ptr && n > ctx->max_batch ? "n exceeds the context's max_batch"
-                      : layout != VIT_PIXELS_HWC && layout != VIT_PIXELS_CHW ? "layout must be VIT_PIXELS_HWC or VIT_PIXELS_CHW"
-                      : ctx->cfg.in_chans > 4 ? "8-bit images take at most 4 channels"
-                      : device_ptr && ((uintptr_t)images & 15) ? "device images must be 16-byte aligned"
-                      : NULL;
-    if (!why)
-        return 0;
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return vh_set_error(1, msg);
+    int rc = 0;
+    if (source_check(who, ctx, src, n))
+        return 1;
+    if ((rc = vh_set_device(ctx->device)) != 0)
+        return rc;
+    return resize_crop_launch(ctx, stream ? stream : ctx->stream, src, n, src->crops);
 }
 
 int vit_hip_forward_device_u8(vit_hip_ctx *ctx, const unsigned char *d_images, int n, int layout,
                               const vit_pixel_norm *norm, float *d_logits, float *d_probs, vh_stream_t stream)
 {
-    if (u8_args("vit_hip_forward_device_u8", ctx, d_images, n, layout, norm, 1))
-        return 1;
-    const struct pixel_src src = {NULL, d_images, layout, norm};
+    const struct ingest_src src = {.kind = INGEST_U8, .on_device = 1, .u8 = d_images, .layout = layout, .norm = norm};
     return forward_device_armed(ctx, "vit_hip_forward_device_u8", &src, n, d_logits, d_probs, stream);
-}
-
-int vit_resize_crop_geometry(int height, int width, const vit_resize_crop *rc, int crop, int *resized_h, int *resized_w, int *top,
-                             int *left)
-{
-    char msg[200];
-    const char *why = !rc || !resized_h || !resized_w || !top || !left ? "NULL argument"
-                      : crop <= 0 ? "crop must be positive"
-                      : height < 1 || width < 1 || height > RESIZE_MAX_SIDE || width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
-                      : rc->filter != VIT_RESIZE_BILINEAR && rc->filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
-                      : rc->resize_short < crop || (long long)rc->resize_short > 4LL * crop ? "resize_short must be in crop..4 x crop"
-                      : NULL;
-    if (why) {
-        snprintf(msg, sizeof msg, "vit_resize_crop_geometry: %s", why);
-        return vh_set_error(1, msg);
-    }
-    /* torchvision's _compute_resized_output_size: the short side becomes resize_short, the long one
-     * int(resize_short * long / short); CenterCrop: int(round((size - crop) / 2.0)), Python's round (half to even) */
-    const long long rs = rc->resize_short;
-    const int nh = height <= width ? (int)rs : (int)((double)(rs * height) / width);
-    const int nw = height <= width ? (int)((double)(rs * width) / height) : (int)rs;
-    *resized_h = nh;
-    *resized_w = nw;
-    *top = (int)nearbyint((nh - crop) / 2.0);
-    *left = (int)nearbyint((nw - crop) / 2.0);
-    return 0;
-}
-
-/* The resize forms' checks that need no device.  norm_needed: the forwards; device: n <= max_batch; slot_bytes: the host
- * form's limit on one image's packed bytes (0 = none) */
-static int resize_args(const char *who, const vit_hip_ctx *ctx, const vit_image_u8 *images, int n, int layout, const vit_resize_crop *rc,
-                       const vit_pixel_norm *norm, int norm_needed, const void *out, int out_needed, int device, size_t slot_bytes)
-{
-    char msg[240];
-    const char *why = !ctx || !images || !rc || (norm_needed && !norm) || (out_needed && !out) ? "NULL argument"
-                      : n <= 0 ? "n must be positive"
-                      : device && n > ctx->max_batch ? "n exceeds the context's max_batch"
-                      : layout != VIT_PIXELS_HWC && layout != VIT_PIXELS_CHW ? "layout must be VIT_PIXELS_HWC or VIT_PIXELS_CHW"
-                      : rc->filter != VIT_RESIZE_BILINEAR && rc->filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
-                      : ctx->cfg.in_chans > 4 ? "8-bit images take at most 4 channels"
-                      : (long)ctx->cfg.img_size * ctx->cfg.in_chans > VH_RESIZE_MAX_ROW_BYTES ? "img_size x in_chans above 3072 bytes per crop row"
-                      : rc->resize_short < ctx->cfg.img_size || rc->resize_short > 4 * ctx->cfg.img_size ? "resize_short must be in img_size..4 x img_size"
-                      : NULL;
-    int bad = -1;
-    if (!why) {
-        const long C = ctx->cfg.in_chans;
-        for (int i = 0; i < n && !why; ++i) {
-            const vit_image_u8 *im = &images[i];
-            const long row = layout == VIT_PIXELS_HWC ? (long)im->width * C : (long)im->width;
-            why = !im->data ? "NULL image data"
-                  : im->height < 1 || im->width < 1 || im->height > RESIZE_MAX_SIDE || im->width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
-                  : im->row_stride < row ? "row_stride below the row's bytes"
-                  : slot_bytes && (size_t)im->height * im->width * C > slot_bytes ? "image larger than a staging slot"
-                  : NULL;
-            bad = i;
-        }
-    }
-    if (!why)
-        return 0;
-    if (bad >= 0)
-        snprintf(msg, sizeof msg, "%s: image %d: %s", who, bad, why);
-    else
-        snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return vh_set_error(1, msg);
 }
 
 int vit_hip_resize_crop_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n, int layout, const vit_resize_crop *rc,
                            unsigned char *d_out, vh_stream_t stream)
 {
-    int rc_ = 0;
-    if (resize_args("vit_hip_resize_crop_u8", ctx, d_images, n, layout, rc, NULL, 0, d_out, 1, 1, 0))
-        return 1;
-    if ((rc_ = vh_set_device(ctx->device)) != 0)
-        return rc_;
-    const struct pixel_src src = {NULL, NULL, layout, NULL, d_images, rc};
-    return resize_crop_launch(ctx, stream ? stream : ctx->stream, &src, n, d_out);
+    const struct ingest_src src = {.kind = INGEST_U8_RESIZED, .on_device = 1, .images = d_images, .rc = rc, .layout = layout,
+                                   .crops_only = 1, .crops = d_out};
+    return crops_launch(ctx, "vit_hip_resize_crop_u8", &src, n, stream);
 }
 
 int vit_hip_forward_device_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n, int layout, const vit_resize_crop *rc,
                                       const vit_pixel_norm *norm, float *d_logits, float *d_probs, vh_stream_t stream)
 {
-    if (resize_args("vit_hip_forward_device_u8_resized", ctx, d_images, n, layout, rc, norm, 1, NULL, 0, 1, 0))
-        return 1;
-    const struct pixel_src src = {NULL, NULL, layout, norm, d_images, rc};
+    const struct ingest_src src = {.kind = INGEST_U8_RESIZED, .on_device = 1, .images = d_images, .rc = rc, .layout = layout, .norm = norm};
     return forward_device_armed(ctx, "vit_hip_forward_device_u8_resized", &src, n, d_logits, d_probs, stream);
 }
 
-/* "who: why" as the thread's error text; returns 1 */
-static int refuse(const char *who, const char *why)
-{
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return vh_set_error(1, msg);
-}
-
-/* ---- boxes: regions of 8-bit images, each resized to img x img as Pillow's Image.resize(size, resample, box=) ---- */
-
-/* NULL, or why `box` is not a box of a height x width image.  Written so that a NaN fails its comparison. */
-static const char *box_why(int height, int width, const float box[4])
-{
-    return !box ? "NULL box"
-           : height < 1 || width < 1 || height > RESIZE_MAX_SIDE || width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
-           : !isfinite(box[0]) || !isfinite(box[1]) || !isfinite(box[2]) || !isfinite(box[3]) ? "box values must be finite"
-           : !(box[0] >= 0.0f) || !(box[1] >= 0.0f) || !(box[2] <= (float)width) || !(box[3] <= (float)height) ? "box outside the image"
-           : !(box[2] - box[0] >= 1.0f) || !(box[3] - box[1] >= 1.0f) ? "box narrower or lower than 1 px"
-           : NULL;
-}
-
-int vit_box_check(int height, int width, const float box[4])
-{
-    const char *why = box_why(height, width, box);
-    return why ? refuse("vit_box_check", why) : 0;
-}
-
-/* Pillow's bounds of output index xx of one axis: the first source index read and how many (resize_coef_kernel's own
- * arithmetic, csrc/resize.hip; this file too is built without fused multiply-adds) */
-static void span_bounds(int in, float in0, float in1, int out, int filter, int xx, int *first, int *taps)
-{
-    const double scale = (double)(in1 - in0) / out;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = (filter == VIT_RESIZE_BICUBIC ? 2.0 : 1.0) * filterscale;
-    const double center = (double)in0 + (xx + 0.5) * scale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0)
-        xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in)
-        xmax = in;
-    *first = xmin;
-    *taps = xmax - xmin;
-}
-
-/* the rows [first, first + count) that the `out` output rows of a validated span read */
-static void box_rows(int height, float top, float bottom, int out, int filter, int *first, int *count)
-{
-    int lo = height, hi = 0;
-    for (int yy = 0; yy < out; ++yy) {
-        int ymin, taps;
-        span_bounds(height, top, bottom, out, filter, yy, &ymin, &taps);
-        lo = ymin < lo ? ymin : lo;
-        hi = ymin + taps > hi ? ymin + taps : hi;
-    }
-    *first = lo;
-    *count = hi - lo;
-}
-
-int vit_box_rows(int height, float top, float bottom, int out, int filter, int *first, int *count)
-{
-    const float box[4] = {0.0f, top, 1.0f, bottom};
-    const char *why = !first || !count ? "NULL argument"
-                      : out < 1 ? "out must be positive"
-                      : filter != VIT_RESIZE_BILINEAR && filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
-                      : box_why(height, 1, box);
-    if (why)
-        return refuse("vit_box_rows", why);
-    box_rows(height, top, bottom, out, filter, first, count);
-    return 0;
-}
-
-int vit_tile_boxes(int height, int width, int tile, int stride, int image, vit_box_u8 *out, int capacity)
-{
-    const char *why = height < 1 || width < 1 || height > RESIZE_MAX_SIDE || width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
-                      : tile < 1 || tile > height || tile > width ? "tile must be in 1..min(height, width)"
-                      : stride < 1 || stride > tile ? "stride must be in 1..tile"
-                      : image < 0 ? "image must not be negative"
-                      : capacity < 0 || (capacity > 0 && !out) ? "NULL out, or a negative capacity"
-                      : NULL;
-    if (why) {
-        refuse("vit_tile_boxes", why);
-        return -1;
-    }
-    /* tiles at 0, stride, ... while they fit; one more, flush to the far edge, when the last of those stops short of it */
-    const int ny = (height - tile) / stride + 1 + ((height - tile) % stride != 0);
-    const int nx = (width - tile) / stride + 1 + ((width - tile) % stride != 0);
-    for (int ty = 0, k = 0; ty < ny; ++ty)
-        for (int tx = 0; tx < nx; ++tx, ++k) {
-            if (k >= capacity)
-                continue;
-            const int y = ty * stride + tile > height ? height - tile : ty * stride;
-            const int x = tx * stride + tile > width ? width - tile : tx * stride;
-            out[k].image = image;
-            out[k].box[0] = (float)x, out[k].box[1] = (float)y;
-            out[k].box[2] = (float)(x + tile), out[k].box[3] = (float)(y + tile);
-        }
-    return ny * nx;
-}
-
-/* The box forms' checks that need no device: every image and every box, before anything is queued.  norm_needed: the
- * forwards; device: n <= max_batch; slot_bytes: the host form's limit on the rows one box reads (0 = none) */
-static int box_args(const char *who, const vit_hip_ctx *ctx, const vit_image_u8 *images, int n_images, const vit_box_u8 *boxes, int n,
-                    int layout, int filter, const vit_pixel_norm *norm, int norm_needed, const void *out, int out_needed, int device,
-                    size_t slot_bytes)
-{
-    char msg[240];
-    const char *why = !ctx || !images || !boxes || (norm_needed && !norm) || (out_needed && !out) ? "NULL argument"
-                      : n <= 0 ? "n must be positive"
-                      : n_images <= 0 ? "n_images must be positive"
-                      : device && n > ctx->max_batch ? "n exceeds the context's max_batch"
-                      : layout != VIT_PIXELS_HWC && layout != VIT_PIXELS_CHW ? "layout must be VIT_PIXELS_HWC or VIT_PIXELS_CHW"
-                      : filter != VIT_RESIZE_BILINEAR && filter != VIT_RESIZE_BICUBIC ? "filter must be VIT_RESIZE_BILINEAR or VIT_RESIZE_BICUBIC"
-                      : ctx->cfg.in_chans > 4 ? "8-bit images take at most 4 channels"
-                      : (long)ctx->cfg.img_size * ctx->cfg.in_chans > VH_RESIZE_MAX_ROW_BYTES ? "img_size x in_chans above 3072 bytes per crop row"
-                      : NULL;
-    const char *what = NULL;
-    int bad = -1;
-    if (!why) {
-        const long C = ctx->cfg.in_chans;
-        for (int i = 0; i < n_images && !why; ++i) {
-            const vit_image_u8 *im = &images[i];
-            const long row = layout == VIT_PIXELS_HWC ? (long)im->width * C : (long)im->width;
-            why = !im->data ? "NULL image data"
-                  : im->height < 1 || im->width < 1 || im->height > RESIZE_MAX_SIDE || im->width > RESIZE_MAX_SIDE ? "height and width must be in 1..16384"
-                  : im->row_stride < row ? "row_stride below the row's bytes"
-                  : NULL;
-            what = "image";
-            bad = i;
-        }
-        for (int i = 0; i < n && !why; ++i) {
-            const vit_box_u8 *b = &boxes[i];
-            what = "box";
-            bad = i;
-            if (b->image < 0 || b->image >= n_images) {
-                why = "image index outside 0..n_images - 1";
-                break;
-            }
-            const vit_image_u8 *im = &images[b->image];
-            why = box_why(im->height, im->width, b->box);
-            if (!why && slot_bytes) {
-                int first, count;
-                box_rows(im->height, b->box[1], b->box[3], ctx->cfg.img_size, filter, &first, &count);
-                if ((size_t)count * im->width * C > slot_bytes)
-                    why = "the rows it reads are larger than a staging slot";
-            }
-        }
-    }
-    if (!why)
-        return 0;
-    if (bad >= 0)
-        snprintf(msg, sizeof msg, "%s: %s %d: %s", who, what, bad, why);
-    else
-        snprintf(msg, sizeof msg, "%s: %s", who, why);
-    return vh_set_error(1, msg);
-}
-
+/* boxes: regions of 8-bit images, each resized to img x img as Pillow's Image.resize(size, resample, box=) */
 int vit_hip_crop_boxes_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n_images, const vit_box_u8 *boxes, int n, int layout,
                           int filter, unsigned char *d_out, vh_stream_t stream)
 {
-    int rc_ = 0;
-    if (box_args("vit_hip_crop_boxes_u8", ctx, d_images, n_images, boxes, n, layout, filter, NULL, 0, d_out, 1, 1, 0))
-        return 1;
-    if ((rc_ = vh_set_device(ctx->device)) != 0)
-        return rc_;
-    const struct pixel_src src = {NULL, NULL, layout, NULL, d_images, NULL, boxes, filter, NULL};
-    return resize_crop_launch(ctx, stream ? stream : ctx->stream, &src, n, d_out);
+    const struct ingest_src src = {.kind = INGEST_U8_BOXES, .on_device = 1, .images = d_images, .n_images = n_images, .boxes = boxes,
+                                   .filter = filter, .layout = layout, .crops_only = 1, .crops = d_out};
+    return crops_launch(ctx, "vit_hip_crop_boxes_u8", &src, n, stream);
 }
 
 int vit_hip_forward_device_u8_boxes(vit_hip_ctx *ctx, const vit_image_u8 *d_images, int n_images, const vit_box_u8 *boxes, int n,
                                     int layout, int filter, const vit_pixel_norm *norm, float *d_logits, float *d_probs,
                                     vh_stream_t stream)
 {
-    if (box_args("vit_hip_forward_device_u8_boxes", ctx, d_images, n_images, boxes, n, layout, filter, norm, 1, NULL, 0, 1, 0))
-        return 1;
-    const struct pixel_src src = {NULL, NULL, layout, norm, d_images, NULL, boxes, filter, NULL};
+    const struct ingest_src src = {.kind = INGEST_U8_BOXES, .on_device = 1, .images = d_images, .n_images = n_images, .boxes = boxes,
+                                   .filter = filter, .layout = layout, .norm = norm};
     return forward_device_armed(ctx, "vit_hip_forward_device_u8_boxes", &src, n, d_logits, d_probs, stream);
 }
 
@@ -1739,7 +1433,7 @@ static int feature_spec_check(const char *who, const vit_config *cfg, const vit_
           : spec->dtype != VIT_FEATURE_F32 && spec->dtype != VIT_FEATURE_BF16 ? "dtype must be VIT_FEATURE_F32 or VIT_FEATURE_BF16"
           : spec->token_layout != VIT_TOKENS_NLC && spec->token_layout != VIT_TOKENS_NCHW ? "token_layout must be VIT_TOKENS_NLC or VIT_TOKENS_NCHW"
           : resolve_taps(cfg, spec->n_taps, spec->taps, layer);
-    return why ? refuse(who, why) : 0;
+    return why ? ingest_refuse(who, why) : 0;
 }
 
 int vit_feature_sizes(const vit_config *cfg, const vit_feature_spec *spec, size_t *cls_elems, size_t *pooled_elems, size_t *tokens_elems)
@@ -1766,7 +1460,7 @@ static int arm(const char *who, vit_hip_ctx *ctx, size_t armed, struct staged re
 {
     int rc = 0;
     if (!ctx)
-        return refuse(who, "NULL context");
+        return ingest_refuse(who, "NULL context");
     TRY(vh_set_device(ctx->device));
     /* the staging of an earlier host request may still be read by its last forward's copies */
     TRY(vh_stream_sync(ctx->stream));
@@ -1794,7 +1488,7 @@ static int set_features(const char *who, vit_hip_ctx *ctx, const vit_feature_spe
                           : !host && (((uintptr_t)bufs->cls | (uintptr_t)bufs->pooled | (uintptr_t)bufs->tokens) & 15) ? "device buffers must be 16-byte aligned"
                           : NULL;
         if (why)
-            return refuse(who, why);
+            return ingest_refuse(who, why);
         fr.form = host ? FEAT_HOST : FEAT_DEVICE;
         fr.spec = *spec;
         fr.out = *bufs;
@@ -1831,7 +1525,7 @@ static int topk_spec_check(const char *who, const vit_config *cfg, const vit_top
                       : spec->k > cfg->num_classes ? "k exceeds num_classes"
                       : spec->score_kind != VIT_TOPK_PROBS && spec->score_kind != VIT_TOPK_LOGITS ? "score_kind must be VIT_TOPK_PROBS or VIT_TOPK_LOGITS"
                       : NULL;
-    return why ? refuse(who, why) : 0;
+    return why ? ingest_refuse(who, why) : 0;
 }
 
 int vit_topk_check(const vit_config *cfg, const vit_topk_spec *spec)
@@ -1851,7 +1545,7 @@ static int set_topk(const char *who, vit_hip_ctx *ctx, const vit_topk_spec *spec
                           : !host && (((uintptr_t)bufs->labels | (uintptr_t)bufs->scores) & 15) ? "device buffers must be 16-byte aligned"
                           : NULL;
         if (why)
-            return refuse(who, why);
+            return ingest_refuse(who, why);
         tk.form = host ? FEAT_HOST : FEAT_DEVICE;
         tk.spec = *spec;
         tk.out = *bufs;
@@ -1885,7 +1579,7 @@ static int attn_spec_check(const char *who, const vit_config *cfg, const vit_att
     why = why ? why
           : cfg->num_heads <= 0 || cfg->embed_dim % cfg->num_heads != 0 ? "bad model config"
           : resolve_taps(cfg, spec->n_taps, spec->taps, layer);
-    return why ? refuse(who, why) : 0;
+    return why ? ingest_refuse(who, why) : 0;
 }
 
 int vit_attn_sizes(const vit_config *cfg, const vit_attn_spec *spec, size_t *heads_elems, size_t *mean_elems)
@@ -1915,7 +1609,7 @@ static int set_attention(const char *who, vit_hip_ctx *ctx, const vit_attn_spec 
                           : !host && (((uintptr_t)bufs->heads | (uintptr_t)bufs->mean) & 15) ? "device buffers must be 16-byte aligned"
                           : NULL;
         if (why)
-            return refuse(who, why);
+            return ingest_refuse(who, why);
         ar.form = host ? FEAT_HOST : FEAT_DEVICE;
         ar.spec = *spec;
         ar.out = *bufs;
@@ -2036,177 +1730,35 @@ static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, const 
             memcpy(probs[first + i], ctx->h_probs[slot] + (size_t)i * NC, NC * sizeof(float));
 }
 
-/* Gather of the separately allocated host images (Network.c:90) -- or of a caller's contiguous 8-bit images -- into one
- * pinned staging slot, on several host threads: a single memcpy stream moves ~3 GB/s, which would cap the host-pointer path
- * below the device-resident rate. */
-struct host_src
-{
-    const ImageData *images;   /* fp32: one allocation per image */
-    const unsigned char *u8;   /* or 8-bit, contiguous */
-    int layout;
-    const vit_pixel_norm *norm;
-    const vit_image_u8 *resize;   /* or 8-bit images of any size, packed into the slot without their row padding */
-    const vit_resize_crop *rc;
-    size_t *packed;               /* resize: the chunk's byte offsets in the slot, [max_batch + 1] */
-    vit_image_u8 *staged;         /* resize: the chunk's descriptors, data in the device slot, [max_batch] */
-    const vit_box_u8 *boxes;      /* or boxes of the images `resize` (rc NULL): only the rows a chunk's boxes read are packed */
-    int filter;
-    struct box_chunk *chunk;      /* boxes: the chunk being staged */
-};
-
-/* A chunk of the box host form.  Its distinct sources lie in the slot one behind the other, each as the rows its boxes read
- * (a bit per source row), in row order, at full width: HWC rows, or per plane for CHW.  The rows of one box are consecutive
- * there, so every box gets an image descriptor of its own that starts at its first row. */
-enum { ROWMAP_BYTES = RESIZE_MAX_SIDE / 8 };
-struct box_chunk
-{
-    int n_src;                   /* distinct sources */
-    int *src_image;              /* [max_batch] their indices into the caller's images */
-    int *src_rows;               /* [max_batch] rows packed of each */
-    size_t *src_off;             /* [max_batch] where each starts in the slot */
-    unsigned char *rowmap;       /* [max_batch][ROWMAP_BYTES] */
-    size_t bytes;                /* of the whole chunk */
-    vit_image_u8 *staged;        /* [max_batch] per box: data in the device slot */
-    struct row_origin *origin;   /* [max_batch] per box */
-    vit_box_u8 *boxes;           /* [max_batch] per box: image = its own index */
-};
-
+/* Gather of the separately allocated host images (Network.c:90) -- or of a caller's contiguous 8-bit images, or of the
+ * sources of a planned chunk -- into one pinned staging slot, on several host threads: a single memcpy stream moves ~3 GB/s,
+ * which would cap the host-pointer path below the device-resident rate. */
 struct gather_job
 {
     char *dst;
-    const struct host_src *src;
-    int first, count;   /* images [first, first + count) of the chunk starting at image `base` */
+    const struct ingest_src *src;
+    const struct ingest_plan *plan;   /* the jobs are the planned chunk's sources; NULL: the images from `base` on */
+    int first, count;                 /* jobs [first, first + count) */
     int base;
-    size_t bytes;       /* per image */
+    size_t per_image;                 /* plan NULL: bytes */
 };
-
-/* one image of a resize chunk, its rows packed: HWC rows of width x C bytes, or C planes of height rows of width bytes */
-static void pack_image(char *dst, const vit_image_u8 *im, int layout, int chans)
-{
-    const size_t row = (size_t)im->width * (layout == VIT_PIXELS_HWC ? chans : 1);
-    const int rows = layout == VIT_PIXELS_HWC ? im->height : im->height * chans;
-    if ((size_t)im->row_stride == row) {
-        memcpy(dst, im->data, row * rows);
-        return;
-    }
-    for (int y = 0; y < rows; ++y)   /* CHW: plane p's row y is row p * height + y at the same stride */
-        memcpy(dst + (size_t)y * row, im->data + (size_t)y * im->row_stride, row);
-}
-
-/* source k of a box chunk: the rows of its map, in order, HWC rows or plane after plane */
-static void pack_rows(char *dst, const struct host_src *src, int k, int chans)
-{
-    const struct box_chunk *ch = src->chunk;
-    const vit_image_u8 *im = &src->resize[ch->src_image[k]];
-    const unsigned char *map = ch->rowmap + (size_t)k * ROWMAP_BYTES;
-    const size_t row = (size_t)im->width * (src->layout == VIT_PIXELS_HWC ? chans : 1);
-    const int planes = src->layout == VIT_PIXELS_HWC ? 1 : chans;
-    dst += ch->src_off[k];
-    for (int p = 0; p < planes; ++p)
-        for (int y = 0; y < im->height; ++y)
-            if (map[y >> 3] >> (y & 7) & 1) {
-                memcpy(dst, im->data + ((size_t)p * im->height + y) * im->row_stride, row);
-                dst += row;
-            }
-}
 
 static void *gather_worker(void *arg)
 {
     const struct gather_job *j = (const struct gather_job *)arg;
     for (int i = j->first; i < j->first + j->count; ++i) {
-        if (j->src->boxes) {
-            pack_rows(j->dst, j->src, i, (int)j->bytes);
+        if (j->plan) {
+            ingest_pack(j->dst, j->plan, j->src, i);
             continue;
         }
-        if (j->src->resize) {
-            pack_image(j->dst + j->src->packed[i], &j->src->resize[j->base + i], j->src->layout, (int)j->bytes);
-            continue;
-        }
-        const void *from = j->src->images ? (const void *)j->src->images[j->base + i].data
-                                          : (const void *)(j->src->u8 + (size_t)(j->base + i) * j->bytes);
-        memcpy(j->dst + (size_t)i * j->bytes, from, j->bytes);
+        const void *from = j->src->kind == INGEST_F32 ? (const void *)j->src->host_f32[j->base + i].data
+                                                      : (const void *)(j->src->u8 + (size_t)(j->base + i) * j->per_image);
+        memcpy(j->dst + (size_t)i * j->per_image, from, j->per_image);
     }
     return NULL;
 }
 
-/* A resize chunk from image `first`: at most max_batch images whose packed bytes fit one staging slot (resize_args has
- * refused any image larger than a slot); fills src->packed and src->staged (data pointers into d_slot) */
-static int resize_chunk(const vit_hip_ctx *ctx, const struct host_src *src, int first, int n, size_t slot_bytes, const unsigned char *d_slot)
-{
-    const size_t C = (size_t)ctx->cfg.in_chans;
-    size_t off = 0;
-    int m = 0;
-    for (; m < ctx->max_batch && first + m < n; ++m) {
-        const vit_image_u8 *im = &src->resize[first + m];
-        const size_t bytes = (size_t)im->height * im->width * C;
-        if (off + bytes > slot_bytes)
-            break;
-        src->packed[m] = off;
-        src->staged[m] = (vit_image_u8){d_slot + off, im->height, im->width,
-                                        (long)im->width * (src->layout == VIT_PIXELS_HWC ? (long)C : 1)};
-        off += bytes;
-    }
-    src->packed[m] = off;
-    return m;
-}
-
-/* A box chunk from box `first`: at most max_batch boxes whose sources' rows, each packed once, fit one staging slot
- * (box_args has refused any box whose own rows do not); fills src->chunk */
-static int box_chunk_build(const vit_hip_ctx *ctx, const struct host_src *src, int first, int n, size_t slot_bytes,
-                           const unsigned char *d_slot)
-{
-    struct box_chunk *ch = src->chunk;
-    const size_t C = (size_t)ctx->cfg.in_chans;
-    const int S = ctx->cfg.img_size, hwc = src->layout == VIT_PIXELS_HWC;
-    int m = 0;
-    ch->n_src = 0;
-    ch->bytes = 0;
-    for (; m < ctx->max_batch && first + m < n; ++m) {
-        const vit_box_u8 *b = &src->boxes[first + m];
-        const vit_image_u8 *im = &src->resize[b->image];
-        int k = 0, row0, count, fresh = 0;
-        while (k < ch->n_src && ch->src_image[k] != b->image)
-            ++k;
-        unsigned char *map = ch->rowmap + (size_t)k * ROWMAP_BYTES;
-        box_rows(im->height, b->box[1], b->box[3], S, src->filter, &row0, &count);
-        for (int y = row0; y < row0 + count; ++y)
-            fresh += k == ch->n_src || !(map[y >> 3] >> (y & 7) & 1);
-        if (ch->bytes + (size_t)fresh * im->width * C > slot_bytes)
-            break;
-        if (k == ch->n_src) {
-            ch->src_image[ch->n_src++] = b->image;
-            ch->src_rows[k] = 0;
-            memset(map, 0, ROWMAP_BYTES);
-        }
-        for (int y = row0; y < row0 + count; ++y)
-            map[y >> 3] |= (unsigned char)(1 << (y & 7));
-        ch->src_rows[k] += fresh;
-        ch->bytes += (size_t)fresh * im->width * C;
-        ch->origin[m].row0 = row0;       /* completed below, once the sources' row counts are final */
-        ch->boxes[m] = *b;
-    }
-    size_t off = 0;
-    for (int k = 0; k < ch->n_src; ++k) {
-        ch->src_off[k] = off;
-        off += (size_t)ch->src_rows[k] * src->resize[ch->src_image[k]].width * C;
-    }
-    for (int i = 0; i < m; ++i) {
-        const vit_image_u8 *im = &src->resize[ch->boxes[i].image];
-        int k = 0, rank = 0;
-        while (ch->src_image[k] != ch->boxes[i].image)
-            ++k;
-        const unsigned char *map = ch->rowmap + (size_t)k * ROWMAP_BYTES;
-        for (int y = 0; y < ch->origin[i].row0; ++y)   /* packed rows of the source ahead of the box's first */
-            rank += map[y >> 3] >> (y & 7) & 1;
-        const long row = (long)im->width * (hwc ? (long)C : 1);
-        ch->staged[i] = (vit_image_u8){d_slot + ch->src_off[k] + (size_t)rank * row, im->height, im->width, row};
-        ch->origin[i].plane_stride = (long)ch->src_rows[k] * row;
-        ch->boxes[i].image = i;
-    }
-    return m;
-}
-
-static void gather_images(void *dst, const struct host_src *src, int base, int m, size_t bytes)
+static void gather_images(void *dst, const struct ingest_src *src, const struct ingest_plan *plan, int base, int m, size_t per_image)
 {
     enum { MAX_THREADS = 8 };
     int nt = m / 16;
@@ -2216,14 +1768,14 @@ static void gather_images(void *dst, const struct host_src *src, int base, int m
     pthread_t tid[MAX_THREADS];
     int started = 0;
     if (nt < 2) {
-        struct gather_job all = {(char *)dst, src, 0, m, base, bytes};
+        struct gather_job all = {.dst = (char *)dst, .src = src, .plan = plan, .first = 0, .count = m, .base = base, .per_image = per_image};
         gather_worker(&all);
         return;
     }
     const int per = (m + nt - 1) / nt;
     for (int t = 0; t < nt; ++t) {
         const int first = t * per, count = first >= m ? 0 : (m - first < per ? m - first : per);
-        jobs[t] = (struct gather_job){(char *)dst, src, first, count, base, bytes};
+        jobs[t] = (struct gather_job){.dst = (char *)dst, .src = src, .plan = plan, .first = first, .count = count, .base = base, .per_image = per_image};
         if (count == 0)
             break;
         if (t == nt - 1 || pthread_create(&tid[started], NULL, gather_worker, &jobs[t]) != 0)
@@ -2235,20 +1787,16 @@ static void gather_images(void *dst, const struct host_src *src, int base, int m
         pthread_join(tid[t], NULL);
 }
 
-/* The bytes of one staging slot of images: max_batch fp32 images */
-static size_t image_slot_bytes(const vit_hip_ctx *ctx)
-{
-    return (size_t)ctx->max_batch * ctx->cfg.in_chans * ctx->cfg.img_size * ctx->cfg.img_size * sizeof(float);
-}
-
 /* Host-pointer forward, software-pipelined over chunks of max_batch images:
  *   host     : gather chunk k into pinned slot k&1   | scatter outputs of chunk k-1
  *   copy strm: H2D chunk k                            (after compute of chunk k-2 released the slot)
  *   compute  : forward chunk k, D2H its logits/probs  (after the H2D)
  * so PCIe and the gather of the separately malloc'd images (Network.c:90) hide under
- * the previous chunk's kernels.  A u8 chunk fills a quarter of a staging slot.  form: FEAT_HOST to serve the armed host
- * requests, FEAT_NONE to serve none. */
-static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n, float *logits, float **probs, int form)
+ * the previous chunk's kernels.  A u8 chunk fills a quarter of a staging slot.  plan: the scratch of the kinds whose chunks
+ * are planned (vit_ingest.h), NULL for images of the model's size.  form: FEAT_HOST to serve the armed host requests,
+ * FEAT_NONE to serve none. */
+static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, struct ingest_plan *plan, int n, float *logits, float **probs,
+                             int form)
 {
     int rc = 0;
     const struct feature_req *fr;
@@ -2258,9 +1806,8 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
         return 1;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
-    const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->u8 ? 1 : sizeof(float));
+    const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->kind == INGEST_F32 ? sizeof(float) : 1);
     const size_t NC = (size_t)c->num_classes;
-    const size_t slot_bytes = image_slot_bytes(ctx);
     /* what comes back per chunk besides the probabilities, in the order it is queued: logits, cls, pooled, labels, scores,
      * heads, mean */
     const struct staged logits_st = {ctx->d_logits, {ctx->h_logits[0], ctx->h_logits[1]}, (char *)logits, NC * sizeof(float)};
@@ -2277,29 +1824,40 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct host_src *src, int n
     int prev_first = 0, prev_m = 0, k = 0;
     for (int first = 0, m = 0; first < n; first += m, ++k) {
         const int s = k & 1;
-        if (src->boxes)    /* cut by count and by bytes; gather_images packs every distinct source's rows (bytes carries C) */
-            m = box_chunk_build(ctx, src, first, n, slot_bytes, (const unsigned char *)ctx->d_images[s]);
-        else if (src->resize)   /* cut by count and by bytes; gather_images packs with per-image offsets (bytes carries C) */
-            m = resize_chunk(ctx, src, first, n, slot_bytes, (const unsigned char *)ctx->d_images[s]);
-        else
-            m = (n - first < ctx->max_batch) ? n - first : ctx->max_batch;
+        /* The chunk, and the device source it becomes once slot s is up.  Images of the model's size: max_batch of them, one
+         * gather job per image.  The planned kinds: cut by count and by bytes, one gather job per distinct source, and the
+         * device reads the plan's items. */
+        struct ingest_src dev = *src;
+        dev.on_device = 1;
+        m = (n - first < ctx->max_batch) ? n - first : ctx->max_batch;
+        size_t up = (size_t)m * bytes;
+        int jobs = m;
+        switch (src->kind) {
+        case INGEST_F32:
+            dev.host_f32 = NULL;
+            dev.f32 = ctx->d_images[s];
+            break;
+        case INGEST_U8:
+            dev.u8 = (const unsigned char *)ctx->d_images[s];
+            break;
+        default:
+            m = ingest_plan_chunk(plan, src, first, n, (const unsigned char *)ctx->d_images[s]);
+            up = plan->bytes;
+            jobs = plan->n_src;
+            dev.items = plan->items;
+        }
         if (m <= 0) {
             rc = vh_set_error(1, "forward: an image does not fit a staging slot");
             goto fail;
         }
-        const size_t up = src->boxes ? src->chunk->bytes : src->resize ? src->packed[m] : (size_t)m * bytes;
         /* slot s was last used by chunk k-2, whose outputs were waited for below */
-        gather_images(ctx->h_images[s], src, first, src->boxes ? src->chunk->n_src : m, src->resize ? (size_t)c->in_chans : bytes);
+        gather_images(ctx->h_images[s], src, plan, first, jobs, bytes);
         if (k >= 2)
             TRY(vh_stream_wait_event(ctx->copy_stream, ctx->comp_done[s]));
         TRY(vh_h2d(ctx->d_images[s], ctx->h_images[s], up, ctx->copy_stream));
         TRY(vh_event_record(ctx->up_done[s], ctx->copy_stream));
 
         TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
-        const struct pixel_src dev = {src->u8 || src->resize ? NULL : ctx->d_images[s],
-                                      src->u8 ? (const unsigned char *)ctx->d_images[s] : NULL, src->layout, src->norm,
-                                      src->boxes ? src->chunk->staged : src->resize ? src->staged : NULL, src->rc,
-                                      src->boxes ? src->chunk->boxes : NULL, src->filter, src->boxes ? src->chunk->origin : NULL};
         TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
@@ -2337,8 +1895,8 @@ static int forward_host_images(vit_hip_ctx *ctx, const ImageData *images, int n,
         if (!images[i].data || images[i].c != c->in_chans || images[i].h != c->img_size ||
             images[i].w != c->img_size)
             return 5;
-    const struct host_src src = {images, NULL, 0, NULL};
-    return forward_pipelined(ctx, &src, n, logits, probs, form);
+    const struct ingest_src src = {.kind = INGEST_F32, .host_f32 = images};
+    return forward_pipelined(ctx, &src, NULL, n, logits, probs, form);
 }
 
 int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs)
@@ -2346,65 +1904,42 @@ int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *log
     return forward_host_images(ctx, images, n, logits, probs, FEAT_HOST);
 }
 
+/* A public host-form forward of 8-bit images: the checks, the call's one scratch allocation where chunks are planned */
+static int forward_host_u8(vit_hip_ctx *ctx, const char *who, const struct ingest_src *src, int n, float *logits, float **probs)
+{
+    if (source_check(who, ctx, src, n))
+        return 1;
+    struct ingest_plan *plan = NULL;
+    if (src->kind != INGEST_U8) {
+        const struct ingest_model model = model_of(ctx);
+        if (!(plan = ingest_plan_new(&model, src->kind)))
+            return ingest_refuse(who, "out of host memory");
+    }
+    const int rc = forward_pipelined(ctx, src, plan, n, logits, probs, FEAT_HOST);
+    ingest_plan_free(plan);
+    return rc;
+}
+
 int vit_hip_forward_u8(vit_hip_ctx *ctx, const unsigned char *images, int n, int layout,
                        const vit_pixel_norm *norm, float *logits, float **probs)
 {
-    if (u8_args("vit_hip_forward_u8", ctx, images, n, layout, norm, 0))
-        return 1;
-    const struct host_src src = {NULL, images, layout, norm};
-    return forward_pipelined(ctx, &src, n, logits, probs, FEAT_HOST);
+    const struct ingest_src src = {.kind = INGEST_U8, .u8 = images, .layout = layout, .norm = norm};
+    return forward_host_u8(ctx, "vit_hip_forward_u8", &src, n, logits, probs);
 }
 
 int vit_hip_forward_u8_resized(vit_hip_ctx *ctx, const vit_image_u8 *images, int n, int layout, const vit_resize_crop *rc,
                                const vit_pixel_norm *norm, float *logits, float **probs)
 {
-    const size_t slot_bytes = ctx ? image_slot_bytes(ctx) : 0;
-    if (resize_args("vit_hip_forward_u8_resized", ctx, images, n, layout, rc, norm, 1, NULL, 0, 0, slot_bytes))
-        return 1;
-    size_t *packed = malloc(((size_t)ctx->max_batch + 1) * sizeof(*packed));
-    vit_image_u8 *staged = malloc((size_t)ctx->max_batch * sizeof(*staged));
-    int rc_ = 1;
-    if (packed && staged) {
-        const struct host_src src = {NULL, NULL, layout, norm, images, rc, packed, staged};
-        rc_ = forward_pipelined(ctx, &src, n, logits, probs, FEAT_HOST);
-    } else {
-        vh_set_error(1, "vit_hip_forward_u8_resized: out of host memory");
-    }
-    free(packed);
-    free(staged);
-    return rc_;
+    const struct ingest_src src = {.kind = INGEST_U8_RESIZED, .images = images, .rc = rc, .layout = layout, .norm = norm};
+    return forward_host_u8(ctx, "vit_hip_forward_u8_resized", &src, n, logits, probs);
 }
 
 int vit_hip_forward_u8_boxes(vit_hip_ctx *ctx, const vit_image_u8 *images, int n_images, const vit_box_u8 *boxes, int n, int layout,
                              int filter, const vit_pixel_norm *norm, float *logits, float **probs)
 {
-    const size_t slot_bytes = ctx ? image_slot_bytes(ctx) : 0;
-    if (box_args("vit_hip_forward_u8_boxes", ctx, images, n_images, boxes, n, layout, filter, norm, 1, NULL, 0, 0, slot_bytes))
-        return 1;
-    const size_t mb = (size_t)ctx->max_batch;
-    struct box_chunk ch = {0};
-    ch.src_image = malloc(mb * sizeof(*ch.src_image));
-    ch.src_rows = malloc(mb * sizeof(*ch.src_rows));
-    ch.src_off = malloc(mb * sizeof(*ch.src_off));
-    ch.rowmap = malloc(mb * ROWMAP_BYTES);
-    ch.staged = malloc(mb * sizeof(*ch.staged));
-    ch.origin = malloc(mb * sizeof(*ch.origin));
-    ch.boxes = malloc(mb * sizeof(*ch.boxes));
-    int rc_ = 1;
-    if (ch.src_image && ch.src_rows && ch.src_off && ch.rowmap && ch.staged && ch.origin && ch.boxes) {
-        const struct host_src src = {NULL, NULL, layout, norm, images, NULL, NULL, NULL, boxes, filter, &ch};
-        rc_ = forward_pipelined(ctx, &src, n, logits, probs, FEAT_HOST);
-    } else {
-        vh_set_error(1, "vit_hip_forward_u8_boxes: out of host memory");
-    }
-    free(ch.src_image);
-    free(ch.src_rows);
-    free(ch.src_off);
-    free(ch.rowmap);
-    free(ch.staged);
-    free(ch.origin);
-    free(ch.boxes);
-    return rc_;
+    const struct ingest_src src = {.kind = INGEST_U8_BOXES, .images = images, .n_images = n_images, .boxes = boxes, .filter = filter,
+                                   .layout = layout, .norm = norm};
+    return forward_host_u8(ctx, "vit_hip_forward_u8_boxes", &src, n, logits, probs);
 }
 
 /* ---- several GPUs behind one call -------------------------------------------------

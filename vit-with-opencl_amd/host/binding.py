@@ -708,6 +708,16 @@ class ViTHip:
         check(self.L.vit_hip_forward(self.ctx, image_array(images), n, fptr(logits), rows), "vit_hip_forward")
         return logits, probs
 
+    def _u8_outputs(self, mean, std, n: int, logits: bool, probs: bool):
+        """What the host 8-bit forwards share: the PixelNorm (`mean` may already be one), and for n images the logits and
+        probabilities arrays (None where not asked for) with their ctypes arguments."""
+        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
+        nc = self.cfg.num_classes
+        out_l = np.empty((n, nc), dtype=np.float32) if logits else None
+        out_p = np.empty((n, nc), dtype=np.float32) if probs else None
+        rows = (f32p * n)(*[fptr(out_p[i]) for i in range(n)]) if probs else None
+        return norm, out_l, out_p, fptr(out_l) if logits else None, rows
+
     def forward_u8(self, images: np.ndarray, mean, std, layout: str = "hwc", logits: bool = True, probs: bool = True):
         """Host 8-bit path: [n][H][W][C] (layout "hwc") or [n][C][H][W] ("chw") uint8, normalised on the GPU with
         pixel_norm(mean, std) -> (logits[n][classes], probs[n][classes]); logits=False / probs=False pass NULL and return
@@ -718,13 +728,9 @@ class ViTHip:
         want = (n, S, S, Ch) if layout == "hwc" else (n, Ch, S, S)
         if images.shape != want:
             raise ValueError(f"forward_u8: images of shape {images.shape}, the context's config takes {want} ({layout})")
-        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
-        nc = cfg.num_classes
-        out_l = np.empty((n, nc), dtype=np.float32) if logits else None
-        out_p = np.empty((n, nc), dtype=np.float32) if probs else None
-        rows = (f32p * n)(*[fptr(out_p[i]) for i in range(n)]) if probs else None
+        norm, out_l, out_p, lp, rows = self._u8_outputs(mean, std, n, logits, probs)
         check(self.L.vit_hip_forward_u8(self.ctx, images.ctypes.data_as(C.POINTER(C.c_ubyte)), n, PIXEL_LAYOUTS[layout],
-                                        C.byref(norm), fptr(out_l) if logits else None, rows), "vit_hip_forward_u8")
+                                        C.byref(norm), lp, rows), "vit_hip_forward_u8")
         return out_l, out_p
 
     def forward_device_u8(self, d_images, n: int, norm: PixelNorm, layout: str = "hwc", d_logits=None, d_probs=None,
@@ -738,15 +744,12 @@ class ViTHip:
         """Host 8-bit images of any size (a list of [h][w][C] or [C][h][w] uint8 arrays), resized (shorter side to
         resize_short) and centre-cropped on the GPU exactly as Pillow + torchvision's CenterCrop, normalised with
         pixel_norm(mean, std) (or a PixelNorm as `mean`) -> (logits, probs) as forward_u8."""
-        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
+        n = len(images)
+        norm, out_l, out_p, lp, rows = self._u8_outputs(mean, std, n, logits, probs)
         descs, keep = host_image_descs(images, layout)
-        n, nc = len(images), self.cfg.num_classes
-        out_l = np.empty((n, nc), dtype=np.float32) if logits else None
-        out_p = np.empty((n, nc), dtype=np.float32) if probs else None
-        rows = (f32p * n)(*[fptr(out_p[i]) for i in range(n)]) if probs else None
         rc = resize_crop(resize_short, filter)
-        check(self.L.vit_hip_forward_u8_resized(self.ctx, descs, n, PIXEL_LAYOUTS[layout], C.byref(rc), C.byref(norm),
-                                                fptr(out_l) if logits else None, rows), "vit_hip_forward_u8_resized")
+        check(self.L.vit_hip_forward_u8_resized(self.ctx, descs, n, PIXEL_LAYOUTS[layout], C.byref(rc), C.byref(norm), lp, rows),
+              "vit_hip_forward_u8_resized")
         del keep
         return out_l, out_p
 
@@ -769,15 +772,11 @@ class ViTHip:
         """Regions of host 8-bit images: images as forward_u8_resized takes them, boxes a list of (image index, (left, top,
         right, bottom)); every box is resized to img x img on the GPU exactly as Pillow's Image.resize(box=), normalised
         with pixel_norm(mean, std) (or a PixelNorm as `mean`) -> (logits, probs) in box order, as forward_u8."""
-        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
+        n = len(boxes)
+        norm, out_l, out_p, lp, rows = self._u8_outputs(mean, std, n, logits, probs)
         descs, keep = host_image_descs(images, layout)
-        n, nc = len(boxes), self.cfg.num_classes
-        out_l = np.empty((n, nc), dtype=np.float32) if logits else None
-        out_p = np.empty((n, nc), dtype=np.float32) if probs else None
-        rows = (f32p * n)(*[fptr(out_p[i]) for i in range(n)]) if probs else None
         check(self.L.vit_hip_forward_u8_boxes(self.ctx, descs, len(images), box_array(boxes), n, PIXEL_LAYOUTS[layout],
-                                              RESIZE_FILTERS[filter], C.byref(norm), fptr(out_l) if logits else None, rows),
-              "vit_hip_forward_u8_boxes")
+                                              RESIZE_FILTERS[filter], C.byref(norm), lp, rows), "vit_hip_forward_u8_boxes")
         del keep
         return out_l, out_p
 
