@@ -19,12 +19,17 @@
  * csrc/vit_ingest.c: the argument checks, the fill of the resize kernel's descriptors, and the planner and packer of the host
  * forms' staging slots.  This file keeps the descriptor ring, the launches and the pipeline over the staging slots.
  *
+ * What a context will run -- the kernels of a forward, the layout of the weight slabs, the size of every arena buffer -- is one
+ * struct vit_plan (csrc/vit_plan.h), made by plan_make before anything is allocated; this file allocates what it says and
+ * branches on its fields.
+ *
  * Operator order per layer (ViT_seq.c:330-370):
  *   y = LN1(x); qkv = y Win^T + bin; a = attention(qkv); x = x + (a Wout^T + bout);
  *   y = LN2(x); h = gelu(y W1^T + b1); x = x + (h W2^T + b2)
  */
 #include "ViT_opencl.h"
 #include "vit_ingest.h"
+#include "vit_plan.h"
 
 #include <math.h>
 #include <pthread.h>
@@ -43,33 +48,6 @@
             goto fail;            \
         }                         \
     } while (0)
-
-/* The mode's GEMM-operand copy of one of the four big matrices of a layer (in_proj, out_proj, fc1, fc2) */
-struct operand
-{
-    void *w;             /* three-part planes (F32; NULL for shapes the planes cannot take), one-part planes (BF16_GEMM),
-                          * two fp16 parts (F32_FP16X2) or MX e4m3 values (FP8_GEMM) */
-    void *scales;        /* FP8_GEMM: the e8m0 block scales of w */
-    float pair_scale;    /* F32_FP16X2: the power of two the fp16 parts were scaled by */
-    /* ln_fold, in_proj and fc1 only (csrc/norm_fold.h): w holds the gamma-scaled matrix; colsum [N] of its rounded values
-     * and the folded bias [N] */
-    float *colsum, *bias_folded;
-};
-
-/* The weight slabs, one device allocation each, in the order a planes file stores them */
-enum { SLAB_F32, SLAB_OPERAND, SLAB_CONV, SLAB_FOLD, N_SLABS };
-
-/* How the planes paths (F32 on planes, BF16_GEMM, FP8_GEMM) run attention: Q|K|V as one-part fp16 planes into a resident
- * kernel -- head_dim 64, or head_dim 80 (ViT-H/14, reduced modes only) which writes the output projection's operand
- * itself -- or fp32 rows through the streaming kernel (T <= 512).  ATTN_LONG: Q|K|V as the mode's planes into the
- * flash-style kernel (csrc/attention_long.hip; any T, head_dim 64 or 80), fp32 rows out into the idle MLP buffer, then
- * rounded / split like the streaming kernel's -- every T > 512, and any T under $VIT_HIP_ATTN=long */
-enum { ATTN_STREAMING, ATTN_HD64, ATTN_HD80, ATTN_LONG };
-
-/* the largest T the streaming kernel (attention_tiled.hip) takes; beyond it only ATTN_LONG runs */
-enum { STREAMING_MAX_TOKENS = 512 };
-
-enum { MAX_DEPTH = 256, MAX_TENSORS = 4 + 12 * MAX_DEPTH + 4 };
 
 /* resize + crop: descriptor slots in flight */
 enum { DESC_RING = 8 };
@@ -90,35 +68,26 @@ struct vit_hip_ctx
     vit_config cfg;
     int device;
     int max_batch;
-    int tokens;
     int n_tensors;
     vh_stream_t stream;
 
-    /* the plan: everything a forward branches on, fixed by ctx_new before anything is allocated */
-    int precision;      /* VIT_PRECISION_* */
-    int ln_fold;        /* every LayerNorm but the final one folded into the projection behind it (csrc/norm_fold.h) */
-    int use_p3;         /* F32: GEMM inputs travel as three-part bf16 planes (y, attn, hid hold 6 bytes per value) */
-    int cls_only_last;  /* use_p3: the last layer's output projection and MLP run on the class-token rows only */
-    int attn_form;      /* ATTN_*, for the planes paths */
-    int fp32_native;    /* $VIT_HIP_GEMM_FP32=native: F32 on fp32 rows, with the fp32 matrix instruction in the patch embedding, the
-                         * attention and every projection without pre-split weights (VH_FP32_NATIVE, VH_ATTN_NATIVE) */
-    int attn_rows_streaming;   /* $VIT_HIP_ATTN=tiled: attention that reads fp32 rows takes the streaming kernel at every shape */
+    /* everything a forward, the weight layout or the arena branches on, and every size, fixed at creation before anything is
+     * allocated (csrc/vit_plan.h) */
+    struct vit_plan plan;
 
-    void *slab[N_SLABS];
-    size_t slab_bytes[N_SLABS];
-    float **w;          /* SLAB_F32: device pointer per tensor index, every tensor in fp32 */
+    void *slab[N_SLABS];   /* of plan.slab_bytes */
+    float **w;         /* SLAB_F32: device pointer per tensor index, every tensor in fp32 */
     struct operand *op; /* SLAB_OPERAND and SLAB_FOLD: [depth][4] (in_proj, out_proj, fc1, fc2) */
     /* SLAB_CONV: conv_proj as planes [Kp/32][parts][E][32]: one part (bf16) for BF16_GEMM / FP8_GEMM
      * (vh_launch_patch_embed_planes), the exact three-part split for F32 (vh_launch_patch_embed_planes3) */
 
-    /* activation arena (rows = max_batch * tokens) */
+    /* activation arena (rows = max_batch * tokens), of the plan's sizes */
     float *x;           /* residual stream      [rows][E]   */
     float *y;           /* LayerNorm output     [rows][E]   */
     float *attn;        /* attention output     [rows][E]   */
     float *qkv;         /* fused Q|K|V          [rows][3E]  */
-    float *hid;         /* MLP hidden           [rows][F]   */
-    size_t ws_bytes;    /* size of hid, which doubles as the patch-gather workspace */
-    float *stats;       /* ln_fold: partial (sum, sum of squares) of the residual rows, [E/128][rows][2] */
+    float *hid;         /* MLP hidden           [rows][F]; plan.ws_bytes: it doubles as the workspace of whatever runs while the MLP is idle */
+    float *stats;      /* ln_fold: partial (sum, sum of squares) of the residual rows, [E/128][rows][2] */
     float *cls;         /* normalised CLS rows  [max_batch][E] */
     float *d_logits;    /* [max_batch][classes] */
     float *d_probs;     /* [max_batch][classes] */
@@ -131,10 +100,9 @@ struct vit_hip_ctx
     vh_stream_t copy_stream;
     vh_event_t up_done[2], comp_done[2], out_done[2];
 
-    /* resize + centre crop (vit_hip_resize_crop_u8, the _resized forwards): the crops land in Q|K|V at crop_off (behind
+    /* resize + centre crop (vit_hip_resize_crop_u8, the _resized forwards): the crops land in Q|K|V at plan.crop_off (behind
      * the fp32 expansion on the fp32-rows paths), the coefficient tables in hid.  Per-call descriptors go up through a ring
      * of pinned slots; a slot is refilled only once the event behind its last reader has completed. */
-    size_t crop_off;
     vh_resize_desc *h_desc[DESC_RING];
     vh_resize_desc *d_desc[DESC_RING];
     vh_event_t desc_done[DESC_RING];
@@ -324,63 +292,17 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     free(ctx);
 }
 
-static const int BIG[4] = {2, 4, 8, 10};   /* in_proj, out_proj, fc1, fc2 weights within a layer's 12 tensors */
-
 /* a layer's 12 fp32 tensors: ln1 w,b; in w,b; out w,b; ln2 w,b; fc1 w,b; fc2 w,b */
 static float **layer_tensors(const vit_hip_ctx *ctx, int l) { return ctx->w + 4 + 12 * l; }
 
-/* the tensor index of operand m = 4 * layer + (0 in_proj, 1 out_proj, 2 fc1, 3 fc2) */
-static int operand_tensor(int m) { return 4 + 12 * (m / 4) + BIG[m % 4]; }
-
-/* The next 256-byte aligned piece of a slab: its address once the slab exists, NULL while only sizing. */
-static void *place(void *slab, size_t *off, size_t bytes)
-{
-    void *p = slab ? (char *)slab + *off : NULL;
-    *off += align_up(bytes, 256);
-    return p;
-}
-
-/* Every tensor's place in the four weight slabs, from (cfg, precision, ln_fold) alone, so a planes file written by one
- * context (vit_hip_export_planes) drops into another's slabs byte for byte.  Called before the slabs exist it only sums
- * their sizes into bytes[] (vit_hip_create_from_planes checks a file's header against them BEFORE anything is
- * allocated); called again once they are allocated, it points ctx->w and ctx->op into them. */
-static void layout_weights(vit_hip_ctx *ctx, size_t bytes[N_SLABS])
-{
-    const vit_config *cfg = &ctx->cfg;
-    const int p = ctx->precision;
-    const int f32_planes = p == VIT_PRECISION_F32 && cfg->embed_dim % 128 == 0 && cfg->mlp_hidden % 128 == 0;
-    /* bytes per weight of the operand copies; FP8_GEMM adds one e8m0 scale per 32 values */
-    const size_t per = p == VIT_PRECISION_BF16_GEMM ? 2 : p == VIT_PRECISION_FP8_GEMM ? 1 : p == VIT_PRECISION_F32_FP16X2 ? 4
-                     : f32_planes ? 6 : 0;
-    const size_t conv_parts = (p == VIT_PRECISION_BF16_GEMM || p == VIT_PRECISION_FP8_GEMM) ? 1 : f32_planes ? 3 : 0;
-    size_t off[N_SLABS] = {0};
-    for (int i = 0; i < ctx->n_tensors; ++i)
-        ctx->w[i] = (float *)place(ctx->slab[SLAB_F32], &off[SLAB_F32], vit_config_tensor_size(cfg, i) * sizeof(float));
-    for (int m = 0; m < 4 * cfg->depth; ++m) {
-        struct operand *o = &ctx->op[m];
-        const size_t cnt = vit_config_tensor_size(cfg, operand_tensor(m));
-        o->w = place(ctx->slab[SLAB_OPERAND], &off[SLAB_OPERAND], cnt * per);
-        if (p == VIT_PRECISION_FP8_GEMM)
-            o->scales = place(ctx->slab[SLAB_OPERAND], &off[SLAB_OPERAND], cnt / 32);
-    }
-    place(ctx->slab[SLAB_CONV], &off[SLAB_CONV],   /* E % 128 == 0 wherever there are parts: already 256-byte aligned */
-          (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * (size_t)cfg->embed_dim * 2 * conv_parts);
-    for (int m = 0; ctx->ln_fold && m < 4 * cfg->depth; m += 2) {   /* in_proj and fc1: one float per output feature each */
-        const size_t nb = vit_config_tensor_size(cfg, operand_tensor(m) + 1) * sizeof(float);
-        ctx->op[m].colsum = (float *)place(ctx->slab[SLAB_FOLD], &off[SLAB_FOLD], nb);
-        ctx->op[m].bias_folded = (float *)place(ctx->slab[SLAB_FOLD], &off[SLAB_FOLD], nb);
-    }
-    memcpy(bytes, off, sizeof(off));
-}
-
+/* The weight slabs of the plan's sizes, and every tensor and operand pointed into them */
 static int alloc_weights(vit_hip_ctx *ctx)
 {
     int rc = 0;
-    layout_weights(ctx, ctx->slab_bytes);
     for (int i = 0; i < N_SLABS; ++i)
-        if (ctx->slab_bytes[i])
-            TRY(vh_malloc(&ctx->slab[i], ctx->slab_bytes[i]));
-    layout_weights(ctx, ctx->slab_bytes);
+        if (ctx->plan.slab_bytes[i])
+            TRY(vh_malloc(&ctx->slab[i], ctx->plan.slab_bytes[i]));
+    plan_layout(&ctx->plan, &ctx->cfg, ctx->slab, ctx->w, ctx->op, NULL);
     return 0;
 fail:
     return rc;
@@ -391,18 +313,18 @@ static int fill_weights(vit_hip_ctx *ctx, const Network *networks)
 {
     int rc = 0;
     const vit_config *cfg = &ctx->cfg;
-    const int p = ctx->precision;
+    const int p = ctx->plan.precision;
     float *d_amax = NULL, *d_scaled = NULL;
     for (int i = 0; i < ctx->n_tensors; ++i)
         TRY(vh_h2d(ctx->w[i], networks[i].data, networks[i].size * sizeof(float), ctx->stream));
     if (p == VIT_PRECISION_F32_FP16X2)
         TRY(vh_malloc((void **)&d_amax, sizeof(float)));
-    if (ctx->ln_fold)   /* gamma-scaled copy of one matrix at a time, before its rounding (the largest is fc1 / in_proj) */
+    if (ctx->plan.ln_fold)   /* gamma-scaled copy of one matrix at a time, before its rounding (the largest is fc1 / in_proj) */
         TRY(vh_malloc((void **)&d_scaled, (size_t)cfg->embed_dim * (size_t)(cfg->mlp_hidden > 3 * cfg->embed_dim ? cfg->mlp_hidden : 3 * cfg->embed_dim) * sizeof(float)));
     for (int m = 0; m < 4 * cfg->depth; ++m) {
         struct operand *o = &ctx->op[m];
         float **lw = layer_tensors(ctx, m / 4);
-        const int idx = operand_tensor(m), k = m % 4, fold = o->colsum != NULL;
+        const int idx = plan_operand_tensor(m), k = m % 4, fold = o->colsum != NULL;
         const int out_f = (int)networks[idx + 1].size, in_f = (int)(networks[idx].size / networks[idx + 1].size);
         const float *src = ctx->w[idx];
         if (fold) {
@@ -453,7 +375,7 @@ static int fill_weights(vit_hip_ctx *ctx, const Network *networks)
         TRY(vh_stream_sync(ctx->stream));   /* the scratch copy is freed below */
     if (ctx->slab[SLAB_CONV])
         TRY(vh_launch_conv_weight_planes_parts(ctx->stream, ctx->w[1], ctx->slab[SLAB_CONV], cfg->embed_dim, cfg->in_chans,
-                                               cfg->patch_size, p == VIT_PRECISION_F32 ? 3 : 1));
+                                               cfg->patch_size, ctx->plan.conv_parts));
 fail:
     if (d_amax)
         vh_free(d_amax);
@@ -464,122 +386,40 @@ fail:
 
 static int alloc_arena(vit_hip_ctx *ctx);
 
-/* $VIT_HIP_PRECISION: F32 unless asked otherwise: "bf16" -> BF16_GEMM, "fp16x2" -> F32_FP16X2, "fp8" -> FP8_GEMM */
-static int env_precision(void)
-{
-    const char *env = getenv("VIT_HIP_PRECISION");
-    return (env && env[0] == 'b') ? VIT_PRECISION_BF16_GEMM
-         : (env && strncmp(env, "fp16x2", 6) == 0) ? VIT_PRECISION_F32_FP16X2
-         : (env && strncmp(env, "fp8", 3) == 0) ? VIT_PRECISION_FP8_GEMM : VIT_PRECISION_F32;
-}
-
+/* $VIT_HIP_PRECISION picks the precision (plan_env_read) */
 int vit_hip_create(vit_hip_ctx **out, const vit_config *cfg, const Network *networks,
                    int n_tensors, int device, int max_batch)
 {
-    return vit_hip_create_ex(out, cfg, networks, n_tensors, device, max_batch, env_precision());
+    struct plan_env env;
+    plan_env_read(&env);
+    return vit_hip_create_ex(out, cfg, networks, n_tensors, device, max_batch, env.precision);
 }
 
-int vit_hip_precision(const vit_hip_ctx *ctx) { return ctx->precision; }
-int vit_hip_ln_fold(const vit_hip_ctx *ctx) { return ctx ? ctx->ln_fold : 0; }
+int vit_hip_precision(const vit_hip_ctx *ctx) { return ctx->plan.precision; }
+int vit_hip_ln_fold(const vit_hip_ctx *ctx) { return ctx ? ctx->plan.ln_fold : 0; }
 
-/* Argument checks shared by both ways of making a context, the plan of its forward pass, and the empty context itself.
- * ln_fold < 0: decide the fold here ($VIT_HIP_LN_FOLD, vit_hip_create_ex); 0 or 1: a planes file's header fixed it, and a
- * fold this context cannot run is refused like any other bad header.  Nothing is allocated on the device. */
+/* Both ways of making a context: the argument checks and the plan of its forward pass (plan_make, under the environment's
+ * switches), and the empty context itself.  ln_fold < 0: the plan decides the fold (vit_hip_create_ex); 0 or 1: a planes
+ * file's header fixed it.  Nothing is allocated on the device. */
 static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int device, int max_batch, int precision, int ln_fold)
 {
+    struct plan_env env;
+    struct vit_plan plan;
     if (!out)
         return 1;
     *out = NULL;
-    if (!cfg || max_batch <= 0)
-        return 1;
-    if (precision != VIT_PRECISION_F32 && precision != VIT_PRECISION_BF16_GEMM && precision != VIT_PRECISION_FP8_GEMM &&
-        precision != VIT_PRECISION_F32_FP16X2)
-        return 1;
-    if (precision == VIT_PRECISION_F32_FP16X2 && (cfg->embed_dim % 128 != 0 || cfg->mlp_hidden % 128 != 0))
-        return 2;
-    if (precision == VIT_PRECISION_FP8_GEMM && (cfg->embed_dim % 256 != 0 || cfg->mlp_hidden % 256 != 0))
-        return 2;
-    if (precision == VIT_PRECISION_BF16_GEMM && (cfg->embed_dim % 128 != 0 || cfg->mlp_hidden % 128 != 0))
-        return 2;
-    if (cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->num_heads <= 0 || cfg->patch_size <= 0 || cfg->img_size <= 0 ||
-        cfg->in_chans <= 0 || cfg->num_classes <= 0 || cfg->mlp_hidden <= 0)
-        return 2;
-    /* sane sizes: what a context may be asked to allocate is bounded whatever a caller or a file header says */
-    if (cfg->depth > MAX_DEPTH || cfg->embed_dim > 16384 || cfg->mlp_hidden > 65536 || cfg->img_size > 4096 || cfg->in_chans > 64 ||
-        cfg->num_classes > (1 << 20) || cfg->num_heads > 1024 || max_batch > (1 << 20))
-        return 2;
-    if (n_tensors != vit_config_num_tensors(cfg))
-        return 2;
-    if (cfg->embed_dim % cfg->num_heads != 0 || cfg->img_size % cfg->patch_size != 0)
-        return 2;
-
-    const int E = cfg->embed_dim, F = cfg->mlp_hidden, H = cfg->num_heads, T = vit_config_tokens(cfg);
-    const int reduced = precision == VIT_PRECISION_BF16_GEMM || precision == VIT_PRECISION_FP8_GEMM;
-    /* F32 by default writes every GEMM input as the exact three-part bf16 split (csrc/gemm_p3.hip), 6 bytes per value;
-     * $VIT_HIP_P3=0 keeps fp32 activations and the in-loop split (csrc/gemm_mfma.hip), $VIT_HIP_GEMM_FP32=native the fp32
-     * matrix instruction */
-    const char *env_p3 = getenv("VIT_HIP_P3"), *env_native = getenv("VIT_HIP_GEMM_FP32");
-    const int fp32_native = env_native && env_native[0] == 'n';
-    const int planes_wanted = !(env_p3 && env_p3[0] == '0') && !fp32_native;
-    const int use_p3 = precision == VIT_PRECISION_F32 && E % 128 == 0 && F % 128 == 0 && planes_wanted &&
-                       (size_t)max_batch * (size_t)T * 64 <= 0xffffffffull;
-    /* the fold's row terms take at most 16 partial sums per row (row_norm_terms); on F32 it needs the planes path */
-    const int fold_fits = E % 128 == 0 && E / 128 <= 16 && (reduced || (precision == VIT_PRECISION_F32 && F % 128 == 0));
-    if (ln_fold < 0) {
-        /* the reduced modes fold unless $VIT_HIP_LN_FOLD=0 (the separate LayerNorm launches of rounds 1-3: the A/B of tests
-         * and bench).  On F32 the fold is a LAB VARIANT, off unless $VIT_HIP_LN_FOLD=1: the same fold on the exact
-         * three-part planes keeps the 1e-4 parity on the goldens, but puts it behind the x - mean cancellation for ~1 %
-         * (docs/LABBOOK.md R4.6). */
-        const char *env = getenv("VIT_HIP_LN_FOLD");
-        ln_fold = fold_fits && (reduced ? !(env && env[0] == '0') : env && env[0] == '1' && planes_wanted);
-    }
-    if (ln_fold && (!fold_fits || (precision == VIT_PRECISION_F32 && !use_p3)))
-        return vh_set_error(2, "vit_hip_create: this shape, precision and batch cannot fold the LayerNorms (the fp32 path "
-                               "needs the planes path)");
-    /* the planes path's LayerNorms write three parts per value through an LDS image that ends at embed_dim 1696
-     * (vh_layer_norm_planes_max_embed, csrc/rowops.hip); the lab fold launches none of them */
-    if (use_p3 && !ln_fold && E > vh_layer_norm_planes_max_embed(3)) {
-        char msg[320];
-        snprintf(msg, sizeof msg, "vit_hip_create: embed_dim=%d: the fp32 planes path's LayerNorm (three-part planes, 96 bytes of "
-                 "LDS per column) takes a LayerNorm width of at most %d",
-                 E, vh_layer_norm_planes_max_embed(3));
-        return vh_set_error(2, msg);
-    }
-    const char *env_ll = getenv("VIT_HIP_LAST_LAYER");
-    /* attention: ATTN_LONG is the only kernel past STREAMING_MAX_TOKENS, and it reads the planes paths' Q|K|V with head_dim
-     * 64 or 80; $VIT_HIP_ATTN=long forces it at any T (tests, A/B), $VIT_HIP_ATTN=tiled the streaming kernel wherever
-     * attention reads fp32 rows (the planes paths' resident kernels are not rows kernels and stay).  Shapes no kernel runs are
-     * refused here, not at every forward. */
-    const char *env_attn = getenv("VIT_HIP_ATTN");
-    const int long_hd = E == 64 * H || E == 80 * H;
-    const int long_wanted = T > STREAMING_MAX_TOKENS || (env_attn && strcmp(env_attn, "long") == 0);
-    if (T > STREAMING_MAX_TOKENS && (precision == VIT_PRECISION_F32_FP16X2 || (precision == VIT_PRECISION_F32 && !use_p3) || !long_hd)) {
-        char msg[320];
-        snprintf(msg, sizeof msg, "vit_hip_create: %d tokens: above %d tokens attention runs on the planes paths (F32 with "
-                 "embed_dim and mlp_hidden multiples of 128 and neither $VIT_HIP_P3=0 nor $VIT_HIP_GEMM_FP32=native, BF16_GEMM, "
-                 "FP8_GEMM; not F32_FP16X2) with head_dim 64 or 80 (precision %d, head_dim %d)",
-                 T, STREAMING_MAX_TOKENS, precision, E / H);
-        return vh_set_error(2, msg);
-    }
-
+    plan_env_read(&env);
+    const int rc = plan_make(&plan, cfg, n_tensors, max_batch, precision, ln_fold, &env);
+    if (rc != 0)
+        return rc;
     vit_hip_ctx *ctx = (vit_hip_ctx *)calloc(1, sizeof(*ctx));
     if (!ctx)
         return 4;
     ctx->cfg = *cfg;
     ctx->device = device;
     ctx->max_batch = max_batch;
-    ctx->tokens = T;
     ctx->n_tensors = n_tensors;
-    ctx->precision = precision;
-    ctx->ln_fold = ln_fold ? 1 : 0;
-    ctx->use_p3 = use_p3;
-    ctx->cls_only_last = use_p3 && !ln_fold && env_ll && strcmp(env_ll, "cls") == 0;
-    ctx->attn_form = !(use_p3 || reduced) ? ATTN_STREAMING
-              : (long_wanted && long_hd) ? ATTN_LONG
-              : (E == 64 * H && T <= 208) ? ATTN_HD64
-              : (reduced && E == 80 * H && T <= 272) ? ATTN_HD80 : ATTN_STREAMING;
-    ctx->fp32_native = fp32_native;
-    ctx->attn_rows_streaming = env_attn && env_attn[0] == 't';
+    ctx->plan = plan;
     ctx->w = (float **)calloc((size_t)n_tensors, sizeof(float *));
     ctx->op = (struct operand *)calloc((size_t)4 * cfg->depth, sizeof(struct operand));
     if (!ctx->w || !ctx->op) {
@@ -631,7 +471,7 @@ fail:
  * reference's order, 256-byte aligned) followed by the mode's operand slab for the four big matrices of every layer
  * (three-part bf16 planes, one-part planes, two fp16 parts, or MX values + scales: csrc/gemm_p3.hip, gemm_mx.hip), the
  * conv_proj planes and, with ln_fold, the fold terms -- behind a header that pins model shape and precision.  Every
- * slab's layout follows from (config, precision, ln_fold) alone (layout_weights), so vit_hip_create_from_planes is one
+ * slab's layout follows from (config, precision, ln_fold) alone (plan_layout), so vit_hip_create_from_planes is one
  * read per slab into its allocation: no fp32 -> format pass, no per-tensor files (the reference's loader opens 152 of
  * them, Network.c:134-218). */
 /* Bumped whenever a repack kernel changes what it writes for the same (config, precision): the slab sizes alone would
@@ -701,7 +541,7 @@ static void pair_scales(const vit_hip_ctx *ctx, float scales[MAX_TENSORS])
 {
     memset(scales, 0, sizeof(float) * (size_t)ctx->n_tensors);
     for (int m = 0; m < 4 * ctx->cfg.depth; ++m)
-        scales[operand_tensor(m)] = ctx->op[m].pair_scale;
+        scales[plan_operand_tensor(m)] = ctx->op[m].pair_scale;
 }
 
 /* Written to `path`.tmp and renamed over `path` when complete: an interrupted export never leaves a truncated file
@@ -727,17 +567,17 @@ int vit_hip_export_planes(vit_hip_ctx *ctx, const char *path)
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, "VITPLN02", 8);
     h.header_bytes = (unsigned)sizeof(h);
-    h.precision = ctx->precision;
+    h.precision = ctx->plan.precision;
     h.n_tensors = ctx->n_tensors;
     const vit_config *c = &ctx->cfg;
     const int ints[8] = {c->img_size, c->patch_size, c->in_chans, c->num_classes, c->embed_dim, c->depth, c->num_heads, c->mlp_hidden};
     memcpy(h.cfg_ints, ints, sizeof(ints));
     h.eps = c->eps;
-    h.w_slab_bytes = ctx->slab_bytes[SLAB_F32];
-    h.planes_bytes = ctx->slab_bytes[SLAB_OPERAND];
-    h.wconv16_bytes = ctx->slab_bytes[SLAB_CONV];
-    h.fold_bytes = ctx->slab_bytes[SLAB_FOLD];
-    h.ln_fold = ctx->ln_fold;
+    h.w_slab_bytes = ctx->plan.slab_bytes[SLAB_F32];
+    h.planes_bytes = ctx->plan.slab_bytes[SLAB_OPERAND];
+    h.wconv16_bytes = ctx->plan.slab_bytes[SLAB_CONV];
+    h.fold_bytes = ctx->plan.slab_bytes[SLAB_FOLD];
+    h.ln_fold = ctx->plan.ln_fold;
     h.layout_version = VIT_PLANES_LAYOUT_VERSION;
     h.scale_floats = (unsigned long long)ctx->n_tensors;
     float scales[MAX_TENSORS];
@@ -747,7 +587,7 @@ int vit_hip_export_planes(vit_hip_ctx *ctx, const char *path)
     if (fwrite(&h, sizeof(h), 1, fp) != 1 || fwrite(scales, sizeof(float), (size_t)ctx->n_tensors, fp) != (size_t)ctx->n_tensors)
         rc = vh_set_error(120, "vit_hip_export_planes: short write");
     for (int i = 0; i < N_SLABS && rc == 0; ++i)
-        rc = copy_file_and_device(ctx, fp, ctx->slab[i], ctx->slab_bytes[i], 1, &hash);
+        rc = copy_file_and_device(ctx, fp, ctx->slab[i], ctx->plan.slab_bytes[i], 1, &hash);
     if (rc == 0) {
         h.checksum = hash;
         if (fseek(fp, 0, SEEK_SET) != 0 || fwrite(&h, sizeof(h), 1, fp) != 1)
@@ -785,15 +625,14 @@ int vit_hip_create_from_planes(vit_hip_ctx **out, const char *path, int device, 
     }
     vit_config cfg = {h.cfg_ints[0], h.cfg_ints[1], h.cfg_ints[2], h.cfg_ints[3], h.cfg_ints[4], h.cfg_ints[5], h.cfg_ints[6],
                       h.cfg_ints[7], h.eps};
-    /* ctx_new bounds every dimension, checks the fold flag and allocates only the host-side tables (n_tensors is tied to depth) */
+    /* ctx_new (plan_make) bounds every dimension, checks the fold flag and allocates only the host-side tables (n_tensors is tied to depth) */
     if (h.n_tensors <= 0 || h.n_tensors > MAX_TENSORS ||
         (rc = ctx_new(&ctx, &cfg, h.n_tensors, device, max_batch, h.precision, h.ln_fold ? 1 : 0)) != 0) {
         fclose(fp);
         return vh_set_error(rc ? rc : 2, "vit_hip_create_from_planes: the header's model shape or precision is not one this library takes");
     }
     /* the slab sizes this library derives from (shape, precision, fold) against the header's, BEFORE anything is allocated */
-    size_t sizes[N_SLABS];
-    layout_weights(ctx, sizes);
+    const size_t *sizes = ctx->plan.slab_bytes;
     if (h.w_slab_bytes != sizes[SLAB_F32] || h.planes_bytes != sizes[SLAB_OPERAND] || h.wconv16_bytes != sizes[SLAB_CONV] ||
         h.fold_bytes != sizes[SLAB_FOLD] || h.scale_floats != (unsigned long long)ctx->n_tensors) {
         rc = vh_set_error(125, "vit_hip_create_from_planes: slab sizes in the file do not match this library's layout");
@@ -806,12 +645,12 @@ int vit_hip_create_from_planes(vit_hip_ctx **out, const char *path, int device, 
     }
     unsigned long long hash = planes_hash(PLANES_HASH_SEED, scales, sizeof(float) * (size_t)ctx->n_tensors);
     for (int m = 0; m < 4 * cfg.depth; ++m)
-        ctx->op[m].pair_scale = scales[operand_tensor(m)];
+        ctx->op[m].pair_scale = scales[plan_operand_tensor(m)];
     TRY(vh_init(device));
     TRY(vh_stream_create(&ctx->stream));
     TRY(alloc_weights(ctx));
     for (int i = 0; i < N_SLABS; ++i)
-        TRY(copy_file_and_device(ctx, fp, ctx->slab[i], ctx->slab_bytes[i], 0, &hash));
+        TRY(copy_file_and_device(ctx, fp, ctx->slab[i], ctx->plan.slab_bytes[i], 0, &hash));
     if (hash != h.checksum) {
         rc = vh_set_error(126, "vit_hip_create_from_planes: payload checksum mismatch (corrupt file)");
         goto fail;
@@ -826,52 +665,22 @@ fail:
     return rc;
 }
 
-/* 1 where the patch embedding runs on planes (an im2row producer); 0 on the fp32-rows paths */
-static int planes_patch_embed(const vit_hip_ctx *ctx)
-{
-    return ctx->ln_fold || ctx->use_p3 || ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
-}
-
-/* The activation arena and the host-pointer path's staging, sized for max_batch images. */
+/* The activation arena, of the plan's sizes, and the host-pointer path's staging, sized for max_batch images. */
 static int alloc_arena(vit_hip_ctx *ctx)
 {
     int rc = 0;
     const vit_config *cfg = &ctx->cfg;
-    const int precision = ctx->precision, max_batch = ctx->max_batch;
-    const size_t E = (size_t)cfg->embed_dim, F = (size_t)cfg->mlp_hidden, NC = (size_t)cfg->num_classes;
-    const size_t rows = (size_t)max_batch * ctx->tokens;
+    const struct vit_plan *plan = &ctx->plan;
+    const int max_batch = ctx->max_batch;
+    const size_t E = (size_t)cfg->embed_dim, NC = (size_t)cfg->num_classes;
     const size_t img = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
-    const size_t act = ctx->use_p3 ? 6 : sizeof(float);   /* bytes per GEMM-input value */
-    TRY(vh_malloc((void **)&ctx->x, rows * E * sizeof(float)));
-    TRY(vh_malloc((void **)&ctx->y, rows * E * act));
-    TRY(vh_malloc((void **)&ctx->attn, rows * E * act));
-    {   /* the fp32-rows paths expand 8-bit images into Q|K|V (vit_hip_forward_device_u8): room for max_batch fp32 images, more
-         * than Q|K|V only for tiny test configs; resized crops (max_batch x img^2 x C bytes) go behind that expansion */
-        const size_t qkv_bytes = rows * 3 * E * act, expanded = planes_patch_embed(ctx) ? 0 : (size_t)max_batch * img * sizeof(float);
-        ctx->crop_off = align_up(expanded, 256);
-        const size_t crops = cfg->in_chans <= 4 ? ctx->crop_off + (size_t)max_batch * img : 0;
-        size_t bytes = qkv_bytes > expanded ? qkv_bytes : expanded;
-        bytes = bytes > crops ? bytes : crops;
-        TRY(vh_malloc((void **)&ctx->qkv, bytes));
-    }
-    {   /* patch geometries that need gathered rows (H/14) borrow the MLP hidden buffer, idle at that point */
-        size_t ws = vh_patch_embed_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->patch_size, cfg->embed_dim);
-        if (ctx->slab[SLAB_CONV]) {   /* the im2row producer's planes: patches x Kp x 2 bytes x parts (a small MLP can be smaller than that) */
-            const size_t grid = (size_t)(cfg->img_size / cfg->patch_size);
-            const size_t planes = (size_t)max_batch * grid * grid * (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * 2 *
-                                  (precision == VIT_PRECISION_F32 ? 3 : 1);
-            ws = ws > planes ? ws : planes;
-        }
-        const size_t hid_bytes = rows * F * act;
-        if (cfg->in_chans <= 4) {   /* the resize's coefficient tables at the largest downscale (more only for tiny configs) */
-            const size_t tables = (size_t)max_batch * ingest_max_table_bytes(cfg->img_size);
-            ws = ws > tables ? ws : tables;
-        }
-        ctx->ws_bytes = ws > hid_bytes ? ws : hid_bytes;
-        TRY(vh_malloc((void **)&ctx->hid, ctx->ws_bytes));
-    }
-    if (ctx->ln_fold)
-        TRY(vh_malloc((void **)&ctx->stats, rows * (E / 128) * 2 * sizeof(float)));
+    TRY(vh_malloc((void **)&ctx->x, plan->x_bytes));
+    TRY(vh_malloc((void **)&ctx->y, plan->y_bytes));
+    TRY(vh_malloc((void **)&ctx->attn, plan->attn_bytes));
+    TRY(vh_malloc((void **)&ctx->qkv, plan->qkv_bytes));
+    TRY(vh_malloc((void **)&ctx->hid, plan->ws_bytes));
+    if (plan->stats_bytes)
+        TRY(vh_malloc((void **)&ctx->stats, plan->stats_bytes));
     TRY(vh_malloc((void **)&ctx->cls, (size_t)max_batch * E * sizeof(float)));
     TRY(vh_malloc((void **)&ctx->d_logits, (size_t)max_batch * NC * sizeof(float)));
     TRY(vh_malloc((void **)&ctx->d_probs, (size_t)max_batch * NC * sizeof(float)));
@@ -899,17 +708,17 @@ fail:
 /* ---- one encoder layer per arithmetic (ViT_seq.c:330-370; Encoder ViT_opencl.c:710-748) ------------------------------
  * Every function enqueues layer l for n images on stream s: y = LN1(x); qkv = y Win^T + bin; a = attention(qkv);
  * x += a Wout^T + bout; y = LN2(x); h = gelu(y W1^T + b1); x += h W2^T + b2 -- in its mode's operand formats.  With
- * ctx->ln_fold the two LayerNorms are not launched: whoever wrote x also left it as the projection's operand in ctx->y
+ * ctx->plan.ln_fold the two LayerNorms are not launched: whoever wrote x also left it as the projection's operand in ctx->y
  * with the rows' partial sums in ctx->stats, and the QKV / fc1 launches apply the row terms (csrc/norm_fold.h). */
 
 /* The plan's arithmetic for fp32 products on fp32 rows (kernelHandler.h) */
-static int fp32_math(const vit_hip_ctx *ctx) { return ctx->fp32_native ? VH_FP32_NATIVE : VH_FP32_SPLIT3; }
+static int fp32_math(const vit_hip_ctx *ctx) { return ctx->plan.fp32_native ? VH_FP32_NATIVE : VH_FP32_SPLIT3; }
 
 /* Attention on fp32 Q|K|V rows into fp32 rows at out, in the plan's kernel */
 static int attention_rows(const vit_hip_ctx *ctx, vh_stream_t s, float *out, int arith, int n)
 {
-    return vh_launch_attention_rows(s, ctx->qkv, out, 0, arith, ctx->attn_rows_streaming ? VH_ATTN_STREAMING : VH_ATTN_AUTO, n,
-                                    ctx->tokens, ctx->cfg.embed_dim, ctx->cfg.num_heads);
+    return vh_launch_attention_rows(s, ctx->qkv, out, 0, arith, ctx->plan.attn_rows_streaming ? VH_ATTN_STREAMING : VH_ATTN_AUTO, n,
+                                    ctx->plan.tokens, ctx->cfg.embed_dim, ctx->cfg.num_heads);
 }
 
 /* The class-token attention maps of layer l when the forward's armed request taps it: one pass over q_cls and the K
@@ -923,14 +732,9 @@ static int attention_tap(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     if (!ar)
         return 0;
     const vit_config *c = &ctx->cfg;
-    const int reduced = ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
-    /* layer_f32_planes' planes_attn, the reduced layers' kind; everything else writes fp32 rows */
-    const int form = reduced ? (ctx->attn_form == ATTN_STREAMING ? VH_QKV_ROWS_F32 : VH_QKV_PLANES_F16)
-                   : ctx->precision == VIT_PRECISION_F32 && ctx->use_p3 && (ctx->attn_form == ATTN_HD64 || ctx->attn_form == ATTN_LONG)
-                       ? VH_QKV_PLANES3 : VH_QKV_ROWS_F32;
     for (int k = 0; k < ar->spec.n_taps; ++k)
         if (ar->layer[k] == l)
-            OP(VIT_OP_ATTENTION, vh_launch_cls_attention(s, ctx->qkv, form, n, ctx->tokens, c->embed_dim, c->num_heads, k,
+            OP(VIT_OP_ATTENTION, vh_launch_cls_attention(s, ctx->qkv, ctx->plan.qkv_form, n, ctx->plan.tokens, c->embed_dim, c->num_heads, k,
                                                          ar->spec.n_taps, ar->out.heads, ar->out.mean));
     return 0;
 fail:
@@ -944,13 +748,13 @@ static int attention_reduced(vit_hip_ctx *ctx, vh_stream_t s, int n, char *attn_
 {
     int rc = 0;
     const vit_config *c = &ctx->cfg;
-    const int E = c->embed_dim, T = ctx->tokens, H = c->num_heads, rows = n * T;
-    if (ctx->attn_form == ATTN_HD64)
+    const int E = c->embed_dim, T = ctx->plan.tokens, H = c->num_heads, rows = n * T;
+    if (ctx->plan.attn_form == ATTN_HD64)
         OP(VIT_OP_ATTENTION, attn_scales ? vh_launch_attention_planes_f16_mx(s, ctx->qkv, ctx->attn, attn_scales, n, T, E, H)
                                          : vh_launch_attention_planes_f16(s, ctx->qkv, ctx->attn, 1, n, T, E, H));
-    else if (ctx->attn_form == ATTN_HD80)
+    else if (ctx->plan.attn_form == ATTN_HD80)
         OP(VIT_OP_ATTENTION, vh_launch_attention_planes_f16_hd80_operand(s, ctx->qkv, ctx->attn, attn_scales, attn_scales ? 2 : 1, n, T, E, H));
-    else if (ctx->attn_form == ATTN_LONG)
+    else if (ctx->plan.attn_form == ATTN_LONG)
         OP(VIT_OP_ATTENTION, (rc = vh_launch_attention_long(s, ctx->qkv, 1, ctx->hid, n, T, E, H)) != 0 ? rc :
                              attn_scales ? vh_launch_quantize_mx_act(s, ctx->hid, ctx->attn, attn_scales, rows, E)
                                          : vh_launch_split_rows(s, ctx->hid, ctx->attn, rows, E, 1));
@@ -968,12 +772,12 @@ static int layer_fp8(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
 {
     int rc = 0;
     const vit_config *c = &ctx->cfg;
-    const int E = c->embed_dim, F = c->mlp_hidden, rows = n * ctx->tokens, fold = ctx->ln_fold, last = l == c->depth - 1;
+    const int E = c->embed_dim, F = c->mlp_hidden, rows = n * ctx->plan.tokens, fold = ctx->plan.ln_fold, last = l == c->depth - 1;
     float **lw = layer_tensors(ctx, l);
     const struct operand *op = ctx->op + 4 * l;
-    char *ys = (char *)ctx->y + align_up((size_t)rows * E, 256), *as_ = (char *)ctx->attn + align_up((size_t)rows * E, 256);
-    char *hs = (char *)ctx->hid + align_up((size_t)rows * F, 256);
-    const int kind = ctx->attn_form == ATTN_STREAMING ? 0 : 2;
+    char *ys = (char *)ctx->y + ctx->plan.e_scales_off, *as_ = (char *)ctx->attn + ctx->plan.e_scales_off;
+    char *hs = (char *)ctx->hid + ctx->plan.hid_scales_off;
+    const int kind = ctx->plan.qkv_form == VH_QKV_PLANES_F16 ? 2 : 0;   /* Q|K|V as one-part fp16 planes, or as fp32 rows */
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_mx(s, ctx->x, lw[0], lw[1], ctx->y, ys, rows, E, E, c->eps));
     OP(VIT_OP_QKV, fold ? vh_launch_linear_mx_norm(s, ctx->qkv, NULL, kind, op[0].w, op[0].scales, ctx->y, ys, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
@@ -1001,10 +805,10 @@ static int layer_bf16(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
 {
     int rc = 0;
     const vit_config *c = &ctx->cfg;
-    const int E = c->embed_dim, F = c->mlp_hidden, rows = n * ctx->tokens, fold = ctx->ln_fold, last = l == c->depth - 1;
+    const int E = c->embed_dim, F = c->mlp_hidden, rows = n * ctx->plan.tokens, fold = ctx->plan.ln_fold, last = l == c->depth - 1;
     float **lw = layer_tensors(ctx, l);
     const struct operand *op = ctx->op + 4 * l;
-    const int kind = ctx->attn_form == ATTN_STREAMING ? 0 : 2;
+    const int kind = ctx->plan.qkv_form == VH_QKV_PLANES_F16 ? 2 : 0;
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_planes(s, ctx->x, lw[0], lw[1], ctx->y, 1, rows, E, E, c->eps));
     OP(VIT_OP_QKV, fold ? vh_launch_linear_planes_norm(s, ctx->qkv, kind, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
@@ -1029,7 +833,7 @@ static int layer_fp16x2(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
 {
     int rc = 0;
     const vit_config *c = &ctx->cfg;
-    const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->tokens, rows = n * T;
+    const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->plan.tokens, rows = n * T;
     float **lw = layer_tensors(ctx, l);
     const struct operand *op = ctx->op + 4 * l;
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, E, c->eps));
@@ -1053,33 +857,33 @@ static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int *
 {
     int rc = 0;
     const vit_config *c = &ctx->cfg;
-    const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->tokens, rows = n * T, fold = ctx->ln_fold, last = l == c->depth - 1;
+    const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->plan.tokens, rows = n * T, fold = ctx->plan.ln_fold, last = l == c->depth - 1;
     float **lw = layer_tensors(ctx, l);
     const struct operand *op = ctx->op + 4 * l;
     /* ATTN_HD64, ATTN_LONG: Q, K, V too travel as planes (only the probabilities are split inside the attention kernel);
      * otherwise the streaming kernel, fp32 rows in.  Both but the resident kernel write fp32 rows (into the idle MLP
      * buffer), then split */
-    const int planes_attn = ctx->attn_form == ATTN_HD64 || ctx->attn_form == ATTN_LONG;
+    const int planes_attn = ctx->plan.qkv_form == VH_QKV_PLANES3;
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, c->eps));
     OP(VIT_OP_QKV, fold ? vh_launch_linear_p3_norm(s, ctx->qkv, planes_attn, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
                         : vh_launch_linear_p3(s, ctx->qkv, planes_attn, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
     TRY(attention_tap(ctx, s, n, l));
-    OP(VIT_OP_ATTENTION, ctx->attn_form == ATTN_HD64 ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
-                         : (rc = ctx->attn_form == ATTN_LONG ? vh_launch_attention_long(s, ctx->qkv, 3, ctx->hid, n, T, E, c->num_heads)
+    OP(VIT_OP_ATTENTION, ctx->plan.attn_form == ATTN_HD64 ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
+                         : (rc = ctx->plan.attn_form == ATTN_LONG ? vh_launch_attention_long(s, ctx->qkv, 3, ctx->hid, n, T, E, c->num_heads)
                                                              : attention_rows(ctx, s, ctx->hid, VH_ATTN_SPLIT3, n)) != 0 ? rc
                          : vh_launch_split3_rows(s, ctx->hid, ctx->attn, rows, E));
-    if (last && ctx->cls_only_last && T >= 4) {
+    if (last && ctx->plan.cls_only_last && ctx->plan.cls_only_ok) {
         /* Opt-in (vit_hip_set_last_layer_cls_only / $VIT_HIP_LAST_LAYER=cls).  The classifier reads row 0 of every
          * image only (ViT_seq.c:511), and behind the last attention no operator mixes rows: the output projection,
          * LayerNorm and MLP of the last layer are evaluated for the n class-token rows instead of n * T, in the
          * Q|K|V buffer the attention has just released.  Same kernels, same k order: identical logits, bit for
          * bit; the residual stream of the other rows (vit_hip_read_tokens) is NOT updated by this layer. */
+        size_t off[3];
+        plan_cls_only_scratch(c, n, off);   /* cls_only_ok: it fits for max_batch rows */
         char *scratch = (char *)ctx->qkv;
         float *x_cls = (float *)scratch;
-        char *attn_cls = scratch + align_up((size_t)n * E * 4, 256);
-        char *y_cls = attn_cls + align_up((size_t)n * E * 6, 256);
-        char *hid_cls = y_cls + align_up((size_t)n * E * 6, 256);
+        char *attn_cls = scratch + off[0], *y_cls = scratch + off[1], *hid_cls = scratch + off[2];
         OP(VIT_OP_OUT_PROJ, (rc = vh_launch_gather_rows(s, ctx->attn, attn_cls, 3 * (E / 32), rows, n, 64, T)) != 0 ? rc :
                             (rc = vh_launch_gather_rows(s, ctx->x, x_cls, 1, rows, n, 4 * E, T)) != 0 ? rc :
                             vh_launch_linear_p3(s, x_cls, 0, op[1].w, attn_cls, lw[5], n, E, E, 0, x_cls));
@@ -1108,7 +912,7 @@ static int layer_f32_rows(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
 {
     int rc = 0;
     const vit_config *c = &ctx->cfg;
-    const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->tokens, rows = n * T;
+    const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->plan.tokens, rows = n * T;
     float **lw = layer_tensors(ctx, l);
     const struct operand *op = ctx->op + 4 * l;   /* pre-split weight planes, when built */
     const int math = fp32_math(ctx);
@@ -1116,7 +920,7 @@ static int layer_f32_rows(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
     OP(VIT_OP_QKV, op[0].w ? vh_launch_linear_w3(s, ctx->qkv, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL)
                          : vh_launch_linear_math(s, ctx->qkv, lw[2], ctx->y, lw[3], rows, E, 3 * E, 0, NULL, math));
     TRY(attention_tap(ctx, s, n, l));
-    OP(VIT_OP_ATTENTION, attention_rows(ctx, s, ctx->attn, ctx->fp32_native ? VH_ATTN_NATIVE : VH_ATTN_SPLIT3, n));
+    OP(VIT_OP_ATTENTION, attention_rows(ctx, s, ctx->attn, ctx->plan.fp32_native ? VH_ATTN_NATIVE : VH_ATTN_SPLIT3, n));
     OP(VIT_OP_OUT_PROJ, op[1].w ? vh_launch_linear_w3(s, ctx->x, op[1].w, ctx->attn, lw[5], rows, E, E, 0, ctx->x)
                               : vh_launch_linear_math(s, ctx->x, lw[4], ctx->attn, lw[5], rows, E, E, 0, ctx->x, math));
     OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, E, c->eps));
@@ -1148,11 +952,11 @@ static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct inge
         const struct ingest_item item = src->items ? src->items[i] : ingest_whole_item(src, i);
         off += ingest_fill_desc(&d[i], &item, S, filter, off);
     }
-    if (off > ctx->ws_bytes)   /* alloc_arena sized hid for max_batch tables at the steepest downscale */
+    if (off > ctx->plan.ws_bytes)   /* the plan sized hid for max_batch tables at the steepest downscale */
         return vh_set_error(1, "resize: coefficient tables exceed the scratch");
     if ((rc_ = vh_h2d(ctx->d_desc[slot], d, (size_t)n * sizeof(*d), s)) != 0)
         return rc_;
-    rc_ = vh_launch_resize_crop_u8(s, ctx->d_desc[slot], n, C, src->layout, filter, S, ctx->hid, ctx->ws_bytes, out);
+    rc_ = vh_launch_resize_crop_u8(s, ctx->d_desc[slot], n, C, src->layout, filter, S, ctx->hid, ctx->plan.ws_bytes, out);
     const int rec = vh_event_record(ctx->desc_done[slot], s);   /* behind the copy even if the launch was refused */
     ctx->desc_live[slot] = rec == 0;
     return rc_ ? rc_ : rec;
@@ -1160,22 +964,21 @@ static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct inge
 
 /* patch embedding + class token + position embedding (ViT_seq.c:437-443), in the form the mode's first layer reads.  8-bit
  * pixels: the planes paths' im2row producer normalises them as it gathers; the fp32-rows paths expand them first into the
- * Q|K|V buffer (idle here; alloc_arena makes it hold max_batch fp32 images).  All of it is one VIT_OP_PATCH_EMBED. */
+ * Q|K|V buffer (idle here; the plan makes it hold max_batch fp32 images).  All of it is one VIT_OP_PATCH_EMBED. */
 static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct ingest_src *src, int n)
 {
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim;
     float **w = ctx->w;
     void *conv = ctx->slab[SLAB_CONV];
-    const int reduced = ctx->precision == VIT_PRECISION_BF16_GEMM || ctx->precision == VIT_PRECISION_FP8_GEMM;
     /* ln_fold: y receives the token rows as the first projection's operand -- planes, or MX values with their scales behind
      * them -- and stats their partial sums (class-token rows included) */
-    char *const y_scales = ctx->precision == VIT_PRECISION_FP8_GEMM ? (char *)ctx->y + align_up((size_t)n * ctx->tokens * E, 256) : NULL;
-    if (src->u8 && planes_patch_embed(ctx))
+    char *const y_scales = ctx->plan.precision == VIT_PRECISION_FP8_GEMM ? (char *)ctx->y + ctx->plan.e_scales_off : NULL;
+    if (src->u8 && ctx->plan.planes_patch_embed)
         return vh_launch_patch_embed_planes_u8(s, src->u8, src->layout, src->norm->scale, src->norm->bias, conv, w[2], w[0], w[3],
-                                               ctx->x, n, c->in_chans, c->img_size, c->patch_size, E, ctx->hid, ctx->ws_bytes,
-                                               ctx->precision == VIT_PRECISION_F32 ? 3 : 1, ctx->ln_fold ? ctx->y : NULL,
-                                               ctx->ln_fold ? y_scales : NULL, ctx->ln_fold ? ctx->stats : NULL);
+                                               ctx->x, n, c->in_chans, c->img_size, c->patch_size, E, ctx->hid, ctx->plan.ws_bytes,
+                                               ctx->plan.conv_parts, ctx->plan.ln_fold ? ctx->y : NULL,
+                                               ctx->plan.ln_fold ? y_scales : NULL, ctx->plan.ln_fold ? ctx->stats : NULL);
     const float *images = src->f32;
     if (src->u8) {
         const int rc = vh_launch_expand_u8(s, src->u8, src->layout, src->norm->scale, src->norm->bias, ctx->qkv, n, c->in_chans,
@@ -1184,20 +987,20 @@ static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct in
             return rc;
         images = ctx->qkv;
     }
-    if (ctx->ln_fold && ctx->precision == VIT_PRECISION_F32)   /* lab variant: the fold on three-part planes */
+    if (ctx->plan.ln_fold && ctx->plan.precision == VIT_PRECISION_F32)   /* lab variant: the fold on three-part planes */
         return vh_launch_patch_embed_planes3_norm(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size,
-                                                  c->patch_size, E, ctx->hid, ctx->ws_bytes, ctx->y, ctx->stats);
-    if (ctx->ln_fold)
+                                                  c->patch_size, E, ctx->hid, ctx->plan.ws_bytes, ctx->y, ctx->stats);
+    if (ctx->plan.ln_fold)
         return vh_launch_patch_embed_planes_norm(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size,
-                                                 c->patch_size, E, ctx->hid, ctx->ws_bytes, ctx->y, y_scales, ctx->stats);
-    if (reduced)   /* reduced modes: im2row to one-part planes (in the MLP buffer, idle here) + the planes GEMM */
-        return vh_launch_patch_embed_planes(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size,
-                                            E, ctx->hid, ctx->ws_bytes);
-    if (ctx->use_p3)   /* the fp32 path on planes: im2row writes the exact three-part split, six products per block */
+                                                 c->patch_size, E, ctx->hid, ctx->plan.ws_bytes, ctx->y, y_scales, ctx->stats);
+    if (ctx->plan.use_p3)   /* the fp32 path on planes: im2row writes the exact three-part split, six products per block */
         return vh_launch_patch_embed_planes3(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size,
-                                             E, ctx->hid, ctx->ws_bytes);
+                                             E, ctx->hid, ctx->plan.ws_bytes);
+    if (ctx->plan.planes_patch_embed)   /* reduced modes: im2row to one-part planes (in the MLP buffer, idle here) + the planes GEMM */
+        return vh_launch_patch_embed_planes(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size,
+                                            E, ctx->hid, ctx->plan.ws_bytes);
     return vh_launch_patch_embed_ws_math(s, images, w[1], w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size, E,
-                                         ctx->hid, ctx->ws_bytes, fp32_math(ctx));
+                                         ctx->hid, ctx->plan.ws_bytes, fp32_math(ctx));
 }
 
 /* The readout behind layer l for tap k of the armed request: one pass over the residual stream (the class rows alone when
@@ -1210,8 +1013,8 @@ static int feature_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct feature_req
     float **tw = ctx->w + 4 + 12 * c->depth;
     OP(VIT_OP_LAYER_NORM, vh_launch_feature_readout(s, ctx->x, cls_rows ? (const float *)ctx->qkv : NULL, c->embed_dim, tw[0], tw[1],
                                                     c->eps, fr->spec.final_norm, fr->spec.l2_normalize, fr->spec.dtype,
-                                                    fr->spec.token_layout, n, ctx->tokens, c->embed_dim, k, fr->spec.n_taps,
-                                                    fr->out.cls, fr->out.pooled, fr->out.tokens, ctx->hid, ctx->ws_bytes));
+                                                    fr->spec.token_layout, n, ctx->plan.tokens, c->embed_dim, k, fr->spec.n_taps,
+                                                    fr->out.cls, fr->out.pooled, fr->out.tokens, ctx->hid, ctx->plan.ws_bytes));
     return 0;
 fail:
     return rc;
@@ -1223,16 +1026,16 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
                           const struct feature_req *fr, const struct topk_req *tk, const struct attn_req *ar)
 {
     int rc = 0;
-    const int cls_only_saved = ctx->cls_only_last;
+    const int cls_only_saved = ctx->plan.cls_only_last;
     ctx->attn_serving = ar;   /* read by the layer functions (attention_tap) */
     TRY(vh_set_device(ctx->device));   /* the current device is per host thread */
     const vit_config *c = &ctx->cfg;
-    const int E = c->embed_dim, T = ctx->tokens, NC = c->num_classes;
+    const int E = c->embed_dim, T = ctx->plan.tokens, NC = c->num_classes;
     vh_stream_t s = stream ? stream : ctx->stream;
 
     struct ingest_src crops;
     if (src->kind == INGEST_U8_RESIZED || src->kind == INGEST_U8_BOXES) {   /* crops into Q|K|V, then the u8 path on them; both count as the patch embedding */
-        unsigned char *out = (unsigned char *)ctx->qkv + ctx->crop_off;
+        unsigned char *out = (unsigned char *)ctx->qkv + ctx->plan.crop_off;
         OP(VIT_OP_PATCH_EMBED, resize_crop_launch(ctx, s, src, n, out));
         crops = (struct ingest_src){.kind = INGEST_U8, .on_device = 1, .u8 = out, .layout = VIT_PIXELS_HWC, .norm = src->norm};
         src = &crops;
@@ -1241,14 +1044,14 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
     int cls_rows = 0;   /* the last layer ran on the class-token rows only (opt-in, fp32 path on planes) */
     /* a request for patch rows of the last layer makes this forward run the last layer on all rows */
     if (fr && fr->layer[fr->spec.n_taps - 1] == c->depth - 1 && (fr->out.pooled || fr->out.tokens))
-        ctx->cls_only_last = 0;
+        ctx->plan.cls_only_last = 0;
     for (int l = 0, k = 0; l < c->depth; ++l) {
-        switch (ctx->precision) {
+        switch (ctx->plan.precision) {
         case VIT_PRECISION_FP8_GEMM: TRY(layer_fp8(ctx, s, n, l)); break;
         case VIT_PRECISION_BF16_GEMM: TRY(layer_bf16(ctx, s, n, l)); break;
         case VIT_PRECISION_F32_FP16X2: TRY(layer_fp16x2(ctx, s, n, l)); break;
         default:
-            if (ctx->use_p3)
+            if (ctx->plan.use_p3)
                 TRY(layer_f32_planes(ctx, s, n, l, &cls_rows));
             else
                 TRY(layer_f32_rows(ctx, s, n, l));
@@ -1256,7 +1059,7 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         if (fr && k < fr->spec.n_taps && fr->layer[k] == l)
             TRY(feature_tap(ctx, s, fr, k++, n, cls_rows));
     }
-    ctx->cls_only_last = cls_only_saved;
+    ctx->plan.cls_only_last = cls_only_saved;
     ctx->attn_serving = NULL;
 
     /* final LayerNorm on the class-token rows -- row i * stride of the residual stream, or compacted at the start of the
@@ -1274,7 +1077,7 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         OP(VIT_OP_SOFTMAX, vh_launch_topk(s, logits, n, NC, tk->spec.k, tk->spec.score_kind, tk->out.labels, tk->out.scores));
     return 0;
 fail:
-    ctx->cls_only_last = cls_only_saved;
+    ctx->plan.cls_only_last = cls_only_saved;
     ctx->attn_serving = NULL;
     return rc;
 }
@@ -1484,7 +1287,7 @@ static int set_features(const char *who, vit_hip_ctx *ctx, const vit_feature_spe
             return 1;
         const char *why = !bufs || (!bufs->cls && !bufs->pooled && !bufs->tokens) ? "no output buffer"
                           : host && bufs->tokens ? "the host form takes cls and pooled only (tokens: use the device form)"
-                          : ctx->tokens < 2 && (bufs->pooled || bufs->tokens) ? "pooled and tokens need at least one patch token"
+                          : ctx->plan.tokens < 2 && (bufs->pooled || bufs->tokens) ? "pooled and tokens need at least one patch token"
                           : !host && (((uintptr_t)bufs->cls | (uintptr_t)bufs->pooled | (uintptr_t)bufs->tokens) & 15) ? "device buffers must be 16-byte aligned"
                           : NULL;
         if (why)
@@ -1614,7 +1417,7 @@ static int set_attention(const char *who, vit_hip_ctx *ctx, const vit_attn_spec 
         ar.spec = *spec;
         ar.out = *bufs;
         if (host) {
-            const size_t per = (size_t)spec->n_taps * ctx->tokens * sizeof(float);
+            const size_t per = (size_t)spec->n_taps * ctx->plan.tokens * sizeof(float);
             ar.st[0] = (struct staged){.host = (char *)bufs->heads, .per_image = per * c->num_heads};
             ar.st[1] = (struct staged){.host = (char *)bufs->mean, .per_image = per};
         }
@@ -1642,8 +1445,8 @@ int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
 {
     if (!ctx)
         return -1;
-    const int before = ctx->cls_only_last;
-    ctx->cls_only_last = on && ctx->use_p3 && !ctx->ln_fold;
+    const int before = ctx->plan.cls_only_last;
+    ctx->plan.cls_only_last = on && ctx->plan.use_p3 && !ctx->plan.ln_fold;   /* a forward takes it where plan.cls_only_ok */
     return before;
 }
 
@@ -1654,7 +1457,7 @@ int vit_hip_read_tokens(vit_hip_ctx *ctx, int n, float *host_out)
     int rc = vh_set_device(ctx->device);
     if (rc)
         return rc;
-    rc = vh_d2h(host_out, ctx->x, (size_t)n * ctx->tokens * ctx->cfg.embed_dim * sizeof(float),
+    rc = vh_d2h(host_out, ctx->x, (size_t)n * ctx->plan.tokens * ctx->cfg.embed_dim * sizeof(float),
                     ctx->stream);
     return rc ? rc : vh_stream_sync(ctx->stream);
 }
@@ -2203,9 +2006,10 @@ void ViT_opencl(ImageData *image, Network *networks, float **probabilities)
         chunk = atoi(envb) < per_device ? atoi(envb) : per_device;
     if (n_devices > 1) {
         /* $VIT_HIP_DEVICES names several GPUs: contiguous shards of the images, one replica per device */
-        const int precision = env_precision();
+        struct plan_env penv;
+        plan_env_read(&penv);
         vit_hip_multi *m = NULL;
-        int rcm = vit_hip_create_multi(&m, &cfg, networks, vit_config_num_tensors(&cfg), devices, n_devices, chunk, precision);
+        int rcm = vit_hip_create_multi(&m, &cfg, networks, vit_config_num_tensors(&cfg), devices, n_devices, chunk, penv.precision);
         if (rcm != 0) {
             printf("[%s:%d] vit_hip_create_multi failed (%d): %s\n", __FILE__, __LINE__, rcm, vh_last_error());
             exit(EXIT_FAILURE);
