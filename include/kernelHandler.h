@@ -336,6 +336,15 @@ int vh_launch_quantize_mx_rows(vh_stream_t s, const float *input, void *values, 
  * take it for `input_scales`.  Weights keep [cols/128][4][rows] (vh_launch_quantize_mx_rows). */
 int vh_launch_quantize_mx_act(vh_stream_t s, const float *input, void *values, void *scales, int rows, int cols);
 size_t vh_mx_act_scale_bytes(int rows, int cols);
+/* Which tile class a planes (vh_launch_linear_planes*, vh_launch_patch_embed_planes*) or MX (vh_launch_linear_mx*) projection
+ * launch of `rows` x N runs on a device of num_cus compute units -- pure, touches no device; both launchers decide by it.
+ * parts: 3 or 1 per value (MX: 1); resid_or_patch: the epilogue adds a residual or is the patch embedding's; small_only:
+ * the launcher's own flag (residual with colA < 2048; the patch embedding with Kp < 2048).  With VH_TILES_256x256_TAIL
+ * *rows_big (may be NULL) is the row at which the 256x256 launch hands over to the 128x128 launch, otherwise 0.
+ * -1 for rows, N or num_cus <= 0.  Results never depend on the class: every tile sums the same products in the same order. */
+enum { VH_GEMM_PLANES = 0, VH_GEMM_MX = 1 };
+enum { VH_TILES_128x256 = 0, VH_TILES_128x128 = 1, VH_TILES_256x256 = 2, VH_TILES_256x256_TAIL = 3 };
+int vh_gemm_tile_class(int family, int parts, int resid_or_patch, int small_only, int rows, int N, int num_cus, int *rows_big);
 /* vh_launch_layer_norm writing its result as an MX tensor (embed_dim % 128 == 0) */
 int vh_launch_layer_norm_mx(vh_stream_t s, const float *input, const float *weight, const float *bias,
                             void *out_values, void *out_scales, int rows, int embed_dim, long in_row_stride, double eps);

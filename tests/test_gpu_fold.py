@@ -13,8 +13,9 @@ the cancellation the fold is exposed to -- is measured and printed."""
 import numpy as np
 import pytest
 
+import gemm_tiles_ref as tiles
 import mx_ref
-from test_gpu_p3 import OP_TOL, _bf16_rne, _dev, _launch, _planes1_to_f32, _planes_f16_to_f32
+from test_gpu_p3 import OP_TOL, _bf16_rne, _dev, _launch, _planes1_to_f32, _planes_f16_to_f32, _tile_class
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +45,18 @@ def _folded_reference(x_oper, stats_rows, w_oper, colsum, bias_f, K, eps=EPS):
     rstd = (np.float32(1.0) / np.sqrt((var.astype(np.float64) + eps).astype(np.float32))).astype(np.float64)
     acc = x_oper.astype(np.float64) @ w_oper.astype(np.float64).T
     return rstd[:, None] * acc - (rstd * mean.astype(np.float64))[:, None] * colsum.astype(np.float64)[None, :] + bias_f.astype(np.float64)[None, :]
+
+
+def _consumer_rows(pkg, family, M, N):
+    """rows a folded consumer is compared on: all of a small problem; of a large one the first and last rows, rows at tile
+    edges and around the row where the launch hands over from 256x256 to 128x128 tiles (the consumers pass small_only = 0;
+    one-part planes at 19700 x 3072 on 256 CUs: row 16384; MX: one launch of 128x256 tiles, no such row)"""
+    if M <= 300:
+        return np.arange(M)
+    rb = _tile_class(pkg, family, 1, False, False, M, N)[1]
+    assert family != tiles.MX or rb == 0
+    around = np.r_[rb - 16:rb + 16, rb + 120:rb + 136] if rb else np.r_[0:0]
+    return np.unique(np.r_[0:24, 240:272, 4090:4102, M - 24:M, around]).astype(np.int64)
 
 
 def _gelu64(v):
@@ -125,7 +138,7 @@ def test_bf16_consumer_applies_the_folded_layernorm(pkg, device, oracle, weights
         d_o = pkg.DeviceBuffer((M * N + 1) // 2)
     _launch(pkg, "vh_launch_linear_planes_norm", None, d_o.ptr, out, d_w1.ptr, d_x1.ptr, d_st.ptr, d_cs.ptr, d_bf.ptr, EPS, M, K, N, gelu)
     got = d_o.to_numpy((M, N)) if out == 0 else _planes1_to_f32(d_o, M, N) if out == 1 else _planes_f16_to_f32(d_o, M, N)
-    rows = np.arange(M) if M <= 300 else np.r_[0:24, 240:272, 4090:4102, M - 24:M]
+    rows = _consumer_rows(pkg, tiles.PLANES, M, N)
     want = _folded_reference(_bf16_rne(x[rows]), stats[:, rows], wr, cs, bf, K)
     if gelu:
         want = _gelu64(want)
@@ -250,7 +263,7 @@ def test_mx_consumer_applies_the_folded_layernorm(pkg, device, oracle, M, N, gel
         d_o, d_os = pkg.DeviceBuffer(M * N), None
     _launch(pkg, "vh_launch_linear_mx_norm", None, d_o.ptr, d_os.ptr if d_os else None, kind, d_wv.ptr, d_wsc.ptr, d_xv.ptr, d_xs.ptr,
             d_st.ptr, d_cs.ptr, d_bf.ptr, EPS, M, K, N, gelu)
-    rows = np.arange(M) if M <= 300 else np.r_[0:24, 240:272, 4090:4102, M - 24:M]
+    rows = _consumer_rows(pkg, tiles.MX, M, N)
     want = _folded_reference(xq[rows], stats[:, rows], wq, cs, bf, K)
     if gelu:
         want = _gelu64(want)

@@ -79,8 +79,8 @@ def test_quantize_mx_rows_is_the_numpy_statement_byte_for_byte(pkg, device, orac
     (300, 768, 3072, 1, False, True),       # fc1 + GELU, quantised output
     (300, 3072, 768, 0, True, False),       # fc2 + residual, long K
     (5, 256, 128, 0, False, True),          # smallest legal shape
-    (19700, 768, 2304, 0, False, False),    # 100 images: 256x256 tiles + a tail launch of 128x128 tiles
-    (56000, 768, 3072, 1, False, True),     # fc1 at scale: big tiles + tail, quantised output
+    (19700, 768, 2304, 0, False, False),    # 100 images: ONE launch of 128x256 tiles (MX never runs 256x256 tiles or a tail)
+    (56000, 768, 3072, 1, False, True),     # fc1 at scale: 128x256 tiles, quantised output
 ])
 def test_linear_mx_vs_float64_products_of_the_dequantised_operands(pkg, device, oracle, M, K, N, gelu, resid, mx_out):
     """Every product of two e4m3 values times two powers of two is exact in fp32, so against float64 sums of the

@@ -13,6 +13,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import gemm_tiles_ref as tiles
+
 pytestmark = pytest.mark.gpu
 
 OP_TOL = 2e-5
@@ -71,17 +73,25 @@ def _sample_rows(M, extra=()):
     return np.array(sorted(idx))
 
 
-def _rows_big(M, K, N, resid, cus=256):
-    """The row where launch_p3 hands over from 256x256 tiles to 128x128 tiles (0: single launch)."""
-    ntiles, mtiles = N // 256, (M + 255) // 256
-    tiles = mtiles * ntiles
-    if N % 256 or 2 * tiles < 5 * cus or (resid and K < 2048):
-        return 0
-    full, rem = tiles // cus, tiles % cus
-    rb = (full * cus // ntiles) * 256
-    if rem == 0 or 4 * rem > 3 * cus or rb <= 0 or rb >= M:
-        return 0
-    return rb
+def _cus():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _tile_class(pkg, family, parts, resid_or_patch, small_only, M, N):
+    """(tile class, hand-over row) of a planes / MX projection launch on this device: the library's rule
+    (vh_gemm_tile_class), which tests/gemm_tiles_ref.py restates"""
+    import ctypes
+    rb = ctypes.c_int(-1)
+    cls = pkg.lib().vh_gemm_tile_class(family, parts, int(resid_or_patch), int(small_only), M, N, _cus(), ctypes.byref(rb))
+    assert (cls, rb.value) == tiles.tile_class(family, parts, resid_or_patch, small_only, M, N, _cus())
+    return cls, rb.value
+
+
+def _rows_big(pkg, family, parts, M, K, N, resid):
+    """The row where vh_launch_linear_planes / vh_launch_linear_mx hand over from 256x256 tiles to 128x128 tiles
+    (0: a single launch, whatever its tile)."""
+    return _tile_class(pkg, family, parts, resid, tiles.linear_small_only(resid, K), M, N)[1]
 
 
 @pytest.mark.parametrize("M,K,N,gelu,resid,planes_out", [
@@ -93,7 +103,7 @@ def _rows_big(M, K, N, resid, cus=256):
     (4300, 768, 3072, 1, False, True),      # 128x128 tiles only (204 big tiles would not fill one round)
     (12608, 3072, 768, 0, True, False),     # fc2 at batch 64: small tiles, long K
     (19700, 768, 2304, 0, False, False),    # QKV at 100 images: 693 big tiles = 2 full rounds + a tail on small tiles
-    (60000, 3072, 768, 0, True, False),     # fc2, 705 big tiles: 2 full rounds of big tiles + a tail launch
+    (60000, 3072, 768, 0, True, False),     # fc2, 705 big tiles: 2.75 rounds, ONE launch of 256x256 tiles at 256 CUs (193 > 3/4 of them)
     (56000, 768, 3072, 1, False, True),     # fc1, 2628 big tiles: 10 rounds + 68 tiles on the small-tile launch
 ])
 def test_linear_p3_matches_in_loop_split_bitwise_and_the_oracle_on_boundary_rows(
@@ -123,7 +133,7 @@ def test_linear_p3_matches_in_loop_split_bitwise_and_the_oracle_on_boundary_rows
         got = d_o.to_numpy((M, N))
     assert np.array_equal(got, ref + 0.0)
     # the oracle on the rows where tiles and launches meet
-    rb = _rows_big(M, K, N, resid)
+    rb = _rows_big(pkg, tiles.PLANES, 3, M, K, N, resid)
     rows = np.arange(M) if M <= 300 else _sample_rows(M, extra=(256, 4096, rb, rb + 128) if rb else (256, 4096))
     want = oracle.linear(x[rows], w, b, N)
     if gelu:
@@ -299,8 +309,9 @@ def test_linear_p3_with_a_permutation_matrix_moves_columns_exactly_at_full_size(
 
 @pytest.mark.parametrize("precision", ["bf16", "fp8"])
 def test_reduced_modes_at_batch_512_are_batch_position_independent(pkg, device, weights, precision):
-    """BASELINE config 3's size in its own precision (and the fp8 mode): big-tile launches, tail launches and the
-    persistent grids give an image the same logits, bit for bit, as a batch of four does."""
+    """BASELINE config 3's size in its own precision (and the fp8 mode): the 128x256-tile launches of the residual producers
+    and of every MX projection, bf16's QKV and fc1 on 256x256 tiles with a tail launch, and the persistent grids give an
+    image the same logits, bit for bit, as a batch of four (128x128 tiles) does."""
     cfg = pkg.preset("vit_b_16")
     imgs = pkg.synth_images(cfg, 0, 512)
     big = pkg.ViTHip(cfg, weights, device=0, max_batch=512, precision=precision)
@@ -328,13 +339,13 @@ def _planes1_to_f32(buf, rows, cols):
     (300, 3072, 768, 0, True, False),      # fc2 + residual
     (5, 128, 128, 0, False, True),         # smallest legal shape
     (19700, 768, 2304, 0, False, False),   # 100 images: 256x256 tiles + a tail launch of 128x128 tiles
-    (60000, 3072, 768, 0, True, False),    # long K, big tiles + tail
+    (60000, 3072, 768, 0, True, False),    # long K; one-part residual: ONE launch of 128x256 tiles, no hand-over row
 ])
 def test_linear_planes_one_part_vs_oracle_on_bf16_rounded_operands(pkg, device, oracle, M, K, N, gelu, resid, planes_out):
     """vh_launch_linear_planes(parts = 1): operands rounded to bf16 by vh_launch_split_rows(parts = 1),
     fp32 accumulation.  The oracle's fp32 loop (ViT_seq.c:295-309) on the SAME rounded operands differs
-    only by summation order, so the fp32 operator tolerance applies (rows sampled around tile and launch
-    boundaries for the large shapes)."""
+    only by summation order, so the fp32 operator tolerance applies (rows sampled around tile boundaries and, where
+    the launch is split, its hand-over row for the large shapes; every row of every class: test_gpu_gemm_tile_classes.py)."""
     x = oracle.synth_fill(M * K, 700 + M, 1.0, 0.1).reshape(M, K)
     w = oracle.synth_fill(N * K, 701 + N, 0.04, 0.0)
     b = oracle.synth_fill(N, 702, 0.1, 0.0)
@@ -354,7 +365,7 @@ def test_linear_planes_one_part_vs_oracle_on_bf16_rounded_operands(pkg, device, 
         _launch(pkg, "vh_launch_linear_planes", None, d_o.ptr, 0, d_w1.ptr, d_x1.ptr, 1, d_b.ptr, M, K, N, gelu,
                 d_o.ptr if resid else None)
         got = d_o.to_numpy((M, N))
-    rb = _rows_big(M, K, N, resid)
+    rb = _rows_big(pkg, tiles.PLANES, 1, M, K, N, resid)
     rows = np.arange(M) if M <= 300 else _sample_rows(M, extra=(256, 4096, rb, rb + 128) if rb else (256, 4096))
     want = oracle.linear(xr[rows], wr.ravel(), b, N)
     if gelu:

@@ -20,7 +20,7 @@
  * (two 16-byte loads and one byte load per fragment and lane, no shuffling).  A and B operands pair up by
  * (lane group, byte), so any assignment works as long as both sides use the same one.
  *
- * Kernel structure = gemm_p3.hip's: tile 256 x 256 (or 128 x 128), every wave owns 32 rows; A fragments go
+ * Kernel structure = gemm_p3.hip's: tile 128 x 256 (or 128 x 128), four waves, every wave owns 32 rows; A fragments go
  * HBM/L2 -> VGPR directly (coalesced thanks to the format), double-buffered one K step ahead; W goes by LDS-DMA
  * into [256][128 B] rows (16-byte chunks swizzled for the permuted fragment rows, see dma_w) plus its scales, two stages; W
  * fragments are taken through a ring of four in registers; one barrier per K step (128 k = 32 MFMAs per wave)
@@ -342,28 +342,20 @@ int launch_mx_tile(hipStream_t st, MxParams p)
 template <int EPI, int OUTK>
 int launch_mx(hipStream_t st, const MxParams &p, int small_only)
 {
-    const int rows = p.row_end - p.row_begin;
-    const int num_cus = vh_device_cus(vh_current_device());
-    const int ntiles = p.N / 256, mtiles = (rows + 255) / 256;
-    const long tiles = (long)mtiles * ntiles;
     /* 128x256 tiles, 4 waves of 32x256, TWO workgroups per CU wherever the problem fills the chip: a K = 768 product is
      * six K steps long, and with one 256x256 workgroup per CU every prologue (first DMA) and every epilogue (GELU, block
      * maxima, quantisation, stores; residual rows) runs with the matrix pipe idle -- with two, one workgroup's epilogue
      * runs under the other's K loop.  Measured (ViT-B/16, batch 512, same call): fc1 0.418 -> 0.356 ms, out-proj
-     * 0.185 -> 0.175, fc2 0.362 -> 0.348, QKV 0.241 -> 0.235; 28.3k -> 29.7k images/s. */
-    if (p.N % 256 == 0 && tiles >= num_cus)
+     * 0.185 -> 0.175, fc2 0.362 -> 0.348, QKV 0.241 -> 0.235; 28.3k -> 29.7k images/s.
+     * Everything smaller, and N % 256 != 0, runs the 128x128 tile.  The rule is vh_gemm_tile_class (gemm_p3.hip): for this
+     * family it knows these two classes only -- one launch, no 256x256 tile, no hand-over row. */
+    const int cls = vh_gemm_tile_class(VH_GEMM_MX, 1, EPI == EPI_RESID, small_only, p.row_end - p.row_begin, p.N,
+                                       vh_device_cus(vh_current_device()), nullptr);
+    if (cls == VH_TILES_128x256)
         return launch_mx_tile<4, 256, EPI, OUTK>(st, p);
-    if (p.N % 256 != 0 || small_only || 2 * tiles < 5 * (long)num_cus)
+    if (cls == VH_TILES_128x128)
         return launch_mx_tile<4, 128, EPI, OUTK>(st, p);
-    const long full = tiles / num_cus, rem = tiles % num_cus;
-    const int rows_big = (int)(full * num_cus / ntiles) * 256;
-    if (rem == 0 || 4 * rem > 3 * num_cus || rows_big <= 0 || rows_big >= rows)
-        return launch_mx_tile<8, 256, EPI, OUTK>(st, p);
-    MxParams big = p, rest = p;
-    big.row_end = p.row_begin + rows_big;
-    rest.row_begin = big.row_end;
-    const int rc = launch_mx_tile<8, 256, EPI, OUTK>(st, big);
-    return rc ? rc : launch_mx_tile<4, 128, EPI, OUTK>(st, rest);
+    return vh_fail(1, "gemm_mx: no tile class for rows=%d N=%d (class %d)", p.row_end - p.row_begin, p.N, cls);
 }
 
 /* fp32 [rows][K] -> MX planes.  One thread per 4 consecutive values, so that a wave reads 1 KiB of a row in one

@@ -441,6 +441,39 @@ int launch_p3_tile(hipStream_t st, P3Params p)
     return 0;
 }
 
+} // namespace
+
+/* The tile rule of launch_p3 below and of launch_mx (gemm_mx.hip): pure, no device -- tests/gemm_tiles_ref.py restates it.
+ * `tiles` counts 256x256 tiles whatever class runs.
+ *  - fp32-row producers on one-part planes (residual and patch-embedding epilogues) and every MX projection: 128x256 tiles, two
+ *    workgroups per CU, once the problem fills the chip (tiles >= num_cus; `small_only` does not apply); below that the
+ *    128x128 tile.  They never run a 256x256 tile: with tiles < num_cus the 2.5 rounds the big tile asks for cannot be there.
+ *  - everything else: the 128x128 tile when N % 256 != 0, `small_only`, or fewer than 2.5 rounds of big tiles; otherwise
+ *    256x256 tiles, the last partly filled round (at most 3/4 of the CUs) handed to a 128x128 launch from row *rows_big on. */
+extern "C" int vh_gemm_tile_class(int family, int parts, int resid_or_patch, int small_only, int rows, int N, int num_cus, int *rows_big)
+{
+    if (rows_big)
+        *rows_big = 0;
+    if (rows <= 0 || N <= 0 || num_cus <= 0)
+        return -1;
+    const bool two_per_cu = family == VH_GEMM_MX || (parts == 1 && resid_or_patch);
+    const int ntiles = N / 256, mtiles = (rows + 255) / 256;
+    const long tiles = (long)mtiles * ntiles;
+    if (two_per_cu && N % 256 == 0 && tiles >= num_cus)
+        return VH_TILES_128x256;
+    if (two_per_cu || N % 256 != 0 || small_only || 2 * tiles < 5 * (long)num_cus)
+        return VH_TILES_128x128;
+    const long full = tiles / num_cus, rem = tiles % num_cus;
+    const int rb = (int)(full * num_cus / ntiles) * 256;
+    if (rem == 0 || 4 * rem > 3 * num_cus || rb <= 0 || rb >= rows)
+        return VH_TILES_256x256;
+    if (rows_big)
+        *rows_big = rb;
+    return VH_TILES_256x256_TAIL;
+}
+
+namespace {
+
 /* Tile choice (measured on ViT-B/16, profiles/r02_*): 256x256 tiles (8 waves of 32x256, one workgroup per
  * CU) where N allows and the grid is at least 2.5 scheduling rounds of them, with the last, partly filled
  * round handed to 128x128 tiles (4 waves of 32x128, two to three workgroups per CU): a grid of r.f rounds
@@ -449,32 +482,38 @@ int launch_p3_tile(hipStream_t st, P3Params p)
  * 128x128 tile alone: at equal work it is within 3 % of the big tile, and it quantises four times finer
  * (batch 64: 5495 against 4947 images/s).  Every tile computes the same k order: results do not depend on
  * the choice.  (Round 4 tried 128x64 tiles for batch 64's N = 768 projections -- 594 tiles of 128x128 sit two on some CUs
- * and three on others -- and lost: twice the A re-reads per MFMA make that tile L2-bound; profiles/r04_bench_batch64_*.) */
+ * and three on others -- and lost: twice the A re-reads per MFMA make that tile L2-bound; profiles/r04_bench_batch64_*.)
+ * This describes the three-part kernels and the one-part projections that write planes or plain fp32 rows (QKV, fc1); the
+ * decision itself is vh_gemm_tile_class above, which both launchers call. */
 template <int EPI, int OUTK, int NPL>
 int launch_p3(hipStream_t st, const P3Params &p, int small_only)
 {
-    const int rows = p.row_end - p.row_begin;
-    const int num_cus = vh_device_cus(vh_current_device());
-    const int ntiles = p.N / 256, mtiles = (rows + 255) / 256;
-    const long tiles = (long)mtiles * ntiles;
     /* One-part operands writing fp32 rows (the reduced modes' output projection, fc2 and patch embedding): 128x256
      * tiles, 4 waves of 32x256, two workgroups per CU -- one workgroup's stores of fp32 rows run under the other's K
      * loop (measured, ViT-B/16 batch 512: out-proj 0.223 -> 0.213 ms, fc2 0.503 -> 0.491, patch embedding 0.29 -> 0.27
-     * against the rule below; the planes-out epilogues of QKV and fc1 measure the same either way). */
-    if ((EPI == EPI_RESID || EPI == EPI_PATCH) && NPL == 1 && p.N % 256 == 0 && tiles >= num_cus)
-        return launch_p3_tile<4, 256, EPI, OUTK, NPL>(st, p);
-    if (p.N % 256 != 0 || small_only || 2 * tiles < 5 * (long)num_cus)
+     * against the 256x256 rule; the planes-out epilogues of QKV and fc1 measure the same either way).  Below a full
+     * chip they run the 128x128 tile; the 256x256 tile is never theirs (vh_gemm_tile_class) and is not instantiated. */
+    constexpr bool TWO_PER_CU = (EPI == EPI_RESID || EPI == EPI_PATCH) && NPL == 1;
+    int rows_big = 0;
+    const int cls = vh_gemm_tile_class(VH_GEMM_PLANES, NPL, EPI == EPI_RESID || EPI == EPI_PATCH, small_only, p.row_end - p.row_begin,
+                                       p.N, vh_device_cus(vh_current_device()), &rows_big);
+    if (cls == VH_TILES_128x128)
         return launch_p3_tile<4, 128, EPI, OUTK, NPL>(st, p);
-    const long full = tiles / num_cus, rem = tiles % num_cus;
-    const int rows_big = (int)(full * num_cus / ntiles) * 256;
-    auto big_tiles = [&](const P3Params &q) { return launch_p3_tile<8, 256, EPI, OUTK, NPL>(st, q); };
-    if (rem == 0 || 4 * rem > 3 * num_cus || rows_big <= 0 || rows_big >= rows)
-        return big_tiles(p);
-    P3Params big = p, rest = p;
-    big.row_end = p.row_begin + rows_big;
-    rest.row_begin = big.row_end;
-    const int rc = big_tiles(big);
-    return rc ? rc : launch_p3_tile<4, 128, EPI, OUTK, NPL>(st, rest);
+    if constexpr (TWO_PER_CU) {
+        if (cls == VH_TILES_128x256)
+            return launch_p3_tile<4, 256, EPI, OUTK, NPL>(st, p);
+    } else {
+        if (cls == VH_TILES_256x256)
+            return launch_p3_tile<8, 256, EPI, OUTK, NPL>(st, p);
+        if (cls == VH_TILES_256x256_TAIL) {
+            P3Params big = p, rest = p;
+            big.row_end = p.row_begin + rows_big;
+            rest.row_begin = big.row_end;
+            const int rc = launch_p3_tile<8, 256, EPI, OUTK, NPL>(st, big);
+            return rc ? rc : launch_p3_tile<4, 128, EPI, OUTK, NPL>(st, rest);
+        }
+    }
+    return vh_fail(1, "gemm_p3: no tile class for rows=%d N=%d (class %d)", p.row_end - p.row_begin, p.N, cls);
 }
 
 /* fp32 [rows][K] <-> planes [K/32][NPL][rows][32]: one thread per 8 consecutive elements */
