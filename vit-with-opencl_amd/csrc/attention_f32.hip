@@ -276,8 +276,18 @@ __global__ __launch_bounds__(64 * NKT) void attention_f32_kernel(const float *__
 #pragma unroll
         for (int j = 0; j < NKT; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                s[j][r] = s[j][r] * inv_sum;
+            for (int r = 0; r < 16; ++r) {
+                float p = s[j][r] * inv_sum;
+                /* Two fp16 parts: the probability is made an fp32 value of its own before it is split.  Left to itself the
+                 * compiler converts the high part from the rounded product (v_cvt_pk_f16_f32) but, for four of a tile's
+                 * sixteen keys, takes the low part's residual from a conversion fused with this multiplication
+                 * (v_fma_mixlo_f16: one rounding of the exact product).  Where the product lies within an fp32 rounding
+                 * of an fp16 tie the two disagree and the parts sum to p +- one fp16 ulp, up to 2^-11 p
+                 * (tests/test_gpu_attention_tiles.py, T = 16). */
+                if (NPL == 2)
+                    asm("" : "+v"(p));
+                s[j][r] = p;
+            }
 
         /* All NKT shares of V_n landed?  (Arrivals were posted at least one MFMA phase
          * ago; this poll normally passes at once.) */
