@@ -427,6 +427,59 @@ int vit_attn_sizes(const vit_config *cfg, const vit_attn_spec *spec, size_t *hea
 int vit_hip_set_attention(vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *d_bufs);
 int vit_hip_set_attention_host(vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *h_bufs);
 
+/* ---- attention rollout: the class token's relevance over the patches through all layers (Abnar & Zuidema, 2020) ----
+ * A rollout request is ARMED on a context like a feature, a top-k or an attention request, and independently of them (all
+ * four may be armed at once).  While armed, every forward through the context also forms, for every layer from
+ * first_layer on, the head-averaged attention matrix of that layer, mixes it half and half with the identity for the
+ * residual branch, multiplies it into a running T x T product per image, and writes the class token's row of the final
+ * product: one or two extra launches per layer between the layer's QKV projection and its attention
+ * (vh_launch_rollout_step, csrc/rollout.hip) and one behind the last layer (vh_launch_rollout_read), all timed under
+ * VIT_OP_ATTENTION.  They read the Q|K|V buffer the projection has just completed; no attention kernel is involved, and
+ * logits, probabilities, features, top-k and attention-map outputs are bit-identical to a forward without rollout armed.
+ * A context that has never been armed, or has been disarmed, launches exactly what it launched before.
+ * Definition.  For image i and layer l, with D = embed_dim / num_heads, Q and K THE VALUES LAYER l'S Q|K|V BUFFER HOLDS IN
+ * THIS CONTEXT'S PLAN decoded exactly to fp32 (the three stored forms of the attention maps above), and `first` =
+ * first_layer resolved to a 0-based layer index:
+ *     s_h[u][t]  = (1/sqrt(D)) * sum_d Q[i*T+u][h*D+d] * K[i*T+t][h*D+d]      u, t in [0, T)
+ *     P_h[u][t]  = exp(s_h[u][t] - max_t s_h[u][.]) / sum_t exp(s_h[u][t] - max_t s_h[u][.])
+ *     A_l[u][t]  = (sum over h ascending of P_h[u][t], in fp32) / (float)H
+ *     R_first    = 0.5 * A_first + 0.5 * I
+ *     R_l        = 0.5 * (A_l . R_{l-1}) + 0.5 * R_{l-1}                        l = first+1 .. depth-1
+ *     rollout[i][t] = R_{depth-1}[0][t]
+ * All arithmetic is fp32 (the two products on the fp32-input matrix instruction, an exact k-ordered fma chain); every sum
+ * runs in an order fixed by (T, H, D, stored form) alone.  No floating-point atomics: an image's output is bit-identical
+ * wherever it sits in the batch and whatever n is.  Every R_l is row-stochastic and non-negative, so rollout[i] sums to 1.
+ * Key 0 is the class token's own weight; keys 1 .. T-1, viewed as [g][g] (g = img / patch), are the map.  Like the
+ * attention maps this is defined on the stored Q|K|V; it is NOT the probabilities any attention kernel forms internally.
+ * Against the definition evaluated in double on the same Q and K a value errs by at most
+ * rollout * 2^-24 * sum over l of (4 (D + 2) S_l + 2 T + H + 70), S_l = the largest sum_d |q_d k_d| / sqrt(D) of layer l.
+ * first_layer: 0-based, or negative from the end, in [-depth, depth).  0 is the standard rollout; a later start discards
+ * the early layers (-1: 0.5 * the last layer's head-mean class row + 0.5 at key 0).
+ * Output: rollout [n][T] fp32.  Scratch: the two running products and the workspace of a step, 3 * max_batch * T * T * 4
+ * bytes of device memory (ViT-B/16 at max_batch 512: 3 x 79 MB; vit_h_14_518 at 64: 3 x 480 MB), allocated when the request
+ * is armed and freed when it is disarmed or the context destroyed; if it cannot be allocated, arming is refused.
+ * Device form (vit_hip_set_rollout): a device buffer [max_batch][T], 16-byte aligned, written asynchronously on the
+ * forward's stream by vit_hip_forward_device, _device_u8, _device_u8_resized and _device_u8_boxes.  Host form
+ * (vit_hip_set_rollout_host): a host buffer for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized / _u8_boxes
+ * calls (each call writes from image 0), across chunks, complete on return; its staging (a device buffer and two pinned
+ * slots of max_batch images) is allocated when it is armed.
+ * spec == NULL disarms.  Arming one form disarms the other; a device-form forward while the host form is armed (and the
+ * reverse) is refused with code 1 and a message, no launch.  Code 1 with a message also for: NULL ctx, first_layer outside
+ * [-depth, depth), a NULL buffer, a misaligned device buffer, a head_dim that is not a multiple of 16 or exceeds 128,
+ * embed_dim % 32 != 0 in a plan that stores Q|K|V as planes, more tokens than the kernel takes
+ * (vh_rollout_max_tokens(head_dim): 1856 at head_dim 128), scratch that cannot be allocated -- all when the request is
+ * armed, not at the first forward.  A refused call leaves the previous request armed.
+ * vit_hip_set_last_layer_cls_only does not matter here: the last layer's Q|K|V is complete before its attention either way.
+ * vit_hip_multi: a context from vit_hip_multi_ctx may be armed for the device forms like any other; vit_hip_forward_multi
+ * and vit_hip_forward_device_multi neither write rollouts nor refuse. */
+typedef struct vit_rollout_spec { int first_layer; } vit_rollout_spec;
+typedef struct vit_rollout_buffers { float *rollout; } vit_rollout_buffers;   /* [n][T] fp32 */
+/* host only, no device: validates spec against cfg; ELEMENTS PER IMAGE of the output (T) and the BYTES PER IMAGE of
+ * max_batch of the device scratch an armed request holds (3 * T * T * 4); each pointer may be NULL; 0, or 1 with a message */
+int vit_rollout_sizes(const vit_config *cfg, const vit_rollout_spec *spec, size_t *rollout_elems, size_t *scratch_bytes_per_image);
+int vit_hip_set_rollout(vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *d_bufs);
+int vit_hip_set_rollout_host(vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *h_bufs);
+
 /* Debug hook: copy the residual stream left by the last forward ([n*tokens][embed], un-normalised; rows other than the
  * class tokens are stale under vit_hip_set_last_layer_cls_only) to the host.  The supported interface to the encoder's
  * output is vit_hip_set_features above. */

@@ -310,6 +310,26 @@ int vh_cls_attention_head_dim_ok(int head_dim);
 int vh_launch_cls_attention(vh_stream_t s, const void *qkv, int qkv_form, int n_images, int tokens, int embed_dim,
                             int num_heads, int tap_index, int n_taps, float *heads, float *mean);
 
+/* Attention rollout, one layer at a time (csrc/rollout.hip; the kernels under vit_hip_set_rollout, include/ViT_opencl.h,
+ * which states the definition).  A step forms A, the head-mean attention matrix [tokens][tokens] of every image, from one
+ * layer's Q|K|V (qkv and qkv_form as vh_launch_cls_attention takes them, every query row instead of the class row), and
+ * folds it into the running product, all [n_images][tokens][tokens] fp32:
+ *   r_prev == NULL   r_next = 0.5 A + 0.5 I                        (one launch)
+ *   otherwise        r_next = 0.5 (A . r_prev) + 0.5 r_prev        (two launches; A goes through `workspace`)
+ * workspace: vh_rollout_workspace(n_images, tokens) bytes, = one such buffer, needed by every step (the running sum over
+ * heads lives there).  r_prev, r_next and workspace are three different buffers; r_prev is only read.  fp32 arithmetic on
+ * the fp32-input matrix instruction (an exact k-ordered fma chain); every sum runs in an order fixed by (tokens,
+ * num_heads, head_dim, form); no atomics: an image's rows are the same bits wherever it sits in the batch.  Rows of every
+ * result are non-negative and sum to 1.  head_dim a multiple of 16, at most 128; embed_dim % 32 == 0 for the planes
+ * forms; pointers 16-byte aligned; 1 <= tokens <= vh_rollout_max_tokens(head_dim) (the score rows of 16 queries stay in
+ * LDS: 1856 at head_dim 128, 2176 at 64).  Anything else: code 1 with a message, no launch.
+ * vh_launch_rollout_read: out[i][t] = r[i][0][t], the class token's row, [n_images][tokens], bit for bit. */
+size_t vh_rollout_workspace(int n_images, int tokens);
+int vh_rollout_max_tokens(int head_dim);
+int vh_launch_rollout_step(vh_stream_t s, const void *qkv, int qkv_form, int n_images, int tokens, int embed_dim, int num_heads,
+                           const float *r_prev /* NULL: identity */, float *r_next, void *workspace);
+int vh_launch_rollout_read(vh_stream_t s, const float *r, int n_images, int tokens, float *out /* [n][T] = row 0 */);
+
 /* ---- reduced-precision attention (the bf16- and fp8-operand modes, BASELINE configs 3 and 5) ----
  * fp32 in, fp32 out; Q, K, V and P rounded to fp16 for the two products (11-bit operands, fp32 accumulation and
  * softmax): far inside those modes' tolerances.  The bf16-operand mode itself runs on one-part planes:

@@ -142,6 +142,19 @@ struct vit_hip_ctx
     } amap;
     const struct attn_req *attn_serving;
 
+    /* rollout request (vit_hip_set_rollout / _host), armed independently of the other three; `roll_serving` as
+     * `attn_serving`.  The scratch is held while armed. */
+    struct rollout_req
+    {
+        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
+        vit_rollout_spec spec;
+        int first;                   /* spec.first_layer resolved */
+        vit_rollout_buffers out;     /* FEAT_DEVICE: the caller's device buffer; FEAT_HOST: st[0].dev */
+        struct staged st[2];         /* FEAT_HOST: rollout; st[1] unused */
+        void *scratch[3];            /* the running product ping-pongs between [0] and [1]; [2]: a step's workspace */
+    } roll;
+    const struct rollout_req *roll_serving;
+
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
     int *prof_class;       /* operator class per recorded launch */
@@ -240,7 +253,8 @@ static void staged_scatter(const struct staged *st, int slot, int first, int m)
     memcpy(st->host + (size_t)first * st->per_image, st->pinned[slot], (size_t)m * st->per_image);
 }
 
-/* The staging of a host-form request: feature (cls, pooled), top-k (labels, scores) or attention maps (heads, mean) */
+/* The staging of a host-form request: feature (cls, pooled), top-k (labels, scores), attention maps (heads, mean) or
+ * rollout (rollout, none) */
 static void request_release(struct staged st[2])
 {
     staged_release(&st[0]);
@@ -260,6 +274,10 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     request_release(ctx->feat.st);
     request_release(ctx->topk.st);
     request_release(ctx->amap.st);
+    request_release(ctx->roll.st);
+    for (int k = 0; k < 3; ++k)
+        if (ctx->roll.scratch[k])
+            vh_free(ctx->roll.scratch[k]);
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
@@ -729,13 +747,19 @@ static int attention_tap(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
 {
     int rc = 0;
     const struct attn_req *ar = ctx->attn_serving;
-    if (!ar)
-        return 0;
+    const struct rollout_req *ro = ctx->roll_serving;
     const vit_config *c = &ctx->cfg;
-    for (int k = 0; k < ar->spec.n_taps; ++k)
+    for (int k = 0; ar && k < ar->spec.n_taps; ++k)
         if (ar->layer[k] == l)
             OP(VIT_OP_ATTENTION, vh_launch_cls_attention(s, ctx->qkv, ctx->plan.qkv_form, n, ctx->plan.tokens, c->embed_dim, c->num_heads, k,
                                                          ar->spec.n_taps, ar->out.heads, ar->out.mean));
+    /* the armed rollout request: this layer's head-mean attention matrix folded into the running product, which
+     * ping-pongs between the request's two buffers (csrc/rollout.hip); forward_device reads the class row behind the last
+     * layer */
+    if (ro && l >= ro->first)
+        OP(VIT_OP_ATTENTION, vh_launch_rollout_step(s, ctx->qkv, ctx->plan.qkv_form, n, ctx->plan.tokens, c->embed_dim, c->num_heads,
+                                                    l == ro->first ? NULL : (const float *)ro->scratch[(l - ro->first + 1) & 1],
+                                                    (float *)ro->scratch[(l - ro->first) & 1], ro->scratch[2]));
     return 0;
 fail:
     return rc;
@@ -1020,14 +1044,16 @@ fail:
     return rc;
 }
 
-/* Everything after the argument checks of the forwards.  fr, tk, ar: the armed feature / top-k / attention-map request to
- * serve, or NULL. */
+/* Everything after the argument checks of the forwards.  fr, tk, ar, ro: the armed feature / top-k / attention-map /
+ * rollout request to serve, or NULL. */
 static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
-                          const struct feature_req *fr, const struct topk_req *tk, const struct attn_req *ar)
+                          const struct feature_req *fr, const struct topk_req *tk, const struct attn_req *ar,
+                          const struct rollout_req *ro)
 {
     int rc = 0;
     const int cls_only_saved = ctx->plan.cls_only_last;
     ctx->attn_serving = ar;   /* read by the layer functions (attention_tap) */
+    ctx->roll_serving = ro;
     TRY(vh_set_device(ctx->device));   /* the current device is per host thread */
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, T = ctx->plan.tokens, NC = c->num_classes;
@@ -1061,6 +1087,9 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
     }
     ctx->plan.cls_only_last = cls_only_saved;
     ctx->attn_serving = NULL;
+    ctx->roll_serving = NULL;
+    if (ro)   /* the class token's row of the last product */
+        OP(VIT_OP_ATTENTION, vh_launch_rollout_read(s, (const float *)ro->scratch[(c->depth - 1 - ro->first) & 1], n, T, ro->out.rollout));
 
     /* final LayerNorm on the class-token rows -- row i * stride of the residual stream, or compacted at the start of the
      * Q|K|V buffer -- classifier, softmax (ViT_seq.c:506-515) */
@@ -1079,6 +1108,7 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
 fail:
     ctx->plan.cls_only_last = cls_only_saved;
     ctx->attn_serving = NULL;
+    ctx->roll_serving = NULL;
     return rc;
 }
 
@@ -1086,16 +1116,18 @@ fail:
  * FEAT_NONE for a call that serves nothing, whatever is armed.  A request armed in the other form refuses the call, the
  * feature request first. */
 static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const struct feature_req **fr, const struct topk_req **tk,
-                          const struct attn_req **ar)
+                          const struct attn_req **ar, const struct rollout_req **ro)
 {
-    static const char *const what[3] = {"feature", "top-k", "attention"}, *const setter[3] = {"features", "topk", "attention"};
-    const int armed[3] = {ctx->feat.form, ctx->topk.form, ctx->amap.form};
+    static const char *const what[4] = {"feature", "top-k", "attention", "rollout"},
+                      *const setter[4] = {"features", "topk", "attention", "rollout"};
+    const int armed[4] = {ctx->feat.form, ctx->topk.form, ctx->amap.form, ctx->roll.form};
     *fr = NULL;
     *tk = NULL;
     *ar = NULL;
+    *ro = NULL;
     if (form == FEAT_NONE)
         return 0;
-    for (int r = 0; r < 3; ++r)
+    for (int r = 0; r < 4; ++r)
         if (armed[r] != FEAT_NONE && armed[r] != form) {
             char msg[200];
             const char *const is = armed[r] == FEAT_HOST ? "host" : "device";
@@ -1106,6 +1138,7 @@ static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const str
     *fr = armed[0] == form ? &ctx->feat : NULL;
     *tk = armed[1] == form ? &ctx->topk : NULL;
     *ar = armed[2] == form ? &ctx->amap : NULL;
+    *ro = armed[3] == form ? &ctx->roll : NULL;
     return 0;
 }
 
@@ -1132,9 +1165,10 @@ static int forward_device_armed(vit_hip_ctx *ctx, const char *who, const struct 
     const struct feature_req *fr;
     const struct topk_req *tk;
     const struct attn_req *ar;
-    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar))
+    const struct rollout_req *ro;
+    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar, &ro))
         return 1;
-    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar);
+    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar, ro);
 }
 
 /* vit_hip_forward_device with no feature output whatever is armed (vit_gather_rccl.c) */
@@ -1143,7 +1177,7 @@ int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n,
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
     const struct ingest_src src = {.kind = INGEST_F32, .on_device = 1, .f32 = d_images};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL, NULL);
 }
 
 int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
@@ -1441,6 +1475,106 @@ int vit_hip_set_attention_host(vit_hip_ctx *ctx, const vit_attn_spec *spec, cons
     return set_attention("vit_hip_set_attention_host", ctx, spec, h_bufs, 1);
 }
 
+/* spec against cfg; first_layer resolved to a layer index */
+static int rollout_spec_check(const char *who, const vit_config *cfg, const vit_rollout_spec *spec, int *first)
+{
+    const char *why = !cfg || !spec ? "NULL argument"
+                      : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ||
+                        cfg->num_heads <= 0 || cfg->embed_dim % cfg->num_heads != 0 ? "bad model config"
+                      : spec->first_layer < -cfg->depth || spec->first_layer >= cfg->depth ? "first_layer lies outside [-depth, depth)"
+                      : NULL;
+    if (why)
+        return ingest_refuse(who, why);
+    *first = spec->first_layer < 0 ? spec->first_layer + cfg->depth : spec->first_layer;
+    return 0;
+}
+
+int vit_rollout_sizes(const vit_config *cfg, const vit_rollout_spec *spec, size_t *rollout_elems, size_t *scratch_bytes_per_image)
+{
+    int first;
+    if (rollout_spec_check("vit_rollout_sizes", cfg, spec, &first))
+        return 1;
+    const size_t T = (size_t)vit_config_tokens(cfg);
+    if (rollout_elems)
+        *rollout_elems = T;
+    if (scratch_bytes_per_image)
+        *scratch_bytes_per_image = 3 * T * T * sizeof(float);
+    return 0;
+}
+
+static void rollout_scratch_free(void *scratch[3])
+{
+    for (int k = 0; k < 3; ++k) {
+        if (scratch[k])
+            vh_free(scratch[k]);
+        scratch[k] = NULL;
+    }
+}
+
+/* Both forms of arming, as set_features; the scratch (two running products and a step's workspace, of max_batch images
+ * each) is made with the first request and kept until the context is disarmed or destroyed */
+static int set_rollout(const char *who, vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *bufs, int host)
+{
+    struct rollout_req ro;
+    int fresh = 0;   /* this call made the scratch */
+    memset(&ro, 0, sizeof ro);
+    if (ctx && spec) {
+        if (rollout_spec_check(who, &ctx->cfg, spec, &ro.first))
+            return 1;
+        const vit_config *c = &ctx->cfg;
+        const int D = c->embed_dim / c->num_heads;
+        const char *why = !bufs || !bufs->rollout ? "no output buffer"
+                          : !vh_cls_attention_head_dim_ok(D) ? "head_dim must be a multiple of 16, at most 128"
+                          : ctx->plan.qkv_form != VH_QKV_ROWS_F32 && c->embed_dim % 32 != 0 ? "embed_dim must be a multiple of 32 where Q|K|V is stored as planes"
+                          : ctx->plan.tokens > vh_rollout_max_tokens(D) ? "too many tokens for the rollout kernel at this head_dim (vh_rollout_max_tokens)"
+                          : !host && ((uintptr_t)bufs->rollout & 15) ? "device buffers must be 16-byte aligned"
+                          : NULL;
+        if (why)
+            return ingest_refuse(who, why);
+        ro.form = host ? FEAT_HOST : FEAT_DEVICE;
+        ro.spec = *spec;
+        ro.out = *bufs;
+        if (host)
+            ro.st[0] = (struct staged){.host = (char *)bufs->rollout, .per_image = (size_t)ctx->plan.tokens * sizeof(float)};
+        memcpy(ro.scratch, ctx->roll.scratch, sizeof ro.scratch);
+        if (!ro.scratch[0]) {
+            const size_t one = vh_rollout_workspace(ctx->max_batch, ctx->plan.tokens);
+            int bad = vh_set_device(ctx->device);
+            for (int k = 0; k < 3 && !bad; ++k)
+                bad = vh_malloc(&ro.scratch[k], one);
+            if (bad) {
+                char msg[160];
+                rollout_scratch_free(ro.scratch);
+                snprintf(msg, sizeof msg, "3 x %zu bytes of device scratch (max_batch x T x T x 4 each) cannot be allocated", one);
+                return ingest_refuse(who, msg);
+            }
+            fresh = 1;
+        }
+    }
+    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, roll.st), ro.st);
+    if (rc != 0) {
+        if (fresh)
+            rollout_scratch_free(ro.scratch);
+        return rc;
+    }
+    if (ro.form == FEAT_NONE)   /* disarmed: behind arm()'s stream sync nothing reads the scratch any more */
+        rollout_scratch_free(ctx->roll.scratch);
+    if (ro.form == FEAT_HOST)
+        ro.out = (vit_rollout_buffers){ro.st[0].dev};
+    ctx->roll = ro;
+    return 0;
+}
+
+int vit_hip_set_rollout(vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *d_bufs)
+{
+    return set_rollout("vit_hip_set_rollout", ctx, spec, d_bufs, 0);
+}
+
+int vit_hip_set_rollout_host(vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *h_bufs)
+{
+    return set_rollout("vit_hip_set_rollout_host", ctx, spec, h_bufs, 1);
+}
+
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
 {
     if (!ctx)
@@ -1472,7 +1606,8 @@ int vit_hip_profile_enable(vit_hip_ctx *ctx, int max_forwards)
     prof_release(ctx);
     if (max_forwards <= 0)
         return 0;
-    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4;   /* + the readouts of an armed feature request + top-k + attention maps */
+    /* + the readouts of an armed feature request + top-k + attention maps + the rollout's steps and read */
+    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4 + ctx->cfg.depth + 1;
     ctx->prof_cap = per_forward * max_forwards;
     ctx->prof_ev = (vh_event_t *)calloc((size_t)2 * ctx->prof_cap, sizeof(vh_event_t));
     ctx->prof_class = (int *)calloc((size_t)ctx->prof_cap, sizeof(int));
@@ -1605,21 +1740,23 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, str
     const struct feature_req *fr;
     const struct topk_req *tk;
     const struct attn_req *ar;
-    if (armed_requests(ctx, "forward", form, &fr, &tk, &ar))
+    const struct rollout_req *ro;
+    if (armed_requests(ctx, "forward", form, &fr, &tk, &ar, &ro))
         return 1;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->kind == INGEST_F32 ? sizeof(float) : 1);
     const size_t NC = (size_t)c->num_classes;
     /* what comes back per chunk besides the probabilities, in the order it is queued: logits, cls, pooled, labels, scores,
-     * heads, mean */
+     * heads, mean, rollout */
     const struct staged logits_st = {ctx->d_logits, {ctx->h_logits[0], ctx->h_logits[1]}, (char *)logits, NC * sizeof(float)};
-    const struct staged *arrays[7];
+    const struct staged *arrays[8];
     int n_arrays = 0;
     if (logits)
         arrays[n_arrays++] = &logits_st;
-    for (int a = 0; a < 6; ++a) {
-        const struct staged *st = a < 2 ? (fr ? &fr->st[a] : NULL) : a < 4 ? (tk ? &tk->st[a - 2] : NULL) : (ar ? &ar->st[a - 4] : NULL);
+    for (int a = 0; a < 7; ++a) {
+        const struct staged *st = a < 2 ? (fr ? &fr->st[a] : NULL) : a < 4 ? (tk ? &tk->st[a - 2] : NULL)
+                                  : a < 6 ? (ar ? &ar->st[a - 4] : NULL) : (ro ? &ro->st[0] : NULL);
         if (st && st->dev)
             arrays[n_arrays++] = st;
     }
@@ -1661,7 +1798,7 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, str
         TRY(vh_event_record(ctx->up_done[s], ctx->copy_stream));
 
         TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
-        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar));
+        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar, ro));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
         int a = 0;

@@ -23,46 +23,13 @@
  * (w0 + w1) + (w2 + w3) -- a function of T alone.  No atomics.
  */
 #include "kernelHandler.h"
+#include "qkv_forms.h"
 #include "vit_kernels.h"
 
 namespace {
 
 constexpr int AM_THREADS = 256;
-constexpr int AM_MAX_HEAD_DIM = 128;
-
-typedef _Float16 am_half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 am_bf16x8 __attribute__((ext_vector_type(8)));
-
-/* per form: columns per piece, lanes per key, pieces a lane can own at head_dim 128 */
-template <int FORM> struct AmForm { static constexpr int PIECE = 8, LPK = 4, MAXP = AM_MAX_HEAD_DIM / 8 / 4; };
-template <> struct AmForm<VH_QKV_ROWS_F32> { static constexpr int PIECE = 4, LPK = 16, MAXP = AM_MAX_HEAD_DIM / 4 / 16; };
-
-/* PIECE columns of row `row` from column `col` (a multiple of PIECE), decoded exactly to fp32 */
-template <int FORM>
-__device__ __forceinline__ void load_piece(const char *__restrict__ qkv, size_t rows, int row_floats, size_t row, int col, float *out)
-{
-    if constexpr (FORM == VH_QKV_ROWS_F32) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(qkv + (row * (size_t)row_floats + (size_t)col) * sizeof(float));
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            out[e] = v[e];
-    } else if constexpr (FORM == VH_QKV_PLANES3) {
-        const char *src = qkv + ((size_t)(col >> 5) * 3 * rows + row) * 64 + (size_t)(col & 31) * 2;
-        am_bf16x8 part[3];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-            part[pl] = __builtin_bit_cast(am_bf16x8, *reinterpret_cast<const f32x4 *>(src + (size_t)pl * rows * 64));
-#pragma unroll
-        for (int e = 0; e < 8; ++e)   /* exact: the parts are disjoint slices of one 24-bit significand */
-            out[e] = ((float)part[0][e] + (float)part[1][e]) + (float)part[2][e];
-    } else {
-        const char *src = qkv + ((size_t)(col >> 5) * rows + row) * 64 + (size_t)(col & 31) * 2;
-        const am_half8 v = __builtin_bit_cast(am_half8, *reinterpret_cast<const f32x4 *>(src));
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-            out[e] = (float)v[e];
-    }
-}
+/* AmForm<FORM> and load_piece<FORM>, the piece loaders per stored form: qkv_forms.h */
 
 __device__ __forceinline__ float am_wave_max(float v)
 {

@@ -69,6 +69,8 @@ EXPORTS = [
     "vh_launch_topk", "vit_topk_check", "vit_hip_set_topk", "vit_hip_set_topk_host", "vit_write_result_file_topk",
     "vh_cls_attention_head_dim_ok", "vh_launch_cls_attention", "vit_attn_sizes", "vit_hip_set_attention",
     "vit_hip_set_attention_host",
+    "vh_rollout_workspace", "vh_rollout_max_tokens", "vh_launch_rollout_step", "vh_launch_rollout_read", "vit_rollout_sizes",
+    "vit_hip_set_rollout", "vit_hip_set_rollout_host",
 ]
 
 # include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
@@ -212,6 +214,36 @@ def attention_sizes(cfg: "VitConfig", spec: AttentionSpec):
     out = [C.c_size_t() for _ in range(2)]
     cs = spec.c_struct()
     check(lib().vit_attn_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_attn_sizes")
+    return tuple(o.value for o in out)
+
+
+class RolloutSpecC(C.Structure):
+    """`vit_rollout_spec` (include/ViT_opencl.h)."""
+
+    _fields_ = [("first_layer", C.c_int)]
+
+
+class RolloutBuffers(C.Structure):
+    """`vit_rollout_buffers` (include/ViT_opencl.h): a device or host pointer."""
+
+    _fields_ = [("rollout", C.c_void_p)]
+
+
+class RolloutSpec:
+    """A rollout request: the first layer of the product (0-based or negative from the end; 0 is the standard rollout)."""
+
+    def __init__(self, first_layer: int = 0):
+        self.first_layer = int(first_layer)
+
+    def c_struct(self) -> RolloutSpecC:
+        return RolloutSpecC(self.first_layer)
+
+
+def rollout_sizes(cfg: "VitConfig", spec: RolloutSpec):
+    """vit_rollout_sizes -> (rollout elements per image, device scratch bytes per image of max_batch)"""
+    out = [C.c_size_t() for _ in range(2)]
+    cs = spec.c_struct()
+    check(lib().vit_rollout_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_rollout_sizes")
     return tuple(o.value for o in out)
 
 
@@ -544,6 +576,15 @@ def lib() -> C.CDLL:
     L.vit_attn_sizes.argtypes = [C.POINTER(VitConfig), asp, szp, szp]
     L.vit_hip_set_attention.argtypes = [voidp, asp, abp]
     L.vit_hip_set_attention_host.argtypes = [voidp, asp, abp]
+    L.vh_rollout_workspace.argtypes = [i, i]
+    L.vh_rollout_workspace.restype = sz
+    L.vh_rollout_max_tokens.argtypes = [i]
+    L.vh_launch_rollout_step.argtypes = [voidp, voidp] + [i] * 5 + [voidp, voidp, voidp]
+    L.vh_launch_rollout_read.argtypes = [voidp, voidp, i, i, voidp]
+    rsp, rbp = C.POINTER(RolloutSpecC), C.POINTER(RolloutBuffers)
+    L.vit_rollout_sizes.argtypes = [C.POINTER(VitConfig), rsp, szp, szp]
+    L.vit_hip_set_rollout.argtypes = [voidp, rsp, rbp]
+    L.vit_hip_set_rollout_host.argtypes = [voidp, rsp, rbp]
     _lib = L
     return L
 
@@ -890,6 +931,31 @@ class ViTHip:
         finally:
             self.set_attention_host(None)
         return logits, heads, mean
+
+    def set_rollout(self, spec, rollout=None):
+        """Arm (spec=None: disarm) the device form: rollout [max_batch][T] is a float32 DeviceBuffer (or device pointer),
+        written by every forward_device* until disarmed."""
+        self._arm("vit_hip_set_rollout", spec, RolloutBuffers, (rollout,), _device_ptr, "_rollout_keep")
+
+    def set_rollout_host(self, spec, rollout=None):
+        """Arm (spec=None: disarm) the host form: rollout [n][T] is a C-contiguous float32 NumPy array for all n images of
+        the coming forward / forward_u8 / forward_u8_resized / forward_u8_boxes calls."""
+        if spec is not None and rollout is not None and not (isinstance(rollout, np.ndarray) and rollout.flags.c_contiguous
+                                                              and rollout.dtype == np.float32):
+            raise ValueError("set_rollout_host: need a C-contiguous float32 array")
+        self._arm("vit_hip_set_rollout_host", spec, RolloutBuffers, (rollout,), _host_ptr, "_rollout_keep")
+
+    def rollout(self, images: np.ndarray, first_layer: int = 0):
+        """fp32 images [n][C][H][W] -> rollout [n][T]: the class token's row of the attention rollout from first_layer on,
+        the host form armed for this one call."""
+        images = np.ascontiguousarray(images, dtype=np.float32)
+        out = np.empty((images.shape[0], self.tokens), dtype=np.float32)
+        self.set_rollout_host(RolloutSpec(first_layer), rollout=out)
+        try:
+            self.forward(images)
+        finally:
+            self.set_rollout_host(None)
+        return out
 
     def read_tokens(self, n: int) -> np.ndarray:
         out = np.empty((n * self.tokens, self.cfg.embed_dim), dtype=np.float32)
