@@ -480,6 +480,65 @@ int vit_rollout_sizes(const vit_config *cfg, const vit_rollout_spec *spec, size_
 int vit_hip_set_rollout(vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *d_bufs);
 int vit_hip_set_rollout_host(vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *h_bufs);
 
+/* ---- gallery search: the k nearest entries of a gallery of embeddings the caller holds in device memory ----
+ * A gallery request is ARMED on a context like a feature, a top-k, an attention or a rollout request, and independently of
+ * them (all five may be armed at once).  While armed, every forward through the context also reads one embedding per
+ * image behind layer `tap` and writes, per image, the k rows of the gallery with the largest inner product with it and
+ * (optionally) those inner products: retrieval and k-NN classification without the [n][E] embeddings or an n x G product
+ * crossing PCIe.  Three extra launches behind the tapped layer (vh_launch_feature_readout, then vh_launch_gallery_topk's
+ * two, csrc/gallery.hip), all timed under VIT_OP_HEAD; logits, probabilities, features, top-k, attention maps and rollout
+ * are bit-identical to a forward without a gallery armed.  A context that has never been armed, or has been disarmed,
+ * launches exactly what it launched before.
+ * The query of image i is BY DEFINITION the vector vit_hip_set_features writes for {n_taps = 1, taps = {tap}, final_norm,
+ * l2_normalize, VIT_FEATURE_F32} as `cls` (VIT_GALLERY_CLS) or `pooled` (VIT_GALLERY_POOLED), bit for bit; it is produced
+ * by the same kernel into a [max_batch][E] fp32 buffer the context holds while armed.  The gallery rows are used as given:
+ * a caller who wants cosine similarity stores unit rows (what l2_normalize = 1 features are) and sets l2_normalize.
+ * score, ranking, indices and scores: as vh_launch_gallery_topk defines them (include/kernelHandler.h) -- score(i, r) =
+ * sum_d query_i[d] * row_r[d] as one fp32 fma chain in an order fixed by embed_dim alone, within (E + 8) * 2^-24 * sum_d
+ * |q_d g_d| of the exact product; by score descending, equal scores by ascending row index, NaN last; an image's result is
+ * the same bits wherever it sits in the batch and whatever n is.
+ * spec: tap is one layer, 0-based or negative from the end (-1 = the last), in [-depth, depth); k in 1..32, k <= n_rows
+ * <= 2^31 - 1; dtype VH_GALLERY_F32 or VH_GALLERY_BF16 rows of embed_dim elements, row_stride elements apart (row_stride
+ * >= embed_dim, row_stride * element size a multiple of 16); d_rows device memory of the context's device, 16-byte
+ * aligned, the CALLER'S, valid and unchanged while armed; embed_dim % 4 == 0, <= 2048.
+ * Output: indices [n][k] int32 and scores [n][k] fp32 (scores may be NULL).  Scratch: the queries and the search's
+ * workspace, per image of max_batch embed_dim * 4 + min(VH_GALLERY_MAX_SPLITS, ceil(n_rows / 128)) * k * 8 bytes of device
+ * memory (ViT-B/16, k = 5, a million rows: 44 KB; k = 32: 265 KB), allocated when the request is armed and freed when it is
+ * disarmed or the context destroyed; if it cannot be allocated, arming is refused.
+ * Device form (vit_hip_set_gallery): device buffers [max_batch][k], 16-byte aligned, written asynchronously on the
+ * forward's stream by vit_hip_forward_device, _device_u8, _device_u8_resized and _device_u8_boxes.  Host form
+ * (vit_hip_set_gallery_host): host buffers for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized / _u8_boxes
+ * calls (each call writes from image 0), across chunks, complete on return; its staging (device buffers and two pinned
+ * slots of max_batch images) is allocated when it is armed.
+ * spec == NULL disarms.  Arming one form disarms the other; a device-form forward while the host form is armed (and the
+ * reverse) is refused with code 1 and a message, no launch.  Code 1 with a message also for: NULL ctx, a source, tap, k,
+ * dtype, n_rows or row_stride outside the above, an embed_dim the search does not take, POOLED on a model without patch
+ * tokens, NULL or misaligned d_rows, no indices buffer, a misaligned device buffer, scratch that cannot be allocated -- all
+ * when the request is armed, not at the first forward.  A refused call leaves the previous request armed.
+ * Under vit_hip_set_last_layer_cls_only: cls of the last layer reads the compacted class rows; pooled of the last layer
+ * makes that forward run the last layer on all rows, as a feature request for pooled does; logits are bit-identical either
+ * way.
+ * vit_hip_multi: a context from vit_hip_multi_ctx may be armed for the device forms like any other; vit_hip_forward_multi
+ * and vit_hip_forward_device_multi neither write gallery results nor refuse.
+ * Out of scope: gallery labels and voting (a one-line lookup on the indices), projection heads of another width (CLIP),
+ * approximate search, galleries sharded over several GPUs. */
+enum { VIT_GALLERY_CLS = 0, VIT_GALLERY_POOLED = 1 };
+typedef struct vit_gallery_spec {
+    int source;        /* VIT_GALLERY_CLS | VIT_GALLERY_POOLED */
+    int tap;           /* one layer, as a vit_feature_spec tap; -1 = the last */
+    int final_norm, l2_normalize;   /* as vit_feature_spec */
+    int k;
+    int dtype;         /* VH_GALLERY_* */
+    long n_rows, row_stride;
+    const void *d_rows;             /* device memory, the caller's, valid while armed */
+} vit_gallery_spec;
+typedef struct vit_gallery_buffers { int *indices; float *scores; } vit_gallery_buffers;   /* scores may be NULL */
+/* host only, no device: validates spec against cfg (everything above but the pointers); the BYTES PER IMAGE of max_batch of
+ * the device scratch an armed request holds; the pointer may be NULL; 0, or 1 with a message */
+int vit_gallery_check(const vit_config *cfg, const vit_gallery_spec *spec, size_t *scratch_bytes_per_max_batch_image);
+int vit_hip_set_gallery(vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *d_bufs);
+int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *h_bufs);
+
 /* Debug hook: copy the residual stream left by the last forward ([n*tokens][embed], un-normalised; rows other than the
  * class tokens are stale under vit_hip_set_last_layer_cls_only) to the host.  The supported interface to the encoder's
  * output is vit_hip_set_features above. */

@@ -495,6 +495,41 @@ int vh_launch_feature_readout(vh_stream_t s, const float *x, const float *cls_ro
                               int n_images, int tokens, int embed_dim, int tap_index, int n_taps, void *cls, void *pooled,
                               void *tokens_out, void *scratch, size_t scratch_bytes);
 
+/* Gallery search (csrc/gallery.hip; the kernels under vit_hip_set_gallery, include/ViT_opencl.h): for every query the k
+ * rows of a gallery with the largest inner product, selected while the gallery streams by -- the n_queries x n_rows score
+ * matrix never exists.  queries [n_queries][embed_dim] fp32, contiguous; rows [n_rows] vectors of embed_dim elements,
+ * row_stride elements apart, fp32 or bf16 (bf16 is decoded exactly to fp32 as it is loaded).
+ * Definition.  score(i, r) = sum_d queries[i][d] * row_r[d], in fp32 on the fp32-input matrix instruction, as ONE fma chain
+ * from +0 in this order of d, fixed by embed_dim alone: for c = 0, 32, 64, ...; for j = 0, 1; for e = 0..3; for g = 0..3:
+ * d = c + 16 j + 4 g + e, where d >= embed_dim contributes fma(0, 0, x) = x.  The bits of score(i, r) depend on the two
+ * vectors only: not on r, on where i sits among the queries, on n_queries, n_rows, splits or dtype.  A sum that is NaN is
+ * returned as 0x7FC00000; a sum is never -0.  Against the exact dot product |error| <= (embed_dim + 8) * 2^-24 * sum_d
+ * |q_d g_d| (with u = 2^-24 a chain of E fma steps errs by at most E u / (1 - E u) <= (E + 2 E^2 u) u <= (E + 0.5) u of
+ * that sum at E <= 2048; the rest of the 8 is slack).
+ * Ranking: vh_launch_topk's rule and 64-bit key -- by score descending, equal scores (-0 == +0) by ascending row index,
+ * NaN below -inf, NaNs by ascending index.  indices[i][0..k) are distinct, in [0, n_rows), best first; scores[i][j] (may be
+ * NULL, which changes no index) are the bits of score(i, indices[i][j]).  The keys of one query are distinct, so the
+ * selected set does not depend on the order in which candidates arrive: integer LDS atomics only, no floating-point
+ * atomics, the same output on every run and for every `splits`.
+ * Two launches: one workgroup per (split of the gallery, tile of vh_gallery_query_tile(n_queries) = 16 or 128 queries)
+ * streams its rows once in tiles of VH_GALLERY_ROW_TILE and leaves its k best keys per query in `workspace`
+ * (vh_gallery_workspace bytes; splits = 0 there: a bound on whatever splits = 0 chooses here); one workgroup per query
+ * then reduces splits * k keys to k.  splits = 0: chosen from (n_queries, n_rows, CU count) so that a small batch still
+ * fills the machine (vh_gallery_splits); any other value gives the same bits.
+ * Limits: 1 <= k <= 32; k <= n_rows <= 2^31 - 1; embed_dim % 4 == 0, 4 <= embed_dim <= 2048; row_stride >= embed_dim and
+ * row_stride * element size a multiple of 16; every pointer 16-byte aligned; n_queries >= 1; 0 <= splits <=
+ * VH_GALLERY_MAX_SPLITS.  Anything else: code 1 with a message, no launch.  No reference counterpart. */
+enum { VH_GALLERY_F32 = 0, VH_GALLERY_BF16 = 1 };
+#define VH_GALLERY_MAX_SPLITS 1024
+#define VH_GALLERY_ROW_TILE 128
+int vh_gallery_query_tile(int n_queries);
+int vh_gallery_splits(int n_queries, long n_rows);   /* what splits = 0 launches on the current device */
+size_t vh_gallery_workspace(int n_queries, long n_rows, int k, int splits);   /* bytes */
+int vh_launch_gallery_topk(vh_stream_t s, const float *queries /* [n][E] fp32 */, int n_queries, int embed_dim,
+                           const void *rows, int dtype, long n_rows, long row_stride /* elements */,
+                           int k, int splits /* 0 = chosen by the launcher */, void *workspace,
+                           int *indices /* [n][k] */, float *scores /* [n][k], may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,18 @@ struct vit_hip_ctx
     } roll;
     const struct rollout_req *roll_serving;
 
+    /* gallery request (vit_hip_set_gallery / _host), armed independently of the other four.  The queries and the search's
+     * workspace are held while armed. */
+    struct gallery_req
+    {
+        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
+        vit_gallery_spec spec;
+        int layer;                   /* spec.tap resolved */
+        vit_gallery_buffers out;     /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: st[].dev */
+        struct staged st[2];         /* FEAT_HOST: indices, scores */
+        void *scratch[2];            /* [0]: the queries [max_batch][E] fp32; [1]: vh_launch_gallery_topk's workspace */
+    } gal;
+
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
     int *prof_class;       /* operator class per recorded launch */
@@ -253,8 +265,8 @@ static void staged_scatter(const struct staged *st, int slot, int first, int m)
     memcpy(st->host + (size_t)first * st->per_image, st->pinned[slot], (size_t)m * st->per_image);
 }
 
-/* The staging of a host-form request: feature (cls, pooled), top-k (labels, scores), attention maps (heads, mean) or
- * rollout (rollout, none) */
+/* The staging of a host-form request: feature (cls, pooled), top-k (labels, scores), attention maps (heads, mean),
+ * rollout (rollout, none) or gallery (indices, scores) */
 static void request_release(struct staged st[2])
 {
     staged_release(&st[0]);
@@ -278,6 +290,10 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     for (int k = 0; k < 3; ++k)
         if (ctx->roll.scratch[k])
             vh_free(ctx->roll.scratch[k]);
+    request_release(ctx->gal.st);
+    for (int k = 0; k < 2; ++k)
+        if (ctx->gal.scratch[k])
+            vh_free(ctx->gal.scratch[k]);
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
@@ -1044,11 +1060,31 @@ fail:
     return rc;
 }
 
-/* Everything after the argument checks of the forwards.  fr, tk, ar, ro: the armed feature / top-k / attention-map /
- * rollout request to serve, or NULL. */
+/* The armed gallery request behind its layer: the queries by the feature readout (cls_rows as feature_tap), then the search
+ * against the caller's rows, timed with the classifier */
+static int gallery_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct gallery_req *ga, int n, int cls_rows)
+{
+    int rc = 0;
+    const vit_config *c = &ctx->cfg;
+    float **tw = ctx->w + 4 + 12 * c->depth;
+    const int pooled = ga->spec.source == VIT_GALLERY_POOLED;
+    OP(VIT_OP_HEAD, vh_launch_feature_readout(s, ctx->x, cls_rows ? (const float *)ctx->qkv : NULL, c->embed_dim, tw[0], tw[1], c->eps,
+                                              ga->spec.final_norm, ga->spec.l2_normalize, VIT_FEATURE_F32, VIT_TOKENS_NLC, n,
+                                              ctx->plan.tokens, c->embed_dim, 0, 1, pooled ? NULL : ga->scratch[0],
+                                              pooled ? ga->scratch[0] : NULL, NULL, ctx->hid, ctx->plan.ws_bytes));
+    OP(VIT_OP_HEAD, vh_launch_gallery_topk(s, (const float *)ga->scratch[0], n, c->embed_dim, ga->spec.d_rows, ga->spec.dtype,
+                                           ga->spec.n_rows, ga->spec.row_stride, ga->spec.k, 0, ga->scratch[1], ga->out.indices,
+                                           ga->out.scores));
+    return 0;
+fail:
+    return rc;
+}
+
+/* Everything after the argument checks of the forwards.  fr, tk, ar, ro, ga: the armed feature / top-k / attention-map /
+ * rollout / gallery request to serve, or NULL. */
 static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
                           const struct feature_req *fr, const struct topk_req *tk, const struct attn_req *ar,
-                          const struct rollout_req *ro)
+                          const struct rollout_req *ro, const struct gallery_req *ga)
 {
     int rc = 0;
     const int cls_only_saved = ctx->plan.cls_only_last;
@@ -1071,6 +1107,8 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
     /* a request for patch rows of the last layer makes this forward run the last layer on all rows */
     if (fr && fr->layer[fr->spec.n_taps - 1] == c->depth - 1 && (fr->out.pooled || fr->out.tokens))
         ctx->plan.cls_only_last = 0;
+    if (ga && ga->layer == c->depth - 1 && ga->spec.source == VIT_GALLERY_POOLED)
+        ctx->plan.cls_only_last = 0;
     for (int l = 0, k = 0; l < c->depth; ++l) {
         switch (ctx->plan.precision) {
         case VIT_PRECISION_FP8_GEMM: TRY(layer_fp8(ctx, s, n, l)); break;
@@ -1084,6 +1122,8 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         }
         if (fr && k < fr->spec.n_taps && fr->layer[k] == l)
             TRY(feature_tap(ctx, s, fr, k++, n, cls_rows));
+        if (ga && ga->layer == l)
+            TRY(gallery_tap(ctx, s, ga, n, cls_rows));
     }
     ctx->plan.cls_only_last = cls_only_saved;
     ctx->attn_serving = NULL;
@@ -1116,18 +1156,19 @@ fail:
  * FEAT_NONE for a call that serves nothing, whatever is armed.  A request armed in the other form refuses the call, the
  * feature request first. */
 static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const struct feature_req **fr, const struct topk_req **tk,
-                          const struct attn_req **ar, const struct rollout_req **ro)
+                          const struct attn_req **ar, const struct rollout_req **ro, const struct gallery_req **ga)
 {
-    static const char *const what[4] = {"feature", "top-k", "attention", "rollout"},
-                      *const setter[4] = {"features", "topk", "attention", "rollout"};
-    const int armed[4] = {ctx->feat.form, ctx->topk.form, ctx->amap.form, ctx->roll.form};
+    static const char *const what[5] = {"feature", "top-k", "attention", "rollout", "gallery"},
+                      *const setter[5] = {"features", "topk", "attention", "rollout", "gallery"};
+    const int armed[5] = {ctx->feat.form, ctx->topk.form, ctx->amap.form, ctx->roll.form, ctx->gal.form};
     *fr = NULL;
     *tk = NULL;
     *ar = NULL;
     *ro = NULL;
+    *ga = NULL;
     if (form == FEAT_NONE)
         return 0;
-    for (int r = 0; r < 4; ++r)
+    for (int r = 0; r < 5; ++r)
         if (armed[r] != FEAT_NONE && armed[r] != form) {
             char msg[200];
             const char *const is = armed[r] == FEAT_HOST ? "host" : "device";
@@ -1139,6 +1180,7 @@ static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const str
     *tk = armed[1] == form ? &ctx->topk : NULL;
     *ar = armed[2] == form ? &ctx->amap : NULL;
     *ro = armed[3] == form ? &ctx->roll : NULL;
+    *ga = armed[4] == form ? &ctx->gal : NULL;
     return 0;
 }
 
@@ -1166,9 +1208,10 @@ static int forward_device_armed(vit_hip_ctx *ctx, const char *who, const struct 
     const struct topk_req *tk;
     const struct attn_req *ar;
     const struct rollout_req *ro;
-    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar, &ro))
+    const struct gallery_req *ga;
+    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar, &ro, &ga))
         return 1;
-    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar, ro);
+    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar, ro, ga);
 }
 
 /* vit_hip_forward_device with no feature output whatever is armed (vit_gather_rccl.c) */
@@ -1177,7 +1220,7 @@ int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n,
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
     const struct ingest_src src = {.kind = INGEST_F32, .on_device = 1, .f32 = d_images};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL, NULL);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL, NULL, NULL);
 }
 
 int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
@@ -1575,6 +1618,105 @@ int vit_hip_set_rollout_host(vit_hip_ctx *ctx, const vit_rollout_spec *spec, con
     return set_rollout("vit_hip_set_rollout_host", ctx, spec, h_bufs, 1);
 }
 
+/* spec against cfg, pointers aside; tap resolved to a layer index, the scratch per image of max_batch */
+static int gallery_spec_check(const char *who, const vit_config *cfg, const vit_gallery_spec *spec, int *layer, size_t *per_image)
+{
+    const char *why = !cfg || !spec ? "NULL argument"
+                      : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
+                      : spec->source != VIT_GALLERY_CLS && spec->source != VIT_GALLERY_POOLED ? "source must be VIT_GALLERY_CLS or VIT_GALLERY_POOLED"
+                      : spec->tap < -cfg->depth || spec->tap >= cfg->depth ? "tap lies outside [-depth, depth)"
+                      : spec->source == VIT_GALLERY_POOLED && vit_config_tokens(cfg) < 2 ? "pooled needs at least one patch token"
+                      : spec->dtype != VH_GALLERY_F32 && spec->dtype != VH_GALLERY_BF16 ? "dtype must be VH_GALLERY_F32 or VH_GALLERY_BF16"
+                      : cfg->embed_dim % 4 != 0 || cfg->embed_dim > 2048 ? "embed_dim must be a multiple of 4, at most 2048"
+                      : spec->k < 1 || spec->k > 32 ? "k must be in 1..32"
+                      : spec->n_rows < spec->k || spec->n_rows > 2147483647L ? "n_rows must be in k..2^31 - 1"
+                      : spec->row_stride < cfg->embed_dim || spec->row_stride > (1L << 40) ||
+                        (spec->row_stride * (spec->dtype == VH_GALLERY_BF16 ? 2 : 4)) % 16 != 0
+                          ? "row_stride must be at least embed_dim, and a multiple of 16 bytes"
+                      : NULL;
+    if (why)
+        return ingest_refuse(who, why);
+    *layer = spec->tap < 0 ? spec->tap + cfg->depth : spec->tap;
+    *per_image = (size_t)cfg->embed_dim * sizeof(float) + vh_gallery_workspace(1, spec->n_rows, spec->k, 0);
+    return 0;
+}
+
+int vit_gallery_check(const vit_config *cfg, const vit_gallery_spec *spec, size_t *scratch_bytes_per_max_batch_image)
+{
+    int layer;
+    size_t per_image;
+    if (gallery_spec_check("vit_gallery_check", cfg, spec, &layer, &per_image))
+        return 1;
+    if (scratch_bytes_per_max_batch_image)
+        *scratch_bytes_per_max_batch_image = per_image;
+    return 0;
+}
+
+static void gallery_scratch_free(void *scratch[2])
+{
+    for (int k = 0; k < 2; ++k) {
+        if (scratch[k])
+            vh_free(scratch[k]);
+        scratch[k] = NULL;
+    }
+}
+
+/* Both forms of arming, as set_features; the scratch depends on the spec (k, n_rows), so every arming makes its own and
+ * the previous request's is freed once the new one stands */
+static int set_gallery(const char *who, vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *bufs, int host)
+{
+    struct gallery_req ga;
+    memset(&ga, 0, sizeof ga);
+    if (ctx && spec) {
+        size_t per_image;
+        if (gallery_spec_check(who, &ctx->cfg, spec, &ga.layer, &per_image))
+            return 1;
+        const char *why = !spec->d_rows ? "no gallery rows"
+                          : (uintptr_t)spec->d_rows & 15 ? "the gallery rows must be 16-byte aligned"
+                          : !bufs || !bufs->indices ? "no indices buffer"
+                          : !host && (((uintptr_t)bufs->indices | (uintptr_t)bufs->scores) & 15) ? "device buffers must be 16-byte aligned"
+                          : NULL;
+        if (why)
+            return ingest_refuse(who, why);
+        ga.form = host ? FEAT_HOST : FEAT_DEVICE;
+        ga.spec = *spec;
+        ga.out = *bufs;
+        if (host) {
+            ga.st[0] = (struct staged){.host = (char *)bufs->indices, .per_image = (size_t)spec->k * sizeof(int)};
+            ga.st[1] = (struct staged){.host = (char *)bufs->scores, .per_image = (size_t)spec->k * sizeof(float)};
+        }
+        const size_t q_bytes = (size_t)ctx->max_batch * ctx->cfg.embed_dim * sizeof(float);
+        const size_t ws_bytes = (size_t)ctx->max_batch * (per_image - (size_t)ctx->cfg.embed_dim * sizeof(float));
+        if (vh_set_device(ctx->device) || vh_malloc(&ga.scratch[0], q_bytes) || vh_malloc(&ga.scratch[1], ws_bytes)) {
+            char msg[160];
+            gallery_scratch_free(ga.scratch);
+            snprintf(msg, sizeof msg, "%zu bytes of device scratch (the queries and the search's workspace) cannot be allocated",
+                     q_bytes + ws_bytes);
+            return ingest_refuse(who, msg);
+        }
+    }
+    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, gal.st), ga.st);
+    if (rc != 0) {
+        gallery_scratch_free(ga.scratch);
+        return rc;
+    }
+    gallery_scratch_free(ctx->gal.scratch);   /* behind arm()'s stream sync nothing reads the previous request's any more */
+    if (ga.form == FEAT_HOST)
+        ga.out = (vit_gallery_buffers){(int *)ga.st[0].dev, (float *)ga.st[1].dev};
+    ctx->gal = ga;
+    return 0;
+}
+
+int vit_hip_set_gallery(vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *d_bufs)
+{
+    return set_gallery("vit_hip_set_gallery", ctx, spec, d_bufs, 0);
+}
+
+int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *h_bufs)
+{
+    return set_gallery("vit_hip_set_gallery_host", ctx, spec, h_bufs, 1);
+}
+
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
 {
     if (!ctx)
@@ -1606,8 +1748,9 @@ int vit_hip_profile_enable(vit_hip_ctx *ctx, int max_forwards)
     prof_release(ctx);
     if (max_forwards <= 0)
         return 0;
-    /* + the readouts of an armed feature request + top-k + attention maps + the rollout's steps and read */
-    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4 + ctx->cfg.depth + 1;
+    /* + the readouts of an armed feature request + top-k + attention maps + the rollout's steps and read + the gallery's
+     * readout and search */
+    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4 + ctx->cfg.depth + 1 + 2;
     ctx->prof_cap = per_forward * max_forwards;
     ctx->prof_ev = (vh_event_t *)calloc((size_t)2 * ctx->prof_cap, sizeof(vh_event_t));
     ctx->prof_class = (int *)calloc((size_t)ctx->prof_cap, sizeof(int));
@@ -1741,22 +1884,24 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, str
     const struct topk_req *tk;
     const struct attn_req *ar;
     const struct rollout_req *ro;
-    if (armed_requests(ctx, "forward", form, &fr, &tk, &ar, &ro))
+    const struct gallery_req *ga;
+    if (armed_requests(ctx, "forward", form, &fr, &tk, &ar, &ro, &ga))
         return 1;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->kind == INGEST_F32 ? sizeof(float) : 1);
     const size_t NC = (size_t)c->num_classes;
     /* what comes back per chunk besides the probabilities, in the order it is queued: logits, cls, pooled, labels, scores,
-     * heads, mean, rollout */
+     * heads, mean, rollout, indices, gallery scores */
     const struct staged logits_st = {ctx->d_logits, {ctx->h_logits[0], ctx->h_logits[1]}, (char *)logits, NC * sizeof(float)};
-    const struct staged *arrays[8];
+    const struct staged *arrays[10];
     int n_arrays = 0;
     if (logits)
         arrays[n_arrays++] = &logits_st;
-    for (int a = 0; a < 7; ++a) {
+    for (int a = 0; a < 9; ++a) {
         const struct staged *st = a < 2 ? (fr ? &fr->st[a] : NULL) : a < 4 ? (tk ? &tk->st[a - 2] : NULL)
-                                  : a < 6 ? (ar ? &ar->st[a - 4] : NULL) : (ro ? &ro->st[0] : NULL);
+                                  : a < 6 ? (ar ? &ar->st[a - 4] : NULL) : a < 7 ? (ro ? &ro->st[0] : NULL)
+                                  : (ga ? &ga->st[a - 7] : NULL);
         if (st && st->dev)
             arrays[n_arrays++] = st;
     }
@@ -1798,7 +1943,7 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, str
         TRY(vh_event_record(ctx->up_done[s], ctx->copy_stream));
 
         TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
-        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar, ro));
+        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar, ro, ga));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
         int a = 0;

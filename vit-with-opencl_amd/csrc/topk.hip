@@ -34,32 +34,6 @@ __device__ __forceinline__ float wave_max(float v)
     return v;
 }
 
-__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-/* larger key = better rank; every key of a real element is > 0 (its low word is >= 0xFFFFFFFF - 65535) */
-__device__ __forceinline__ unsigned long long rank_key(float v, int idx)
-{
-    unsigned b = __builtin_bit_cast(unsigned, v);
-    unsigned hi;
-    if (v != v)
-        hi = 0u;                                  /* NaN: below -inf (whose image is 0x007FFFFF) */
-    else {
-        if (v == 0.0f)
-            b = 0u;                               /* -0 and +0 are equal */
-        hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    return ((unsigned long long)hi << 32) | (0xFFFFFFFFu - (unsigned)idx);
-}
-
 template <bool REG>
 __global__ __launch_bounds__(TK_THREADS) void topk_kernel(const float *__restrict__ in, int length, int k, int probs,
                                                          int *__restrict__ labels, float *__restrict__ scores)

@@ -58,6 +58,35 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+/* Maximum of a 64-bit key over the 64 lanes of a wave, in every lane */
+__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+/* The ranking key of topk.hip and gallery.hip: larger key = better rank.  The order-preserving unsigned image of the float
+ * (-0 folded to +0, NaN -> 0, so below -inf) above 0xFFFFFFFF - index: keys of distinct indices are distinct, equal values
+ * rank by ascending index.  Every key of a real element is > 0 (index < 2^31: its low word is > 0x80000000). */
+__device__ __forceinline__ unsigned long long rank_key(float v, int idx)
+{
+    unsigned b = __builtin_bit_cast(unsigned, v);
+    unsigned hi;
+    if (v != v)
+        hi = 0u;                                  /* NaN: below -inf (whose image is 0x007FFFFF) */
+    else {
+        if (v == 0.0f)
+            b = 0u;                               /* -0 and +0 are equal */
+        hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    }
+    return ((unsigned long long)hi << 32) | (0xFFFFFFFFu - (unsigned)idx);
+}
+
 /* Workgroup barrier for LDS hand-overs only: this wave's LDS operations have completed (lgkmcnt), global loads stay
  * in flight.  __syncthreads() is a full workgroup fence -- it also drains vmcnt, i.e. it waits for prefetches issued a
  * few hundred cycles earlier and puts the whole load latency into every step of a pipelined loop. */

@@ -71,6 +71,8 @@ EXPORTS = [
     "vit_hip_set_attention_host",
     "vh_rollout_workspace", "vh_rollout_max_tokens", "vh_launch_rollout_step", "vh_launch_rollout_read", "vit_rollout_sizes",
     "vit_hip_set_rollout", "vit_hip_set_rollout_host",
+    "vh_gallery_query_tile", "vh_gallery_splits", "vh_gallery_workspace", "vh_launch_gallery_topk", "vit_gallery_check",
+    "vit_hip_set_gallery", "vit_hip_set_gallery_host",
 ]
 
 # include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
@@ -245,6 +247,48 @@ def rollout_sizes(cfg: "VitConfig", spec: RolloutSpec):
     cs = spec.c_struct()
     check(lib().vit_rollout_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_rollout_sizes")
     return tuple(o.value for o in out)
+
+
+class GallerySpecC(C.Structure):
+    """`vit_gallery_spec` (include/ViT_opencl.h)."""
+
+    _fields_ = [("source", C.c_int), ("tap", C.c_int), ("final_norm", C.c_int), ("l2_normalize", C.c_int), ("k", C.c_int),
+                ("dtype", C.c_int), ("n_rows", C.c_long), ("row_stride", C.c_long), ("d_rows", C.c_void_p)]
+
+
+class GalleryBuffers(C.Structure):
+    """`vit_gallery_buffers` (include/ViT_opencl.h): device or host pointers; scores may be NULL."""
+
+    _fields_ = [("indices", C.c_void_p), ("scores", C.c_void_p)]
+
+
+GALLERY_SOURCES = {"cls": 0, "pooled": 1}
+GALLERY_DTYPES = {"f32": 0, "bf16": 1}
+GALLERY_MAX_SPLITS, GALLERY_ROW_TILE = 1024, 128   # VH_GALLERY_MAX_SPLITS, VH_GALLERY_ROW_TILE (include/kernelHandler.h)
+
+
+class GallerySpec:
+    """A gallery request: the k (1..32) rows nearest to the "cls" | "pooled" embedding behind layer `tap`, read as a
+    FeatureSpec((tap,), final_norm, l2_normalize) would give it.  The rows themselves (n_rows, row_stride in elements,
+    dtype "f32" | "bf16", d_rows a device pointer) are filled in by ViTHip.set_gallery from the array it is given."""
+
+    def __init__(self, k: int = 5, source: str = "cls", tap: int = -1, final_norm: bool = True, l2_normalize: bool = True,
+                 dtype: str = "f32", n_rows: int = 0, row_stride: int = 0, d_rows=None):
+        self.k, self.source, self.tap = int(k), source, int(tap)
+        self.final_norm, self.l2_normalize = bool(final_norm), bool(l2_normalize)
+        self.dtype, self.n_rows, self.row_stride, self.d_rows = dtype, int(n_rows), int(row_stride), d_rows
+
+    def c_struct(self) -> GallerySpecC:
+        return GallerySpecC(GALLERY_SOURCES[self.source], self.tap, int(self.final_norm), int(self.l2_normalize), self.k,
+                            GALLERY_DTYPES[self.dtype], self.n_rows, self.row_stride, _device_ptr(self.d_rows))
+
+
+def gallery_check(cfg: "VitConfig", spec: GallerySpec) -> int:
+    """vit_gallery_check -> device scratch bytes per image of max_batch; raises VitHipError with the library's message"""
+    out = C.c_size_t()
+    cs = spec.c_struct()
+    check(lib().vit_gallery_check(C.byref(cfg), C.byref(cs), C.byref(out)), "vit_gallery_check")
+    return out.value
 
 
 def topk_check(cfg: "VitConfig", spec: TopKSpec) -> None:
@@ -585,6 +629,15 @@ def lib() -> C.CDLL:
     L.vit_rollout_sizes.argtypes = [C.POINTER(VitConfig), rsp, szp, szp]
     L.vit_hip_set_rollout.argtypes = [voidp, rsp, rbp]
     L.vit_hip_set_rollout_host.argtypes = [voidp, rsp, rbp]
+    L.vh_gallery_query_tile.argtypes = [i]
+    L.vh_gallery_splits.argtypes = [i, C.c_long]
+    L.vh_gallery_workspace.argtypes = [i, C.c_long, i, i]
+    L.vh_gallery_workspace.restype = sz
+    L.vh_launch_gallery_topk.argtypes = [voidp, voidp, i, i, voidp, i, C.c_long, C.c_long, i, i, voidp, voidp, voidp]
+    gsp, gbp = C.POINTER(GallerySpecC), C.POINTER(GalleryBuffers)
+    L.vit_gallery_check.argtypes = [C.POINTER(VitConfig), gsp, szp]
+    L.vit_hip_set_gallery.argtypes = [voidp, gsp, gbp]
+    L.vit_hip_set_gallery_host.argtypes = [voidp, gsp, gbp]
     _lib = L
     return L
 
@@ -844,7 +897,7 @@ class ViTHip:
         check(self.L.vh_stream_sync(self.stream), "vh_stream_sync")
 
     def _arm(self, entry, spec, buffers, arrays, ptr, keep):
-        """What the four setters share: the C entry point `entry` gets spec's C struct and the `buffers` struct of
+        """What the five setters share: the C entry point `entry` gets spec's C struct and the `buffers` struct of
         ptr(array) per array, and the attribute `keep` holds the arrays alive; spec=None disarms."""
         if spec is None:
             cs = bufs = None
@@ -956,6 +1009,55 @@ class ViTHip:
         finally:
             self.set_rollout_host(None)
         return out
+
+    def _gallery_rows(self, spec, rows):
+        """spec with the rows filled in: a [G][E] float32 array, or uint16 bf16 bits, is uploaded once into a DeviceBuffer
+        this object keeps while armed; a DeviceBuffer is taken as spec describes it (dtype, n_rows, row_stride)."""
+        if isinstance(rows, DeviceBuffer):
+            spec.d_rows = rows
+            spec.row_stride = spec.row_stride or self.cfg.embed_dim
+            spec.n_rows = spec.n_rows or rows.count // spec.row_stride
+            return spec
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.dtype not in (np.dtype(np.float32), np.dtype(np.uint16)):
+            raise ValueError("set_gallery: rows must be a [G][E] float32 array, uint16 bf16 bits, or a DeviceBuffer")
+        spec.dtype = "f32" if rows.dtype == np.float32 else "bf16"
+        spec.n_rows, spec.row_stride = rows.shape
+        spec.d_rows = DeviceBuffer.from_numpy(rows, dtype=rows.dtype)
+        return spec
+
+    def set_gallery(self, spec, rows=None, indices=None, scores=None):
+        """Arm (spec=None: disarm) the device form: indices (int32) / scores (float32, may be None) are DeviceBuffers (or
+        device pointers) of [max_batch][k], written by every forward_device* until disarmed.  rows: see _gallery_rows."""
+        if spec is not None:
+            spec = self._gallery_rows(spec, rows)
+        self._arm("vit_hip_set_gallery", spec, GalleryBuffers, (indices, scores), _device_ptr, "_gallery_keep")
+        self._gallery_rows_keep = None if spec is None else spec.d_rows
+
+    def set_gallery_host(self, spec, rows=None, indices=None, scores=None):
+        """Arm (spec=None: disarm) the host form: indices (int32 [n][k]) / scores (float32 [n][k], may be None) are
+        C-contiguous NumPy arrays for all n images of the coming forward / forward_u8 / forward_u8_resized / _boxes calls."""
+        for a, dt in ((indices, np.int32), (scores, np.float32)):
+            if spec is not None and a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == dt):
+                raise ValueError("set_gallery_host: need C-contiguous int32 indices and float32 scores")
+        if spec is not None:
+            spec = self._gallery_rows(spec, rows)
+        self._arm("vit_hip_set_gallery_host", spec, GalleryBuffers, (indices, scores), _host_ptr, "_gallery_keep")
+        self._gallery_rows_keep = None if spec is None else spec.d_rows
+
+    def search(self, images: np.ndarray, rows, k: int = 5, source: str = "cls", tap: int = -1, final_norm: bool = True,
+               l2_normalize: bool = True):
+        """fp32 images [n][C][H][W] -> (indices[n][k] int32, scores[n][k] float32): the k rows of the gallery `rows` nearest
+        to every image's embedding, the host form armed for this one call; no embedding crosses PCIe."""
+        images = np.ascontiguousarray(images, dtype=np.float32)
+        n = images.shape[0]
+        indices, out = np.empty((n, k), dtype=np.int32), np.empty((n, k), dtype=np.float32)
+        self.set_gallery_host(GallerySpec(k, source, tap, final_norm, l2_normalize), rows, indices=indices, scores=out)
+        try:
+            check(self.L.vit_hip_forward(self.ctx, image_array(images), n, None, None), "vit_hip_forward")
+        finally:
+            self.set_gallery_host(None)
+        return indices, out
 
     def read_tokens(self, n: int) -> np.ndarray:
         out = np.empty((n * self.tokens, self.cfg.embed_dim), dtype=np.float32)
