@@ -539,6 +539,61 @@ int vit_gallery_check(const vit_config *cfg, const vit_gallery_spec *spec, size_
 int vit_hip_set_gallery(vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *d_bufs);
 int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *h_bufs);
 
+/* ---- dense head: a label per pixel from the patch tokens (semantic segmentation by a linear head) ----
+ * A dense request is ARMED on a context like the other five requests, and independently of them (all six may be armed at
+ * once).  While armed, every forward through the context also applies the caller's linear head W [n_labels][E], b to every
+ * patch token behind layer `tap`, upsamples the n_labels logits per patch bilinearly from the g x g patch grid (g = img_size
+ * / patch_size) to out_h x out_w and writes, per pixel, the best label as one byte: 50 KB per 224 x 224 image instead of
+ * the 600 KB of its patch tokens.  Two or three extra launches behind the tapped layer (vh_launch_feature_readout when
+ * final_norm is set, vh_launch_dense_logits, vh_launch_dense_labels, csrc/dense_head.hip), all timed under VIT_OP_HEAD;
+ * logits, probabilities and the other five requests' outputs are bit-identical to a forward without a dense request.  A
+ * context that has never been armed, or has been disarmed, launches exactly what it launched before.
+ * The token row x_p of patch p is BY DEFINITION the vector vit_hip_set_features writes as `tokens` for {n_taps = 1, taps =
+ * {tap}, final_norm, VIT_FEATURE_F32, VIT_TOKENS_NLC}, bit for bit (the class token is no part of it): with final_norm the
+ * same kernel writes them into the MLP buffer, idle behind fc2, when that holds max_batch * (T - 1) * E floats, and into
+ * scratch of the request's own otherwise; without, the residual stream's patch rows are read in place.
+ * Patch logits, upsampling, labels, scores and their error bound: as vh_launch_dense_logits and vh_launch_dense_labels
+ * define them (include/kernelHandler.h), with GH = GW = g; an image's outputs are the same bits wherever it sits in the
+ * batch and whatever n is.
+ * spec: tap is one layer, 0-based or negative from the end (-1 = the last), in [-depth, depth); n_labels in 2..256; out_h,
+ * out_w in 1..4096, 0 = the model's img_size; d_weight [n_labels] rows of embed_dim fp32, weight_stride elements apart
+ * (>= embed_dim, a multiple of 4), d_bias [n_labels] fp32 or NULL: device memory of the context's device, 16-byte aligned,
+ * the CALLER'S, valid and unchanged while armed.  The model needs embed_dim % 4 == 0, <= 2048, T - 1 == g * g >= 1, g <= 64.
+ * Outputs: labels u8 [n][out_h][out_w] (required); scores fp32 [n][out_h][out_w] and patch_logits fp32 [n][T - 1][n_labels]
+ * (either may be NULL; asking for them changes no label).  Scratch, allocated when the request is armed and freed when it
+ * is disarmed or the context destroyed (if it cannot be allocated, arming is refused): the patch logits [max_batch][T - 1]
+ * [n_labels] fp32 when the caller gives no buffer for them, and the normalised tokens as said above; vit_dense_sizes gives
+ * an upper bound per image of max_batch ((T - 1) * (n_labels + embed_dim) * 4 bytes).
+ * Device form (vit_hip_set_dense): device buffers for max_batch images, 16-byte aligned, written asynchronously on the
+ * forward's stream by vit_hip_forward_device, _device_u8, _device_u8_resized and _device_u8_boxes.  Host form
+ * (vit_hip_set_dense_host): a host buffer of labels for ALL n images of the coming vit_hip_forward / _u8 / _u8_resized /
+ * _u8_boxes calls (each call writes from image 0), across chunks, complete on return; it serves labels only -- scores and
+ * patch_logits are refused there, as tokens are for features; its staging is allocated when it is armed.
+ * spec == NULL disarms.  Arming one form disarms the other; a device-form forward while the host form is armed (and the
+ * reverse) is refused with code 1 and a message, no launch.  Code 1 with a message also for: NULL ctx, a tap, n_labels,
+ * out_h, out_w or weight_stride outside the above, a model the head does not take, NULL or misaligned d_weight, misaligned
+ * d_bias, no labels buffer, a misaligned device buffer, scratch that cannot be allocated -- all when the request is armed,
+ * not at the first forward.  A refused call leaves the previous request armed.
+ * Under vit_hip_set_last_layer_cls_only: a tap on the last layer makes that forward run the last layer on all rows, as a
+ * feature request for pooled does; logits are bit-identical either way.
+ * vit_hip_multi: vit_hip_forward_multi and vit_hip_forward_device_multi neither write labels nor refuse.
+ * Out of scope: per-pixel probabilities, multi-layer or non-linear decode heads, antialiased or bicubic upsampling, more
+ * than 256 labels. */
+typedef struct vit_dense_spec {
+    int tap, final_norm;          /* as vit_gallery_spec */
+    int n_labels, out_h, out_w;   /* out_h/out_w 0 = the model's img_size */
+    long weight_stride;
+    const float *d_weight, *d_bias;   /* device, the caller's; d_bias may be NULL */
+} vit_dense_spec;
+typedef struct vit_dense_buffers { unsigned char *labels; float *scores, *patch_logits; } vit_dense_buffers;
+/* host only, no device: validates spec against cfg (everything above but the pointers); bytes of labels and elements of
+ * scores and patch_logits PER IMAGE, and an upper bound on the device scratch per image of max_batch; any pointer may be
+ * NULL; 0, or 1 with a message */
+int vit_dense_sizes(const vit_config *cfg, const vit_dense_spec *spec, size_t *labels_bytes, size_t *scores_elems,
+                    size_t *patch_logits_elems, size_t *scratch_bytes_per_image);
+int vit_hip_set_dense(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *d_bufs);
+int vit_hip_set_dense_host(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *h_bufs);
+
 /* Debug hook: copy the residual stream left by the last forward ([n*tokens][embed], un-normalised; rows other than the
  * class tokens are stale under vit_hip_set_last_layer_cls_only) to the host.  The supported interface to the encoder's
  * output is vit_hip_set_features above. */

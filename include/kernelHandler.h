@@ -530,6 +530,63 @@ int vh_launch_gallery_topk(vh_stream_t s, const float *queries /* [n][E] fp32 */
                            int k, int splits /* 0 = chosen by the launcher */, void *workspace,
                            int *indices /* [n][k] */, float *scores /* [n][k], may be NULL */);
 
+/* Dense head (csrc/dense_head.hip; the kernels under vit_hip_set_dense, include/ViT_opencl.h): a label per pixel from the
+ * patch tokens of a GH x GW grid -- a linear head over every token, bilinear upsampling of the C logits per patch to
+ * out_h x out_w, the best label per pixel.  Two launchers; u = 2^-24 below.
+ * Definition.
+ * Patch logits (vh_launch_dense_logits).  Token row p of image i is the E fp32 values at rows + i * image_stride + p *
+ * row_stride (elements); what lies between rows is never read, so `rows` may point at the first patch row of a residual
+ * stream (x + E, image_stride = T * E, row_stride = E) or at contiguous tokens.  W [C][E] fp32, rows weight_stride apart
+ * (padding never read); b [C] fp32 or NULL.  L[p][c] = (sum_d x_p[d] * W[c][d]) + b[c]: the sum in fp32 on the fp32-input
+ * matrix instruction as ONE fma chain from +0 in vh_launch_gallery_topk's order of d (for c0 = 0, 32, ...; j = 0, 1; e =
+ * 0..3; g = 0..3: d = c0 + 16 j + 4 g + e, d >= E contributing fma(0, 0, x) = x), then b[c] added as one fp32 add; with no
+ * bias the sum's own bits (the same bits as the gallery search's score of the two vectors).  The bits of L[p][c] depend on
+ * x_p, W[c] and b[c] only: not on p, the image, n_images, patches, C or any tiling.
+ * Upsampling and labels (vh_launch_dense_labels): bilinear, half-pixel centres, no antialiasing, edges clamped -- what
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False) computes -- in these fp32 expressions, each
+ * operation rounded once, fmaf fused:
+ *   ry = (float)GH / (float)out_h;  sy = fmaxf(fmaf((float)y + 0.5f, ry, -0.5f), 0.0f);  r0 = min((int)sy, GH - 1);
+ *   r1 = min(r0 + 1, GH - 1);  wy = sy - (float)r0;  uy = 1.0f - wy;   and rx, sx, c0, c1, wx, ux from x, GW, out_w alike;
+ *   top = fmaf(wx, L[r0,c1][c], ux * L[r0,c0][c]);  bot = fmaf(wx, L[r1,c1][c], ux * L[r1,c0][c]);
+ *   v[c] = fmaf(wy, bot, uy * top)                  (horizontal first, then vertical)
+ * so v[c] is a function of (y, x, out_h, out_w, GH, GW) and the four corner values only.  An infinite corner under a zero
+ * weight gives NaN, as it does in that framework.
+ * labels[i][y][x] = the c that vh_launch_topk's rule ranks first among v[0..C): the largest, equal values (-0 == +0) to the
+ * lowest c, NaN below -inf (all NaN: 0).  scores[i][y][x] (may be NULL, which changes no label) = that v[c]'s bits, a NaN
+ * as 0x7FC00000.
+ * Error bound, against this definition evaluated in float64 (coordinates, floors and lerps included) on the same fp32 x,
+ * W, b, per (pixel, class):
+ *   |v - v64| <= max over the four corners of (E + 8) u (sum_d |x_d w_d| + |b|)  +  k(GH, GW) u M,   k = 4 (GH + GW) + 16,
+ * M = the largest |L64[.][c]| over patch rows r0 - 1 .. r0 + 2 and columns c0 - 1 .. c0 + 2 inside the grid (r0, c0 the
+ * float64 cell: the four corners and their neighbours).  Derivation.  A corner: the chain errs by at most (E + 0.5) u of
+ * sum |x w| (vh_launch_gallery_topk), the bias add by u |L| <= (1 + ..) u (sum |x w| + |b|); E + 8 covers both, and the
+ * lerp weights are non-negative and sum to at most 1 + u, so the corners' errors reach v with at most their maximum.  The
+ * coordinate: ry = (GH / out_h)(1 + e1), sy = (t ry - 0.5)(1 + e2) with t = y + 0.5 exact, |e| <= u, t / out_h < 1 and
+ * |t ry - 0.5| < GH give |sy - sy64| < 2 GH u (the clamp at 0 is 1-Lipschitz); wy = sy - r0 is exact.  The bilinear
+ * surface is continuous and piecewise linear with slope at most 2 M along either axis, also where (int)sy and the float64
+ * floor differ by one -- then sy64 is within 2 GH u of the cell border, the value moves by at most |ds| times the slopes of
+ * the two adjacent cells, whose corners M spans -- hence 4 GH u M + 4 GW u M.  The three lerps: ux, the product and the
+ * fma each round once, <= 3 u M per lerp, the vertical one carrying the horizontal errors on: <= 7 u M.  The remaining 9
+ * are slack (second-order terms, the float64 side's own rounding).
+ * The labels kernel works per (image, patch row r0) on the band of output rows that share r0 and keeps patch rows r0, r1 x C
+ * in LDS (2 * grid_w * (C | 1) * 4 bytes; 76 KB at grid_w = 37, C = 256).  Integer and LDS operations only: no atomics, the
+ * same output on every run.
+ * Limits: 2 <= n_labels <= VH_DENSE_MAX_LABELS; embed_dim % 4 == 0, 4 <= embed_dim <= 2048; 1 <= out_h, out_w <= 4096;
+ * 1 <= grid_h, grid_w <= VH_DENSE_MAX_GRID (LDS at C = 256: 129 KB of the CU's 160); weight_stride >= embed_dim and a
+ * multiple of 4, as row_stride; image_stride >= patches * row_stride, a multiple of 4; n_images, patches >= 1, n_images *
+ * patches < 2^31 - 128; every pointer 16-byte aligned.  Anything else: code 1 with a message that starts with the
+ * launcher's name, no launch, nothing written.  No reference counterpart. */
+#define VH_DENSE_MAX_LABELS 256
+#define VH_DENSE_MAX_GRID 64
+#define VH_DENSE_TOKEN_TILE 128   /* token rows per workgroup of the logits kernel */
+int vh_launch_dense_logits(vh_stream_t s, const float *rows, long image_stride, long row_stride /* elements */, int n_images,
+                           int patches, int embed_dim, const float *weight /* [C][E] */, long weight_stride,
+                           const float *bias /* [C], may be NULL */, int n_labels,
+                           float *patch_logits /* [n][patches][n_labels] fp32 */);
+int vh_launch_dense_labels(vh_stream_t s, const float *patch_logits /* [n][grid_h * grid_w][n_labels] */, int n_images,
+                           int grid_h, int grid_w, int n_labels, int out_h, int out_w,
+                           unsigned char *labels /* u8 [n][out_h][out_w] */, float *scores /* fp32, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

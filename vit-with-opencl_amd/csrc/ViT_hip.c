@@ -167,6 +167,19 @@ struct vit_hip_ctx
         void *scratch[2];            /* [0]: the queries [max_batch][E] fp32; [1]: vh_launch_gallery_topk's workspace */
     } gal;
 
+    /* dense request (vit_hip_set_dense / _host), armed independently of the other five.  Scratch is held while armed. */
+    struct dense_req
+    {
+        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
+        vit_dense_spec spec;
+        int layer, grid;             /* spec.tap resolved; img_size / patch_size */
+        int out_h, out_w;            /* spec's, 0 resolved to img_size */
+        vit_dense_buffers out;       /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: labels = st[0].dev */
+        struct staged st[2];         /* FEAT_HOST: labels; st[1] unused */
+        void *scratch[2];            /* [0]: the patch logits, when the caller gives no buffer; [1]: the normalised tokens,
+                                      * when final_norm is set and the MLP buffer does not hold them */
+    } dense;
+
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
     int *prof_class;       /* operator class per recorded launch */
@@ -266,7 +279,7 @@ static void staged_scatter(const struct staged *st, int slot, int first, int m)
 }
 
 /* The staging of a host-form request: feature (cls, pooled), top-k (labels, scores), attention maps (heads, mean),
- * rollout (rollout, none) or gallery (indices, scores) */
+ * rollout (rollout, none), gallery (indices, scores) or dense (labels, none) */
 static void request_release(struct staged st[2])
 {
     staged_release(&st[0]);
@@ -294,6 +307,10 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     for (int k = 0; k < 2; ++k)
         if (ctx->gal.scratch[k])
             vh_free(ctx->gal.scratch[k]);
+    request_release(ctx->dense.st);
+    for (int k = 0; k < 2; ++k)
+        if (ctx->dense.scratch[k])
+            vh_free(ctx->dense.scratch[k]);
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
@@ -1080,11 +1097,39 @@ fail:
     return rc;
 }
 
-/* Everything after the argument checks of the forwards.  fr, tk, ar, ro, ga: the armed feature / top-k / attention-map /
- * rollout / gallery request to serve, or NULL. */
+/* The armed dense request behind its layer: the token rows (normalised by the feature readout into the MLP buffer, idle
+ * behind fc2, or into the request's scratch; without final_norm the residual stream's patch rows in place), the patch
+ * logits, the labels; timed with the classifier */
+static int dense_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct dense_req *de, int n)
+{
+    int rc = 0;
+    const vit_config *c = &ctx->cfg;
+    float **tw = ctx->w + 4 + 12 * c->depth;
+    const int E = c->embed_dim, T = ctx->plan.tokens, P = T - 1;
+    const float *rows = ctx->x + E;
+    long image_stride = (long)T * E;
+    if (de->spec.final_norm) {
+        float *tok = de->scratch[1] ? (float *)de->scratch[1] : ctx->hid;
+        OP(VIT_OP_HEAD, vh_launch_feature_readout(s, ctx->x, NULL, E, tw[0], tw[1], c->eps, 1, 0, VIT_FEATURE_F32, VIT_TOKENS_NLC, n, T, E,
+                                                  0, 1, NULL, NULL, tok, NULL, 0));
+        rows = tok;
+        image_stride = (long)P * E;
+    }
+    float *pl = de->out.patch_logits ? de->out.patch_logits : (float *)de->scratch[0];
+    OP(VIT_OP_HEAD, vh_launch_dense_logits(s, rows, image_stride, E, n, P, E, de->spec.d_weight, de->spec.weight_stride, de->spec.d_bias,
+                                           de->spec.n_labels, pl));
+    OP(VIT_OP_HEAD, vh_launch_dense_labels(s, pl, n, de->grid, de->grid, de->spec.n_labels, de->out_h, de->out_w, de->out.labels,
+                                           de->out.scores));
+    return 0;
+fail:
+    return rc;
+}
+
+/* Everything after the argument checks of the forwards.  fr, tk, ar, ro, ga, de: the armed feature / top-k / attention-map /
+ * rollout / gallery / dense request to serve, or NULL. */
 static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
                           const struct feature_req *fr, const struct topk_req *tk, const struct attn_req *ar,
-                          const struct rollout_req *ro, const struct gallery_req *ga)
+                          const struct rollout_req *ro, const struct gallery_req *ga, const struct dense_req *de)
 {
     int rc = 0;
     const int cls_only_saved = ctx->plan.cls_only_last;
@@ -1109,6 +1154,8 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         ctx->plan.cls_only_last = 0;
     if (ga && ga->layer == c->depth - 1 && ga->spec.source == VIT_GALLERY_POOLED)
         ctx->plan.cls_only_last = 0;
+    if (de && de->layer == c->depth - 1)
+        ctx->plan.cls_only_last = 0;
     for (int l = 0, k = 0; l < c->depth; ++l) {
         switch (ctx->plan.precision) {
         case VIT_PRECISION_FP8_GEMM: TRY(layer_fp8(ctx, s, n, l)); break;
@@ -1124,6 +1171,8 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
             TRY(feature_tap(ctx, s, fr, k++, n, cls_rows));
         if (ga && ga->layer == l)
             TRY(gallery_tap(ctx, s, ga, n, cls_rows));
+        if (de && de->layer == l)
+            TRY(dense_tap(ctx, s, de, n));
     }
     ctx->plan.cls_only_last = cls_only_saved;
     ctx->attn_serving = NULL;
@@ -1156,19 +1205,21 @@ fail:
  * FEAT_NONE for a call that serves nothing, whatever is armed.  A request armed in the other form refuses the call, the
  * feature request first. */
 static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const struct feature_req **fr, const struct topk_req **tk,
-                          const struct attn_req **ar, const struct rollout_req **ro, const struct gallery_req **ga)
+                          const struct attn_req **ar, const struct rollout_req **ro, const struct gallery_req **ga,
+                          const struct dense_req **de)
 {
-    static const char *const what[5] = {"feature", "top-k", "attention", "rollout", "gallery"},
-                      *const setter[5] = {"features", "topk", "attention", "rollout", "gallery"};
-    const int armed[5] = {ctx->feat.form, ctx->topk.form, ctx->amap.form, ctx->roll.form, ctx->gal.form};
+    static const char *const what[6] = {"feature", "top-k", "attention", "rollout", "gallery", "dense"},
+                      *const setter[6] = {"features", "topk", "attention", "rollout", "gallery", "dense"};
+    const int armed[6] = {ctx->feat.form, ctx->topk.form, ctx->amap.form, ctx->roll.form, ctx->gal.form, ctx->dense.form};
     *fr = NULL;
     *tk = NULL;
     *ar = NULL;
     *ro = NULL;
     *ga = NULL;
+    *de = NULL;
     if (form == FEAT_NONE)
         return 0;
-    for (int r = 0; r < 5; ++r)
+    for (int r = 0; r < 6; ++r)
         if (armed[r] != FEAT_NONE && armed[r] != form) {
             char msg[200];
             const char *const is = armed[r] == FEAT_HOST ? "host" : "device";
@@ -1181,6 +1232,7 @@ static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const str
     *ar = armed[2] == form ? &ctx->amap : NULL;
     *ro = armed[3] == form ? &ctx->roll : NULL;
     *ga = armed[4] == form ? &ctx->gal : NULL;
+    *de = armed[5] == form ? &ctx->dense : NULL;
     return 0;
 }
 
@@ -1209,9 +1261,10 @@ static int forward_device_armed(vit_hip_ctx *ctx, const char *who, const struct 
     const struct attn_req *ar;
     const struct rollout_req *ro;
     const struct gallery_req *ga;
-    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar, &ro, &ga))
+    const struct dense_req *de;
+    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar, &ro, &ga, &de))
         return 1;
-    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar, ro, ga);
+    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar, ro, ga, de);
 }
 
 /* vit_hip_forward_device with no feature output whatever is armed (vit_gather_rccl.c) */
@@ -1220,7 +1273,7 @@ int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n,
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
     const struct ingest_src src = {.kind = INGEST_F32, .on_device = 1, .f32 = d_images};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL, NULL, NULL);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL, NULL, NULL, NULL);
 }
 
 int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
@@ -1717,6 +1770,117 @@ int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, con
     return set_gallery("vit_hip_set_gallery_host", ctx, spec, h_bufs, 1);
 }
 
+/* spec against cfg, pointers aside; tap resolved to a layer index, the grid, the output size */
+static int dense_spec_check(const char *who, const vit_config *cfg, const vit_dense_spec *spec, int *layer, int *grid, int *out_h, int *out_w)
+{
+    const int g = cfg && cfg->patch_size > 0 ? cfg->img_size / cfg->patch_size : 0;
+    const char *why = !cfg || !spec ? "NULL argument"
+                      : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
+                      : spec->tap < -cfg->depth || spec->tap >= cfg->depth ? "tap lies outside [-depth, depth)"
+                      : vit_config_tokens(cfg) < 2 || vit_config_tokens(cfg) - 1 != g * g ? "the model needs a square grid of at least one patch token"
+                      : g > VH_DENSE_MAX_GRID ? "the patch grid must be at most 64 x 64"
+                      : cfg->embed_dim % 4 != 0 || cfg->embed_dim > 2048 ? "embed_dim must be a multiple of 4, at most 2048"
+                      : spec->n_labels < 2 || spec->n_labels > VH_DENSE_MAX_LABELS ? "n_labels must be in 2..256"
+                      : spec->out_h < 0 || spec->out_h > 4096 || spec->out_w < 0 || spec->out_w > 4096 ||
+                        (spec->out_h == 0 && cfg->img_size > 4096) || (spec->out_w == 0 && cfg->img_size > 4096)
+                          ? "out_h and out_w must be in 1..4096 (0: the model's img_size)"
+                      : spec->weight_stride < cfg->embed_dim || spec->weight_stride > (1L << 40) || spec->weight_stride % 4 != 0
+                          ? "weight_stride must be at least embed_dim, and a multiple of 4"
+                      : NULL;
+    if (why)
+        return ingest_refuse(who, why);
+    *layer = spec->tap < 0 ? spec->tap + cfg->depth : spec->tap;
+    *grid = g;
+    *out_h = spec->out_h ? spec->out_h : cfg->img_size;
+    *out_w = spec->out_w ? spec->out_w : cfg->img_size;
+    return 0;
+}
+
+int vit_dense_sizes(const vit_config *cfg, const vit_dense_spec *spec, size_t *labels_bytes, size_t *scores_elems,
+                    size_t *patch_logits_elems, size_t *scratch_bytes_per_image)
+{
+    int layer, grid, out_h, out_w;
+    if (dense_spec_check("vit_dense_sizes", cfg, spec, &layer, &grid, &out_h, &out_w))
+        return 1;
+    const size_t P = (size_t)grid * grid;
+    if (labels_bytes)
+        *labels_bytes = (size_t)out_h * out_w;
+    if (scores_elems)
+        *scores_elems = (size_t)out_h * out_w;
+    if (patch_logits_elems)
+        *patch_logits_elems = P * spec->n_labels;
+    if (scratch_bytes_per_image)
+        *scratch_bytes_per_image = P * ((size_t)spec->n_labels + (spec->final_norm ? (size_t)cfg->embed_dim : 0)) * sizeof(float);
+    return 0;
+}
+
+static void dense_scratch_free(void *scratch[2])
+{
+    for (int k = 0; k < 2; ++k) {
+        if (scratch[k])
+            vh_free(scratch[k]);
+        scratch[k] = NULL;
+    }
+}
+
+/* Both forms of arming, as set_gallery: every arming makes its own scratch, the previous request's is freed once the new
+ * one stands */
+static int set_dense(const char *who, vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *bufs, int host)
+{
+    struct dense_req de;
+    memset(&de, 0, sizeof de);
+    if (ctx && spec) {
+        if (dense_spec_check(who, &ctx->cfg, spec, &de.layer, &de.grid, &de.out_h, &de.out_w))
+            return 1;
+        const char *why = !spec->d_weight ? "no head weight"
+                          : ((uintptr_t)spec->d_weight | (uintptr_t)spec->d_bias) & 15 ? "the head's weight and bias must be 16-byte aligned"
+                          : !bufs || !bufs->labels ? "no labels buffer"
+                          : host && (bufs->scores || bufs->patch_logits) ? "the host form takes labels only (scores, patch_logits: use the device form)"
+                          : !host && (((uintptr_t)bufs->labels | (uintptr_t)bufs->scores | (uintptr_t)bufs->patch_logits) & 15)
+                              ? "device buffers must be 16-byte aligned"
+                          : NULL;
+        if (why)
+            return ingest_refuse(who, why);
+        de.form = host ? FEAT_HOST : FEAT_DEVICE;
+        de.spec = *spec;
+        de.out = *bufs;
+        if (host)
+            de.st[0] = (struct staged){.host = (char *)bufs->labels, .per_image = (size_t)de.out_h * de.out_w};
+        const size_t P = (size_t)ctx->plan.tokens - 1;
+        const size_t pl_bytes = bufs->patch_logits ? 0 : (size_t)ctx->max_batch * P * spec->n_labels * sizeof(float);
+        size_t tok_bytes = spec->final_norm ? (size_t)ctx->max_batch * P * ctx->cfg.embed_dim * sizeof(float) : 0;
+        if (tok_bytes <= ctx->plan.ws_bytes)
+            tok_bytes = 0;   /* they go through the MLP buffer */
+        if (vh_set_device(ctx->device) || (pl_bytes && vh_malloc(&de.scratch[0], pl_bytes)) || (tok_bytes && vh_malloc(&de.scratch[1], tok_bytes))) {
+            char msg[160];
+            dense_scratch_free(de.scratch);
+            snprintf(msg, sizeof msg, "%zu bytes of device scratch (the patch logits and the normalised tokens) cannot be allocated",
+                     pl_bytes + tok_bytes);
+            return ingest_refuse(who, msg);
+        }
+    }
+    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, dense.st), de.st);
+    if (rc != 0) {
+        dense_scratch_free(de.scratch);
+        return rc;
+    }
+    dense_scratch_free(ctx->dense.scratch);   /* behind arm()'s stream sync nothing reads the previous request's any more */
+    if (de.form == FEAT_HOST)
+        de.out = (vit_dense_buffers){(unsigned char *)de.st[0].dev, NULL, NULL};
+    ctx->dense = de;
+    return 0;
+}
+
+int vit_hip_set_dense(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *d_bufs)
+{
+    return set_dense("vit_hip_set_dense", ctx, spec, d_bufs, 0);
+}
+
+int vit_hip_set_dense_host(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *h_bufs)
+{
+    return set_dense("vit_hip_set_dense_host", ctx, spec, h_bufs, 1);
+}
+
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
 {
     if (!ctx)
@@ -1749,8 +1913,8 @@ int vit_hip_profile_enable(vit_hip_ctx *ctx, int max_forwards)
     if (max_forwards <= 0)
         return 0;
     /* + the readouts of an armed feature request + top-k + attention maps + the rollout's steps and read + the gallery's
-     * readout and search */
-    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4 + ctx->cfg.depth + 1 + 2;
+     * readout and search + the dense head's readout, logits and labels */
+    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4 + ctx->cfg.depth + 1 + 2 + 3;
     ctx->prof_cap = per_forward * max_forwards;
     ctx->prof_ev = (vh_event_t *)calloc((size_t)2 * ctx->prof_cap, sizeof(vh_event_t));
     ctx->prof_class = (int *)calloc((size_t)ctx->prof_cap, sizeof(int));
@@ -1885,23 +2049,24 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, str
     const struct attn_req *ar;
     const struct rollout_req *ro;
     const struct gallery_req *ga;
-    if (armed_requests(ctx, "forward", form, &fr, &tk, &ar, &ro, &ga))
+    const struct dense_req *de;
+    if (armed_requests(ctx, "forward", form, &fr, &tk, &ar, &ro, &ga, &de))
         return 1;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->kind == INGEST_F32 ? sizeof(float) : 1);
     const size_t NC = (size_t)c->num_classes;
     /* what comes back per chunk besides the probabilities, in the order it is queued: logits, cls, pooled, labels, scores,
-     * heads, mean, rollout, indices, gallery scores */
+     * heads, mean, rollout, indices, gallery scores, dense labels */
     const struct staged logits_st = {ctx->d_logits, {ctx->h_logits[0], ctx->h_logits[1]}, (char *)logits, NC * sizeof(float)};
-    const struct staged *arrays[10];
+    const struct staged *arrays[11];
     int n_arrays = 0;
     if (logits)
         arrays[n_arrays++] = &logits_st;
-    for (int a = 0; a < 9; ++a) {
+    for (int a = 0; a < 10; ++a) {
         const struct staged *st = a < 2 ? (fr ? &fr->st[a] : NULL) : a < 4 ? (tk ? &tk->st[a - 2] : NULL)
                                   : a < 6 ? (ar ? &ar->st[a - 4] : NULL) : a < 7 ? (ro ? &ro->st[0] : NULL)
-                                  : (ga ? &ga->st[a - 7] : NULL);
+                                  : a < 9 ? (ga ? &ga->st[a - 7] : NULL) : (de ? &de->st[0] : NULL);
         if (st && st->dev)
             arrays[n_arrays++] = st;
     }
@@ -1943,7 +2108,7 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, str
         TRY(vh_event_record(ctx->up_done[s], ctx->copy_stream));
 
         TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
-        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar, ro, ga));
+        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar, ro, ga, de));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
         int a = 0;

@@ -73,6 +73,7 @@ EXPORTS = [
     "vit_hip_set_rollout", "vit_hip_set_rollout_host",
     "vh_gallery_query_tile", "vh_gallery_splits", "vh_gallery_workspace", "vh_launch_gallery_topk", "vit_gallery_check",
     "vit_hip_set_gallery", "vit_hip_set_gallery_host",
+    "vh_launch_dense_logits", "vh_launch_dense_labels", "vit_dense_sizes", "vit_hip_set_dense", "vit_hip_set_dense_host",
 ]
 
 # include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
@@ -289,6 +290,47 @@ def gallery_check(cfg: "VitConfig", spec: GallerySpec) -> int:
     cs = spec.c_struct()
     check(lib().vit_gallery_check(C.byref(cfg), C.byref(cs), C.byref(out)), "vit_gallery_check")
     return out.value
+
+
+class DenseSpecC(C.Structure):
+    """`vit_dense_spec` (include/ViT_opencl.h)."""
+
+    _fields_ = [("tap", C.c_int), ("final_norm", C.c_int), ("n_labels", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int),
+                ("weight_stride", C.c_long), ("d_weight", C.c_void_p), ("d_bias", C.c_void_p)]
+
+
+class DenseBuffers(C.Structure):
+    """`vit_dense_buffers` (include/ViT_opencl.h): device or host pointers; scores and patch_logits may be NULL."""
+
+    _fields_ = [("labels", C.c_void_p), ("scores", C.c_void_p), ("patch_logits", C.c_void_p)]
+
+
+DENSE_MAX_LABELS, DENSE_MAX_GRID, DENSE_TOKEN_TILE = 256, 64, 128   # VH_DENSE_* (include/kernelHandler.h)
+
+
+class DenseSpec:
+    """A dense request: a label per pixel of an out_h x out_w map (0: the model's img_size) from a linear head of n_labels
+    (2..256) rows over the patch tokens behind layer `tap`, read as a FeatureSpec((tap,), final_norm) would give them.  The
+    head (weight_stride in elements, d_weight / d_bias device pointers) is filled in by ViTHip.set_dense from the arrays
+    it is given."""
+
+    def __init__(self, n_labels: int = 0, out_h: int = 0, out_w: int = 0, tap: int = -1, final_norm: bool = True,
+                 weight_stride: int = 0, d_weight=None, d_bias=None):
+        self.n_labels, self.out_h, self.out_w, self.tap = int(n_labels), int(out_h), int(out_w), int(tap)
+        self.final_norm, self.weight_stride, self.d_weight, self.d_bias = bool(final_norm), int(weight_stride), d_weight, d_bias
+
+    def c_struct(self) -> DenseSpecC:
+        return DenseSpecC(self.tap, int(self.final_norm), self.n_labels, self.out_h, self.out_w, self.weight_stride,
+                          _device_ptr(self.d_weight), _device_ptr(self.d_bias))
+
+
+def dense_sizes(cfg: "VitConfig", spec: DenseSpec):
+    """vit_dense_sizes -> (labels bytes, scores elements, patch_logits elements, scratch bytes) per image; raises
+    VitHipError with the library's message"""
+    out = [C.c_size_t() for _ in range(4)]
+    cs = spec.c_struct()
+    check(lib().vit_dense_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_dense_sizes")
+    return tuple(o.value for o in out)
 
 
 def topk_check(cfg: "VitConfig", spec: TopKSpec) -> None:
@@ -638,6 +680,12 @@ def lib() -> C.CDLL:
     L.vit_gallery_check.argtypes = [C.POINTER(VitConfig), gsp, szp]
     L.vit_hip_set_gallery.argtypes = [voidp, gsp, gbp]
     L.vit_hip_set_gallery_host.argtypes = [voidp, gsp, gbp]
+    L.vh_launch_dense_logits.argtypes = [voidp, voidp, C.c_long, C.c_long, i, i, i, voidp, C.c_long, voidp, i, voidp]
+    L.vh_launch_dense_labels.argtypes = [voidp, voidp, i, i, i, i, i, i, voidp, voidp]
+    dsp, dbp = C.POINTER(DenseSpecC), C.POINTER(DenseBuffers)
+    L.vit_dense_sizes.argtypes = [C.POINTER(VitConfig), dsp, szp, szp, szp, szp]
+    L.vit_hip_set_dense.argtypes = [voidp, dsp, dbp]
+    L.vit_hip_set_dense_host.argtypes = [voidp, dsp, dbp]
     _lib = L
     return L
 
@@ -897,7 +945,7 @@ class ViTHip:
         check(self.L.vh_stream_sync(self.stream), "vh_stream_sync")
 
     def _arm(self, entry, spec, buffers, arrays, ptr, keep):
-        """What the five setters share: the C entry point `entry` gets spec's C struct and the `buffers` struct of
+        """What the six setters share: the C entry point `entry` gets spec's C struct and the `buffers` struct of
         ptr(array) per array, and the attribute `keep` holds the arrays alive; spec=None disarms."""
         if spec is None:
             cs = bufs = None
@@ -1058,6 +1106,56 @@ class ViTHip:
         finally:
             self.set_gallery_host(None)
         return indices, out
+
+    def _dense_head(self, spec, weight, bias):
+        """spec with the head filled in: a [C][E] float32 weight and a [C] bias (or None) are uploaded once into
+        DeviceBuffers this object keeps while armed; DeviceBuffers are taken as spec describes them."""
+        if isinstance(weight, DeviceBuffer):
+            spec.d_weight, spec.d_bias = weight, bias
+            spec.weight_stride = spec.weight_stride or self.cfg.embed_dim
+            spec.n_labels = spec.n_labels or weight.count // spec.weight_stride
+            return spec
+        weight = np.asarray(weight)
+        if weight.ndim != 2 or weight.dtype != np.float32 or (bias is not None and np.asarray(bias).shape != weight.shape[:1]):
+            raise ValueError("set_dense: weight must be a [C][E] float32 array (or a DeviceBuffer), bias [C] or None")
+        spec.n_labels, spec.weight_stride = weight.shape
+        spec.d_weight = DeviceBuffer.from_numpy(weight)
+        spec.d_bias = None if bias is None else DeviceBuffer.from_numpy(np.asarray(bias, dtype=np.float32))
+        return spec
+
+    def set_dense(self, spec, weight=None, bias=None, labels=None, scores=None, patch_logits=None):
+        """Arm (spec=None: disarm) the device form: labels (uint8 [max_batch][out_h][out_w]), scores (float32, the same
+        shape, may be None) and patch_logits (float32 [max_batch][T-1][n_labels], may be None) are DeviceBuffers (or device
+        pointers), written by every forward_device* until disarmed.  weight, bias: see _dense_head."""
+        if spec is not None:
+            spec = self._dense_head(spec, weight, bias)
+        self._arm("vit_hip_set_dense", spec, DenseBuffers, (labels, scores, patch_logits), _device_ptr, "_dense_keep")
+        self._dense_head_keep = None if spec is None else (spec.d_weight, spec.d_bias)
+
+    def set_dense_host(self, spec, weight=None, bias=None, labels=None):
+        """Arm (spec=None: disarm) the host form: labels is a C-contiguous uint8 [n][out_h][out_w] NumPy array for all n
+        images of the coming forward / forward_u8 / forward_u8_resized / _boxes calls."""
+        if spec is not None and not (isinstance(labels, np.ndarray) and labels.flags.c_contiguous and labels.dtype == np.uint8):
+            raise ValueError("set_dense_host: need C-contiguous uint8 labels")
+        if spec is not None:
+            spec = self._dense_head(spec, weight, bias)
+        self._arm("vit_hip_set_dense_host", spec, DenseBuffers, (labels, None, None), _host_ptr, "_dense_keep")
+        self._dense_head_keep = None if spec is None else (spec.d_weight, spec.d_bias)
+
+    def segment(self, images: np.ndarray, weight, bias=None, size=None, tap: int = -1, final_norm: bool = True):
+        """fp32 images [n][C][H][W] -> labels [n][H][W] uint8: the label a linear head (weight [C][E], bias [C] or None)
+        over the patch tokens gives every pixel of an output of `size` (an int or (height, width); None: the model's
+        img_size), the host form armed for this one call."""
+        images = np.ascontiguousarray(images, dtype=np.float32)
+        n = images.shape[0]
+        h, w = (size, size) if isinstance(size, int) else size if size is not None else (self.cfg.img_size, self.cfg.img_size)
+        labels = np.empty((n, h, w), dtype=np.uint8)
+        self.set_dense_host(DenseSpec(0, h, w, tap, final_norm), weight, bias, labels=labels)
+        try:
+            check(self.L.vit_hip_forward(self.ctx, image_array(images), n, None, None), "vit_hip_forward")
+        finally:
+            self.set_dense_host(None)
+        return labels
 
     def read_tokens(self, n: int) -> np.ndarray:
         out = np.empty((n * self.tokens, self.cfg.embed_dim), dtype=np.float32)
