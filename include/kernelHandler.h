@@ -223,7 +223,9 @@ int vh_launch_attention_planes_f16_hd80_operand(vh_stream_t s, const void *qkv_p
  * softmax; nothing grows with tokens).  qkv_planes: the QKV projection's planes, parts 3 = the exact three-part bf16 split
  * [3*embed_dim/32][3][rows][32] (the fp32 path; fp32 products of the splits), parts 1 = one-part fp16 [3*embed_dim/32][rows][32]
  * (the reduced modes; the arithmetic of vh_launch_attention_f16).  output: fp32 rows [rows][embed_dim], rows =
- * n_images*tokens.  head_dim 64 or 80, tokens >= 1. */
+ * n_images*tokens.  head_dim 64 or 80, embed_dim % 32 == 0 (an even head count at head_dim 80), tokens >= 1, pointers
+ * 16-byte aligned; anything else: code 1 with a message, no launch.  A row's result depends on its own image and head alone
+ * (no split over keys, no atomics): the same bits alone and in a batch. */
 int vh_launch_attention_long(vh_stream_t s, const void *qkv_planes, int parts, float *output, int n_images, int tokens,
                              int embed_dim, int num_heads);
 /* vh_launch_linear on planes: input_planes [colA/32][3][rowA][32], weight_planes [colA/32][3][colB][32];
@@ -259,8 +261,9 @@ int vh_launch_attention(vh_stream_t s, const float *qkv, float *output, int n_im
  *   arith     how Q.K^T and P.V reach the matrix cores: the exact three-part bf16 split, the fp32 matrix instruction, two
  *             fp16 parts (vh_launch_attention_h2), operands rounded to fp16 (vh_launch_attention_f16)
  *   kernel    AUTO: K and V of a head resident in LDS where head_dim is 64 and tokens <= 208, else streamed through it
- *             (head_dim 64, 80 or 128, tokens <= 512); STREAMING: streamed at any shape.  The streaming kernel
- *             has fp32 products (SPLIT3, NATIVE, FP16X2) or fp16 operands (FP16)
+ *             (head_dim 64, 80 or 128, tokens <= 512: anything else is refused); STREAMING: streamed at every shape the
+ *             streaming kernel takes, the resident ones included.  The streaming kernel has fp32 products on the fp32 matrix
+ *             instruction (SPLIT3, NATIVE and FP16X2 give the same bits there) or fp16 operands (FP16), and writes fp32 rows
  *   out_kind  0 fp32 rows; 3 three-part planes (vh_launch_attention_p3: SPLIT3) and 4 one-part bf16 planes
  *             (vh_launch_attention_planes_bf16: FP16) are written by the resident kernel only: AUTO on its shapes */
 enum { VH_ATTN_NATIVE = 0, VH_ATTN_FP16 = 1, VH_ATTN_FP16X2 = 2, VH_ATTN_SPLIT3 = 3 };

@@ -467,7 +467,8 @@ extern "C" int vh_launch_attention_rows(vh_stream_t s, const float *qkv, void *o
     /* Resident K/V (this file) where one head's K and V fit the LDS three times over; otherwise, or when asked for,
      * the streaming kernel (fp16 operands there too) */
     if (!resident || kernel == VH_ATTN_STREAMING)
-        return vh_attention_tiled(s, qkv, output, 0, arith == VH_ATTN_FP16, n_images, tokens, embed_dim, num_heads);
+        return vh_attention_tiled(s, qkv, static_cast<float *>(output), arith == VH_ATTN_FP16, n_images, tokens, embed_dim,
+                                  num_heads);
     hipStream_t st = (hipStream_t)s;
     switch ((tokens + 31) / 32) {
     case 1: return launch<1>(st, qkv, output, out_kind, arith, n_images, tokens, embed_dim, num_heads);

@@ -250,7 +250,8 @@ int launch_long(hipStream_t st, const char *qkv, float *out, int n_images, int T
 
 /* qkv_planes: the QKV projection's planes -- parts 3: exact three-part bf16 [3E/32][3][rows][32] (vh_launch_linear_p3
  * with output_planes), parts 1: one-part fp16 [3E/32][rows][32] (vh_launch_linear_planes / _mx_planes_f16, kind 2);
- * rows = n_images * tokens.  output: fp32 rows [rows][embed_dim].  head_dim 64 or 80, any tokens >= 1. */
+ * rows = n_images * tokens.  output: fp32 rows [rows][embed_dim].  head_dim 64 or 80, embed_dim % 32 == 0 (whole planes: an
+ * even head count at head_dim 80), any tokens >= 1. */
 extern "C" int vh_launch_attention_long(vh_stream_t s, const void *qkv_planes, int parts, float *output, int n_images, int tokens,
                                         int embed_dim, int num_heads)
 {

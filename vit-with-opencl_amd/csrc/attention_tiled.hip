@@ -13,7 +13,7 @@
  *  - One workgroup = 4 waves = 64 queries of one (image, head); a wave owns 16 queries
  *    (the MFMA column, lane & 15) and holds their whole score row in registers:
  *    4 x ceil(T/16) accumulators per lane, each lane group (lane >> 4) four keys of a tile.
- *  - K, then V, stream through two 32-key LDS buffers (global_load_dwordx4 -> ds_write_b128,
+ *  - K, then V, stream through two 64-key LDS buffers (global_load_dwordx4 -> ds_write_b128,
  *    the next chunk's loads in flight under the current chunk's MFMAs).  Rows are padded to
  *    D + 4 words: the K fragment (ds_read_b128, 16 keys x one 16-byte chunk per lane group)
  *    and the V fragment (ds_read_b32, 16 consecutive d of four keys) are both conflict-free.
@@ -39,9 +39,9 @@ constexpr int QB_MIN = 64;   /* queries per workgroup = 16 x NW waves, NW = 4 or
  * the four contraction steps of a lane group become ONE v_mfma_f32_16x16x16_f16 -- its lane layout (row l & 15,
  * k = 4 (l >> 4) + i) is exactly the permuted contraction described above.  fp32 accumulation and softmax; the
  * arithmetic of vh_launch_attention_f16 for head dimensions and token counts the resident kernels do not take. */
-template <int D, int NJ, bool OUTBF16, bool LOWP, int NW> /* NJ 16-key tiles: T <= 16*NJ; NW waves of 16 queries */
+template <int D, int NJ, bool LOWP, int NW> /* NJ 16-key tiles: T <= 16*NJ; NW waves of 16 queries */
 __global__ __launch_bounds__(64 * NW, 2) void attention_tiled_kernel(const float *__restrict__ qkv,
-                                                                 void *__restrict__ out, int T, int E, int H,
+                                                                 float *__restrict__ out, int T, int E, int H,
                                                                  int n_qblocks, float scale_log2e)
 {
     constexpr int DS = D + 4;                    /* LDS row stride in words */
@@ -222,30 +222,21 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_tiled_kernel(const float
     if (q_row < T) {
         const size_t o = ((size_t)img * T + q_row) * E + (size_t)h * D + 4 * g;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            if (OUTBF16) {
-                typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-                const bf16x4 v = {(__bf16)O[dt][0], (__bf16)O[dt][1], (__bf16)O[dt][2], (__bf16)O[dt][3]};
-                *reinterpret_cast<bf16x4 *>(static_cast<__bf16 *>(out) + o + 16 * dt) = v;
-            } else {
-                *reinterpret_cast<f32x4 *>(static_cast<float *>(out) + o + 16 * dt) = O[dt];
-            }
-        }
+        for (int dt = 0; dt < DT; ++dt)
+            *reinterpret_cast<f32x4 *>(out + o + 16 * dt) = O[dt];
     }
 }
 
 template <int D, int NJ, int NW>
-int launch_nw(hipStream_t st, const float *qkv, void *out, int out_bf16, int lowp, int n_images, int T, int E, int H)
+int launch_nw(hipStream_t st, const float *qkv, float *out, int lowp, int n_images, int T, int E, int H)
 {
     const int n_qblocks = (T + 16 * NW - 1) / (16 * NW);
     const dim3 grid((unsigned)(n_images * H * n_qblocks)), block(64 * NW);
     const float c = 1.4426950408889634f / sqrtf((float)D);
     if (lowp)
-        hipLaunchKernelGGL((attention_tiled_kernel<D, NJ, false, true, NW>), grid, block, 0, st, qkv, out, T, E, H, n_qblocks, c);
-    else if (out_bf16)
-        hipLaunchKernelGGL((attention_tiled_kernel<D, NJ, true, false, NW>), grid, block, 0, st, qkv, out, T, E, H, n_qblocks, c);
+        hipLaunchKernelGGL((attention_tiled_kernel<D, NJ, true, NW>), grid, block, 0, st, qkv, out, T, E, H, n_qblocks, c);
     else
-        hipLaunchKernelGGL((attention_tiled_kernel<D, NJ, false, false, NW>), grid, block, 0, st, qkv, out, T, E, H, n_qblocks, c);
+        hipLaunchKernelGGL((attention_tiled_kernel<D, NJ, false, NW>), grid, block, 0, st, qkv, out, T, E, H, n_qblocks, c);
     VH_LAUNCH_CHECK("attention_tiled_kernel");
     return 0;
 }
@@ -254,30 +245,30 @@ int launch_nw(hipStream_t st, const float *qkv, void *out, int out_bf16, int low
  * wave) against 2, 3 and 6 waves -- 0.71 ms against 0.90, 0.92 and 0.95: fewer passes over K and V do not pay for
  * fewer workgroups in flight. */
 template <int D, int NJ>
-int launch_nj(hipStream_t st, const float *qkv, void *out, int out_bf16, int lowp, int n_images, int T, int E, int H)
+int launch_nj(hipStream_t st, const float *qkv, float *out, int lowp, int n_images, int T, int E, int H)
 {
-    return launch_nw<D, NJ, 4>(st, qkv, out, out_bf16, lowp, n_images, T, E, H);
+    return launch_nw<D, NJ, 4>(st, qkv, out, lowp, n_images, T, E, H);
 }
 
 template <int D>
-int launch_d(hipStream_t st, const float *qkv, void *out, int out_bf16, int lowp, int n_images, int T, int E, int H)
+int launch_d(hipStream_t st, const float *qkv, float *out, int lowp, int n_images, int T, int E, int H)
 {
     if (T <= 128)
-        return launch_nj<D, 8>(st, qkv, out, out_bf16, lowp, n_images, T, E, H);
+        return launch_nj<D, 8>(st, qkv, out, lowp, n_images, T, E, H);
     if (T <= 272)
-        return launch_nj<D, 17>(st, qkv, out, out_bf16, lowp, n_images, T, E, H);
-    return launch_nj<D, 32>(st, qkv, out, out_bf16, lowp, n_images, T, E, H);
+        return launch_nj<D, 17>(st, qkv, out, lowp, n_images, T, E, H);
+    return launch_nj<D, 32>(st, qkv, out, lowp, n_images, T, E, H);
 }
 
 } // namespace
 
-/* Called by vh_launch_attention / vh_launch_attention_bf16 (attention_f32.hip) for the shapes
- * outside the resident-K/V kernel; arguments are already checked for null / positivity. */
-int vh_attention_tiled(vh_stream_t s, const float *qkv, void *output, int out_bf16, int lowp, int n_images, int tokens,
-                       int embed_dim, int num_heads)
+/* Called by vh_launch_attention_rows (attention_f32.hip) for the shapes outside the resident-K/V kernel, or when the
+ * streaming kernel is asked for; fp32 rows out; arguments are already checked for null / positivity.  Per head_dim
+ * (64, 80, 128): three register classes NJ x {fp32 products, fp16 operands} = 18 kernels, each of them run by
+ * tests/test_gpu_attention_stream.py. */
+int vh_attention_tiled(vh_stream_t s, const float *qkv, float *output, int lowp, int n_images, int tokens, int embed_dim,
+                       int num_heads)
 {
-    if (lowp && out_bf16)
-        return vh_fail(1, "vh_launch_attention: the fp16-operand streaming kernel writes fp32 rows only");
     const int D = embed_dim / num_heads;
     if (D * num_heads != embed_dim || tokens > 512 || ((size_t)n_images * num_heads * ((tokens + QB_MIN - 1) / QB_MIN)) >> 31)
         return vh_fail(1, "vh_launch_attention: embed=%d heads=%d tokens=%d outside the supported range "
@@ -286,9 +277,9 @@ int vh_attention_tiled(vh_stream_t s, const float *qkv, void *output, int out_bf
         return vh_fail(1, "vh_launch_attention: qkv / output must be 16-byte aligned");
     hipStream_t st = (hipStream_t)s;
     switch (D) {
-    case 64: return launch_d<64>(st, qkv, output, out_bf16, lowp, n_images, tokens, embed_dim, num_heads);
-    case 80: return launch_d<80>(st, qkv, output, out_bf16, lowp, n_images, tokens, embed_dim, num_heads);
-    case 128: return launch_d<128>(st, qkv, output, out_bf16, lowp, n_images, tokens, embed_dim, num_heads);
+    case 64: return launch_d<64>(st, qkv, output, lowp, n_images, tokens, embed_dim, num_heads);
+    case 80: return launch_d<80>(st, qkv, output, lowp, n_images, tokens, embed_dim, num_heads);
+    case 128: return launch_d<128>(st, qkv, output, lowp, n_images, tokens, embed_dim, num_heads);
     default:
         return vh_fail(1, "vh_launch_attention: head_dim %d is not built (64, 80, 128)", D);
     }

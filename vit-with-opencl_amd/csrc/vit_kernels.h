@@ -102,9 +102,9 @@ int vh_fail(int code, const char *fmt, ...);
 /* Converts a hipError_t into the launcher return convention, recording text. */
 int vh_hip_status(hipError_t e, const char *what);
 
-/* attention_tiled.hip: the shapes the resident-K/V attention kernel does not take. */
-int vh_attention_tiled(void *stream, const float *qkv, void *output, int out_bf16, int lowp, int n_images, int tokens,
-                       int embed_dim, int num_heads);
+/* attention_tiled.hip: the shapes the resident-K/V attention kernel does not take; fp32 rows out. */
+int vh_attention_tiled(void *stream, const float *qkv, float *output, int lowp, int n_images, int tokens, int embed_dim,
+                       int num_heads);
 
 /* gemm_mfma.hip: token 0 of every image = class token + pos_embed[0] (ViT_seq.c:90-93,114-117) */
 int vh_cls_rows(hipStream_t st, const float *cls_token, const float *pos_embed, float *tokens, int n_images,
