@@ -30,10 +30,10 @@
 #include "ViT_opencl.h"
 #include "vit_ingest.h"
 #include "vit_plan.h"
+#include "vit_requests.h"
 
 #include <math.h>
 #include <pthread.h>
-#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -51,17 +51,6 @@
 
 /* resize + crop: descriptor slots in flight */
 enum { DESC_RING = 8 };
-
-enum { FEAT_NONE, FEAT_DEVICE, FEAT_HOST };
-
-/* One array of a host-form forward: written on the device for a chunk, copied into the chunk's pinned slot, scattered into
- * the caller's memory at image `first`.  dev NULL: the array is not asked for. */
-struct staged
-{
-    void *dev, *pinned[2];   /* for max_batch images: the device buffer, and a pinned one per slot */
-    char *host;              /* the caller's memory, for all n images of a call */
-    size_t per_image;        /* bytes */
-};
 
 struct vit_hip_ctx
 {
@@ -109,76 +98,10 @@ struct vit_hip_ctx
     int desc_live[DESC_RING];
     int desc_next;
 
-    /* feature request (vit_hip_set_features / _host): what is armed, the taps resolved to layer indices, and where the
-     * embeddings go.  The host form writes into device buffers of its own and carries them through two pinned slots. */
-    struct feature_req
-    {
-        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
-        vit_feature_spec spec;
-        int layer[4];                /* spec.taps resolved, ascending */
-        vit_feature_buffers out;     /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: st[].dev */
-        struct staged st[2];         /* FEAT_HOST: cls, pooled */
-    } feat;
-
-    /* top-k request (vit_hip_set_topk / _host), armed independently of the feature request.  The host form selects into
-     * device buffers of its own and carries the pairs through two pinned slots. */
-    struct topk_req
-    {
-        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
-        vit_topk_spec spec;
-        vit_topk_buffers out;        /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: st[].dev */
-        struct staged st[2];         /* FEAT_HOST: labels, scores */
-    } topk;
-
-    /* attention-map request (vit_hip_set_attention / _host), armed independently of the other two.  `attn_serving` is the
-     * request the running forward serves: forward_device sets it for its layer functions and clears it on both exits. */
-    struct attn_req
-    {
-        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
-        vit_attn_spec spec;
-        int layer[4];                /* spec.taps resolved, ascending */
-        vit_attn_buffers out;        /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: st[].dev */
-        struct staged st[2];         /* FEAT_HOST: heads, mean */
-    } amap;
-    const struct attn_req *attn_serving;
-
-    /* rollout request (vit_hip_set_rollout / _host), armed independently of the other three; `roll_serving` as
-     * `attn_serving`.  The scratch is held while armed. */
-    struct rollout_req
-    {
-        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
-        vit_rollout_spec spec;
-        int first;                   /* spec.first_layer resolved */
-        vit_rollout_buffers out;     /* FEAT_DEVICE: the caller's device buffer; FEAT_HOST: st[0].dev */
-        struct staged st[2];         /* FEAT_HOST: rollout; st[1] unused */
-        void *scratch[3];            /* the running product ping-pongs between [0] and [1]; [2]: a step's workspace */
-    } roll;
-    const struct rollout_req *roll_serving;
-
-    /* gallery request (vit_hip_set_gallery / _host), armed independently of the other four.  The queries and the search's
-     * workspace are held while armed. */
-    struct gallery_req
-    {
-        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
-        vit_gallery_spec spec;
-        int layer;                   /* spec.tap resolved */
-        vit_gallery_buffers out;     /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: st[].dev */
-        struct staged st[2];         /* FEAT_HOST: indices, scores */
-        void *scratch[2];            /* [0]: the queries [max_batch][E] fp32; [1]: vh_launch_gallery_topk's workspace */
-    } gal;
-
-    /* dense request (vit_hip_set_dense / _host), armed independently of the other five.  Scratch is held while armed. */
-    struct dense_req
-    {
-        int form;                    /* FEAT_NONE, FEAT_DEVICE, FEAT_HOST */
-        vit_dense_spec spec;
-        int layer, grid;             /* spec.tap resolved; img_size / patch_size */
-        int out_h, out_w;            /* spec's, 0 resolved to img_size */
-        vit_dense_buffers out;       /* FEAT_DEVICE: the caller's device buffers; FEAT_HOST: labels = st[0].dev */
-        struct staged st[2];         /* FEAT_HOST: labels; st[1] unused */
-        void *scratch[2];            /* [0]: the patch logits, when the caller gives no buffer; [1]: the normalised tokens,
-                                      * when final_norm is set and the MLP buffer does not hold them */
-    } dense;
+    /* the armed outputs (csrc/vit_requests.h), and what of them the running forward serves: forward_device sets it for its
+     * layer functions (attention_tap) and clears it when it returns; NULL between forwards */
+    struct requests req;
+    const struct serving *serving;
 
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
@@ -245,27 +168,6 @@ const float *vit_hip_weight(const vit_hip_ctx *ctx, int idx)
     return (idx >= 0 && idx < ctx->n_tensors) ? ctx->w[idx] : NULL;
 }
 
-/* The device buffer for max_batch images of st->per_image bytes and the two pinned slots; what a failure leaves behind,
- * staged_release frees */
-static int staged_alloc(const vit_hip_ctx *ctx, struct staged *st)
-{
-    const size_t bytes = (size_t)ctx->max_batch * st->per_image;
-    int rc = vh_malloc(&st->dev, bytes);
-    for (int slot = 0; slot < 2 && rc == 0; ++slot)
-        rc = vh_host_alloc(&st->pinned[slot], bytes);
-    return rc;
-}
-
-static void staged_release(struct staged *st)
-{
-    if (st->dev) vh_free(st->dev);
-    st->dev = NULL;
-    for (int slot = 0; slot < 2; ++slot) {
-        if (st->pinned[slot]) vh_host_free(st->pinned[slot]);
-        st->pinned[slot] = NULL;
-    }
-}
-
 /* Queue the copy of a chunk of m images into its pinned slot */
 static int staged_d2h(const vit_hip_ctx *ctx, const struct staged *st, int slot, int m)
 {
@@ -278,14 +180,6 @@ static void staged_scatter(const struct staged *st, int slot, int first, int m)
     memcpy(st->host + (size_t)first * st->per_image, st->pinned[slot], (size_t)m * st->per_image);
 }
 
-/* The staging of a host-form request: feature (cls, pooled), top-k (labels, scores), attention maps (heads, mean),
- * rollout (rollout, none), gallery (indices, scores) or dense (labels, none) */
-static void request_release(struct staged st[2])
-{
-    staged_release(&st[0]);
-    staged_release(&st[1]);
-}
-
 void vit_hip_destroy(vit_hip_ctx *ctx)
 {
     if (!ctx)
@@ -296,21 +190,7 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
         vh_stream_sync(ctx->stream);
     }
     prof_release(ctx);
-    request_release(ctx->feat.st);
-    request_release(ctx->topk.st);
-    request_release(ctx->amap.st);
-    request_release(ctx->roll.st);
-    for (int k = 0; k < 3; ++k)
-        if (ctx->roll.scratch[k])
-            vh_free(ctx->roll.scratch[k]);
-    request_release(ctx->gal.st);
-    for (int k = 0; k < 2; ++k)
-        if (ctx->gal.scratch[k])
-            vh_free(ctx->gal.scratch[k]);
-    request_release(ctx->dense.st);
-    for (int k = 0; k < 2; ++k)
-        if (ctx->dense.scratch[k])
-            vh_free(ctx->dense.scratch[k]);
+    requests_release(&ctx->req);
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
@@ -779,8 +659,8 @@ static int attention_rows(const vit_hip_ctx *ctx, vh_stream_t s, float *out, int
 static int attention_tap(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
 {
     int rc = 0;
-    const struct attn_req *ar = ctx->attn_serving;
-    const struct rollout_req *ro = ctx->roll_serving;
+    const struct attn_req *ar = ctx->serving->ar;
+    const struct rollout_req *ro = ctx->serving->ro;
     const vit_config *c = &ctx->cfg;
     for (int k = 0; ar && k < ar->spec.n_taps; ++k)
         if (ar->layer[k] == l)
@@ -791,8 +671,8 @@ static int attention_tap(vit_hip_ctx *ctx, vh_stream_t s, int n, int l)
      * layer */
     if (ro && l >= ro->first)
         OP(VIT_OP_ATTENTION, vh_launch_rollout_step(s, ctx->qkv, ctx->plan.qkv_form, n, ctx->plan.tokens, c->embed_dim, c->num_heads,
-                                                    l == ro->first ? NULL : (const float *)ro->scratch[(l - ro->first + 1) & 1],
-                                                    (float *)ro->scratch[(l - ro->first) & 1], ro->scratch[2]));
+                                                    l == ro->first ? NULL : (const float *)ro->head.scratch[(l - ro->first + 1) & 1],
+                                                    (float *)ro->head.scratch[(l - ro->first) & 1], ro->head.scratch[2]));
     return 0;
 fail:
     return rc;
@@ -908,9 +788,9 @@ fail:
 
 /* F32, the default: GEMM inputs as exact three-part planes written by LayerNorm, attention and the fc1 epilogue.  ln_fold
  * here is the LAB VARIANT ($VIT_HIP_LN_FOLD=1, docs/LABBOOK.md R4.6): ctx->y then holds the split of x itself.
- * *cls_rows is set when the last layer ran on the class-token rows only (opt-in): the final LayerNorm then reads them
- * compacted at the start of the Q|K|V buffer. */
-static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int *cls_rows)
+ * cls_only: this forward runs the last layer on the class-token rows only (opt-in); *cls_rows is set when it did: the final
+ * LayerNorm then reads them compacted at the start of the Q|K|V buffer. */
+static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int cls_only, int *cls_rows)
 {
     int rc = 0;
     const vit_config *c = &ctx->cfg;
@@ -930,7 +810,7 @@ static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int *
                          : (rc = ctx->plan.attn_form == ATTN_LONG ? vh_launch_attention_long(s, ctx->qkv, 3, ctx->hid, n, T, E, c->num_heads)
                                                              : attention_rows(ctx, s, ctx->hid, VH_ATTN_SPLIT3, n)) != 0 ? rc
                          : vh_launch_split3_rows(s, ctx->hid, ctx->attn, rows, E));
-    if (last && ctx->plan.cls_only_last && ctx->plan.cls_only_ok) {
+    if (last && cls_only) {
         /* Opt-in (vit_hip_set_last_layer_cls_only / $VIT_HIP_LAST_LAYER=cls).  The classifier reads row 0 of every
          * image only (ViT_seq.c:511), and behind the last attention no operator mixes rows: the output projection,
          * LayerNorm and MLP of the last layer are evaluated for the n class-token rows instead of n * T, in the
@@ -1087,10 +967,10 @@ static int gallery_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct gallery_req
     const int pooled = ga->spec.source == VIT_GALLERY_POOLED;
     OP(VIT_OP_HEAD, vh_launch_feature_readout(s, ctx->x, cls_rows ? (const float *)ctx->qkv : NULL, c->embed_dim, tw[0], tw[1], c->eps,
                                               ga->spec.final_norm, ga->spec.l2_normalize, VIT_FEATURE_F32, VIT_TOKENS_NLC, n,
-                                              ctx->plan.tokens, c->embed_dim, 0, 1, pooled ? NULL : ga->scratch[0],
-                                              pooled ? ga->scratch[0] : NULL, NULL, ctx->hid, ctx->plan.ws_bytes));
-    OP(VIT_OP_HEAD, vh_launch_gallery_topk(s, (const float *)ga->scratch[0], n, c->embed_dim, ga->spec.d_rows, ga->spec.dtype,
-                                           ga->spec.n_rows, ga->spec.row_stride, ga->spec.k, 0, ga->scratch[1], ga->out.indices,
+                                              ctx->plan.tokens, c->embed_dim, 0, 1, pooled ? NULL : ga->head.scratch[0],
+                                              pooled ? ga->head.scratch[0] : NULL, NULL, ctx->hid, ctx->plan.ws_bytes));
+    OP(VIT_OP_HEAD, vh_launch_gallery_topk(s, (const float *)ga->head.scratch[0], n, c->embed_dim, ga->spec.d_rows, ga->spec.dtype,
+                                           ga->spec.n_rows, ga->spec.row_stride, ga->spec.k, 0, ga->head.scratch[1], ga->out.indices,
                                            ga->out.scores));
     return 0;
 fail:
@@ -1109,13 +989,13 @@ static int dense_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct dense_req *de
     const float *rows = ctx->x + E;
     long image_stride = (long)T * E;
     if (de->spec.final_norm) {
-        float *tok = de->scratch[1] ? (float *)de->scratch[1] : ctx->hid;
+        float *tok = de->head.scratch[1] ? (float *)de->head.scratch[1] : ctx->hid;
         OP(VIT_OP_HEAD, vh_launch_feature_readout(s, ctx->x, NULL, E, tw[0], tw[1], c->eps, 1, 0, VIT_FEATURE_F32, VIT_TOKENS_NLC, n, T, E,
                                                   0, 1, NULL, NULL, tok, NULL, 0));
         rows = tok;
         image_stride = (long)P * E;
     }
-    float *pl = de->out.patch_logits ? de->out.patch_logits : (float *)de->scratch[0];
+    float *pl = de->out.patch_logits ? de->out.patch_logits : (float *)de->head.scratch[0];
     OP(VIT_OP_HEAD, vh_launch_dense_logits(s, rows, image_stride, E, n, P, E, de->spec.d_weight, de->spec.weight_stride, de->spec.d_bias,
                                            de->spec.n_labels, pl));
     OP(VIT_OP_HEAD, vh_launch_dense_labels(s, pl, n, de->grid, de->grid, de->spec.n_labels, de->out_h, de->out_w, de->out.labels,
@@ -1125,16 +1005,19 @@ fail:
     return rc;
 }
 
-/* Everything after the argument checks of the forwards.  fr, tk, ar, ro, ga, de: the armed feature / top-k / attention-map /
- * rollout / gallery / dense request to serve, or NULL. */
+/* Everything after the argument checks of the forwards.  sv: the armed requests to serve; NULL: none */
 static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n, float *d_logits, float *d_probs, vh_stream_t stream,
-                          const struct feature_req *fr, const struct topk_req *tk, const struct attn_req *ar,
-                          const struct rollout_req *ro, const struct gallery_req *ga, const struct dense_req *de)
+                          const struct serving *sv)
 {
+    static const struct serving none;
     int rc = 0;
-    const int cls_only_saved = ctx->plan.cls_only_last;
-    ctx->attn_serving = ar;   /* read by the layer functions (attention_tap) */
-    ctx->roll_serving = ro;
+    sv = sv ? sv : &none;
+    const struct feature_req *fr = sv->fr;
+    const struct topk_req *tk = sv->tk;
+    const struct rollout_req *ro = sv->ro;
+    const struct gallery_req *ga = sv->ga;
+    const struct dense_req *de = sv->de;
+    ctx->serving = sv;   /* read by the layer functions (attention_tap) */
     TRY(vh_set_device(ctx->device));   /* the current device is per host thread */
     const vit_config *c = &ctx->cfg;
     const int E = c->embed_dim, T = ctx->plan.tokens, NC = c->num_classes;
@@ -1150,12 +1033,7 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
     OP(VIT_OP_PATCH_EMBED, patch_embed_launches(ctx, s, src, n));
     int cls_rows = 0;   /* the last layer ran on the class-token rows only (opt-in, fp32 path on planes) */
     /* a request for patch rows of the last layer makes this forward run the last layer on all rows */
-    if (fr && fr->layer[fr->spec.n_taps - 1] == c->depth - 1 && (fr->out.pooled || fr->out.tokens))
-        ctx->plan.cls_only_last = 0;
-    if (ga && ga->layer == c->depth - 1 && ga->spec.source == VIT_GALLERY_POOLED)
-        ctx->plan.cls_only_last = 0;
-    if (de && de->layer == c->depth - 1)
-        ctx->plan.cls_only_last = 0;
+    const int cls_only = ctx->plan.cls_only_last && ctx->plan.cls_only_ok && !serving_needs_last_layer_rows(sv, c->depth);
     for (int l = 0, k = 0; l < c->depth; ++l) {
         switch (ctx->plan.precision) {
         case VIT_PRECISION_FP8_GEMM: TRY(layer_fp8(ctx, s, n, l)); break;
@@ -1163,7 +1041,7 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         case VIT_PRECISION_F32_FP16X2: TRY(layer_fp16x2(ctx, s, n, l)); break;
         default:
             if (ctx->plan.use_p3)
-                TRY(layer_f32_planes(ctx, s, n, l, &cls_rows));
+                TRY(layer_f32_planes(ctx, s, n, l, cls_only, &cls_rows));
             else
                 TRY(layer_f32_rows(ctx, s, n, l));
         }
@@ -1174,11 +1052,8 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         if (de && de->layer == l)
             TRY(dense_tap(ctx, s, de, n));
     }
-    ctx->plan.cls_only_last = cls_only_saved;
-    ctx->attn_serving = NULL;
-    ctx->roll_serving = NULL;
     if (ro)   /* the class token's row of the last product */
-        OP(VIT_OP_ATTENTION, vh_launch_rollout_read(s, (const float *)ro->scratch[(c->depth - 1 - ro->first) & 1], n, T, ro->out.rollout));
+        OP(VIT_OP_ATTENTION, vh_launch_rollout_read(s, (const float *)ro->head.scratch[(c->depth - 1 - ro->first) & 1], n, T, ro->out.rollout));
 
     /* final LayerNorm on the class-token rows -- row i * stride of the residual stream, or compacted at the start of the
      * Q|K|V buffer -- classifier, softmax (ViT_seq.c:506-515) */
@@ -1193,47 +1068,9 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         OP(VIT_OP_SOFTMAX, vh_launch_softmax(s, logits, d_probs, n, NC));
     if (tk)   /* the k best of every row of the fp32 logits: one launch, whatever the precision mode */
         OP(VIT_OP_SOFTMAX, vh_launch_topk(s, logits, n, NC, tk->spec.k, tk->spec.score_kind, tk->out.labels, tk->out.scores));
-    return 0;
 fail:
-    ctx->plan.cls_only_last = cls_only_saved;
-    ctx->attn_serving = NULL;
-    ctx->roll_serving = NULL;
+    ctx->serving = NULL;
     return rc;
-}
-
-/* The armed requests a forward of the function `who` serves.  form: what that call can serve -- FEAT_DEVICE, FEAT_HOST, or
- * FEAT_NONE for a call that serves nothing, whatever is armed.  A request armed in the other form refuses the call, the
- * feature request first. */
-static int armed_requests(vit_hip_ctx *ctx, const char *who, int form, const struct feature_req **fr, const struct topk_req **tk,
-                          const struct attn_req **ar, const struct rollout_req **ro, const struct gallery_req **ga,
-                          const struct dense_req **de)
-{
-    static const char *const what[6] = {"feature", "top-k", "attention", "rollout", "gallery", "dense"},
-                      *const setter[6] = {"features", "topk", "attention", "rollout", "gallery", "dense"};
-    const int armed[6] = {ctx->feat.form, ctx->topk.form, ctx->amap.form, ctx->roll.form, ctx->gal.form, ctx->dense.form};
-    *fr = NULL;
-    *tk = NULL;
-    *ar = NULL;
-    *ro = NULL;
-    *ga = NULL;
-    *de = NULL;
-    if (form == FEAT_NONE)
-        return 0;
-    for (int r = 0; r < 6; ++r)
-        if (armed[r] != FEAT_NONE && armed[r] != form) {
-            char msg[200];
-            const char *const is = armed[r] == FEAT_HOST ? "host" : "device";
-            snprintf(msg, sizeof msg, "%s: the context is armed for %s %s buffers (vit_hip_set_%s%s); disarm it or use the %s forms", who, is,
-                     what[r], setter[r], armed[r] == FEAT_HOST ? "_host" : "", is);
-            return vh_set_error(1, msg);
-        }
-    *fr = armed[0] == form ? &ctx->feat : NULL;
-    *tk = armed[1] == form ? &ctx->topk : NULL;
-    *ar = armed[2] == form ? &ctx->amap : NULL;
-    *ro = armed[3] == form ? &ctx->roll : NULL;
-    *ga = armed[4] == form ? &ctx->gal : NULL;
-    *de = armed[5] == form ? &ctx->dense : NULL;
-    return 0;
 }
 
 /* What the ingest path needs of a context; a staging slot of images holds max_batch fp32 images */
@@ -1256,15 +1093,10 @@ static int source_check(const char *who, const vit_hip_ctx *ctx, const struct in
 static int forward_device_armed(vit_hip_ctx *ctx, const char *who, const struct ingest_src *src, int n, float *d_logits, float *d_probs,
                                 vh_stream_t stream)
 {
-    const struct feature_req *fr;
-    const struct topk_req *tk;
-    const struct attn_req *ar;
-    const struct rollout_req *ro;
-    const struct gallery_req *ga;
-    const struct dense_req *de;
-    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || armed_requests(ctx, who, FEAT_DEVICE, &fr, &tk, &ar, &ro, &ga, &de))
+    struct serving sv;
+    if ((src->kind != INGEST_F32 && source_check(who, ctx, src, n)) || requests_serving(&ctx->req, who, FEAT_DEVICE, &sv))
         return 1;
-    return forward_device(ctx, src, n, d_logits, d_probs, stream, fr, tk, ar, ro, ga, de);
+    return forward_device(ctx, src, n, d_logits, d_probs, stream, &sv);
 }
 
 /* vit_hip_forward_device with no feature output whatever is armed (vit_gather_rccl.c) */
@@ -1273,7 +1105,7 @@ int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n,
     if (!ctx || !d_images || n <= 0 || n > ctx->max_batch)
         return 1;
     const struct ingest_src src = {.kind = INGEST_F32, .on_device = 1, .f32 = d_images};
-    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL, NULL, NULL, NULL, NULL, NULL);
+    return forward_device(ctx, &src, n, d_logits, d_probs, stream, NULL);
 }
 
 int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits,
@@ -1336,550 +1168,29 @@ int vit_hip_forward_device_u8_boxes(vit_hip_ctx *ctx, const vit_image_u8 *d_imag
     return forward_device_armed(ctx, "vit_hip_forward_device_u8_boxes", &src, n, d_logits, d_probs, stream);
 }
 
-/* What the spec checks of a feature and of an attention-map request share; NULL, or why not: the config and the count of taps ... */
-static const char *taps_count_check(const vit_config *cfg, int n_taps)
-{
-    return cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
-           : n_taps < 1 || n_taps > 4 ? "n_taps must be in 1..4"
-           : NULL;
-}
-
-/* ... and the taps themselves (1 <= n_taps <= 4), resolved to ascending layer indices */
-static const char *resolve_taps(const vit_config *cfg, int n_taps, const int taps[4], int layer[4])
-{
-    for (int k = 0; k < n_taps; ++k) {
-        const int t = taps[k];
-        if (t < -cfg->depth || t >= cfg->depth)
-            return "a tap lies outside [-depth, depth)";
-        if (k > 0 && (t < 0 ? t + cfg->depth : t) <= layer[k - 1])
-            return "taps must be strictly ascending once resolved";
-        layer[k] = t < 0 ? t + cfg->depth : t;
+/* The public setters, both forms of each: requests_set_* on the context's requests and on what arming reads of the context */
+#define SETTER(name, kind, spec_t, bufs_t, host)                                                                                 \
+    int name(vit_hip_ctx *ctx, const spec_t *spec, const bufs_t *bufs)                                                           \
+    {                                                                                                                            \
+        if (!ctx)                                                                                                                \
+            return ingest_refuse(#name, "NULL context");                                                                         \
+        const struct request_model m = {.device = ctx->device, .max_batch = ctx->max_batch, .stream = ctx->stream, .cfg = &ctx->cfg, \
+                                        .tokens = ctx->plan.tokens, .qkv_form = ctx->plan.qkv_form, .ws_bytes = ctx->plan.ws_bytes}; \
+        return requests_set_##kind(#name, &m, &ctx->req, spec, bufs, host);                                                      \
     }
-    return NULL;
-}
-
-/* spec against cfg; the taps resolved to ascending layer indices */
-static int feature_spec_check(const char *who, const vit_config *cfg, const vit_feature_spec *spec, int layer[4])
-{
-    const char *why = !cfg || !spec ? "NULL argument" : taps_count_check(cfg, spec->n_taps);
-    why = why ? why
-          : spec->dtype != VIT_FEATURE_F32 && spec->dtype != VIT_FEATURE_BF16 ? "dtype must be VIT_FEATURE_F32 or VIT_FEATURE_BF16"
-          : spec->token_layout != VIT_TOKENS_NLC && spec->token_layout != VIT_TOKENS_NCHW ? "token_layout must be VIT_TOKENS_NLC or VIT_TOKENS_NCHW"
-          : resolve_taps(cfg, spec->n_taps, spec->taps, layer);
-    return why ? ingest_refuse(who, why) : 0;
-}
-
-int vit_feature_sizes(const vit_config *cfg, const vit_feature_spec *spec, size_t *cls_elems, size_t *pooled_elems, size_t *tokens_elems)
-{
-    int layer[4];
-    if (feature_spec_check("vit_feature_sizes", cfg, spec, layer))
-        return 1;
-    const size_t per = (size_t)spec->n_taps * (size_t)cfg->embed_dim, patches = (size_t)vit_config_tokens(cfg) - 1;
-    if (cls_elems)
-        *cls_elems = per;
-    if (pooled_elems)
-        *pooled_elems = patches ? per : 0;
-    if (tokens_elems)
-        *tokens_elems = per * patches;
-    return 0;
-}
-
-/* What arming a feature, a top-k and an attention-map request share, behind their own spec and buffer checks (skipped
- * without a context, which is refused here).  req: the new request's staged arrays; the host form has named the caller's memory and the bytes per
- * image of those it wants, and their stages are made here.  armed: where the context keeps the request's staged arrays.
- * Returns 0 with the old request's staging released, for the caller to store the new request; on failure the previous
- * request stays armed and nothing leaks. */
-static int arm(const char *who, vit_hip_ctx *ctx, size_t armed, struct staged req[2])
-{
-    int rc = 0;
-    if (!ctx)
-        return ingest_refuse(who, "NULL context");
-    TRY(vh_set_device(ctx->device));
-    /* the staging of an earlier host request may still be read by its last forward's copies */
-    TRY(vh_stream_sync(ctx->stream));
-    for (int k = 0; k < 2; ++k)
-        if (req[k].host)
-            TRY(staged_alloc(ctx, &req[k]));
-    request_release((struct staged *)((char *)ctx + armed));
-    return 0;
-fail:
-    request_release(req);
-    return rc;
-}
-
-/* Both forms of arming; host: bufs are host memory, staged through device buffers and pinned slots made by arm() */
-static int set_features(const char *who, vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *bufs, int host)
-{
-    struct feature_req fr;
-    memset(&fr, 0, sizeof fr);
-    if (ctx && spec) {
-        if (feature_spec_check(who, &ctx->cfg, spec, fr.layer))
-            return 1;
-        const char *why = !bufs || (!bufs->cls && !bufs->pooled && !bufs->tokens) ? "no output buffer"
-                          : host && bufs->tokens ? "the host form takes cls and pooled only (tokens: use the device form)"
-                          : ctx->plan.tokens < 2 && (bufs->pooled || bufs->tokens) ? "pooled and tokens need at least one patch token"
-                          : !host && (((uintptr_t)bufs->cls | (uintptr_t)bufs->pooled | (uintptr_t)bufs->tokens) & 15) ? "device buffers must be 16-byte aligned"
-                          : NULL;
-        if (why)
-            return ingest_refuse(who, why);
-        fr.form = host ? FEAT_HOST : FEAT_DEVICE;
-        fr.spec = *spec;
-        fr.out = *bufs;
-        if (host) {
-            const size_t per = (size_t)spec->n_taps * ctx->cfg.embed_dim * (spec->dtype == VIT_FEATURE_BF16 ? 2 : 4);
-            fr.st[0] = (struct staged){.host = (char *)bufs->cls, .per_image = per};
-            fr.st[1] = (struct staged){.host = (char *)bufs->pooled, .per_image = per};
-        }
-    }
-    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, feat.st), fr.st);
-    if (rc != 0)
-        return rc;
-    if (fr.form == FEAT_HOST)
-        fr.out = (vit_feature_buffers){fr.st[0].dev, fr.st[1].dev, NULL};
-    ctx->feat = fr;
-    return 0;
-}
-
-int vit_hip_set_features(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *d_bufs)
-{
-    return set_features("vit_hip_set_features", ctx, spec, d_bufs, 0);
-}
-
-int vit_hip_set_features_host(vit_hip_ctx *ctx, const vit_feature_spec *spec, const vit_feature_buffers *h_bufs)
-{
-    return set_features("vit_hip_set_features_host", ctx, spec, h_bufs, 1);
-}
-
-static int topk_spec_check(const char *who, const vit_config *cfg, const vit_topk_spec *spec)
-{
-    const char *why = !cfg || !spec ? "NULL argument"
-                      : cfg->num_classes < 1 || cfg->num_classes > 65536 ? "num_classes must be in 1..65536"
-                      : spec->k < 1 || spec->k > 32 ? "k must be in 1..32"
-                      : spec->k > cfg->num_classes ? "k exceeds num_classes"
-                      : spec->score_kind != VIT_TOPK_PROBS && spec->score_kind != VIT_TOPK_LOGITS ? "score_kind must be VIT_TOPK_PROBS or VIT_TOPK_LOGITS"
-                      : NULL;
-    return why ? ingest_refuse(who, why) : 0;
-}
-
-int vit_topk_check(const vit_config *cfg, const vit_topk_spec *spec)
-{
-    return topk_spec_check("vit_topk_check", cfg, spec);
-}
-
-/* Both forms of arming, as set_features */
-static int set_topk(const char *who, vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *bufs, int host)
-{
-    struct topk_req tk;
-    memset(&tk, 0, sizeof tk);
-    if (ctx && spec) {
-        if (topk_spec_check(who, &ctx->cfg, spec))
-            return 1;
-        const char *why = !bufs || !bufs->labels ? "no labels buffer"
-                          : !host && (((uintptr_t)bufs->labels | (uintptr_t)bufs->scores) & 15) ? "device buffers must be 16-byte aligned"
-                          : NULL;
-        if (why)
-            return ingest_refuse(who, why);
-        tk.form = host ? FEAT_HOST : FEAT_DEVICE;
-        tk.spec = *spec;
-        tk.out = *bufs;
-        if (host) {
-            tk.st[0] = (struct staged){.host = (char *)bufs->labels, .per_image = (size_t)spec->k * sizeof(int)};
-            tk.st[1] = (struct staged){.host = (char *)bufs->scores, .per_image = (size_t)spec->k * sizeof(float)};
-        }
-    }
-    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, topk.st), tk.st);
-    if (rc != 0)
-        return rc;
-    if (tk.form == FEAT_HOST)
-        tk.out = (vit_topk_buffers){tk.st[0].dev, tk.st[1].dev};
-    ctx->topk = tk;
-    return 0;
-}
-
-int vit_hip_set_topk(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *d_bufs)
-{
-    return set_topk("vit_hip_set_topk", ctx, spec, d_bufs, 0);
-}
-
-int vit_hip_set_topk_host(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit_topk_buffers *h_bufs)
-{
-    return set_topk("vit_hip_set_topk_host", ctx, spec, h_bufs, 1);
-}
-
-static int attn_spec_check(const char *who, const vit_config *cfg, const vit_attn_spec *spec, int layer[4])
-{
-    const char *why = !cfg || !spec ? "NULL argument" : taps_count_check(cfg, spec->n_taps);
-    why = why ? why
-          : cfg->num_heads <= 0 || cfg->embed_dim % cfg->num_heads != 0 ? "bad model config"
-          : resolve_taps(cfg, spec->n_taps, spec->taps, layer);
-    return why ? ingest_refuse(who, why) : 0;
-}
-
-int vit_attn_sizes(const vit_config *cfg, const vit_attn_spec *spec, size_t *heads_elems, size_t *mean_elems)
-{
-    int layer[4];
-    if (attn_spec_check("vit_attn_sizes", cfg, spec, layer))
-        return 1;
-    const size_t per = (size_t)spec->n_taps * (size_t)vit_config_tokens(cfg);
-    if (heads_elems)
-        *heads_elems = per * (size_t)cfg->num_heads;
-    if (mean_elems)
-        *mean_elems = per;
-    return 0;
-}
-
-/* Both forms of arming, as set_features */
-static int set_attention(const char *who, vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *bufs, int host)
-{
-    struct attn_req ar;
-    memset(&ar, 0, sizeof ar);
-    if (ctx && spec) {
-        if (attn_spec_check(who, &ctx->cfg, spec, ar.layer))
-            return 1;
-        const vit_config *c = &ctx->cfg;
-        const char *why = !bufs || (!bufs->heads && !bufs->mean) ? "no output buffer"
-                          : !vh_cls_attention_head_dim_ok(c->embed_dim / c->num_heads) ? "head_dim must be a multiple of 16, at most 128"
-                          : !host && (((uintptr_t)bufs->heads | (uintptr_t)bufs->mean) & 15) ? "device buffers must be 16-byte aligned"
-                          : NULL;
-        if (why)
-            return ingest_refuse(who, why);
-        ar.form = host ? FEAT_HOST : FEAT_DEVICE;
-        ar.spec = *spec;
-        ar.out = *bufs;
-        if (host) {
-            const size_t per = (size_t)spec->n_taps * ctx->plan.tokens * sizeof(float);
-            ar.st[0] = (struct staged){.host = (char *)bufs->heads, .per_image = per * c->num_heads};
-            ar.st[1] = (struct staged){.host = (char *)bufs->mean, .per_image = per};
-        }
-    }
-    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, amap.st), ar.st);
-    if (rc != 0)
-        return rc;
-    if (ar.form == FEAT_HOST)
-        ar.out = (vit_attn_buffers){ar.st[0].dev, ar.st[1].dev};
-    ctx->amap = ar;
-    return 0;
-}
-
-int vit_hip_set_attention(vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *d_bufs)
-{
-    return set_attention("vit_hip_set_attention", ctx, spec, d_bufs, 0);
-}
-
-int vit_hip_set_attention_host(vit_hip_ctx *ctx, const vit_attn_spec *spec, const vit_attn_buffers *h_bufs)
-{
-    return set_attention("vit_hip_set_attention_host", ctx, spec, h_bufs, 1);
-}
-
-/* spec against cfg; first_layer resolved to a layer index */
-static int rollout_spec_check(const char *who, const vit_config *cfg, const vit_rollout_spec *spec, int *first)
-{
-    const char *why = !cfg || !spec ? "NULL argument"
-                      : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ||
-                        cfg->num_heads <= 0 || cfg->embed_dim % cfg->num_heads != 0 ? "bad model config"
-                      : spec->first_layer < -cfg->depth || spec->first_layer >= cfg->depth ? "first_layer lies outside [-depth, depth)"
-                      : NULL;
-    if (why)
-        return ingest_refuse(who, why);
-    *first = spec->first_layer < 0 ? spec->first_layer + cfg->depth : spec->first_layer;
-    return 0;
-}
-
-int vit_rollout_sizes(const vit_config *cfg, const vit_rollout_spec *spec, size_t *rollout_elems, size_t *scratch_bytes_per_image)
-{
-    int first;
-    if (rollout_spec_check("vit_rollout_sizes", cfg, spec, &first))
-        return 1;
-    const size_t T = (size_t)vit_config_tokens(cfg);
-    if (rollout_elems)
-        *rollout_elems = T;
-    if (scratch_bytes_per_image)
-        *scratch_bytes_per_image = 3 * T * T * sizeof(float);
-    return 0;
-}
-
-static void rollout_scratch_free(void *scratch[3])
-{
-    for (int k = 0; k < 3; ++k) {
-        if (scratch[k])
-            vh_free(scratch[k]);
-        scratch[k] = NULL;
-    }
-}
-
-/* Both forms of arming, as set_features; the scratch (two running products and a step's workspace, of max_batch images
- * each) is made with the first request and kept until the context is disarmed or destroyed */
-static int set_rollout(const char *who, vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *bufs, int host)
-{
-    struct rollout_req ro;
-    int fresh = 0;   /* this call made the scratch */
-    memset(&ro, 0, sizeof ro);
-    if (ctx && spec) {
-        if (rollout_spec_check(who, &ctx->cfg, spec, &ro.first))
-            return 1;
-        const vit_config *c = &ctx->cfg;
-        const int D = c->embed_dim / c->num_heads;
-        const char *why = !bufs || !bufs->rollout ? "no output buffer"
-                          : !vh_cls_attention_head_dim_ok(D) ? "head_dim must be a multiple of 16, at most 128"
-                          : ctx->plan.qkv_form != VH_QKV_ROWS_F32 && c->embed_dim % 32 != 0 ? "embed_dim must be a multiple of 32 where Q|K|V is stored as planes"
-                          : ctx->plan.tokens > vh_rollout_max_tokens(D) ? "too many tokens for the rollout kernel at this head_dim (vh_rollout_max_tokens)"
-                          : !host && ((uintptr_t)bufs->rollout & 15) ? "device buffers must be 16-byte aligned"
-                          : NULL;
-        if (why)
-            return ingest_refuse(who, why);
-        ro.form = host ? FEAT_HOST : FEAT_DEVICE;
-        ro.spec = *spec;
-        ro.out = *bufs;
-        if (host)
-            ro.st[0] = (struct staged){.host = (char *)bufs->rollout, .per_image = (size_t)ctx->plan.tokens * sizeof(float)};
-        memcpy(ro.scratch, ctx->roll.scratch, sizeof ro.scratch);
-        if (!ro.scratch[0]) {
-            const size_t one = vh_rollout_workspace(ctx->max_batch, ctx->plan.tokens);
-            int bad = vh_set_device(ctx->device);
-            for (int k = 0; k < 3 && !bad; ++k)
-                bad = vh_malloc(&ro.scratch[k], one);
-            if (bad) {
-                char msg[160];
-                rollout_scratch_free(ro.scratch);
-                snprintf(msg, sizeof msg, "3 x %zu bytes of device scratch (max_batch x T x T x 4 each) cannot be allocated", one);
-                return ingest_refuse(who, msg);
-            }
-            fresh = 1;
-        }
-    }
-    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, roll.st), ro.st);
-    if (rc != 0) {
-        if (fresh)
-            rollout_scratch_free(ro.scratch);
-        return rc;
-    }
-    if (ro.form == FEAT_NONE)   /* disarmed: behind arm()'s stream sync nothing reads the scratch any more */
-        rollout_scratch_free(ctx->roll.scratch);
-    if (ro.form == FEAT_HOST)
-        ro.out = (vit_rollout_buffers){ro.st[0].dev};
-    ctx->roll = ro;
-    return 0;
-}
-
-int vit_hip_set_rollout(vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *d_bufs)
-{
-    return set_rollout("vit_hip_set_rollout", ctx, spec, d_bufs, 0);
-}
-
-int vit_hip_set_rollout_host(vit_hip_ctx *ctx, const vit_rollout_spec *spec, const vit_rollout_buffers *h_bufs)
-{
-    return set_rollout("vit_hip_set_rollout_host", ctx, spec, h_bufs, 1);
-}
-
-/* spec against cfg, pointers aside; tap resolved to a layer index, the scratch per image of max_batch */
-static int gallery_spec_check(const char *who, const vit_config *cfg, const vit_gallery_spec *spec, int *layer, size_t *per_image)
-{
-    const char *why = !cfg || !spec ? "NULL argument"
-                      : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
-                      : spec->source != VIT_GALLERY_CLS && spec->source != VIT_GALLERY_POOLED ? "source must be VIT_GALLERY_CLS or VIT_GALLERY_POOLED"
-                      : spec->tap < -cfg->depth || spec->tap >= cfg->depth ? "tap lies outside [-depth, depth)"
-                      : spec->source == VIT_GALLERY_POOLED && vit_config_tokens(cfg) < 2 ? "pooled needs at least one patch token"
-                      : spec->dtype != VH_GALLERY_F32 && spec->dtype != VH_GALLERY_BF16 ? "dtype must be VH_GALLERY_F32 or VH_GALLERY_BF16"
-                      : cfg->embed_dim % 4 != 0 || cfg->embed_dim > 2048 ? "embed_dim must be a multiple of 4, at most 2048"
-                      : spec->k < 1 || spec->k > 32 ? "k must be in 1..32"
-                      : spec->n_rows < spec->k || spec->n_rows > 2147483647L ? "n_rows must be in k..2^31 - 1"
-                      : spec->row_stride < cfg->embed_dim || spec->row_stride > (1L << 40) ||
-                        (spec->row_stride * (spec->dtype == VH_GALLERY_BF16 ? 2 : 4)) % 16 != 0
-                          ? "row_stride must be at least embed_dim, and a multiple of 16 bytes"
-                      : NULL;
-    if (why)
-        return ingest_refuse(who, why);
-    *layer = spec->tap < 0 ? spec->tap + cfg->depth : spec->tap;
-    *per_image = (size_t)cfg->embed_dim * sizeof(float) + vh_gallery_workspace(1, spec->n_rows, spec->k, 0);
-    return 0;
-}
-
-int vit_gallery_check(const vit_config *cfg, const vit_gallery_spec *spec, size_t *scratch_bytes_per_max_batch_image)
-{
-    int layer;
-    size_t per_image;
-    if (gallery_spec_check("vit_gallery_check", cfg, spec, &layer, &per_image))
-        return 1;
-    if (scratch_bytes_per_max_batch_image)
-        *scratch_bytes_per_max_batch_image = per_image;
-    return 0;
-}
-
-static void gallery_scratch_free(void *scratch[2])
-{
-    for (int k = 0; k < 2; ++k) {
-        if (scratch[k])
-            vh_free(scratch[k]);
-        scratch[k] = NULL;
-    }
-}
-
-/* Both forms of arming, as set_features; the scratch depends on the spec (k, n_rows), so every arming makes its own and
- * the previous request's is freed once the new one stands */
-static int set_gallery(const char *who, vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *bufs, int host)
-{
-    struct gallery_req ga;
-    memset(&ga, 0, sizeof ga);
-    if (ctx && spec) {
-        size_t per_image;
-        if (gallery_spec_check(who, &ctx->cfg, spec, &ga.layer, &per_image))
-            return 1;
-        const char *why = !spec->d_rows ? "no gallery rows"
-                          : (uintptr_t)spec->d_rows & 15 ? "the gallery rows must be 16-byte aligned"
-                          : !bufs || !bufs->indices ? "no indices buffer"
-                          : !host && (((uintptr_t)bufs->indices | (uintptr_t)bufs->scores) & 15) ? "device buffers must be 16-byte aligned"
-                          : NULL;
-        if (why)
-            return ingest_refuse(who, why);
-        ga.form = host ? FEAT_HOST : FEAT_DEVICE;
-        ga.spec = *spec;
-        ga.out = *bufs;
-        if (host) {
-            ga.st[0] = (struct staged){.host = (char *)bufs->indices, .per_image = (size_t)spec->k * sizeof(int)};
-            ga.st[1] = (struct staged){.host = (char *)bufs->scores, .per_image = (size_t)spec->k * sizeof(float)};
-        }
-        const size_t q_bytes = (size_t)ctx->max_batch * ctx->cfg.embed_dim * sizeof(float);
-        const size_t ws_bytes = (size_t)ctx->max_batch * (per_image - (size_t)ctx->cfg.embed_dim * sizeof(float));
-        if (vh_set_device(ctx->device) || vh_malloc(&ga.scratch[0], q_bytes) || vh_malloc(&ga.scratch[1], ws_bytes)) {
-            char msg[160];
-            gallery_scratch_free(ga.scratch);
-            snprintf(msg, sizeof msg, "%zu bytes of device scratch (the queries and the search's workspace) cannot be allocated",
-                     q_bytes + ws_bytes);
-            return ingest_refuse(who, msg);
-        }
-    }
-    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, gal.st), ga.st);
-    if (rc != 0) {
-        gallery_scratch_free(ga.scratch);
-        return rc;
-    }
-    gallery_scratch_free(ctx->gal.scratch);   /* behind arm()'s stream sync nothing reads the previous request's any more */
-    if (ga.form == FEAT_HOST)
-        ga.out = (vit_gallery_buffers){(int *)ga.st[0].dev, (float *)ga.st[1].dev};
-    ctx->gal = ga;
-    return 0;
-}
-
-int vit_hip_set_gallery(vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *d_bufs)
-{
-    return set_gallery("vit_hip_set_gallery", ctx, spec, d_bufs, 0);
-}
-
-int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, const vit_gallery_buffers *h_bufs)
-{
-    return set_gallery("vit_hip_set_gallery_host", ctx, spec, h_bufs, 1);
-}
-
-/* spec against cfg, pointers aside; tap resolved to a layer index, the grid, the output size */
-static int dense_spec_check(const char *who, const vit_config *cfg, const vit_dense_spec *spec, int *layer, int *grid, int *out_h, int *out_w)
-{
-    const int g = cfg && cfg->patch_size > 0 ? cfg->img_size / cfg->patch_size : 0;
-    const char *why = !cfg || !spec ? "NULL argument"
-                      : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
-                      : spec->tap < -cfg->depth || spec->tap >= cfg->depth ? "tap lies outside [-depth, depth)"
-                      : vit_config_tokens(cfg) < 2 || vit_config_tokens(cfg) - 1 != g * g ? "the model needs a square grid of at least one patch token"
-                      : g > VH_DENSE_MAX_GRID ? "the patch grid must be at most 64 x 64"
-                      : cfg->embed_dim % 4 != 0 || cfg->embed_dim > 2048 ? "embed_dim must be a multiple of 4, at most 2048"
-                      : spec->n_labels < 2 || spec->n_labels > VH_DENSE_MAX_LABELS ? "n_labels must be in 2..256"
-                      : spec->out_h < 0 || spec->out_h > 4096 || spec->out_w < 0 || spec->out_w > 4096 ||
-                        (spec->out_h == 0 && cfg->img_size > 4096) || (spec->out_w == 0 && cfg->img_size > 4096)
-                          ? "out_h and out_w must be in 1..4096 (0: the model's img_size)"
-                      : spec->weight_stride < cfg->embed_dim || spec->weight_stride > (1L << 40) || spec->weight_stride % 4 != 0
-                          ? "weight_stride must be at least embed_dim, and a multiple of 4"
-                      : NULL;
-    if (why)
-        return ingest_refuse(who, why);
-    *layer = spec->tap < 0 ? spec->tap + cfg->depth : spec->tap;
-    *grid = g;
-    *out_h = spec->out_h ? spec->out_h : cfg->img_size;
-    *out_w = spec->out_w ? spec->out_w : cfg->img_size;
-    return 0;
-}
-
-int vit_dense_sizes(const vit_config *cfg, const vit_dense_spec *spec, size_t *labels_bytes, size_t *scores_elems,
-                    size_t *patch_logits_elems, size_t *scratch_bytes_per_image)
-{
-    int layer, grid, out_h, out_w;
-    if (dense_spec_check("vit_dense_sizes", cfg, spec, &layer, &grid, &out_h, &out_w))
-        return 1;
-    const size_t P = (size_t)grid * grid;
-    if (labels_bytes)
-        *labels_bytes = (size_t)out_h * out_w;
-    if (scores_elems)
-        *scores_elems = (size_t)out_h * out_w;
-    if (patch_logits_elems)
-        *patch_logits_elems = P * spec->n_labels;
-    if (scratch_bytes_per_image)
-        *scratch_bytes_per_image = P * ((size_t)spec->n_labels + (spec->final_norm ? (size_t)cfg->embed_dim : 0)) * sizeof(float);
-    return 0;
-}
-
-static void dense_scratch_free(void *scratch[2])
-{
-    for (int k = 0; k < 2; ++k) {
-        if (scratch[k])
-            vh_free(scratch[k]);
-        scratch[k] = NULL;
-    }
-}
-
-/* Both forms of arming, as set_gallery: every arming makes its own scratch, the previous request's is freed once the new
- * one stands */
-static int set_dense(const char *who, vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *bufs, int host)
-{
-    struct dense_req de;
-    memset(&de, 0, sizeof de);
-    if (ctx && spec) {
-        if (dense_spec_check(who, &ctx->cfg, spec, &de.layer, &de.grid, &de.out_h, &de.out_w))
-            return 1;
-        const char *why = !spec->d_weight ? "no head weight"
-                          : ((uintptr_t)spec->d_weight | (uintptr_t)spec->d_bias) & 15 ? "the head's weight and bias must be 16-byte aligned"
-                          : !bufs || !bufs->labels ? "no labels buffer"
-                          : host && (bufs->scores || bufs->patch_logits) ? "the host form takes labels only (scores, patch_logits: use the device form)"
-                          : !host && (((uintptr_t)bufs->labels | (uintptr_t)bufs->scores | (uintptr_t)bufs->patch_logits) & 15)
-                              ? "device buffers must be 16-byte aligned"
-                          : NULL;
-        if (why)
-            return ingest_refuse(who, why);
-        de.form = host ? FEAT_HOST : FEAT_DEVICE;
-        de.spec = *spec;
-        de.out = *bufs;
-        if (host)
-            de.st[0] = (struct staged){.host = (char *)bufs->labels, .per_image = (size_t)de.out_h * de.out_w};
-        const size_t P = (size_t)ctx->plan.tokens - 1;
-        const size_t pl_bytes = bufs->patch_logits ? 0 : (size_t)ctx->max_batch * P * spec->n_labels * sizeof(float);
-        size_t tok_bytes = spec->final_norm ? (size_t)ctx->max_batch * P * ctx->cfg.embed_dim * sizeof(float) : 0;
-        if (tok_bytes <= ctx->plan.ws_bytes)
-            tok_bytes = 0;   /* they go through the MLP buffer */
-        if (vh_set_device(ctx->device) || (pl_bytes && vh_malloc(&de.scratch[0], pl_bytes)) || (tok_bytes && vh_malloc(&de.scratch[1], tok_bytes))) {
-            char msg[160];
-            dense_scratch_free(de.scratch);
-            snprintf(msg, sizeof msg, "%zu bytes of device scratch (the patch logits and the normalised tokens) cannot be allocated",
-                     pl_bytes + tok_bytes);
-            return ingest_refuse(who, msg);
-        }
-    }
-    const int rc = arm(who, ctx, offsetof(vit_hip_ctx, dense.st), de.st);
-    if (rc != 0) {
-        dense_scratch_free(de.scratch);
-        return rc;
-    }
-    dense_scratch_free(ctx->dense.scratch);   /* behind arm()'s stream sync nothing reads the previous request's any more */
-    if (de.form == FEAT_HOST)
-        de.out = (vit_dense_buffers){(unsigned char *)de.st[0].dev, NULL, NULL};
-    ctx->dense = de;
-    return 0;
-}
-
-int vit_hip_set_dense(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *d_bufs)
-{
-    return set_dense("vit_hip_set_dense", ctx, spec, d_bufs, 0);
-}
-
-int vit_hip_set_dense_host(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *h_bufs)
-{
-    return set_dense("vit_hip_set_dense_host", ctx, spec, h_bufs, 1);
-}
+SETTER(vit_hip_set_features, features, vit_feature_spec, vit_feature_buffers, 0)
+SETTER(vit_hip_set_features_host, features, vit_feature_spec, vit_feature_buffers, 1)
+SETTER(vit_hip_set_topk, topk, vit_topk_spec, vit_topk_buffers, 0)
+SETTER(vit_hip_set_topk_host, topk, vit_topk_spec, vit_topk_buffers, 1)
+SETTER(vit_hip_set_attention, attention, vit_attn_spec, vit_attn_buffers, 0)
+SETTER(vit_hip_set_attention_host, attention, vit_attn_spec, vit_attn_buffers, 1)
+SETTER(vit_hip_set_rollout, rollout, vit_rollout_spec, vit_rollout_buffers, 0)
+SETTER(vit_hip_set_rollout_host, rollout, vit_rollout_spec, vit_rollout_buffers, 1)
+SETTER(vit_hip_set_gallery, gallery, vit_gallery_spec, vit_gallery_buffers, 0)
+SETTER(vit_hip_set_gallery_host, gallery, vit_gallery_spec, vit_gallery_buffers, 1)
+SETTER(vit_hip_set_dense, dense, vit_dense_spec, vit_dense_buffers, 0)
+SETTER(vit_hip_set_dense_host, dense, vit_dense_spec, vit_dense_buffers, 1)
+#undef SETTER
 
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
 {
@@ -2044,32 +1355,21 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, str
                              int form)
 {
     int rc = 0;
-    const struct feature_req *fr;
-    const struct topk_req *tk;
-    const struct attn_req *ar;
-    const struct rollout_req *ro;
-    const struct gallery_req *ga;
-    const struct dense_req *de;
-    if (armed_requests(ctx, "forward", form, &fr, &tk, &ar, &ro, &ga, &de))
+    struct serving sv;
+    if (requests_serving(&ctx->req, "forward", form, &sv))
         return 1;
     TRY(vh_set_device(ctx->device));
     const vit_config *c = &ctx->cfg;
     const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->kind == INGEST_F32 ? sizeof(float) : 1);
     const size_t NC = (size_t)c->num_classes;
-    /* what comes back per chunk besides the probabilities, in the order it is queued: logits, cls, pooled, labels, scores,
-     * heads, mean, rollout, indices, gallery scores, dense labels */
+    /* what comes back per chunk besides the probabilities, in the order it is queued: the logits, then the served requests'
+     * arrays (serving_staged) */
     const struct staged logits_st = {ctx->d_logits, {ctx->h_logits[0], ctx->h_logits[1]}, (char *)logits, NC * sizeof(float)};
-    const struct staged *arrays[11];
+    const struct staged *arrays[1 + MAX_STAGED];
     int n_arrays = 0;
     if (logits)
         arrays[n_arrays++] = &logits_st;
-    for (int a = 0; a < 10; ++a) {
-        const struct staged *st = a < 2 ? (fr ? &fr->st[a] : NULL) : a < 4 ? (tk ? &tk->st[a - 2] : NULL)
-                                  : a < 6 ? (ar ? &ar->st[a - 4] : NULL) : a < 7 ? (ro ? &ro->st[0] : NULL)
-                                  : a < 9 ? (ga ? &ga->st[a - 7] : NULL) : (de ? &de->st[0] : NULL);
-        if (st && st->dev)
-            arrays[n_arrays++] = st;
-    }
+    n_arrays += serving_staged(&sv, arrays + n_arrays);
 
     int prev_first = 0, prev_m = 0, k = 0;
     for (int first = 0, m = 0; first < n; first += m, ++k) {
@@ -2108,7 +1408,7 @@ static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, str
         TRY(vh_event_record(ctx->up_done[s], ctx->copy_stream));
 
         TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
-        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, fr, tk, ar, ro, ga, de));
+        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, &sv));
         TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
         /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
         int a = 0;

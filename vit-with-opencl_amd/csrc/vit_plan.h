@@ -71,7 +71,7 @@ struct vit_plan
     int ln_fold;        /* every LayerNorm but the final one folded into the projection behind it (csrc/norm_fold.h) */
     int use_p3;         /* F32: GEMM inputs travel as three-part bf16 planes (y, attn, hid hold 6 bytes per value) */
     int cls_only_last;  /* the last layer's output projection and MLP run on the class-token rows only, where cls_only_ok: the
-                         * one field that changes after creation (vit_hip_set_last_layer_cls_only, and a forward for its own run) */
+                         * one field that changes after creation (vit_hip_set_last_layer_cls_only alone; a forward only reads it) */
     int attn_form;      /* ATTN_*, for the planes paths */
     int fp32_native;    /* $VIT_HIP_GEMM_FP32=native: F32 on fp32 rows, with the fp32 matrix instruction in the patch embedding, the
                          * attention and every projection without pre-split weights (VH_FP32_NATIVE, VH_ATTN_NATIVE) */
