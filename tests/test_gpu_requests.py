@@ -1,4 +1,4 @@
-"""All six armed outputs at once through the host form's copy-back (forward_pipelined over serving_staged,
+"""All six armed outputs at once through the host form's copy-back (pipeline_run over serving_staged,
 csrc/vit_requests.h): 9 images on a context of max_batch 4 are three chunks -- both pinned slots used twice and a ragged last
 chunk of one image -- with logits and probabilities asked for too.  Every array must have the bits the device forms give
 with all six armed, run chunk by chunk on the same images."""

@@ -17,7 +17,8 @@
  * What a forward reads -- fp32 or 8-bit pixels, of the model's size or resized / cropped from boxes first, in device or in
  * host memory -- is one struct ingest_src (csrc/vit_ingest.h).  Everything about 8-bit sources that needs no device lives in
  * csrc/vit_ingest.c: the argument checks, the fill of the resize kernel's descriptors, and the planner and packer of the host
- * forms' staging slots.  This file keeps the descriptor ring, the launches and the pipeline over the staging slots.
+ * forms' staging slots.  The staging slots themselves, the chunk loop of the host forms over them and the descriptor ring are
+ * csrc/vit_pipeline.c; this file keeps the launches.
  *
  * What a context will run -- the kernels of a forward, the layout of the weight slabs, the size of every arena buffer -- is one
  * struct vit_plan (csrc/vit_plan.h), made by plan_make before anything is allocated; this file allocates what it says and
@@ -29,6 +30,7 @@
  */
 #include "ViT_opencl.h"
 #include "vit_ingest.h"
+#include "vit_pipeline.h"
 #include "vit_plan.h"
 #include "vit_requests.h"
 
@@ -48,9 +50,6 @@
             goto fail;            \
         }                         \
     } while (0)
-
-/* resize + crop: descriptor slots in flight */
-enum { DESC_RING = 8 };
 
 struct vit_hip_ctx
 {
@@ -80,23 +79,10 @@ struct vit_hip_ctx
     float *cls;         /* normalised CLS rows  [max_batch][E] */
     float *d_logits;    /* [max_batch][classes] */
     float *d_probs;     /* [max_batch][classes] */
-    /* host-pointer API: two staging slots so that gathering + uploading chunk k+1
-     * overlaps the compute of chunk k (pinned host memory, second stream, events) */
-    float *d_images[2]; /* [max_batch][C][H][W] */
-    float *h_images[2];
-    float *h_logits[2];
-    float *h_probs[2];
-    vh_stream_t copy_stream;
-    vh_event_t up_done[2], comp_done[2], out_done[2];
-
-    /* resize + centre crop (vit_hip_resize_crop_u8, the _resized forwards): the crops land in Q|K|V at plan.crop_off (behind
-     * the fp32 expansion on the fp32-rows paths), the coefficient tables in hid.  Per-call descriptors go up through a ring
-     * of pinned slots; a slot is refilled only once the event behind its last reader has completed. */
-    vh_resize_desc *h_desc[DESC_RING];
-    vh_resize_desc *d_desc[DESC_RING];
-    vh_event_t desc_done[DESC_RING];
-    int desc_live[DESC_RING];
-    int desc_next;
+    /* host-pointer API: the staging slots, copy stream and events of the chunk loop, and the descriptor ring of the resize
+     * launches (csrc/vit_pipeline.h).  resize + centre crop (vit_hip_resize_crop_u8, the _resized forwards): the crops land
+     * in Q|K|V at plan.crop_off (behind the fp32 expansion on the fp32-rows paths), the coefficient tables in hid. */
+    struct pipeline pipe;
 
     /* the armed outputs (csrc/vit_requests.h), and what of them the running forward serves: forward_device sets it for its
      * layer functions (attention_tap) and clears it when it returns; NULL between forwards */
@@ -168,18 +154,6 @@ const float *vit_hip_weight(const vit_hip_ctx *ctx, int idx)
     return (idx >= 0 && idx < ctx->n_tensors) ? ctx->w[idx] : NULL;
 }
 
-/* Queue the copy of a chunk of m images into its pinned slot */
-static int staged_d2h(const vit_hip_ctx *ctx, const struct staged *st, int slot, int m)
-{
-    return vh_d2h(st->pinned[slot], st->dev, (size_t)m * st->per_image, ctx->stream);
-}
-
-/* A chunk of m images from its pinned slot into the caller's memory, at image `first` */
-static void staged_scatter(const struct staged *st, int slot, int first, int m)
-{
-    memcpy(st->host + (size_t)first * st->per_image, st->pinned[slot], (size_t)m * st->per_image);
-}
-
 void vit_hip_destroy(vit_hip_ctx *ctx)
 {
     if (!ctx)
@@ -194,28 +168,11 @@ void vit_hip_destroy(vit_hip_ctx *ctx)
     for (int i = 0; i < N_SLABS; ++i)
         if (ctx->slab[i])
             vh_free(ctx->slab[i]);
-    float *dev[] = {ctx->x, ctx->y, ctx->attn, ctx->qkv, ctx->hid, ctx->stats,
-                    ctx->cls, ctx->d_logits, ctx->d_probs, ctx->d_images[0], ctx->d_images[1]};
+    float *dev[] = {ctx->x, ctx->y, ctx->attn, ctx->qkv, ctx->hid, ctx->stats, ctx->cls, ctx->d_logits, ctx->d_probs};
     for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); ++i)
         if (dev[i])
             vh_free(dev[i]);
-    float *host[] = {ctx->h_images[0], ctx->h_images[1], ctx->h_logits[0], ctx->h_logits[1],
-                     ctx->h_probs[0], ctx->h_probs[1]};
-    for (size_t i = 0; i < sizeof(host) / sizeof(host[0]); ++i)
-        if (host[i])
-            vh_host_free(host[i]);
-    for (int i = 0; i < DESC_RING; ++i) {
-        if (ctx->d_desc[i]) vh_free(ctx->d_desc[i]);
-        if (ctx->h_desc[i]) vh_host_free(ctx->h_desc[i]);
-        if (ctx->desc_done[i]) vh_event_destroy(ctx->desc_done[i]);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (ctx->up_done[i]) vh_event_destroy(ctx->up_done[i]);
-        if (ctx->comp_done[i]) vh_event_destroy(ctx->comp_done[i]);
-        if (ctx->out_done[i]) vh_event_destroy(ctx->out_done[i]);
-    }
-    if (ctx->copy_stream)
-        vh_stream_destroy(ctx->copy_stream);
+    pipeline_release(&ctx->pipe);
     if (ctx->stream)
         vh_stream_destroy(ctx->stream);
     free(ctx->w);
@@ -596,7 +553,7 @@ fail:
     return rc;
 }
 
-/* The activation arena, of the plan's sizes, and the host-pointer path's staging, sized for max_batch images. */
+/* The activation arena, of the plan's sizes, and the host-pointer path's pipeline, sized for max_batch images. */
 static int alloc_arena(vit_hip_ctx *ctx)
 {
     int rc = 0;
@@ -604,7 +561,6 @@ static int alloc_arena(vit_hip_ctx *ctx)
     const struct vit_plan *plan = &ctx->plan;
     const int max_batch = ctx->max_batch;
     const size_t E = (size_t)cfg->embed_dim, NC = (size_t)cfg->num_classes;
-    const size_t img = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
     TRY(vh_malloc((void **)&ctx->x, plan->x_bytes));
     TRY(vh_malloc((void **)&ctx->y, plan->y_bytes));
     TRY(vh_malloc((void **)&ctx->attn, plan->attn_bytes));
@@ -615,21 +571,10 @@ static int alloc_arena(vit_hip_ctx *ctx)
     TRY(vh_malloc((void **)&ctx->cls, (size_t)max_batch * E * sizeof(float)));
     TRY(vh_malloc((void **)&ctx->d_logits, (size_t)max_batch * NC * sizeof(float)));
     TRY(vh_malloc((void **)&ctx->d_probs, (size_t)max_batch * NC * sizeof(float)));
-    TRY(vh_stream_create(&ctx->copy_stream));
-    for (int i = 0; i < 2; ++i) {
-        TRY(vh_malloc((void **)&ctx->d_images[i], (size_t)max_batch * img * sizeof(float)));
-        TRY(vh_host_alloc((void **)&ctx->h_images[i], (size_t)max_batch * img * sizeof(float)));
-        TRY(vh_host_alloc((void **)&ctx->h_logits[i], (size_t)max_batch * NC * sizeof(float)));
-        TRY(vh_host_alloc((void **)&ctx->h_probs[i], (size_t)max_batch * NC * sizeof(float)));
-        TRY(vh_event_create(&ctx->up_done[i]));
-        TRY(vh_event_create(&ctx->comp_done[i]));
-        TRY(vh_event_create(&ctx->out_done[i]));
-    }
-    for (int i = 0; i < DESC_RING; ++i) {
-        TRY(vh_malloc((void **)&ctx->d_desc[i], (size_t)max_batch * sizeof(vh_resize_desc)));
-        TRY(vh_host_alloc((void **)&ctx->h_desc[i], (size_t)max_batch * sizeof(vh_resize_desc)));
-        TRY(vh_event_create(&ctx->desc_done[i]));
-    }
+    const struct pipeline_model pm = {.device = ctx->device, .max_batch = max_batch, .classes = cfg->num_classes, .stream = ctx->stream,
+                                      .image_bytes = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size * sizeof(float),
+                                      .d_logits = ctx->d_logits, .d_probs = ctx->d_probs};
+    TRY(pipeline_make(&ctx->pipe, &pm));
     TRY(vh_stream_sync(ctx->stream));
     return 0;
 fail:
@@ -878,12 +823,10 @@ static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct inge
     int rc_ = 0;
     const vit_config *c = &ctx->cfg;
     const int filter = ingest_filter(src);
-    const int S = c->img_size, C = c->in_chans, slot = ctx->desc_next;
-    ctx->desc_next = (slot + 1) % DESC_RING;
-    if (ctx->desc_live[slot] && (rc_ = vh_event_sync(ctx->desc_done[slot])) != 0)
+    const int S = c->img_size, C = c->in_chans;
+    vh_resize_desc *d, *d_desc;
+    if ((rc_ = pipeline_desc_take(&ctx->pipe, &d, &d_desc)) != 0)
         return rc_;
-    ctx->desc_live[slot] = 0;
-    vh_resize_desc *d = ctx->h_desc[slot];
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         const struct ingest_item item = src->items ? src->items[i] : ingest_whole_item(src, i);
@@ -891,11 +834,10 @@ static int resize_crop_launch(vit_hip_ctx *ctx, vh_stream_t s, const struct inge
     }
     if (off > ctx->plan.ws_bytes)   /* the plan sized hid for max_batch tables at the steepest downscale */
         return vh_set_error(1, "resize: coefficient tables exceed the scratch");
-    if ((rc_ = vh_h2d(ctx->d_desc[slot], d, (size_t)n * sizeof(*d), s)) != 0)
+    if ((rc_ = vh_h2d(d_desc, d, (size_t)n * sizeof(*d), s)) != 0)
         return rc_;
-    rc_ = vh_launch_resize_crop_u8(s, ctx->d_desc[slot], n, C, src->layout, filter, S, ctx->hid, ctx->plan.ws_bytes, out);
-    const int rec = vh_event_record(ctx->desc_done[slot], s);   /* behind the copy even if the launch was refused */
-    ctx->desc_live[slot] = rec == 0;
+    rc_ = vh_launch_resize_crop_u8(s, d_desc, n, C, src->layout, filter, S, ctx->hid, ctx->plan.ws_bytes, out);
+    const int rec = pipeline_desc_done(&ctx->pipe, s);   /* behind the copy even if the launch was refused */
     return rc_ ? rc_ : rec;
 }
 
@@ -1274,166 +1216,23 @@ fail:
     return rc;
 }
 
-/* The outputs of one finished chunk from its pinned slot into the caller's memory.  The probabilities keep a scatter of
- * their own: the ABI hands them over as float **, one allocation per image (Network.c:90), which no struct staged describes. */
-static void scatter_outputs(vit_hip_ctx *ctx, int slot, int first, int m, const struct staged *const *arrays, int n_arrays, float **probs)
+/* The forward of a chunk, as the pipeline calls it (csrc/vit_pipeline.h) */
+static int forward_chunk(void *arg, const struct ingest_src *dev, int m, float *d_logits, float *d_probs, const struct serving *sv)
 {
-    const size_t NC = (size_t)ctx->cfg.num_classes;
-    for (int a = 0; a < n_arrays; ++a)
-        staged_scatter(arrays[a], slot, first, m);
-    if (probs)
-        for (int i = 0; i < m; ++i)
-            memcpy(probs[first + i], ctx->h_probs[slot] + (size_t)i * NC, NC * sizeof(float));
+    vit_hip_ctx *ctx = (vit_hip_ctx *)arg;
+    return forward_device(ctx, dev, m, d_logits, d_probs, ctx->stream, sv);
 }
 
-/* Gather of the separately allocated host images (Network.c:90) -- or of a caller's contiguous 8-bit images, or of the
- * sources of a planned chunk -- into one pinned staging slot, on several host threads: a single memcpy stream moves ~3 GB/s,
- * which would cap the host-pointer path below the device-resident rate. */
-struct gather_job
-{
-    char *dst;
-    const struct ingest_src *src;
-    const struct ingest_plan *plan;   /* the jobs are the planned chunk's sources; NULL: the images from `base` on */
-    int first, count;                 /* jobs [first, first + count) */
-    int base;
-    size_t per_image;                 /* plan NULL: bytes */
-};
-
-static void *gather_worker(void *arg)
-{
-    const struct gather_job *j = (const struct gather_job *)arg;
-    for (int i = j->first; i < j->first + j->count; ++i) {
-        if (j->plan) {
-            ingest_pack(j->dst, j->plan, j->src, i);
-            continue;
-        }
-        const void *from = j->src->kind == INGEST_F32 ? (const void *)j->src->host_f32[j->base + i].data
-                                                      : (const void *)(j->src->u8 + (size_t)(j->base + i) * j->per_image);
-        memcpy(j->dst + (size_t)i * j->per_image, from, j->per_image);
-    }
-    return NULL;
-}
-
-static void gather_images(void *dst, const struct ingest_src *src, const struct ingest_plan *plan, int base, int m, size_t per_image)
-{
-    enum { MAX_THREADS = 8 };
-    int nt = m / 16;
-    if (nt > MAX_THREADS)
-        nt = MAX_THREADS;
-    struct gather_job jobs[MAX_THREADS];
-    pthread_t tid[MAX_THREADS];
-    int started = 0;
-    if (nt < 2) {
-        struct gather_job all = {.dst = (char *)dst, .src = src, .plan = plan, .first = 0, .count = m, .base = base, .per_image = per_image};
-        gather_worker(&all);
-        return;
-    }
-    const int per = (m + nt - 1) / nt;
-    for (int t = 0; t < nt; ++t) {
-        const int first = t * per, count = first >= m ? 0 : (m - first < per ? m - first : per);
-        jobs[t] = (struct gather_job){.dst = (char *)dst, .src = src, .plan = plan, .first = first, .count = count, .base = base, .per_image = per_image};
-        if (count == 0)
-            break;
-        if (t == nt - 1 || pthread_create(&tid[started], NULL, gather_worker, &jobs[t]) != 0)
-            gather_worker(&jobs[t]);          /* the last share (or a failed create) runs here */
-        else
-            ++started;
-    }
-    for (int t = 0; t < started; ++t)
-        pthread_join(tid[t], NULL);
-}
-
-/* Host-pointer forward, software-pipelined over chunks of max_batch images:
- *   host     : gather chunk k into pinned slot k&1   | scatter outputs of chunk k-1
- *   copy strm: H2D chunk k                            (after compute of chunk k-2 released the slot)
- *   compute  : forward chunk k, D2H its logits/probs  (after the H2D)
- * so PCIe and the gather of the separately malloc'd images (Network.c:90) hide under
- * the previous chunk's kernels.  A u8 chunk fills a quarter of a staging slot.  plan: the scratch of the kinds whose chunks
- * are planned (vit_ingest.h), NULL for images of the model's size.  form: FEAT_HOST to serve the armed host requests,
+/* Host-pointer forward, pipelined over chunks of max_batch images (pipeline_run).  plan: the scratch of the kinds whose
+ * chunks are planned (vit_ingest.h), NULL for images of the model's size.  form: FEAT_HOST to serve the armed host requests,
  * FEAT_NONE to serve none. */
 static int forward_pipelined(vit_hip_ctx *ctx, const struct ingest_src *src, struct ingest_plan *plan, int n, float *logits, float **probs,
                              int form)
 {
-    int rc = 0;
     struct serving sv;
     if (requests_serving(&ctx->req, "forward", form, &sv))
         return 1;
-    TRY(vh_set_device(ctx->device));
-    const vit_config *c = &ctx->cfg;
-    const size_t bytes = (size_t)c->in_chans * c->img_size * c->img_size * (src->kind == INGEST_F32 ? sizeof(float) : 1);
-    const size_t NC = (size_t)c->num_classes;
-    /* what comes back per chunk besides the probabilities, in the order it is queued: the logits, then the served requests'
-     * arrays (serving_staged) */
-    const struct staged logits_st = {ctx->d_logits, {ctx->h_logits[0], ctx->h_logits[1]}, (char *)logits, NC * sizeof(float)};
-    const struct staged *arrays[1 + MAX_STAGED];
-    int n_arrays = 0;
-    if (logits)
-        arrays[n_arrays++] = &logits_st;
-    n_arrays += serving_staged(&sv, arrays + n_arrays);
-
-    int prev_first = 0, prev_m = 0, k = 0;
-    for (int first = 0, m = 0; first < n; first += m, ++k) {
-        const int s = k & 1;
-        /* The chunk, and the device source it becomes once slot s is up.  Images of the model's size: max_batch of them, one
-         * gather job per image.  The planned kinds: cut by count and by bytes, one gather job per distinct source, and the
-         * device reads the plan's items. */
-        struct ingest_src dev = *src;
-        dev.on_device = 1;
-        m = (n - first < ctx->max_batch) ? n - first : ctx->max_batch;
-        size_t up = (size_t)m * bytes;
-        int jobs = m;
-        switch (src->kind) {
-        case INGEST_F32:
-            dev.host_f32 = NULL;
-            dev.f32 = ctx->d_images[s];
-            break;
-        case INGEST_U8:
-            dev.u8 = (const unsigned char *)ctx->d_images[s];
-            break;
-        default:
-            m = ingest_plan_chunk(plan, src, first, n, (const unsigned char *)ctx->d_images[s]);
-            up = plan->bytes;
-            jobs = plan->n_src;
-            dev.items = plan->items;
-        }
-        if (m <= 0) {
-            rc = vh_set_error(1, "forward: an image does not fit a staging slot");
-            goto fail;
-        }
-        /* slot s was last used by chunk k-2, whose outputs were waited for below */
-        gather_images(ctx->h_images[s], src, plan, first, jobs, bytes);
-        if (k >= 2)
-            TRY(vh_stream_wait_event(ctx->copy_stream, ctx->comp_done[s]));
-        TRY(vh_h2d(ctx->d_images[s], ctx->h_images[s], up, ctx->copy_stream));
-        TRY(vh_event_record(ctx->up_done[s], ctx->copy_stream));
-
-        TRY(vh_stream_wait_event(ctx->stream, ctx->up_done[s]));
-        TRY(forward_device(ctx, &dev, m, ctx->d_logits, probs ? ctx->d_probs : NULL, ctx->stream, &sv));
-        TRY(vh_event_record(ctx->comp_done[s], ctx->stream));
-        /* only what the caller asked for comes back: with neither, an armed top-k request's pairs are the chunk's whole D2H traffic */
-        int a = 0;
-        if (logits)
-            TRY(staged_d2h(ctx, arrays[a++], s, m));
-        if (probs)   /* queued between the logits and the armed requests' arrays */
-            TRY(vh_d2h(ctx->h_probs[s], ctx->d_probs, (size_t)m * NC * sizeof(float), ctx->stream));
-        for (; a < n_arrays; ++a)
-            TRY(staged_d2h(ctx, arrays[a], s, m));
-        TRY(vh_event_record(ctx->out_done[s], ctx->stream));
-
-        if (k >= 1) { /* finish chunk k-1 while chunk k runs */
-            TRY(vh_event_sync(ctx->out_done[s ^ 1]));
-            scatter_outputs(ctx, s ^ 1, prev_first, prev_m, arrays, n_arrays, probs);
-        }
-        prev_first = first;
-        prev_m = m;
-    }
-    TRY(vh_event_sync(ctx->out_done[(k - 1) & 1]));
-    scatter_outputs(ctx, (k - 1) & 1, prev_first, prev_m, arrays, n_arrays, probs);
-    return 0;
-fail:
-    vh_stream_sync(ctx->copy_stream);
-    vh_stream_sync(ctx->stream);
-    return rc;
+    return pipeline_run(&ctx->pipe, src, plan, n, logits, probs, &sv, forward_chunk, ctx);
 }
 
 static int forward_host_images(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs, int form)

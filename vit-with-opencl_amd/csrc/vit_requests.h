@@ -21,7 +21,8 @@ enum { FEAT_NONE, FEAT_DEVICE, FEAT_HOST };
 struct staged
 {
     void *dev, *pinned[2];   /* for max_batch images: the device buffer, and a pinned one per slot */
-    char *host;              /* the caller's memory, for all n images of a call */
+    char *host;              /* the caller's memory, for all n images of a call ... */
+    float **rows;            /* ... or, when set, one row per image instead (the probabilities, Network.c:90) */
     size_t per_image;        /* bytes */
 };
 
