@@ -1,6 +1,6 @@
 #!/bin/bash
 # Host-side AddressSanitizer + UBSan pass over the library's C files (ViT_hip.c, vit_plan.c, vit_ingest.c, vit_requests.c,
-# vit_pipeline.c, vit_gather_rccl.c, vit_config.c, Network_posix.c, vit_report.c): a second copy of the library with those objects
+# vit_pipeline.c, vit_planes_file.c, vit_multi.c, vit_gather_rccl.c, vit_config.c, Network_posix.c, vit_report.c): a second copy of the library with those objects
 # instrumented (the HIP objects are the ordinary ones -- GPU sanitizers are not available on this pool), loaded by the tests through $VIT_HIP_LIB under an ASan
 # preload.  Usage:  tools/host_asan.sh build            (container or GPU box; needs the ordinary build's *.o)
 #                   tools/host_asan.sh build-all        (also the host halves of the nine .hip files; a few minutes)
@@ -14,7 +14,7 @@ CSRC="$ROOT/vit-with-opencl_amd/csrc"
 case "${1:-}" in
 build)
     mkdir -p "$OUT"
-    for f in ViT_hip vit_plan vit_ingest vit_requests vit_pipeline vit_gather_rccl vit_config Network_posix vit_report; do
+    for f in ViT_hip vit_plan vit_ingest vit_requests vit_pipeline vit_planes_file vit_multi vit_gather_rccl vit_config Network_posix vit_report; do
         gcc -O1 -g -fPIC -ffp-contract=off -std=c11 -Wall -D_POSIX_C_SOURCE=200809L -fsanitize=address,undefined \
             -fno-omit-frame-pointer -I"$ROOT/include" -I"$CSRC" -c "$CSRC/$f.c" -o "$OUT/$f.o"
     done
@@ -24,7 +24,7 @@ build)
     echo "built $OUT/libvit_hip_asan.so" ;;
 build-all)   # the HOST halves of the .hip files (launchers: argument checks, tile rules) instrumented as well; device code untouched
     mkdir -p "$OUT"
-    for f in ViT_hip vit_plan vit_ingest vit_requests vit_pipeline vit_gather_rccl vit_config Network_posix vit_report; do
+    for f in ViT_hip vit_plan vit_ingest vit_requests vit_pipeline vit_planes_file vit_multi vit_gather_rccl vit_config Network_posix vit_report; do
         gcc -O1 -g -fPIC -ffp-contract=off -std=c11 -Wall -D_POSIX_C_SOURCE=200809L -fsanitize=address,undefined \
             -fno-omit-frame-pointer -I"$ROOT/include" -I"$CSRC" -c "$CSRC/$f.c" -o "$OUT/$f.o"
     done

@@ -24,18 +24,24 @@
  * struct vit_plan (csrc/vit_plan.h), made by plan_make before anything is allocated; this file allocates what it says and
  * branches on its fields.
  *
+ * What is left here is the context (both ways of making one end in ctx_finish), the layer functions, the forwards and the
+ * drop-in ViT_opencl().  The repacked-weights file -- format, writer, reader and every refusal of a header -- is
+ * csrc/vit_planes_file.c; shards and device replicas are csrc/vit_multi.c, and what the three files of the multi-GPU forms
+ * share is declared once in csrc/vit_multi.h.
+ *
  * Operator order per layer (ViT_seq.c:330-370):
  *   y = LN1(x); qkv = y Win^T + bin; a = attention(qkv); x = x + (a Wout^T + bout);
  *   y = LN2(x); h = gelu(y W1^T + b1); x = x + (h W2^T + b2)
  */
 #include "ViT_opencl.h"
 #include "vit_ingest.h"
+#include "vit_multi.h"
 #include "vit_pipeline.h"
 #include "vit_plan.h"
+#include "vit_planes_file.h"
 #include "vit_requests.h"
 
 #include <math.h>
-#include <pthread.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -135,13 +141,6 @@ static void prof_release(vit_hip_ctx *ctx)
     ctx->prof_ev = NULL;
     ctx->prof_class = NULL;
     ctx->prof_cap = ctx->prof_used = 0;
-}
-
-static double wall_seconds(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
 const vit_config *vit_hip_config(const vit_hip_ctx *ctx) { return &ctx->cfg; }
@@ -274,6 +273,22 @@ fail:
 
 static int alloc_arena(vit_hip_ctx *ctx);
 
+/* A context from ctx_new to usable, for both ways of making one: the device, the stream, the weight slabs -- filled from
+ * the caller's tensors, or read from an open planes file -- and the arena.  On any failure the context is destroyed. */
+static int ctx_finish(vit_hip_ctx *ctx, const Network *networks, struct planes_file *pf)
+{
+    int rc = 0;
+    TRY(vh_init(ctx->device));
+    TRY(vh_stream_create(&ctx->stream));
+    TRY(alloc_weights(ctx));
+    TRY(networks ? fill_weights(ctx, networks) : planes_file_read_slabs(pf, ctx->slab, ctx->stream));
+    TRY(alloc_arena(ctx));
+    return 0;
+fail:
+    vit_hip_destroy(ctx);
+    return rc;
+}
+
 /* $VIT_HIP_PRECISION picks the precision (plan_env_read) */
 int vit_hip_create(vit_hip_ctx **out, const vit_config *cfg, const Network *networks,
                    int n_tensors, int device, int max_batch)
@@ -286,20 +301,11 @@ int vit_hip_create(vit_hip_ctx **out, const vit_config *cfg, const Network *netw
 int vit_hip_precision(const vit_hip_ctx *ctx) { return ctx->plan.precision; }
 int vit_hip_ln_fold(const vit_hip_ctx *ctx) { return ctx ? ctx->plan.ln_fold : 0; }
 
-/* Both ways of making a context: the argument checks and the plan of its forward pass (plan_make, under the environment's
- * switches), and the empty context itself.  ln_fold < 0: the plan decides the fold (vit_hip_create_ex); 0 or 1: a planes
- * file's header fixed it.  Nothing is allocated on the device. */
-static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int device, int max_batch, int precision, int ln_fold)
+/* Both ways of making a context: the empty context around the plan of its forward pass, which plan_make has accepted
+ * (vit_hip_create_ex, where the plan decides the fold; planes_file_open, where the file's header fixed it).  Nothing is
+ * allocated on the device. */
+static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int device, int max_batch, const struct vit_plan *plan)
 {
-    struct plan_env env;
-    struct vit_plan plan;
-    if (!out)
-        return 1;
-    *out = NULL;
-    plan_env_read(&env);
-    const int rc = plan_make(&plan, cfg, n_tensors, max_batch, precision, ln_fold, &env);
-    if (rc != 0)
-        return rc;
     vit_hip_ctx *ctx = (vit_hip_ctx *)calloc(1, sizeof(*ctx));
     if (!ctx)
         return 4;
@@ -307,7 +313,7 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
     ctx->device = device;
     ctx->max_batch = max_batch;
     ctx->n_tensors = n_tensors;
-    ctx->plan = plan;
+    ctx->plan = *plan;
     ctx->w = (float **)calloc((size_t)n_tensors, sizeof(float *));
     ctx->op = (struct operand *)calloc((size_t)4 * cfg->depth, sizeof(struct operand));
     if (!ctx->w || !ctx->op) {
@@ -339,90 +345,21 @@ int vit_hip_create_ex(vit_hip_ctx **out, const vit_config *cfg, const Network *n
                     networks[i].data ? networks[i].size : (size_t)0, vit_config_tensor_size(cfg, i));
             return 3;
         }
-    vit_hip_ctx *ctx = NULL;
-    if ((rc = ctx_new(&ctx, cfg, n_tensors, device, max_batch, precision, -1)) != 0)
+    struct plan_env env;
+    struct vit_plan plan;
+    plan_env_read(&env);
+    if ((rc = plan_make(&plan, cfg, n_tensors, max_batch, precision, -1, &env)) != 0)
         return rc;
-    TRY(vh_init(device));
-    TRY(vh_stream_create(&ctx->stream));
-    TRY(alloc_weights(ctx));
-    TRY(fill_weights(ctx, networks));
-    TRY(alloc_arena(ctx));
+    vit_hip_ctx *ctx = NULL;
+    if ((rc = ctx_new(&ctx, cfg, n_tensors, device, max_batch, &plan)) != 0)
+        return rc;
+    if ((rc = ctx_finish(ctx, networks, NULL)) != 0)
+        return rc;
     *out = ctx;
     return 0;
-fail:
-    vit_hip_destroy(ctx);
-    return rc;
 }
 
-/* ---- repacked weights on disk (the offline half of the weight-format tooling) --------------------------
- * vit_hip_export_planes writes what a context holds in HBM after its repack -- the fp32 slab (all tensors, the
- * reference's order, 256-byte aligned) followed by the mode's operand slab for the four big matrices of every layer
- * (three-part bf16 planes, one-part planes, two fp16 parts, or MX values + scales: csrc/gemm_p3.hip, gemm_mx.hip), the
- * conv_proj planes and, with ln_fold, the fold terms -- behind a header that pins model shape and precision.  Every
- * slab's layout follows from (config, precision, ln_fold) alone (plan_layout), so vit_hip_create_from_planes is one
- * read per slab into its allocation: no fp32 -> format pass, no per-tensor files (the reference's loader opens 152 of
- * them, Network.c:134-218). */
-/* Bumped whenever a repack kernel changes what it writes for the same (config, precision): the slab sizes alone would
- * not notice (csrc/gemm_p3.hip planes, csrc/gemm_mx.hip MX values / scale order, the fold terms of csrc/norm_fold.h). */
-#define VIT_PLANES_LAYOUT_VERSION 2
-
-struct planes_header
-{
-    char magic[8];                 /* "VITPLN02" */
-    unsigned header_bytes;
-    int precision, n_tensors;
-    int cfg_ints[8];               /* img, patch, chans, classes, embed, depth, heads, mlp_hidden */
-    double eps;
-    unsigned long long w_slab_bytes, planes_bytes, wconv16_bytes, scale_floats;   /* scale_floats = n_tensors (pair_scales) */
-    unsigned long long fold_bytes; /* colsum + folded bias of the gamma-scaled matrices (ln_fold) */
-    int ln_fold, layout_version;
-    unsigned long long checksum;   /* of everything behind the header, in file order (planes_hash) */
-};
-
-/* FNV-1a over 64-bit words (the payload slabs are all multiples of 8 bytes; a tail is taken byte-wise) */
-static unsigned long long planes_hash(unsigned long long h, const void *data, size_t bytes)
-{
-    const unsigned long long *w = (const unsigned long long *)data;
-    for (size_t i = 0; i < bytes / 8; ++i)
-        h = (h ^ w[i]) * 0x100000001b3ull;
-    const unsigned char *t = (const unsigned char *)data + (bytes & ~(size_t)7);
-    for (size_t i = 0; i < (bytes & 7); ++i)
-        h = (h ^ t[i]) * 0x100000001b3ull;
-    return h;
-}
-#define PLANES_HASH_SEED 0xcbf29ce484222325ull
-
-static int copy_file_and_device(vit_hip_ctx *ctx, FILE *fp, void *dev, size_t bytes, int to_file, unsigned long long *hash)
-{
-    enum { CHUNK = 64 << 20 };
-    int rc = 0;
-    void *host = NULL;
-    if (bytes == 0)
-        return 0;
-    TRY(vh_host_alloc(&host, bytes < CHUNK ? bytes : (size_t)CHUNK));
-    for (size_t off = 0; off < bytes && rc == 0; off += CHUNK) {
-        const size_t n = bytes - off < CHUNK ? bytes - off : (size_t)CHUNK;
-        if (to_file) {
-            if ((rc = vh_d2h(host, (char *)dev + off, n, ctx->stream)) != 0 || (rc = vh_stream_sync(ctx->stream)) != 0)
-                break;
-            *hash = planes_hash(*hash, host, n);
-            if (fwrite(host, 1, n, fp) != n)
-                rc = vh_set_error(120, "vit_hip_export_planes: short write");
-        } else {
-            if (fread(host, 1, n, fp) != n) {
-                rc = vh_set_error(121, "vit_hip_create_from_planes: file is shorter than its header says");
-                break;
-            }
-            *hash = planes_hash(*hash, host, n);
-            if ((rc = vh_h2d((char *)dev + off, host, n, ctx->stream)) != 0 || (rc = vh_stream_sync(ctx->stream)) != 0)
-                break;
-        }
-    }
-fail:
-    if (host)
-        vh_host_free(host);
-    return rc;
-}
+/* ---- repacked weights on disk: the format, the writer and the reader are csrc/vit_planes_file.c ---------------------- */
 
 /* The planes file keeps one fp16-pair scale per tensor index: zero but at the big matrices of F32_FP16X2. */
 static void pair_scales(const vit_hip_ctx *ctx, float scales[MAX_TENSORS])
@@ -432,124 +369,38 @@ static void pair_scales(const vit_hip_ctx *ctx, float scales[MAX_TENSORS])
         scales[plan_operand_tensor(m)] = ctx->op[m].pair_scale;
 }
 
-/* Written to `path`.tmp and renamed over `path` when complete: an interrupted export never leaves a truncated file
- * under the name a later run will open. */
 int vit_hip_export_planes(vit_hip_ctx *ctx, const char *path)
 {
     int rc = 0;
     if (!ctx || !path)
         return vh_set_error(1, "vit_hip_export_planes: null argument");
-    TRY(vh_set_device(ctx->device));
-    const size_t plen = strlen(path);
-    char *tmp = (char *)malloc(plen + 5);
-    if (!tmp)
-        return vh_set_error(4, "vit_hip_export_planes: out of host memory");
-    memcpy(tmp, path, plen);
-    memcpy(tmp + plen, ".tmp", 5);
-    FILE *fp = fopen(tmp, "wb");
-    if (!fp) {
-        free(tmp);
-        return vh_set_error(122, "vit_hip_export_planes: cannot open the file for writing");
-    }
-    struct planes_header h;
-    memset(&h, 0, sizeof(h));
-    memcpy(h.magic, "VITPLN02", 8);
-    h.header_bytes = (unsigned)sizeof(h);
-    h.precision = ctx->plan.precision;
-    h.n_tensors = ctx->n_tensors;
-    const vit_config *c = &ctx->cfg;
-    const int ints[8] = {c->img_size, c->patch_size, c->in_chans, c->num_classes, c->embed_dim, c->depth, c->num_heads, c->mlp_hidden};
-    memcpy(h.cfg_ints, ints, sizeof(ints));
-    h.eps = c->eps;
-    h.w_slab_bytes = ctx->plan.slab_bytes[SLAB_F32];
-    h.planes_bytes = ctx->plan.slab_bytes[SLAB_OPERAND];
-    h.wconv16_bytes = ctx->plan.slab_bytes[SLAB_CONV];
-    h.fold_bytes = ctx->plan.slab_bytes[SLAB_FOLD];
-    h.ln_fold = ctx->plan.ln_fold;
-    h.layout_version = VIT_PLANES_LAYOUT_VERSION;
-    h.scale_floats = (unsigned long long)ctx->n_tensors;
+    if ((rc = vh_set_device(ctx->device)) != 0)
+        return rc;
     float scales[MAX_TENSORS];
     pair_scales(ctx, scales);
-    unsigned long long hash = planes_hash(PLANES_HASH_SEED, scales, sizeof(float) * (size_t)ctx->n_tensors);
-    /* the header goes first with a zero checksum and is rewritten once the payload has been hashed */
-    if (fwrite(&h, sizeof(h), 1, fp) != 1 || fwrite(scales, sizeof(float), (size_t)ctx->n_tensors, fp) != (size_t)ctx->n_tensors)
-        rc = vh_set_error(120, "vit_hip_export_planes: short write");
-    for (int i = 0; i < N_SLABS && rc == 0; ++i)
-        rc = copy_file_and_device(ctx, fp, ctx->slab[i], ctx->plan.slab_bytes[i], 1, &hash);
-    if (rc == 0) {
-        h.checksum = hash;
-        if (fseek(fp, 0, SEEK_SET) != 0 || fwrite(&h, sizeof(h), 1, fp) != 1)
-            rc = vh_set_error(120, "vit_hip_export_planes: short write");
-    }
-    if (fclose(fp) != 0 && rc == 0)
-        rc = vh_set_error(120, "vit_hip_export_planes: short write");
-    if (rc == 0 && rename(tmp, path) != 0)
-        rc = vh_set_error(122, "vit_hip_export_planes: cannot move the finished file into place");
-    if (rc != 0)
-        remove(tmp);
-    free(tmp);
-    return rc;
-fail:
-    return rc;
+    return planes_file_write(path, &ctx->cfg, &ctx->plan, ctx->n_tensors, scales, ctx->slab, ctx->stream);
 }
 
+/* The header decides shape, precision and fold (planes_file_open: every refusal falls there, before a device is touched or
+ * anything allocated); the context adopts its plan and the slabs are read into their allocations. */
 int vit_hip_create_from_planes(vit_hip_ctx **out, const char *path, int device, int max_batch)
 {
     int rc = 0;
+    struct planes_file pf;
     if (!out)
         return 1;
     *out = NULL;
-    if (!path)
-        return vh_set_error(1, "vit_hip_create_from_planes: null path");
-    FILE *fp = fopen(path, "rb");
-    if (!fp)
-        return vh_set_error(123, "vit_hip_create_from_planes: cannot open the file");
-    struct planes_header h;
+    if ((rc = planes_file_open(&pf, path, max_batch)) != 0)
+        return rc;
     vit_hip_ctx *ctx = NULL;
-    if (fread(&h, sizeof(h), 1, fp) != 1 || memcmp(h.magic, "VITPLN02", 8) != 0 || h.header_bytes != sizeof(h) ||
-        h.layout_version != VIT_PLANES_LAYOUT_VERSION) {
-        fclose(fp);
-        return vh_set_error(124, "vit_hip_create_from_planes: not a planes file of this library version (magic, header size or operand-layout version)");
-    }
-    vit_config cfg = {h.cfg_ints[0], h.cfg_ints[1], h.cfg_ints[2], h.cfg_ints[3], h.cfg_ints[4], h.cfg_ints[5], h.cfg_ints[6],
-                      h.cfg_ints[7], h.eps};
-    /* ctx_new (plan_make) bounds every dimension, checks the fold flag and allocates only the host-side tables (n_tensors is tied to depth) */
-    if (h.n_tensors <= 0 || h.n_tensors > MAX_TENSORS ||
-        (rc = ctx_new(&ctx, &cfg, h.n_tensors, device, max_batch, h.precision, h.ln_fold ? 1 : 0)) != 0) {
-        fclose(fp);
-        return vh_set_error(rc ? rc : 2, "vit_hip_create_from_planes: the header's model shape or precision is not one this library takes");
-    }
-    /* the slab sizes this library derives from (shape, precision, fold) against the header's, BEFORE anything is allocated */
-    const size_t *sizes = ctx->plan.slab_bytes;
-    if (h.w_slab_bytes != sizes[SLAB_F32] || h.planes_bytes != sizes[SLAB_OPERAND] || h.wconv16_bytes != sizes[SLAB_CONV] ||
-        h.fold_bytes != sizes[SLAB_FOLD] || h.scale_floats != (unsigned long long)ctx->n_tensors) {
-        rc = vh_set_error(125, "vit_hip_create_from_planes: slab sizes in the file do not match this library's layout");
-        goto fail;
-    }
-    float scales[MAX_TENSORS];
-    if (fread(scales, sizeof(float), (size_t)ctx->n_tensors, fp) != (size_t)ctx->n_tensors) {
-        rc = vh_set_error(124, "vit_hip_create_from_planes: truncated header");
-        goto fail;
-    }
-    unsigned long long hash = planes_hash(PLANES_HASH_SEED, scales, sizeof(float) * (size_t)ctx->n_tensors);
-    for (int m = 0; m < 4 * cfg.depth; ++m)
-        ctx->op[m].pair_scale = scales[plan_operand_tensor(m)];
-    TRY(vh_init(device));
-    TRY(vh_stream_create(&ctx->stream));
-    TRY(alloc_weights(ctx));
-    for (int i = 0; i < N_SLABS; ++i)
-        TRY(copy_file_and_device(ctx, fp, ctx->slab[i], ctx->plan.slab_bytes[i], 0, &hash));
-    if (hash != h.checksum) {
-        rc = vh_set_error(126, "vit_hip_create_from_planes: payload checksum mismatch (corrupt file)");
-        goto fail;
-    }
-    TRY(alloc_arena(ctx));
-    fclose(fp);
-    *out = ctx;
-    return 0;
-fail:
-    fclose(fp);
-    vit_hip_destroy(ctx);
+    if ((rc = ctx_new(&ctx, &pf.cfg, pf.n_tensors, device, max_batch, &pf.plan)) == 0) {
+        for (int m = 0; m < 4 * pf.cfg.depth; ++m)
+            ctx->op[m].pair_scale = pf.scales[plan_operand_tensor(m)];
+        if ((rc = ctx_finish(ctx, NULL, &pf)) == 0)
+            *out = ctx;
+    } else   /* out of host memory: the status with the text it has always come with */
+        vh_set_error(rc, "vit_hip_create_from_planes: the header's model shape or precision is not one this library takes");
+    planes_file_close(&pf);
     return rc;
 }
 
@@ -1253,6 +1104,12 @@ int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *log
     return forward_host_images(ctx, images, n, logits, probs, FEAT_HOST);
 }
 
+/* vit_hip_forward with no armed output served, whatever is armed (vit_multi.c) */
+int vit_hip_forward_plain(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits, float **probs)
+{
+    return forward_host_images(ctx, images, n, logits, probs, FEAT_NONE);
+}
+
 /* A public host-form forward of 8-bit images: the checks, the call's one scratch allocation where chunks are planned */
 static int forward_host_u8(vit_hip_ctx *ctx, const char *who, const struct ingest_src *src, int n, float *logits, float **probs)
 {
@@ -1289,200 +1146,6 @@ int vit_hip_forward_u8_boxes(vit_hip_ctx *ctx, const vit_image_u8 *images, int n
     const struct ingest_src src = {.kind = INGEST_U8_BOXES, .images = images, .n_images = n_images, .boxes = boxes, .filter = filter,
                                    .layout = layout, .norm = norm};
     return forward_host_u8(ctx, "vit_hip_forward_u8_boxes", &src, n, logits, probs);
-}
-
-/* ---- several GPUs behind one call -------------------------------------------------
- * Images never interact (the reference processes them strictly one at a time, ViT_opencl.c:926), so
- * the batch is cut into contiguous shards, one per device; every device holds a full replica of the
- * weights (346 MB for ViT-B/16) and is driven by its own host thread, context and stream.  A thread
- * writes its shard's outputs straight into the caller's arrays, so inside one process the "gather of
- * the class logits" is this scatter -- no collective.  (bench.py's one-process-per-GPU form gathers
- * with RCCL instead.) */
-
-void vit_shard_range(int total, int shard, int n_shards, int *lo, int *hi)
-{
-    const int per = n_shards > 0 ? (total + n_shards - 1) / n_shards : total;
-    int a = shard * per, b;
-    if (a > total)
-        a = total;
-    b = a + per;
-    if (b > total)
-        b = total;
-    *lo = a;
-    *hi = b;
-}
-
-struct shard_job
-{
-    int (*fn)(void *arg, int shard, int lo, int hi);
-    void *arg;
-    int shard, lo, hi, rc;
-    double ms;          /* wall time of fn on its thread */
-    char err[256];
-};
-
-static void *shard_worker(void *p)
-{
-    struct shard_job *j = (struct shard_job *)p;
-    const double t0 = wall_seconds();
-    j->rc = j->fn(j->arg, j->shard, j->lo, j->hi);
-    j->ms = 1e3 * (wall_seconds() - t0);
-    if (j->rc != 0)
-        snprintf(j->err, sizeof(j->err), "%s", vh_last_error());   /* the error text is per thread */
-    return NULL;
-}
-
-/* Run fn(arg, s, lo_s, hi_s) for the n_shards contiguous shards of [0, total), each non-empty shard
- * on its own host thread (shard 0 on the caller's); returns 0 or the first failing shard's status. */
-int vit_shard_run(int total, int n_shards, int (*fn)(void *arg, int shard, int lo, int hi), void *arg)
-{
-    return vit_shard_run_timed(total, n_shards, fn, arg, NULL);
-}
-
-/* The same; ms_per_shard[s] (may be NULL) receives the wall time shard s's fn took on its thread (0 for an empty shard). */
-int vit_shard_run_timed(int total, int n_shards, int (*fn)(void *arg, int shard, int lo, int hi), void *arg, double *ms_per_shard)
-{
-    enum { MAX_SHARDS = 64 };
-    if (total < 0 || n_shards <= 0 || n_shards > MAX_SHARDS || !fn)
-        return 1;
-    struct shard_job jobs[MAX_SHARDS];
-    pthread_t tid[MAX_SHARDS];
-    int threaded[MAX_SHARDS];
-    for (int s = 0; s < n_shards; ++s) {
-        jobs[s] = (struct shard_job){fn, arg, s, 0, 0, 0, 0.0, ""};
-        vit_shard_range(total, s, n_shards, &jobs[s].lo, &jobs[s].hi);
-        threaded[s] = 0;
-    }
-    for (int s = 1; s < n_shards; ++s)
-        if (jobs[s].hi > jobs[s].lo)
-            threaded[s] = pthread_create(&tid[s], NULL, shard_worker, &jobs[s]) == 0;
-    for (int s = 0; s < n_shards; ++s)
-        if (!threaded[s] && jobs[s].hi > jobs[s].lo)
-            shard_worker(&jobs[s]);               /* shard 0, and any shard whose thread could not start */
-    for (int s = 1; s < n_shards; ++s)
-        if (threaded[s])
-            pthread_join(tid[s], NULL);
-    if (ms_per_shard)
-        for (int s = 0; s < n_shards; ++s)
-            ms_per_shard[s] = jobs[s].ms;
-    for (int s = 0; s < n_shards; ++s)
-        if (jobs[s].rc != 0) {
-            fprintf(stderr, "vit_shard_run: shard %d [%d, %d) failed with status %d: %s\n", s, jobs[s].lo, jobs[s].hi,
-                    jobs[s].rc, jobs[s].err);
-            return jobs[s].rc;
-        }
-    return 0;
-}
-
-struct vit_hip_multi
-{
-    int n_devices;
-    vit_hip_ctx **ctx;
-    /* creation arguments, read by the per-device threads */
-    const vit_config *cfg;
-    const Network *networks;
-    const int *devices;
-    int n_tensors, max_batch, precision;
-    /* forward arguments */
-    const ImageData *images;
-    float *logits;
-    float **probs;
-    void *gather;   /* RCCL communicators of vit_hip_forward_device_multi (vit_gather_rccl.c), made on first use */
-    double enqueue_ms[64];   /* vit_hip_forward_device_multi: host time each device's thread spent enqueuing its shard, last call */
-};
-
-void vit_gather_release(void *state);
-void **vit_hip_multi_gather_slot(vit_hip_multi *m) { return &m->gather; }
-double *vit_hip_multi_enqueue_ms_slot(vit_hip_multi *m) { return m->enqueue_ms; }
-
-int vit_hip_multi_last_enqueue_ms(const vit_hip_multi *m, double *ms, int capacity)
-{
-    if (!m || !ms || capacity < m->n_devices)
-        return -1;
-    for (int d = 0; d < m->n_devices; ++d)
-        ms[d] = m->enqueue_ms[d];
-    return m->n_devices;
-}
-
-static int multi_create_one(void *arg, int shard, int lo, int hi)
-{
-    vit_hip_multi *m = (vit_hip_multi *)arg;
-    (void)lo;
-    (void)hi;
-    return vit_hip_create_ex(&m->ctx[shard], m->cfg, m->networks, m->n_tensors, m->devices[shard], m->max_batch,
-                             m->precision);
-}
-
-int vit_hip_create_multi(vit_hip_multi **out, const vit_config *cfg, const Network *networks, int n_tensors,
-                         const int *devices, int n_devices, int max_batch_per_device, int precision)
-{
-    if (!out || !cfg || !networks || !devices || n_devices <= 0 || n_devices > 64 || max_batch_per_device <= 0)
-        return 1;
-    *out = NULL;
-    vit_hip_multi *m = (vit_hip_multi *)calloc(1, sizeof(*m));
-    if (!m)
-        return 4;
-    m->ctx = (vit_hip_ctx **)calloc((size_t)n_devices, sizeof(*m->ctx));
-    int *devs = (int *)malloc(sizeof(int) * (size_t)n_devices);
-    if (!m->ctx || !devs) {
-        free(m->ctx);
-        free(devs);
-        free(m);
-        return 4;
-    }
-    memcpy(devs, devices, sizeof(int) * (size_t)n_devices);
-    m->n_devices = n_devices;
-    m->cfg = cfg;
-    m->networks = networks;
-    m->devices = devs;
-    m->n_tensors = n_tensors;
-    m->max_batch = max_batch_per_device;
-    m->precision = precision;
-    /* one "shard" per device: the replicas are built side by side (weight upload + repack each) */
-    const int rc = vit_shard_run(n_devices, n_devices, multi_create_one, m);
-    m->cfg = NULL;
-    m->networks = NULL;
-    if (rc != 0) {
-        vit_hip_destroy_multi(m);
-        return rc;
-    }
-    *out = m;
-    return 0;
-}
-
-void vit_hip_destroy_multi(vit_hip_multi *m)
-{
-    if (!m)
-        return;
-    vit_gather_release(m->gather);
-    for (int d = 0; d < m->n_devices; ++d)
-        vit_hip_destroy(m->ctx[d]);
-    free((void *)m->devices);
-    free(m->ctx);
-    free(m);
-}
-
-int vit_hip_multi_devices(const vit_hip_multi *m) { return m ? m->n_devices : 0; }
-vit_hip_ctx *vit_hip_multi_ctx(const vit_hip_multi *m, int i) { return (m && i >= 0 && i < m->n_devices) ? m->ctx[i] : NULL; }
-
-static int multi_forward_one(void *arg, int shard, int lo, int hi)
-{
-    vit_hip_multi *m = (vit_hip_multi *)arg;
-    const size_t NC = (size_t)vit_hip_config(m->ctx[shard])->num_classes;
-    /* no feature, top-k or attention-map output, whatever a caller armed on the shard's context */
-    return forward_host_images(m->ctx[shard], m->images + lo, hi - lo, m->logits ? m->logits + (size_t)lo * NC : NULL,
-                               m->probs ? m->probs + lo : NULL, FEAT_NONE);
-}
-
-/* Not re-entrant on one vit_hip_multi (like vit_hip_forward on one context). */
-int vit_hip_forward_multi(vit_hip_multi *m, const ImageData *images, int n, float *logits, float **probs)
-{
-    if (!m || !images || n <= 0)
-        return 1;
-    m->images = images;
-    m->logits = logits;
-    m->probs = probs;
-    return vit_shard_run(n, m->n_devices, multi_forward_one, m);
 }
 
 /* $VIT_HIP_DEVICES: "all", or a comma-separated list of device ids; returns the count written. */

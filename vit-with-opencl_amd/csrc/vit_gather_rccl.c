@@ -13,7 +13,7 @@
  * HIP runtime) gets THAT copy, so that the communicators run on the HIP runtime this library is bound to.
  */
 #define _GNU_SOURCE
-#include "ViT_opencl.h"
+#include "vit_multi.h"
 
 #include <dlfcn.h>
 #include <stdio.h>
@@ -36,13 +36,6 @@ struct vit_gather_state
     rccl_comm_t *comms;
     int n;
 };
-
-/* ViT_hip.c: where a vit_hip_multi keeps this state, and a context's own logits buffer */
-void **vit_hip_multi_gather_slot(vit_hip_multi *m);
-float *vit_hip_logits_buffer(vit_hip_ctx *ctx);
-int vit_hip_device(const vit_hip_ctx *ctx);
-int vit_hip_forward_device_plain(vit_hip_ctx *ctx, const float *d_images, int n, float *d_logits, float *d_probs, vh_stream_t stream);
-double *vit_hip_multi_enqueue_ms_slot(vit_hip_multi *m);
 
 static int fail(int code, const char *what, const char *detail)
 {
@@ -68,9 +61,8 @@ void vit_gather_release(void *state)
 
 static int gather_state(vit_hip_multi *m, struct vit_gather_state **out)
 {
-    void **slot = vit_hip_multi_gather_slot(m);
-    if (*slot) {
-        *out = (struct vit_gather_state *)*slot;
+    if (m->gather) {
+        *out = (struct vit_gather_state *)m->gather;
         return 0;
     }
     struct vit_gather_state *g = (struct vit_gather_state *)calloc(1, sizeof(*g));
@@ -126,7 +118,7 @@ static int gather_state(vit_hip_multi *m, struct vit_gather_state **out)
         free(g);
         return fail(113, "ncclCommInitAll failed", e);
     }
-    *slot = g;
+    m->gather = g;
     *out = g;
     return 0;
 }
@@ -200,7 +192,7 @@ int vit_hip_forward_device_multi(vit_hip_multi *m, const float *const *d_images,
 
     /* every shard's forward, asynchronous on its device's stream, entered from its own host thread */
     struct enqueue_job job = {m, d_images, counts, d_logits_root};
-    rc = vit_shard_run_timed(n, n, enqueue_shard, &job, vit_hip_multi_enqueue_ms_slot(m));
+    rc = vit_shard_run_timed(n, n, enqueue_shard, &job, m->enqueue_ms);
     if (rc)
         return sync_all(m, rc);   /* the other shards' kernels still write their logits buffers: wait them out */
 
