@@ -129,6 +129,37 @@ int vit_hip_ln_fold(const vit_hip_ctx *ctx);
 int vit_hip_export_planes(vit_hip_ctx *ctx, const char *path);
 int vit_hip_create_from_planes(vit_hip_ctx **out, const char *path, int device, int max_batch);
 
+/* ---- the same model at another resolution: a context derived on the GPU from one that exists ----
+ * A context runs at the resolution its pos_embedding (tensor 3) was trained at: vit_hip_create_ex refuses any other row
+ * count (code 3).  vit_hip_create_at_resolution makes a NEW context for the same weights at another img_size from a context
+ * `src` that already exists -- created from host tensors or from a planes file -- without host tensors:
+ *   - tensor 3 is produced by vh_launch_resample_pos_embed (include/kernelHandler.h states the definition and its error
+ *     bound; csrc/pos_resample.hip) with prefix = 1 and the square grids img_size / patch_size of the two contexts;
+ *   - every other weight is copied device to device in the form it already has: the three slabs of GEMM operands,
+ *     conv_proj planes and folded LayerNorm terms whole, the fp32 tensors one by one into the new layout.  Nothing is
+ *     re-split, re-quantised or re-folded, so the derived context holds the bits a context created at img_size from the
+ *     same tensors -- with that pos_embedding -- would hold, and computes the same logits bit for bit.
+ * The derived context is an ordinary context: it takes every entry point, every armed output and vit_hip_export_planes;
+ * nothing records that it was derived, and nothing is shared -- destroying `src` afterwards leaves it whole.
+ * Inherited from src: the device, the precision, the LayerNorm fold (vit_hip_ln_fold) and the fp16-pair scales.  Read
+ * afresh, as at every creation: the $VIT_HIP_* switches.  Not inherited: armed requests, vit_hip_set_last_layer_cls_only.
+ * max_batch <= 0: src's.  how == NULL: bicubic, align_corners 0 (the Hugging Face ViT's and DINO's convention; {BICUBIC, 1}
+ * is torchvision's interpolate_embeddings).
+ * src is only read; its stream is synchronised first, the new context's before returning.  Refusals come before anything
+ * is allocated, leave *out NULL and src untouched: code 1 with a message for a NULL out or src and for what
+ * vit_resample_check refuses; code 2 with a message for a target shape this precision and these switches do not run (for
+ * instance F32_FP16X2, or $VIT_HIP_P3=0, above 512 tokens) or whose operand slabs would differ in size from src's.  On a
+ * failure behind that (out of device memory) the new context is destroyed.
+ * Out of scope: weights shared between contexts, non-square inputs, antialiased resampling (timm's default: another
+ * kernel constant), vit_hip_create_multi, and examples/vit_main.c (which reads the reference's 224-pixel files). */
+enum { VIT_POS_BICUBIC = 0, VIT_POS_BILINEAR = 1 };
+typedef struct vit_pos_resample { int mode; int align_corners; } vit_pos_resample;   /* NULL = bicubic, align_corners 0 */
+/* host only, touches no device: 0 and *out_cfg = *src with img_size replaced; 1 with a message for a null or bad
+ * argument (img_size <= 0 or not a multiple of patch_size, a grid side above 512, unknown mode, align_corners not 0 / 1) */
+int vit_resample_check(const vit_config *src, int img_size, const vit_pos_resample *how, vit_config *out_cfg);
+int vit_hip_create_at_resolution(vit_hip_ctx **out, const vit_hip_ctx *src, int img_size, int max_batch,
+                                 const vit_pos_resample *how);
+
 /* FP8_GEMM (BASELINE config 5: "fp8 weights (CDNA4 fp8 MFMA)"): the same four matrices and their inputs as block-scaled
  * fp8 -- OCP "MX": e4m3 elements, one power-of-two scale per 32 consecutive K elements, computed where the tensor
  * is produced (weights at context creation; LayerNorm, the fc1 epilogue and the attention output at run time), so

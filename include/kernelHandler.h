@@ -590,6 +590,48 @@ int vh_launch_dense_labels(vh_stream_t s, const float *patch_logits /* [n][grid_
                            int grid_h, int grid_w, int n_labels, int out_h, int out_w,
                            unsigned char *labels /* u8 [n][out_h][out_w] */, float *scores /* fp32, may be NULL */);
 
+/* Position embedding resampled to another patch grid (csrc/pos_resample.hip; the kernel under vit_hip_create_at_resolution,
+ * include/ViT_opencl.h).  src [prefix + in_h * in_w][E] fp32 -> dst [prefix + out_h * out_w][E] fp32, both contiguous.
+ * Definition.  The first `prefix` rows (the class token's) are copied bit for bit.  The remaining rows are a row-major
+ * in_h x in_w grid of E-vectors, resampled channel by channel to out_h x out_w: what
+ *     torch.nn.functional.interpolate(grid[None], size=(out_h, out_w), mode=mode, align_corners=align_corners,
+ *                                     antialias=False)
+ * computes on a float64 copy of the grid ([E][in_h][in_w]), rounded to fp32 once.  All coordinate and weight arithmetic and
+ * every sum is float64.  Per axis (in, out, output index o):
+ *   align_corners 0:  scale = (double)in / out;                           s = (o + 0.5) * scale - 0.5
+ *   align_corners 1:  scale = out > 1 ? (double)(in - 1) / (out - 1) : 0; s = o * scale
+ * VH_POS_BICUBIC (the Keys kernel, A = -0.75): i0 = floor(s), t = s - i0 (s is NOT clamped); taps i0 - 1 .. i0 + 2, each
+ * index clamped to [0, in - 1]; weights c2(t + 1), c1(t), c1(1 - t), c2(2 - t) with
+ *   c1(x) = ((A + 2) x - (A + 3)) x^2 + 1          c2(x) = ((A x - 5 A) x + 8 A) x - 4 A
+ * VH_POS_BILINEAR: with align_corners 0, s = max(s, 0); i0 = min((int)s, in - 1), i1 = min(i0 + 1, in - 1); weights
+ * 1 - (s - i0) and s - i0.
+ * Value: v = sum_j wy_j * (sum_i wx_i * p[iy_j][ix_i]), i and j ascending, horizontal first, in float64; dst = (float)v.
+ * Equal grids (in_h == out_h and in_w == out_w) are a plain copy, bit for bit, in either mode.
+ * Which convention is whose: (bicubic, align_corners 0) is the Hugging Face ViT's interpolate_pos_encoding and DINO's;
+ * (bicubic, align_corners 1) is torchvision's interpolate_embeddings.  antialias=True (timm's default) is another kernel
+ * and is not built.
+ * Error bound, against this definition evaluated in float64 (tests/pos_resample_ref.py): per element
+ *   |got - want| <= 2^-24 |want| + 2^-40 M,     M = the largest |p| of the source grid.
+ * The first term is the one final rounding.  The second covers float64 rounding and contraction differences in about 40
+ * operations whose absolute weights sum to at most 1.375^2 = 1.89 (the bicubic weights of an axis sum to 1 and their
+ * magnitudes to at most 1.375; a coordinate is a handful of float64 operations on values below 2^10, so a weight errs by
+ * ~2^-50): (40 x 2^-53 + ..) x 1.89 M is below 2^-46 M, the rest is slack.  Where two evaluations of a coordinate fall on
+ * either side of an integer the interpolant is continuous across the knot (cubic convolution and the linear interpolant
+ * both are), so the bound does not change there.
+ * float64 costs nothing here: the kernel is memory-bound (NT^2 = 16 or 4 float4 loads per 4 outputs against some 200 double
+ * operations per thread) and runs once per derived context, not per forward.
+ * A thread owns one output token and 4 consecutive channels (float4 loads and stores, consecutive lanes on consecutive
+ * channels) and computes its at most 8 weights itself; no LDS, no atomics.  The bits of a channel's output depend on that
+ * channel's grid values and the four sizes only -- not on embed_dim or on the other channels.
+ * Limits: embed_dim % 4 == 0, embed_dim >= 4; every grid side in 1..512; prefix in 0..8; mode and align_corners as above;
+ * src and dst distinct, not overlapping, 16-byte aligned.  Anything else: code 1 with a message that starts with the
+ * launcher's name, no launch, nothing written. */
+enum { VH_POS_BICUBIC = 0, VH_POS_BILINEAR = 1 };
+int vh_launch_resample_pos_embed(vh_stream_t s, const float *src /* [prefix + in_h*in_w][E] */,
+                                 float *dst /* [prefix + out_h*out_w][E] */, int prefix,
+                                 int in_h, int in_w, int out_h, int out_w, int embed_dim,
+                                 int mode, int align_corners);
+
 #ifdef __cplusplus
 }
 #endif

@@ -271,17 +271,41 @@ fail:
     return rc;
 }
 
+/* The weights of a context at another resolution (vit_hip_create_at_resolution): everything device to device in the form
+ * `from` holds it -- the operand, conv_proj and fold slabs whole (their layout does not depend on img_size; the caller has
+ * checked the sizes), the fp32 tensors one by one into this context's SLAB_F32 layout -- except pos_embedding, resampled
+ * from from's grid to this one's.  `from` is only read, after its stream has drained. */
+static int derive_weights(vit_hip_ctx *ctx, const vit_hip_ctx *from, const vit_pos_resample *how)
+{
+    int rc = 0;
+    static const int whole[] = {SLAB_OPERAND, SLAB_CONV, SLAB_FOLD};
+    const int grid_in = from->cfg.img_size / from->cfg.patch_size, grid_out = ctx->cfg.img_size / ctx->cfg.patch_size;
+    TRY(vh_stream_sync(from->stream));
+    for (size_t i = 0; i < sizeof(whole) / sizeof(whole[0]); ++i)
+        if (ctx->plan.slab_bytes[whole[i]])
+            TRY(vh_d2d(ctx->slab[whole[i]], from->slab[whole[i]], ctx->plan.slab_bytes[whole[i]], ctx->stream));
+    for (int i = 0; i < ctx->n_tensors; ++i)
+        if (i != 3)
+            TRY(vh_d2d(ctx->w[i], from->w[i], vit_config_tensor_size(&ctx->cfg, i) * sizeof(float), ctx->stream));
+    TRY(vh_launch_resample_pos_embed(ctx->stream, from->w[3], ctx->w[3], 1, grid_in, grid_in, grid_out, grid_out, ctx->cfg.embed_dim,
+                                     how ? how->mode : VIT_POS_BICUBIC, how ? how->align_corners : 0));
+fail:
+    return rc;
+}
+
 static int alloc_arena(vit_hip_ctx *ctx);
 
-/* A context from ctx_new to usable, for both ways of making one: the device, the stream, the weight slabs -- filled from
- * the caller's tensors, or read from an open planes file -- and the arena.  On any failure the context is destroyed. */
-static int ctx_finish(vit_hip_ctx *ctx, const Network *networks, struct planes_file *pf)
+/* A context from ctx_new to usable, for the three ways of making one: the device, the stream, the weight slabs -- filled
+ * from the caller's tensors, read from an open planes file, or derived from another context's -- and the arena (which ends
+ * by draining the stream).  On any failure the context is destroyed. */
+static int ctx_finish(vit_hip_ctx *ctx, const Network *networks, struct planes_file *pf, const vit_hip_ctx *from,
+                      const vit_pos_resample *how)
 {
     int rc = 0;
     TRY(vh_init(ctx->device));
     TRY(vh_stream_create(&ctx->stream));
     TRY(alloc_weights(ctx));
-    TRY(networks ? fill_weights(ctx, networks) : planes_file_read_slabs(pf, ctx->slab, ctx->stream));
+    TRY(networks ? fill_weights(ctx, networks) : pf ? planes_file_read_slabs(pf, ctx->slab, ctx->stream) : derive_weights(ctx, from, how));
     TRY(alloc_arena(ctx));
     return 0;
 fail:
@@ -353,7 +377,51 @@ int vit_hip_create_ex(vit_hip_ctx **out, const vit_config *cfg, const Network *n
     vit_hip_ctx *ctx = NULL;
     if ((rc = ctx_new(&ctx, cfg, n_tensors, device, max_batch, &plan)) != 0)
         return rc;
-    if ((rc = ctx_finish(ctx, networks, NULL)) != 0)
+    if ((rc = ctx_finish(ctx, networks, NULL, NULL, NULL)) != 0)
+        return rc;
+    *out = ctx;
+    return 0;
+}
+
+/* The same model at another img_size, from the weights `src` holds on its device (include/ViT_opencl.h).  Every refusal
+ * falls before anything is allocated: the arguments (vit_resample_check), the plan of the target shape under src's
+ * precision and fold and this moment's switches, and the slabs that are copied whole. */
+int vit_hip_create_at_resolution(vit_hip_ctx **out, const vit_hip_ctx *src, int img_size, int max_batch,
+                                 const vit_pos_resample *how)
+{
+    int rc = 0;
+    if (!out)
+        return vh_set_error(1, "vit_hip_create_at_resolution: null argument (out)");
+    *out = NULL;
+    if (!src)
+        return vh_set_error(1, "vit_hip_create_at_resolution: null argument (src)");
+    vit_config cfg;
+    if ((rc = vit_resample_check(&src->cfg, img_size, how, &cfg)) != 0)
+        return rc;
+    if (max_batch <= 0)
+        max_batch = src->max_batch;
+    struct plan_env env;
+    struct vit_plan plan;
+    plan_env_read(&env);
+    /* plan_make words most of its refusals itself; the others keep this text */
+    vh_set_error(2, "vit_hip_create_at_resolution: no plan runs the source's precision and LayerNorm fold at this img_size and max_batch");
+    if ((rc = plan_make(&plan, &cfg, src->n_tensors, max_batch, src->plan.precision, src->plan.ln_fold, &env)) != 0)
+        return rc;
+    (void)vh_set_error(0, "");   /* accepted: that text was no failure */
+    static const int whole[] = {SLAB_OPERAND, SLAB_CONV, SLAB_FOLD};
+    for (size_t i = 0; i < sizeof(whole) / sizeof(whole[0]); ++i)
+        if (plan.slab_bytes[whole[i]] != src->plan.slab_bytes[whole[i]]) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "vit_hip_create_at_resolution: weight slab %d would hold %zu bytes at img_size=%d, the source's holds %zu",
+                     whole[i], plan.slab_bytes[whole[i]], img_size, src->plan.slab_bytes[whole[i]]);
+            return vh_set_error(2, msg);
+        }
+    vit_hip_ctx *ctx = NULL;
+    if ((rc = ctx_new(&ctx, &cfg, src->n_tensors, src->device, max_batch, &plan)) != 0)
+        return vh_set_error(rc, "vit_hip_create_at_resolution: out of host memory");
+    for (int m = 0; m < 4 * cfg.depth; ++m)
+        ctx->op[m].pair_scale = src->op[m].pair_scale;
+    if ((rc = ctx_finish(ctx, NULL, NULL, src, how)) != 0)
         return rc;
     *out = ctx;
     return 0;
@@ -396,7 +464,7 @@ int vit_hip_create_from_planes(vit_hip_ctx **out, const char *path, int device, 
     if ((rc = ctx_new(&ctx, &pf.cfg, pf.n_tensors, device, max_batch, &pf.plan)) == 0) {
         for (int m = 0; m < 4 * pf.cfg.depth; ++m)
             ctx->op[m].pair_scale = pf.scales[plan_operand_tensor(m)];
-        if ((rc = ctx_finish(ctx, NULL, &pf)) == 0)
+        if ((rc = ctx_finish(ctx, NULL, &pf, NULL, NULL)) == 0)
             *out = ctx;
     } else   /* out of host memory: the status with the text it has always come with */
         vh_set_error(rc, "vit_hip_create_from_planes: the header's model shape or precision is not one this library takes");

@@ -88,6 +88,44 @@ size_t vit_config_tensor_size(const vit_config *cfg, int idx)
     }
 }
 
+/* This file is also linked into the oracle's CPU harness, which has no device shim: the error text is recorded where the
+ * shim (or a test's stand-in for it) is linked, and the status is returned either way. */
+extern int vh_set_error(int code, const char *message) __attribute__((weak));
+
+static int resample_refuse(const char *fmt, int a, int b)
+{
+    char msg[192];
+    snprintf(msg, sizeof msg, fmt, a, b);
+    return vh_set_error ? vh_set_error(1, msg) : 1;
+}
+
+/* The argument checks of vit_hip_create_at_resolution that need no context: the target config of a source config at
+ * another img_size, and the resampling of its position grid (vh_launch_resample_pos_embed's limits). */
+int vit_resample_check(const vit_config *src, int img_size, const vit_pos_resample *how, vit_config *out_cfg)
+{
+    enum { MAX_GRID = 512 };
+    if (!src || !out_cfg)
+        return resample_refuse("vit_resample_check: null argument (src, out_cfg)", 0, 0);
+    if (src->patch_size <= 0 || src->img_size <= 0 || src->img_size % src->patch_size != 0 ||
+        src->img_size / src->patch_size > MAX_GRID)
+        return resample_refuse("vit_resample_check: the source's img_size=%d must be a positive multiple of its patch_size=%d, "
+                               "at most 512 patches a side", src->img_size, src->patch_size);
+    if (img_size <= 0 || img_size % src->patch_size != 0)
+        return resample_refuse("vit_resample_check: img_size=%d must be a positive multiple of patch_size=%d", img_size,
+                               src->patch_size);
+    if (img_size / src->patch_size > MAX_GRID)
+        return resample_refuse("vit_resample_check: img_size=%d gives %d patches a side, the position grid takes at most 512",
+                               img_size, img_size / src->patch_size);
+    if (how && how->mode != VIT_POS_BICUBIC && how->mode != VIT_POS_BILINEAR)
+        return resample_refuse("vit_resample_check: mode=%d must be VIT_POS_BICUBIC (%d) or VIT_POS_BILINEAR (1)", how->mode,
+                               VIT_POS_BICUBIC);
+    if (how && how->align_corners != 0 && how->align_corners != 1)
+        return resample_refuse("vit_resample_check: align_corners=%d must be %d or 1", how->align_corners, 0);
+    *out_cfg = *src;
+    out_cfg->img_size = img_size;
+    return 0;
+}
+
 /* splitmix64 finaliser used as a counter-based generator: value i of stream
  * `seed` depends on (seed, i) only, so any slice can be produced in parallel
  * and a numpy twin (host/synth.py) reproduces it bit for bit. */

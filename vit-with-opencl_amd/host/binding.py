@@ -74,6 +74,7 @@ EXPORTS = [
     "vh_gallery_query_tile", "vh_gallery_splits", "vh_gallery_workspace", "vh_launch_gallery_topk", "vit_gallery_check",
     "vit_hip_set_gallery", "vit_hip_set_gallery_host",
     "vh_launch_dense_logits", "vh_launch_dense_labels", "vit_dense_sizes", "vit_hip_set_dense", "vit_hip_set_dense_host",
+    "vh_launch_resample_pos_embed", "vit_resample_check", "vit_hip_create_at_resolution",
 ]
 
 # include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
@@ -331,6 +332,45 @@ def dense_sizes(cfg: "VitConfig", spec: DenseSpec):
     cs = spec.c_struct()
     check(lib().vit_dense_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_dense_sizes")
     return tuple(o.value for o in out)
+
+
+class PosResampleC(C.Structure):
+    """`vit_pos_resample` (include/ViT_opencl.h)."""
+
+    _fields_ = [("mode", C.c_int), ("align_corners", C.c_int)]
+
+
+POS_MODES = {"bicubic": 0, "bilinear": 1}   # VIT_POS_* / VH_POS_*
+
+
+def _pos_mode(mode) -> int:
+    """a mode by name, or its number handed through (the refusals of unknown numbers are the library's)"""
+    return POS_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def resample_check(cfg: "VitConfig", img_size: int, mode="bicubic", align_corners=False) -> "VitConfig":
+    """vit_resample_check -> cfg at img_size; raises VitHipError with the library's message"""
+    how, out = PosResampleC(_pos_mode(mode), int(align_corners)), VitConfig()
+    check(lib().vit_resample_check(C.byref(cfg), int(img_size), C.byref(how), C.byref(out)), "vit_resample_check")
+    return out
+
+
+def resample_pos_embed(pos: np.ndarray, prefix: int, in_hw, out_hw, mode="bicubic", align_corners=False) -> np.ndarray:
+    """vh_launch_resample_pos_embed on pos [prefix + in_h * in_w][E] float32 -> [prefix + out_h * out_w][E]: uploads,
+    launches on the null stream and downloads (tests)."""
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    (in_h, in_w), (out_h, out_w) = in_hw, out_hw
+    if pos.ndim != 2 or pos.shape[0] != prefix + in_h * in_w:
+        raise ValueError(f"resample_pos_embed: pos of shape {pos.shape}, need [{prefix} + {in_h} * {in_w}][E]")
+    E = pos.shape[1]
+    d_src, d_dst = DeviceBuffer.from_numpy(pos), DeviceBuffer((prefix + out_h * out_w) * E)
+    try:
+        check(lib().vh_launch_resample_pos_embed(None, d_src.ptr, d_dst.ptr, prefix, in_h, in_w, out_h, out_w, E, _pos_mode(mode),
+                                                 int(align_corners)), "vh_launch_resample_pos_embed")
+        return d_dst.to_numpy((prefix + out_h * out_w, E))
+    finally:
+        d_src.free()
+        d_dst.free()
 
 
 def topk_check(cfg: "VitConfig", spec: TopKSpec) -> None:
@@ -686,6 +726,12 @@ def lib() -> C.CDLL:
     L.vit_dense_sizes.argtypes = [C.POINTER(VitConfig), dsp, szp, szp, szp, szp]
     L.vit_hip_set_dense.argtypes = [voidp, dsp, dbp]
     L.vit_hip_set_dense_host.argtypes = [voidp, dsp, dbp]
+    prp = C.POINTER(PosResampleC)
+    L.vh_launch_resample_pos_embed.argtypes = [voidp, voidp, voidp] + [i] * 8
+    L.vit_resample_check.argtypes = [C.POINTER(VitConfig), i, prp, C.POINTER(VitConfig)]
+    L.vit_hip_create_at_resolution.argtypes = [C.POINTER(voidp), voidp, i, i, prp]
+    L.vit_hip_config.argtypes = [voidp]
+    L.vit_hip_config.restype = C.POINTER(VitConfig)
     _lib = L
     return L
 
@@ -833,6 +879,31 @@ class ViTHip:
         self.precision = {v: k for k, v in cls.PRECISIONS.items()}[self.L.vit_hip_precision(self.ctx)]
         self.max_batch, self.tokens = max_batch, tokens(self.cfg)
         return self
+
+    def at_resolution(self, img_size: int, max_batch=None, mode="bicubic", align_corners=False) -> "ViTHip":
+        """A NEW context for the same weights at another img_size (vit_hip_create_at_resolution): the position grid
+        resampled on the GPU (mode "bicubic" | "bilinear"), every other weight copied device to device.  max_batch None:
+        this context's.  This context stays as it is and may be closed before or after the new one."""
+        new = type(self).__new__(type(self))
+        new.L, new._weights, new.ctx = self.L, None, voidp()
+        how = PosResampleC(_pos_mode(mode), int(align_corners))
+        check(self.L.vit_hip_create_at_resolution(C.byref(new.ctx), self.ctx, int(img_size), int(max_batch or 0), C.byref(how)),
+              "vit_hip_create_at_resolution")
+        new.cfg = VitConfig.from_buffer_copy(self.L.vit_hip_config(new.ctx).contents)
+        new.precision = self.precision
+        new.max_batch, new.tokens = self.L.vit_hip_max_batch(new.ctx), tokens(new.cfg)
+        return new
+
+    def weight(self, idx: int) -> np.ndarray:
+        """Tensor idx as the context holds it in fp32 (vit_hip_weight), read back to the host."""
+        ptr = self.L.vit_hip_weight(self.ctx, int(idx))
+        if not ptr:
+            raise IndexError(f"weight: no tensor {idx}")
+        self.sync()
+        out = np.empty(self.L.vit_config_tensor_size(C.byref(self.cfg), int(idx)), dtype=np.float32)
+        check(self.L.vh_d2h(out.ctypes.data_as(voidp), ptr, out.nbytes, None), "vh_d2h")
+        check(self.L.vh_device_sync(), "vh_device_sync")
+        return out
 
     def export_planes(self, path) -> None:
         check(self.L.vit_hip_export_planes(self.ctx, str(path).encode()), "vit_hip_export_planes")
