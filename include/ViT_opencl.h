@@ -30,7 +30,7 @@ extern "C" {
  * ViT_seq.c:10-21 and ViT_opencl.c:13-24; here it is data. */
 typedef struct vit_config
 {
-    int img_size;    /* 224 */
+    int img_size;    /* 224: the input's height, and its width too unless img_width says otherwise */
     int patch_size;  /* 16  */
     int in_chans;    /* 3   */
     int num_classes; /* 1000 */
@@ -39,6 +39,7 @@ typedef struct vit_config
     int num_heads;   /* 12  */
     int mlp_hidden;  /* (int)(embed_dim * mlp_ratio) = 3072 */
     double eps;      /* LayerNorm epsilon, a double literal in the reference (1e-6) */
+    int img_width;   /* 0: img_size (a square input); otherwise the input is img_size rows by img_width columns */
 } vit_config;
 
 /* Fill `cfg` with a named preset: "vit_b_16" (the reference's only
@@ -74,8 +75,25 @@ typedef struct vit_config
  *                              plan among them) are not affected. */
 int vit_config_preset(vit_config *cfg, const char *name);
 
+/* Non-square inputs.  A context takes images of img_size rows by img_width columns (both multiples of patch_size, at most
+ * 4096; at most 512 patches a side); its patches form a gh x gw grid, row-major, and T = gh * gw + 1.  Everything behind the
+ * patch embedding depends on T alone.  A square input has ONE representation inside the library: wherever a config enters it
+ * (vit_hip_create*, vit_resample_check*, the plan) img_width == img_size is stored as 0, so vit_hip_config() of a square
+ * context reports img_width 0 whichever way it was asked for, and a square context computes, launches and exports exactly
+ * what it did before the field existed.
+ * vit_config_canonical: host only; *out = that form of *cfg, every byte written (out may be cfg); 0, or 1 with a message
+ * that begins with `who` (NULL: its own name) for a NULL argument, an img_width that is not a positive multiple of
+ * patch_size or is above 4096, or a non-square config with a grid side above 512.  vit_hip_create* refuse with it (code 1)
+ * before anything is allocated; a pos_embedding (tensor 3) of the wrong row count stays code 3.
+ * Still square only, and refused on a non-square context with code 1 and a message that says "non-square" before any upload
+ * or launch: the resize and box ingest forms (vit_hip_resize_crop_u8, vit_hip_crop_boxes_u8, vit_hip_forward*_u8_resized,
+ * vit_hip_forward*_u8_boxes: their crops are img x img) and vit_hip_export_planes. */
+int vit_config_canonical(const vit_config *cfg, vit_config *out, const char *who);
+void vit_config_grid(const vit_config *cfg, int *grid_h, int *grid_w);   /* img_size / patch, width / patch; either may be NULL */
+int vit_config_sizeof(void);                       /* sizeof(vit_config), for bindings that restate the struct */
+
 /* Derived sizes. */
-int vit_config_tokens(const vit_config *cfg);      /* (img/patch)^2 + 1 */
+int vit_config_tokens(const vit_config *cfg);      /* grid_h * grid_w + 1 */
 int vit_config_num_tensors(const vit_config *cfg); /* 4 + 12*depth + 4 (152 for B/16) */
 /* Element count tensor `idx` must have (torchvision state-dict order,
  * reference index map: ViT_seq.c:437-513, ViT_opencl.c:159,280-295). */
@@ -125,16 +143,20 @@ int vit_hip_ln_fold(const vit_hip_ctx *ctx);
  * matrices of every layer (three-part bf16 planes / one-part planes / fp16 pairs / MX values + scales) -- behind a
  * header that pins the model shape and precision; create_from_planes builds an identical context from that ONE file
  * (three reads into three allocations; the reference's loader opens 152 files, Network.c:134-218).  Logits of the two
- * contexts are bit-identical. */
+ * contexts are bit-identical.
+ * The header pins ONE image side, so export refuses a non-square context (code 1, "non-square", nothing written).  No weight
+ * but pos_embedding depends on the input size: the way to a non-square context from a file is to load the square file and
+ * call vit_hip_create_at_size on it. */
 int vit_hip_export_planes(vit_hip_ctx *ctx, const char *path);
 int vit_hip_create_from_planes(vit_hip_ctx **out, const char *path, int device, int max_batch);
 
 /* ---- the same model at another resolution: a context derived on the GPU from one that exists ----
  * A context runs at the resolution its pos_embedding (tensor 3) was trained at: vit_hip_create_ex refuses any other row
- * count (code 3).  vit_hip_create_at_resolution makes a NEW context for the same weights at another img_size from a context
- * `src` that already exists -- created from host tensors or from a planes file -- without host tensors:
+ * count (code 3).  vit_hip_create_at_size makes a NEW context for the same weights at another img_height x img_width from a
+ * context `src` that already exists -- created from host tensors or from a planes file, square or not -- without host
+ * tensors; vit_hip_create_at_resolution(.., s, ..) is vit_hip_create_at_size(.., s, s, ..) under its own name:
  *   - tensor 3 is produced by vh_launch_resample_pos_embed (include/kernelHandler.h states the definition and its error
- *     bound; csrc/pos_resample.hip) with prefix = 1 and the square grids img_size / patch_size of the two contexts;
+ *     bound; csrc/pos_resample.hip) with prefix = 1 and the gh x gw patch grids of the two contexts;
  *   - every other weight is copied device to device in the form it already has: the three slabs of GEMM operands,
  *     conv_proj planes and folded LayerNorm terms whole, the fp32 tensors one by one into the new layout.  Nothing is
  *     re-split, re-quantised or re-folded, so the derived context holds the bits a context created at img_size from the
@@ -150,13 +172,17 @@ int vit_hip_create_from_planes(vit_hip_ctx **out, const char *path, int device, 
  * vit_resample_check refuses; code 2 with a message for a target shape this precision and these switches do not run (for
  * instance F32_FP16X2, or $VIT_HIP_P3=0, above 512 tokens) or whose operand slabs would differ in size from src's.  On a
  * failure behind that (out of device memory) the new context is destroyed.
- * Out of scope: weights shared between contexts, non-square inputs, antialiased resampling (timm's default: another
- * kernel constant), vit_hip_create_multi, and examples/vit_main.c (which reads the reference's 224-pixel files). */
+ * Out of scope: weights shared between contexts, antialiased resampling (timm's default: another kernel constant),
+ * vit_hip_create_multi, and examples/vit_main.c (which reads the reference's 224-pixel files). */
 enum { VIT_POS_BICUBIC = 0, VIT_POS_BILINEAR = 1 };
 typedef struct vit_pos_resample { int mode; int align_corners; } vit_pos_resample;   /* NULL = bicubic, align_corners 0 */
-/* host only, touches no device: 0 and *out_cfg = *src with img_size replaced; 1 with a message for a null or bad
- * argument (img_size <= 0 or not a multiple of patch_size, a grid side above 512, unknown mode, align_corners not 0 / 1) */
+/* host only, touches no device: 0 and *out_cfg = *src with the two sides replaced, in the canonical form (out_cfg may be
+ * src); 1 with a message for a null or bad argument (a side <= 0 or not a multiple of patch_size, a grid side above 512,
+ * unknown mode, align_corners not 0 / 1).  vit_resample_check(src, s, ..) is vit_resample_check_hw(src, s, s, ..). */
+int vit_resample_check_hw(const vit_config *src, int img_height, int img_width, const vit_pos_resample *how, vit_config *out_cfg);
 int vit_resample_check(const vit_config *src, int img_size, const vit_pos_resample *how, vit_config *out_cfg);
+int vit_hip_create_at_size(vit_hip_ctx **out, const vit_hip_ctx *src, int img_height, int img_width, int max_batch,
+                           const vit_pos_resample *how);
 int vit_hip_create_at_resolution(vit_hip_ctx **out, const vit_hip_ctx *src, int img_size, int max_batch,
                                  const vit_pos_resample *how);
 
@@ -180,7 +206,7 @@ int vit_hip_create_at_resolution(vit_hip_ctx **out, const vit_hip_ctx *src, int 
 int vit_hip_forward(vit_hip_ctx *ctx, const ImageData *images, int n, float *logits,
                     float **probs);
 
-/* Device-resident forward: d_images is [n][C][H][W] fp32 already in HBM,
+/* Device-resident forward: d_images is [n][C][H][W] fp32 already in HBM (H = img_size, W = the config's width),
  * n <= max_batch; d_logits / d_probs ([n][num_classes] device buffers) may each
  * be NULL.  Asynchronous on `stream`.  A NULL / 0 handle means the CONTEXT'S OWN stream (vit_hip_stream(), created
  * non-blocking), not HIP's legacy null stream: work a caller has queued on the null stream, or on a framework's
@@ -193,12 +219,13 @@ int vit_hip_forward_device(vit_hip_ctx *ctx, const float *d_images, int n, float
  * x = (float)u * scale[c] + bias[c]; the product and the sum are each rounded to fp32 (no fused multiply-add), so the
  * logits are bit-identical to the fp32 entry points fed the same images normalised on the host with that arithmetic. */
 typedef struct vit_pixel_norm { float scale[4]; float bias[4]; } vit_pixel_norm;
-/* [n][img][img][C] as PIL / NumPy / OpenCV give it (RGB order), or [n][C][img][img] as torchvision.io gives it */
+/* [n][H][W][C] as PIL / NumPy / OpenCV give it (RGB order), or [n][C][H][W] as torchvision.io gives it; H = img_size rows,
+ * W = the config's width */
 enum { VIT_PIXELS_HWC = 0, VIT_PIXELS_CHW = 1 };
 /* scale = 1 / (255 std[c]), bias = -mean[c] / std[c], both computed in double and then rounded to float;
  * mean and std on the 0..1 scale, as torchvision's Normalize takes them; chans 1..4, std > 0; returns 0 or 1 */
 int vit_pixel_norm_from_mean_std(vit_pixel_norm *out, const float *mean, const float *std, int chans);
-/* Device-resident form: d_images contiguous [n][img][img][C] or [n][C][img][img] bytes in HBM, 16-byte aligned, geometry of
+/* Device-resident form: d_images contiguous [n][H][W][C] or [n][C][H][W] bytes in HBM, 16-byte aligned, geometry of
  * the context's config (in_chans <= 4), n <= max_batch; otherwise as vit_hip_forward_device.  On the planes paths the
  * patch embedding's gather reads the bytes and normalises them (no fp32 image in HBM); on the fp32-rows paths
  * ($VIT_HIP_P3=0, $VIT_HIP_GEMM_FP32=native, F32_FP16X2) a small kernel expands them first.  Code 1 (with a message, no
@@ -340,8 +367,8 @@ int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on);
  *                 (a zero vector stays zero)
  *   dtype         VIT_FEATURE_BF16 = the fp32 result rounded to nearest even; nothing else differs
  * Layouts are image-major: cls and pooled are [n][n_taps][E] (per image the taps concatenated in ascending layer order:
- * what a linear probe consumes); tokens is [n][n_taps][T-1][E] (VIT_TOKENS_NLC) or [n][n_taps][E][g][g] (VIT_TOKENS_NCHW,
- * g = img / patch).  The class token is never part of tokens.  pooled = mean over the T-1 patch rows of the values
+ * what a linear probe consumes); tokens is [n][n_taps][T-1][E] (VIT_TOKENS_NLC) or [n][n_taps][E][gh][gw] (VIT_TOKENS_NCHW,
+ * the patch grid of vit_config_grid: the memory of [E][T-1]).  The class token is never part of tokens.  pooled = mean over the T-1 patch rows of the values
  * tokens holds BEFORE any narrowing to bf16 (normalise, then pool, when final_norm is set).  Outputs depend on the image
  * only: bit-identical wherever it sits in the batch and whatever n is (fixed-order sums, no floating-point atomics).
  * Device form (vit_hip_set_features): device buffers, 16-byte aligned, for up to max_batch images; written asynchronously
@@ -431,8 +458,8 @@ int vit_hip_set_topk_host(vit_hip_ctx *ctx, const vit_topk_spec *spec, const vit
  * output is NOT the probability matrix an attention kernel forms internally (those differ per kernel: exp2 with a folded
  * scale, P rounded to fp16, online softmax); against the definition evaluated in double on the same Q and K a value p
  * errs by at most (4 (D + 2) S + T + 64) 2^-24 p, S = max_t sum_d |q_d k_d| / sqrt(D).
- * Key 0 is the class token itself, so every row of heads (and of mean) sums to 1; keys 1 .. T-1, viewed as [g][g]
- * (g = img / patch), are the map.  taps are those of vit_feature_spec: layers, 0-based or negative from the end, strictly
+ * Key 0 is the class token itself, so every row of heads (and of mean) sums to 1; keys 1 .. T-1, viewed as [gh][gw]
+ * (vit_config_grid), are the map.  taps are those of vit_feature_spec: layers, 0-based or negative from the end, strictly
  * ascending once resolved; here the layer's own attention is read, not its output.
  * Both outputs are fp32 and image-major: heads [n][n_taps][H][T], mean [n][n_taps][T]; either may be NULL, not both, and
  * mean has the same bits whether heads is asked for or not.  No floating-point atomics: an image's output is
@@ -480,7 +507,7 @@ int vit_hip_set_attention_host(vit_hip_ctx *ctx, const vit_attn_spec *spec, cons
  * All arithmetic is fp32 (the two products on the fp32-input matrix instruction, an exact k-ordered fma chain); every sum
  * runs in an order fixed by (T, H, D, stored form) alone.  No floating-point atomics: an image's output is bit-identical
  * wherever it sits in the batch and whatever n is.  Every R_l is row-stochastic and non-negative, so rollout[i] sums to 1.
- * Key 0 is the class token's own weight; keys 1 .. T-1, viewed as [g][g] (g = img / patch), are the map.  Like the
+ * Key 0 is the class token's own weight; keys 1 .. T-1, viewed as [gh][gw] (vit_config_grid), are the map.  Like the
  * attention maps this is defined on the stored Q|K|V; it is NOT the probabilities any attention kernel forms internally.
  * Against the definition evaluated in double on the same Q and K a value errs by at most
  * rollout * 2^-24 * sum over l of (4 (D + 2) S_l + 2 T + H + 70), S_l = the largest sum_d |q_d k_d| / sqrt(D) of layer l.
@@ -573,8 +600,8 @@ int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, con
 /* ---- dense head: a label per pixel from the patch tokens (semantic segmentation by a linear head) ----
  * A dense request is ARMED on a context like the other five requests, and independently of them (all six may be armed at
  * once).  While armed, every forward through the context also applies the caller's linear head W [n_labels][E], b to every
- * patch token behind layer `tap`, upsamples the n_labels logits per patch bilinearly from the g x g patch grid (g = img_size
- * / patch_size) to out_h x out_w and writes, per pixel, the best label as one byte: 50 KB per 224 x 224 image instead of
+ * patch token behind layer `tap`, upsamples the n_labels logits per patch bilinearly from the gh x gw patch grid
+ * (vit_config_grid) to out_h x out_w and writes, per pixel, the best label as one byte: 50 KB per 224 x 224 image instead of
  * the 600 KB of its patch tokens.  Two or three extra launches behind the tapped layer (vh_launch_feature_readout when
  * final_norm is set, vh_launch_dense_logits, vh_launch_dense_labels, csrc/dense_head.hip), all timed under VIT_OP_HEAD;
  * logits, probabilities and the other five requests' outputs are bit-identical to a forward without a dense request.  A
@@ -584,12 +611,12 @@ int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, con
  * same kernel writes them into the MLP buffer, idle behind fc2, when that holds max_batch * (T - 1) * E floats, and into
  * scratch of the request's own otherwise; without, the residual stream's patch rows are read in place.
  * Patch logits, upsampling, labels, scores and their error bound: as vh_launch_dense_logits and vh_launch_dense_labels
- * define them (include/kernelHandler.h), with GH = GW = g; an image's outputs are the same bits wherever it sits in the
+ * define them (include/kernelHandler.h), with GH = gh, GW = gw; an image's outputs are the same bits wherever it sits in the
  * batch and whatever n is.
  * spec: tap is one layer, 0-based or negative from the end (-1 = the last), in [-depth, depth); n_labels in 2..256; out_h,
- * out_w in 1..4096, 0 = the model's img_size; d_weight [n_labels] rows of embed_dim fp32, weight_stride elements apart
+ * out_w in 1..4096, 0 = the model's img_size (out_h) and width (out_w); d_weight [n_labels] rows of embed_dim fp32, weight_stride elements apart
  * (>= embed_dim, a multiple of 4), d_bias [n_labels] fp32 or NULL: device memory of the context's device, 16-byte aligned,
- * the CALLER'S, valid and unchanged while armed.  The model needs embed_dim % 4 == 0, <= 2048, T - 1 == g * g >= 1, g <= 64.
+ * the CALLER'S, valid and unchanged while armed.  The model needs embed_dim % 4 == 0, <= 2048, T - 1 == gh * gw >= 1, gh and gw <= 64.
  * Outputs: labels u8 [n][out_h][out_w] (required); scores fp32 [n][out_h][out_w] and patch_logits fp32 [n][T - 1][n_labels]
  * (either may be NULL; asking for them changes no label).  Scratch, allocated when the request is armed and freed when it
  * is disarmed or the context destroyed (if it cannot be allocated, arming is refused): the patch logits [max_batch][T - 1]
@@ -612,7 +639,7 @@ int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, con
  * than 256 labels. */
 typedef struct vit_dense_spec {
     int tap, final_norm;          /* as vit_gallery_spec */
-    int n_labels, out_h, out_w;   /* out_h/out_w 0 = the model's img_size */
+    int n_labels, out_h, out_w;   /* out_h 0 = the model's img_size, out_w 0 = its width */
     long weight_stride;
     const float *d_weight, *d_bias;   /* device, the caller's; d_bias may be NULL */
 } vit_dense_spec;

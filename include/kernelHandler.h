@@ -452,6 +452,30 @@ int vh_launch_patch_embed_planes_u8(vh_stream_t s, const unsigned char *images, 
 int vh_launch_expand_u8(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias, float *out,
                         int n_images, int in_chans, int img_size);
 
+/* ---- images of img_h rows by img_w columns: the three general forms the square entries above forward to ----
+ * An image is [in_chans][img_h][img_w] (fp32, 8-bit CHW) or [img_h][img_w][in_chans] (8-bit HWC); both sides are multiples of
+ * patch_size; the patches of an image are row-major in its (img_h / patch) x (img_w / patch) grid, tokens = their count + 1,
+ * and a patch row's K values and their order are those of the square forms.  Only the row pitch (img_w) and the plane size
+ * (img_h * img_w) differ, and the vector-load conditions are conditions on img_w.
+ * _planes_hw: every planes variant.  Exactly one of images_f32 and images_u8 is given (layout, scale and bias belong to the
+ * 8-bit one and are ignored otherwise); parts, operand_out, operand_scales_out and row_stats_out select what
+ * vh_launch_patch_embed_planes / _planes3 / _planes_norm / _planes3_norm do, as in vh_launch_patch_embed_planes_u8.
+ * _rows_hw: vh_launch_patch_embed_ws_math, with vh_patch_embed_workspace_hw bytes of workspace (0 where patch % 4 == 0,
+ * in_chans * patch^2 % 32 == 0 and img_w % 4 == 0: gathered on load).
+ * _expand_u8_hw: vh_launch_expand_u8. */
+int vh_launch_patch_embed_planes_hw(vh_stream_t s, const float *images_f32, const unsigned char *images_u8, int layout,
+                                    const float *scale, const float *bias, const void *conv_w_planes, const float *conv_b,
+                                    const float *cls_token, const float *pos_embed, float *tokens, int n_images, int in_chans,
+                                    int img_h, int img_w, int patch_size, int embed_dim, void *workspace, size_t workspace_bytes,
+                                    int parts, void *operand_out, void *operand_scales_out, float *row_stats_out);
+size_t vh_patch_embed_workspace_hw(int n_images, int in_chans, int img_h, int img_w, int patch_size, int embed_dim);
+int vh_launch_patch_embed_rows_hw(vh_stream_t s, const float *images, const float *conv_w, const float *conv_b,
+                                  const float *cls_token, const float *pos_embed, float *tokens, int n_images, int in_chans,
+                                  int img_h, int img_w, int patch_size, int embed_dim, void *workspace, size_t workspace_bytes,
+                                  int fp32_math);
+int vh_launch_expand_u8_hw(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias, float *out,
+                           int n_images, int in_chans, int img_h, int img_w);
+
 /* ---- Pillow-exact resize + crop of 8-bit images (csrc/resize.hip; vit_hip_resize_crop_u8, vit_hip_crop_boxes_u8) ----
  * One output image: its source, and per axis Pillow's precompute_coeffs(in, in0, in1, out) -- the source span [in0, in1)
  * (C floats, as Pillow takes a box) resized to `out` samples, of which the crop indices first .. first + crop - 1 are

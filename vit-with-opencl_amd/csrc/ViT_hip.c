@@ -144,6 +144,8 @@ static void prof_release(vit_hip_ctx *ctx)
 }
 
 const vit_config *vit_hip_config(const vit_hip_ctx *ctx) { return &ctx->cfg; }
+/* columns of an input image; its rows are cfg.img_size */
+static int ctx_width(const vit_hip_ctx *ctx) { return ctx->cfg.img_width ? ctx->cfg.img_width : ctx->cfg.img_size; }
 int vit_hip_device(const vit_hip_ctx *ctx) { return ctx->device; }
 float *vit_hip_logits_buffer(vit_hip_ctx *ctx) { return ctx->d_logits; }   /* [max_batch][classes], vit_gather_rccl.c */
 vh_stream_t vit_hip_stream(const vit_hip_ctx *ctx) { return ctx->stream; }
@@ -187,8 +189,11 @@ static int alloc_weights(vit_hip_ctx *ctx)
 {
     int rc = 0;
     for (int i = 0; i < N_SLABS; ++i)
-        if (ctx->plan.slab_bytes[i])
+        if (ctx->plan.slab_bytes[i]) {
             TRY(vh_malloc(&ctx->slab[i], ctx->plan.slab_bytes[i]));
+            /* the alignment gaps between the pieces too: what vit_hip_export_planes writes depends on the weights alone */
+            TRY(vh_memset(ctx->slab[i], 0, ctx->plan.slab_bytes[i], ctx->stream));
+        }
     plan_layout(&ctx->plan, &ctx->cfg, ctx->slab, ctx->w, ctx->op, NULL);
     return 0;
 fail:
@@ -271,15 +276,17 @@ fail:
     return rc;
 }
 
-/* The weights of a context at another resolution (vit_hip_create_at_resolution): everything device to device in the form
- * `from` holds it -- the operand, conv_proj and fold slabs whole (their layout does not depend on img_size; the caller has
+/* The weights of a context at another input size (vit_hip_create_at_size): everything device to device in the form
+ * `from` holds it -- the operand, conv_proj and fold slabs whole (their layout does not depend on the input size; the caller has
  * checked the sizes), the fp32 tensors one by one into this context's SLAB_F32 layout -- except pos_embedding, resampled
  * from from's grid to this one's.  `from` is only read, after its stream has drained. */
 static int derive_weights(vit_hip_ctx *ctx, const vit_hip_ctx *from, const vit_pos_resample *how)
 {
     int rc = 0;
     static const int whole[] = {SLAB_OPERAND, SLAB_CONV, SLAB_FOLD};
-    const int grid_in = from->cfg.img_size / from->cfg.patch_size, grid_out = ctx->cfg.img_size / ctx->cfg.patch_size;
+    int gh_in, gw_in, gh_out, gw_out;
+    vit_config_grid(&from->cfg, &gh_in, &gw_in);
+    vit_config_grid(&ctx->cfg, &gh_out, &gw_out);
     TRY(vh_stream_sync(from->stream));
     for (size_t i = 0; i < sizeof(whole) / sizeof(whole[0]); ++i)
         if (ctx->plan.slab_bytes[whole[i]])
@@ -287,7 +294,7 @@ static int derive_weights(vit_hip_ctx *ctx, const vit_hip_ctx *from, const vit_p
     for (int i = 0; i < ctx->n_tensors; ++i)
         if (i != 3)
             TRY(vh_d2d(ctx->w[i], from->w[i], vit_config_tensor_size(&ctx->cfg, i) * sizeof(float), ctx->stream));
-    TRY(vh_launch_resample_pos_embed(ctx->stream, from->w[3], ctx->w[3], 1, grid_in, grid_in, grid_out, grid_out, ctx->cfg.embed_dim,
+    TRY(vh_launch_resample_pos_embed(ctx->stream, from->w[3], ctx->w[3], 1, gh_in, gw_in, gh_out, gw_out, ctx->cfg.embed_dim,
                                      how ? how->mode : VIT_POS_BICUBIC, how ? how->align_corners : 0));
 fail:
     return rc;
@@ -350,15 +357,19 @@ static int ctx_new(vit_hip_ctx **out, const vit_config *cfg, int n_tensors, int 
     return 0;
 }
 
-int vit_hip_create_ex(vit_hip_ctx **out, const vit_config *cfg, const Network *networks,
+int vit_hip_create_ex(vit_hip_ctx **out, const vit_config *cfg_in, const Network *networks,
                       int n_tensors, int device, int max_batch, int precision)
 {
     int rc = 0;
     if (!out)
         return 1;
     *out = NULL;
-    if (!networks || !cfg)
+    if (!networks || !cfg_in)
         return 1;
+    vit_config canon;   /* img_width == img_size stored as 0; another width checked here, before the tensors are looked at */
+    if ((rc = vit_config_canonical(cfg_in, &canon, "vit_hip_create")) != 0)
+        return rc;
+    const vit_config *cfg = &canon;
     if (n_tensors != vit_config_num_tensors(cfg))
         return 2;
     /* The reference never checks its tensors (a missing file is a NULL
@@ -383,20 +394,26 @@ int vit_hip_create_ex(vit_hip_ctx **out, const vit_config *cfg, const Network *n
     return 0;
 }
 
-/* The same model at another img_size, from the weights `src` holds on its device (include/ViT_opencl.h).  Every refusal
- * falls before anything is allocated: the arguments (vit_resample_check), the plan of the target shape under src's
- * precision and fold and this moment's switches, and the slabs that are copied whole. */
-int vit_hip_create_at_resolution(vit_hip_ctx **out, const vit_hip_ctx *src, int img_size, int max_batch,
-                                 const vit_pos_resample *how)
+/* The same model at another input size, from the weights `src` holds on its device (include/ViT_opencl.h).  Every refusal
+ * falls before anything is allocated: the arguments (vit_resample_check_hw), the plan of the target shape under src's
+ * precision and fold and this moment's switches, and the slabs that are copied whole.  square: the call came as
+ * vit_hip_create_at_resolution, whose messages speak of one img_size. */
+static int create_at_size(vit_hip_ctx **out, const vit_hip_ctx *src, int img_height, int img_width, int max_batch,
+                          const vit_pos_resample *how, int square)
 {
     int rc = 0;
-    if (!out)
-        return vh_set_error(1, "vit_hip_create_at_resolution: null argument (out)");
+    char msg[240];
+    const char *const who = square ? "vit_hip_create_at_resolution" : "vit_hip_create_at_size";
+    if (!out || !src) {
+        if (out)
+            *out = NULL;
+        snprintf(msg, sizeof msg, "%s: null argument (%s)", who, out ? "src" : "out");
+        return vh_set_error(1, msg);
+    }
     *out = NULL;
-    if (!src)
-        return vh_set_error(1, "vit_hip_create_at_resolution: null argument (src)");
     vit_config cfg;
-    if ((rc = vit_resample_check(&src->cfg, img_size, how, &cfg)) != 0)
+    if ((rc = square ? vit_resample_check(&src->cfg, img_height, how, &cfg)
+                     : vit_resample_check_hw(&src->cfg, img_height, img_width, how, &cfg)) != 0)
         return rc;
     if (max_batch <= 0)
         max_batch = src->max_batch;
@@ -404,27 +421,41 @@ int vit_hip_create_at_resolution(vit_hip_ctx **out, const vit_hip_ctx *src, int 
     struct vit_plan plan;
     plan_env_read(&env);
     /* plan_make words most of its refusals itself; the others keep this text */
-    vh_set_error(2, "vit_hip_create_at_resolution: no plan runs the source's precision and LayerNorm fold at this img_size and max_batch");
+    snprintf(msg, sizeof msg, "%s: no plan runs the source's precision and LayerNorm fold at this img_size and max_batch", who);
+    vh_set_error(2, msg);
     if ((rc = plan_make(&plan, &cfg, src->n_tensors, max_batch, src->plan.precision, src->plan.ln_fold, &env)) != 0)
         return rc;
     (void)vh_set_error(0, "");   /* accepted: that text was no failure */
     static const int whole[] = {SLAB_OPERAND, SLAB_CONV, SLAB_FOLD};
     for (size_t i = 0; i < sizeof(whole) / sizeof(whole[0]); ++i)
         if (plan.slab_bytes[whole[i]] != src->plan.slab_bytes[whole[i]]) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "vit_hip_create_at_resolution: weight slab %d would hold %zu bytes at img_size=%d, the source's holds %zu",
-                     whole[i], plan.slab_bytes[whole[i]], img_size, src->plan.slab_bytes[whole[i]]);
+            snprintf(msg, sizeof msg, "%s: weight slab %d would hold %zu bytes at img_size=%d, the source's holds %zu",
+                     who, whole[i], plan.slab_bytes[whole[i]], img_height, src->plan.slab_bytes[whole[i]]);
             return vh_set_error(2, msg);
         }
     vit_hip_ctx *ctx = NULL;
-    if ((rc = ctx_new(&ctx, &cfg, src->n_tensors, src->device, max_batch, &plan)) != 0)
-        return vh_set_error(rc, "vit_hip_create_at_resolution: out of host memory");
+    if ((rc = ctx_new(&ctx, &cfg, src->n_tensors, src->device, max_batch, &plan)) != 0) {
+        snprintf(msg, sizeof msg, "%s: out of host memory", who);
+        return vh_set_error(rc, msg);
+    }
     for (int m = 0; m < 4 * cfg.depth; ++m)
         ctx->op[m].pair_scale = src->op[m].pair_scale;
     if ((rc = ctx_finish(ctx, NULL, NULL, src, how)) != 0)
         return rc;
     *out = ctx;
     return 0;
+}
+
+int vit_hip_create_at_size(vit_hip_ctx **out, const vit_hip_ctx *src, int img_height, int img_width, int max_batch,
+                           const vit_pos_resample *how)
+{
+    return create_at_size(out, src, img_height, img_width, max_batch, how, 0);
+}
+
+int vit_hip_create_at_resolution(vit_hip_ctx **out, const vit_hip_ctx *src, int img_size, int max_batch,
+                                 const vit_pos_resample *how)
+{
+    return create_at_size(out, src, img_size, img_size, max_batch, how, 1);
 }
 
 /* ---- repacked weights on disk: the format, the writer and the reader are csrc/vit_planes_file.c ---------------------- */
@@ -442,6 +473,9 @@ int vit_hip_export_planes(vit_hip_ctx *ctx, const char *path)
     int rc = 0;
     if (!ctx || !path)
         return vh_set_error(1, "vit_hip_export_planes: null argument");
+    if (ctx->cfg.img_width != 0)   /* the header pins one side; nothing but pos_embedding depends on the size */
+        return vh_set_error(1, "vit_hip_export_planes: the context's input is non-square and the file's header holds one side: "
+                               "export the square context and derive this one from it (vit_hip_create_at_size)");
     if ((rc = vh_set_device(ctx->device)) != 0)
         return rc;
     float scales[MAX_TENSORS];
@@ -491,7 +525,7 @@ static int alloc_arena(vit_hip_ctx *ctx)
     TRY(vh_malloc((void **)&ctx->d_logits, (size_t)max_batch * NC * sizeof(float)));
     TRY(vh_malloc((void **)&ctx->d_probs, (size_t)max_batch * NC * sizeof(float)));
     const struct pipeline_model pm = {.device = ctx->device, .max_batch = max_batch, .classes = cfg->num_classes, .stream = ctx->stream,
-                                      .image_bytes = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size * sizeof(float),
+                                      .image_bytes = (size_t)cfg->in_chans * cfg->img_size * ctx_width(ctx) * sizeof(float),
                                       .d_logits = ctx->d_logits, .d_probs = ctx->d_probs};
     TRY(pipeline_make(&ctx->pipe, &pm));
     TRY(vh_stream_sync(ctx->stream));
@@ -772,32 +806,25 @@ static int patch_embed_launches(vit_hip_ctx *ctx, vh_stream_t s, const struct in
     /* ln_fold: y receives the token rows as the first projection's operand -- planes, or MX values with their scales behind
      * them -- and stats their partial sums (class-token rows included) */
     char *const y_scales = ctx->plan.precision == VIT_PRECISION_FP8_GEMM ? (char *)ctx->y + ctx->plan.e_scales_off : NULL;
-    if (src->u8 && ctx->plan.planes_patch_embed)
-        return vh_launch_patch_embed_planes_u8(s, src->u8, src->layout, src->norm->scale, src->norm->bias, conv, w[2], w[0], w[3],
-                                               ctx->x, n, c->in_chans, c->img_size, c->patch_size, E, ctx->hid, ctx->plan.ws_bytes,
-                                               ctx->plan.conv_parts, ctx->plan.ln_fold ? ctx->y : NULL,
-                                               ctx->plan.ln_fold ? y_scales : NULL, ctx->plan.ln_fold ? ctx->stats : NULL);
+    const int img_h = c->img_size, img_w = ctx_width(ctx);
+    if (ctx->plan.planes_patch_embed) {
+        /* one launcher for every planes variant: the fp32 or the 8-bit pixels (normalised as they are gathered), the plan's
+         * parts -- three on the fp32 path, one in the reduced modes -- and, under ln_fold, the first projection's operand */
+        const int fold = ctx->plan.ln_fold;
+        return vh_launch_patch_embed_planes_hw(s, src->u8 ? NULL : src->f32, src->u8, src->layout, src->u8 ? src->norm->scale : NULL,
+                                               src->u8 ? src->norm->bias : NULL, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, img_h,
+                                               img_w, c->patch_size, E, ctx->hid, ctx->plan.ws_bytes, ctx->plan.conv_parts,
+                                               fold ? ctx->y : NULL, fold ? y_scales : NULL, fold ? ctx->stats : NULL);
+    }
     const float *images = src->f32;
     if (src->u8) {
-        const int rc = vh_launch_expand_u8(s, src->u8, src->layout, src->norm->scale, src->norm->bias, ctx->qkv, n, c->in_chans,
-                                           c->img_size);
+        const int rc = vh_launch_expand_u8_hw(s, src->u8, src->layout, src->norm->scale, src->norm->bias, ctx->qkv, n, c->in_chans,
+                                              img_h, img_w);
         if (rc)
             return rc;
         images = ctx->qkv;
     }
-    if (ctx->plan.ln_fold && ctx->plan.precision == VIT_PRECISION_F32)   /* lab variant: the fold on three-part planes */
-        return vh_launch_patch_embed_planes3_norm(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size,
-                                                  c->patch_size, E, ctx->hid, ctx->plan.ws_bytes, ctx->y, ctx->stats);
-    if (ctx->plan.ln_fold)
-        return vh_launch_patch_embed_planes_norm(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size,
-                                                 c->patch_size, E, ctx->hid, ctx->plan.ws_bytes, ctx->y, y_scales, ctx->stats);
-    if (ctx->plan.use_p3)   /* the fp32 path on planes: im2row writes the exact three-part split, six products per block */
-        return vh_launch_patch_embed_planes3(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size,
-                                             E, ctx->hid, ctx->plan.ws_bytes);
-    if (ctx->plan.planes_patch_embed)   /* reduced modes: im2row to one-part planes (in the MLP buffer, idle here) + the planes GEMM */
-        return vh_launch_patch_embed_planes(s, images, conv, w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size,
-                                            E, ctx->hid, ctx->plan.ws_bytes);
-    return vh_launch_patch_embed_ws_math(s, images, w[1], w[2], w[0], w[3], ctx->x, n, c->in_chans, c->img_size, c->patch_size, E,
+    return vh_launch_patch_embed_rows_hw(s, images, w[1], w[2], w[0], w[3], ctx->x, n, c->in_chans, img_h, img_w, c->patch_size, E,
                                          ctx->hid, ctx->plan.ws_bytes, fp32_math(ctx));
 }
 
@@ -859,7 +886,7 @@ static int dense_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct dense_req *de
     float *pl = de->out.patch_logits ? de->out.patch_logits : (float *)de->head.scratch[0];
     OP(VIT_OP_HEAD, vh_launch_dense_logits(s, rows, image_stride, E, n, P, E, de->spec.d_weight, de->spec.weight_stride, de->spec.d_bias,
                                            de->spec.n_labels, pl));
-    OP(VIT_OP_HEAD, vh_launch_dense_labels(s, pl, n, de->grid, de->grid, de->spec.n_labels, de->out_h, de->out_w, de->out.labels,
+    OP(VIT_OP_HEAD, vh_launch_dense_labels(s, pl, n, de->grid_h, de->grid_w, de->spec.n_labels, de->out_h, de->out_w, de->out.labels,
                                            de->out.scores));
     return 0;
 fail:
@@ -938,8 +965,8 @@ fail:
 static struct ingest_model model_of(const vit_hip_ctx *ctx)
 {
     const vit_config *c = &ctx->cfg;
-    return (struct ingest_model){.max_batch = ctx->max_batch, .in_chans = c->in_chans, .img_size = c->img_size,
-                                 .slot_bytes = (size_t)ctx->max_batch * c->in_chans * c->img_size * c->img_size * sizeof(float)};
+    return (struct ingest_model){.max_batch = ctx->max_batch, .in_chans = c->in_chans, .img_size = c->img_size, .img_width = c->img_width,
+                                 .slot_bytes = (size_t)ctx->max_batch * c->in_chans * c->img_size * ctx_width(ctx) * sizeof(float)};
 }
 
 /* The argument checks of an 8-bit form (ingest_check); a NULL context is refused there, not read here */
@@ -1161,7 +1188,7 @@ static int forward_host_images(vit_hip_ctx *ctx, const ImageData *images, int n,
     const vit_config *c = &ctx->cfg;
     for (int i = 0; i < n; ++i)
         if (!images[i].data || images[i].c != c->in_chans || images[i].h != c->img_size ||
-            images[i].w != c->img_size)
+            images[i].w != ctx_width(ctx))
             return 5;
     const struct ingest_src src = {.kind = INGEST_F32, .host_f32 = images};
     return forward_pipelined(ctx, &src, NULL, n, logits, probs, form);

@@ -44,6 +44,7 @@
 #include "vit_kernels.h"
 #include "fp32_split.h"
 #include "gemm_common.h"
+#include "patch_geometry.h"
 
 #include <cstdint>
 
@@ -90,8 +91,8 @@ struct GemmParams {
     void *C;                  /* output: fp32 or bf16 */
     int M, N, K;
     int mtiles, ntiles;
-    /* patch-embed geometry (A_PATCH / EPI_PATCH only) */
-    int img, patch, chans, grid, tokens;
+    /* patch-embed geometry (A_PATCH / EPI_PATCH only): img_h x img_w pixels, grid patches per patch row, np patches per image */
+    int img_h, img_w, patch, chans, grid, np, tokens;
 };
 
 /* The native fp32 matrix instruction (v_mfma_f32_32x32x2_f32: exact fp32, 1/16 of the bf16 rate): the
@@ -125,11 +126,11 @@ __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_f32_kernel(
         if (AMODE == A_ROWS) {
             a_src[i] = static_cast<const char *>(p.A) + (size_t)m * p.K * ES + 16 * chunk;
         } else {
-            const int np = p.grid * p.grid;
+            const int np = p.np;
             const int b = m / np, pp = m - b * np;
             const int oh = pp / p.grid, ow = pp - oh * p.grid;
             a_src[i] = reinterpret_cast<const char *>(
-                static_cast<const float *>(p.A) + ((size_t)b * p.chans * p.img + (size_t)oh * p.patch) * p.img +
+                static_cast<const float *>(p.A) + ((size_t)b * p.chans * p.img_h + (size_t)oh * p.patch) * p.img_w +
                 (size_t)ow * p.patch);
         }
     }
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_f32_kernel(
                 const int k = kt * BK + a_k[i], pp2 = p.patch * p.patch;
                 const int ic = k / pp2, rem = k - ic * pp2;
                 const int kh = rem / p.patch, kw = rem - kh * p.patch;
-                ap = a_src[i] + (((size_t)ic * p.img + kh) * p.img + kw) * 4;
+                ap = a_src[i] + (((size_t)ic * p.img_h + kh) * p.img_w + kw) * 4;
             }
             __builtin_amdgcn_global_load_lds((gptr_t)ap, (lptr_t)(As + (wave * T::CHA + i) * 8 * BK), 16, 0, 0);
         }
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_f32_kernel(
             size_t orow = (size_t)row;
             const float *posrow = nullptr;
             if (EPI == EPI_PATCH) {
-                const int np = p.grid * p.grid;
+                const int np = p.np;
                 const int b = row / np, pp = row - b * np;
                 orow = (size_t)b * p.tokens + 1 + pp;
                 posrow = p.pos + (size_t)(1 + pp) * p.N;
@@ -281,11 +282,11 @@ struct Staging {
             if (AMODE == A_ROWS) {
                 a_src[i] = static_cast<const char *>(p.A) + (size_t)m * p.K * ES + 16 * chunk;
             } else {
-                const int np = p.grid * p.grid;
+                const int np = p.np;
                 const int b = m / np, pp = m - b * np;
                 const int oh = pp / p.grid, ow = pp - oh * p.grid;
                 a_src[i] = reinterpret_cast<const char *>(
-                    static_cast<const float *>(p.A) + ((size_t)b * p.chans * p.img + (size_t)oh * p.patch) * p.img +
+                    static_cast<const float *>(p.A) + ((size_t)b * p.chans * p.img_h + (size_t)oh * p.patch) * p.img_w +
                     (size_t)ow * p.patch);
             }
         }
@@ -327,7 +328,7 @@ struct Staging {
                 const int k = kt * BK + a_k[i], pp2 = p.patch * p.patch;
                 const int ic = k / pp2, rem = k - ic * pp2;
                 const int kh = rem / p.patch, kw = rem - kh * p.patch;
-                ap = a_src[i] + (((size_t)ic * p.img + kh) * p.img + kw) * 4;
+                ap = a_src[i] + (((size_t)ic * p.img_h + kh) * p.img_w + kw) * 4;
             }
             __builtin_amdgcn_global_load_lds((gptr_t)ap, (lptr_t)(As + (wave * T::CHA + i) * 8 * BK), 16, 0, 0);
         }
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(T::NT, T::MIN_WAVES_PER_SIMD) void gemm_mf16_kernel
         size_t orow = (size_t)row;
         const float *posrow = nullptr;
         if (EPI == EPI_PATCH) {
-            const int np = p.grid * p.grid;
+            const int np = p.np;
             const int b = row / np, pp = row - b * np;
             orow = (size_t)b * p.tokens + 1 + pp;
             posrow = p.pos + (size_t)(1 + pp) * p.N;
@@ -894,7 +895,7 @@ namespace {
  * ViT-H/14: 3*14*14 = 588): the patches are gathered once into rows of Kp = roundup(K, 32)
  * floats, zero-padded, and the weights are padded alike; then it is an ordinary rows GEMM. */
 __global__ void im2row_pad_kernel(const float *__restrict__ images, float *__restrict__ rows, int n_rows, int chans,
-                                  int img, int patch, int grid, int K, int Kp)
+                                  int img_h, int img_w, int patch, int grid, int np, int K, int Kp)
 {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)n_rows * Kp)
@@ -902,9 +903,9 @@ __global__ void im2row_pad_kernel(const float *__restrict__ images, float *__res
     const int m = (int)(idx / Kp), k = (int)(idx - (size_t)m * Kp);
     float v = 0.0f;
     if (k < K) {
-        const int np = grid * grid, b = m / np, pp = m - b * np, oh = pp / grid, ow = pp - oh * grid;
+        const int b = m / np, pp = m - b * np, oh = pp / grid, ow = pp - oh * grid;
         const int pp2 = patch * patch, ic = k / pp2, rem = k - ic * pp2, kh = rem / patch, kw = rem - kh * patch;
-        v = images[(((size_t)b * chans + ic) * img + (size_t)oh * patch + kh) * img + (size_t)ow * patch + kw];
+        v = images[(((size_t)b * chans + ic) * img_h + (size_t)oh * patch + kh) * img_w + (size_t)ow * patch + kw];
     }
     rows[idx] = v;
 }
@@ -916,11 +917,6 @@ __global__ void pad_rows_kernel(const float *__restrict__ in, float *__restrict_
         return;
     const int r = (int)(idx / Kp), k = (int)(idx - (size_t)r * Kp);
     out[idx] = k < K ? in[(size_t)r * K + k] : 0.0f;
-}
-
-bool patch_direct(int in_chans, int img_size, int patch_size)
-{
-    return patch_size % 4 == 0 && (in_chans * patch_size * patch_size) % BK == 0 && img_size % 4 == 0;
 }
 
 } // namespace
@@ -935,41 +931,44 @@ int vh_cls_rows(hipStream_t st, const float *cls_token, const float *pos_embed, 
     return 0;
 }
 
-extern "C" size_t vh_patch_embed_workspace(int n_images, int in_chans, int img_size, int patch_size, int embed_dim)
+extern "C" size_t vh_patch_embed_workspace_hw(int n_images, int in_chans, int img_h, int img_w, int patch_size, int embed_dim)
 {
-    if (n_images <= 0 || in_chans <= 0 || img_size <= 0 || patch_size <= 0 || embed_dim <= 0 ||
-        img_size % patch_size != 0 || patch_direct(in_chans, img_size, patch_size))
-        return 0;
-    const size_t grid = img_size / patch_size, K = (size_t)in_chans * patch_size * patch_size;
-    const size_t Kp = (K + BK - 1) / BK * BK;
-    return ((size_t)n_images * grid * grid + (size_t)embed_dim) * Kp * sizeof(float);
+    static_assert(VH_PATCH_ROWS_K_STEP == BK, "csrc/patch_geometry.h restates the K step");
+    return vh_patch_rows_workspace_hw(n_images, in_chans, img_h, img_w, patch_size, embed_dim);
 }
 
-extern "C" int vh_launch_patch_embed_ws_math(vh_stream_t s, const float *images, const float *conv_w, const float *conv_b,
+extern "C" size_t vh_patch_embed_workspace(int n_images, int in_chans, int img_size, int patch_size, int embed_dim)
+{
+    return vh_patch_embed_workspace_hw(n_images, in_chans, img_size, img_size, patch_size, embed_dim);
+}
+
+/* The fp32-rows patch embedding of an img_h x img_w image: the row pitch is img_w, a plane img_h * img_w, the patches of an
+ * image row-major in its (img_h / patch) x (img_w / patch) grid.  Every square entry below forwards here. */
+extern "C" int vh_launch_patch_embed_rows_hw(vh_stream_t s, const float *images, const float *conv_w, const float *conv_b,
                                              const float *cls_token, const float *pos_embed, float *tokens, int n_images,
-                                             int in_chans, int img_size, int patch_size, int embed_dim, void *workspace,
+                                             int in_chans, int img_h, int img_w, int patch_size, int embed_dim, void *workspace,
                                              size_t workspace_bytes, int fp32_math)
 {
     if (fp32_math != VH_FP32_SPLIT3 && fp32_math != VH_FP32_NATIVE)
         return vh_fail(1, "vh_launch_patch_embed: unknown fp32_math %d", fp32_math);
     if (!images || !conv_w || !conv_b || !cls_token || !pos_embed || !tokens)
         return vh_fail(1, "vh_launch_patch_embed: null pointer argument");
-    if (n_images <= 0 || in_chans <= 0 || img_size <= 0 || patch_size <= 0 || embed_dim <= 0 ||
-        img_size % patch_size != 0)
+    if (n_images <= 0 || in_chans <= 0 || img_h <= 0 || img_w <= 0 || patch_size <= 0 || embed_dim <= 0 ||
+        img_h % patch_size != 0 || img_w % patch_size != 0)
         return vh_fail(1, "vh_launch_patch_embed: bad geometry");
     const int K = in_chans * patch_size * patch_size;
-    const int grid = img_size / patch_size;
-    const bool direct = patch_direct(in_chans, img_size, patch_size);
-    const size_t need = vh_patch_embed_workspace(n_images, in_chans, img_size, patch_size, embed_dim);
+    const int grid = img_w / patch_size, np = (img_h / patch_size) * grid;
+    const bool direct = vh_patch_direct_hw(in_chans, img_w, patch_size);
+    const size_t need = vh_patch_embed_workspace_hw(n_images, in_chans, img_h, img_w, patch_size, embed_dim);
     if (!direct && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)))
         return vh_fail(1, "vh_launch_patch_embed: patch=%d (K=%d) is not a multiple of 4 / %d: this geometry needs "
                           "vh_launch_patch_embed_ws with %zu bytes of workspace", patch_size, K, BK, need);
 
     GemmParams p = {};
     p.A = images; p.W = conv_w; p.bias = conv_b; p.pos = pos_embed; p.C = tokens;
-    p.M = n_images * grid * grid; p.N = embed_dim; p.K = K;
-    p.img = img_size; p.patch = patch_size; p.chans = in_chans; p.grid = grid;
-    p.tokens = grid * grid + 1;
+    p.M = n_images * np; p.N = embed_dim; p.K = K;
+    p.img_h = img_h; p.img_w = img_w; p.patch = patch_size; p.chans = in_chans; p.grid = grid; p.np = np;
+    p.tokens = np + 1;
     hipStream_t st = (hipStream_t)s;
 
     if (int rc = vh_cls_rows(st, cls_token, pos_embed, tokens, n_images, p.tokens, embed_dim))
@@ -981,13 +980,22 @@ extern "C" int vh_launch_patch_embed_ws_math(vh_stream_t s, const float *images,
     float *rows = static_cast<float *>(workspace), *wpad = rows + (size_t)p.M * Kp;
     const size_t n1 = (size_t)p.M * Kp, n2 = (size_t)embed_dim * Kp;
     hipLaunchKernelGGL(im2row_pad_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, images, rows, p.M,
-                       in_chans, img_size, patch_size, grid, K, Kp);
+                       in_chans, img_h, img_w, patch_size, grid, np, K, Kp);
     VH_LAUNCH_CHECK("im2row_pad_kernel");
     hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, conv_w, wpad,
                        embed_dim, K, Kp);
     VH_LAUNCH_CHECK("pad_rows_kernel");
     p.A = rows; p.W = wpad; p.K = Kp;
     return launch<A_ROWS, EPI_PATCH>(st, p, fp32_math);
+}
+
+extern "C" int vh_launch_patch_embed_ws_math(vh_stream_t s, const float *images, const float *conv_w, const float *conv_b,
+                                             const float *cls_token, const float *pos_embed, float *tokens, int n_images,
+                                             int in_chans, int img_size, int patch_size, int embed_dim, void *workspace,
+                                             size_t workspace_bytes, int fp32_math)
+{
+    return vh_launch_patch_embed_rows_hw(s, images, conv_w, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size,
+                                         img_size, patch_size, embed_dim, workspace, workspace_bytes, fp32_math);
 }
 
 extern "C" int vh_launch_patch_embed_ws(vh_stream_t s, const float *images, const float *conv_w, const float *conv_b,

@@ -949,7 +949,7 @@ namespace {
  * two chunks of a (row, kh) pair up to 64, consecutive patches of an image row to runs of a KiB. */
 template <int NPL>   /* 1: pixels rounded to bf16 (reduced modes); 3: the exact three-part split (the fp32 path) */
 __global__ void im2row_planes_kernel(const float *__restrict__ images, char *__restrict__ planes, int n_rows, int chans,
-                                     int img, int patch, int grid, int K, int Kp)
+                                     int img_h, int img_w, int patch, int grid, int np, int K, int Kp)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)n_rows * (Kp >> 3))
@@ -958,13 +958,13 @@ __global__ void im2row_planes_kernel(const float *__restrict__ images, char *__r
     const size_t rm = i >> 2;
     const int kt = (int)(rm / n_rows), m = (int)(rm - (size_t)kt * n_rows);
     const int k0 = 32 * kt + 8 * c;
-    const int np = grid * grid, b = m / np, pp = m - b * np, oh = pp / grid, ow = pp - oh * grid;
-    const float *base = images + ((size_t)b * chans * img + (size_t)oh * patch) * img + (size_t)ow * patch;
+    const int b = m / np, pp = m - b * np, oh = pp / grid, ow = pp - oh * grid;
+    const float *base = images + ((size_t)b * chans * img_h + (size_t)oh * patch) * img_w + (size_t)ow * patch;
     const int pp2 = patch * patch;
     f32x4 u = {0.0f, 0.0f, 0.0f, 0.0f}, v = u;
-    if ((patch & 7) == 0 && (img & 3) == 0 && k0 + 8 <= K) {
+    if ((patch & 7) == 0 && (img_w & 3) == 0 && k0 + 8 <= K) {
         const int ic = k0 / pp2, rem = k0 - ic * pp2, kh = rem / patch, kw = rem - kh * patch;
-        const float *src = base + ((size_t)ic * img + kh) * img + kw;
+        const float *src = base + ((size_t)ic * img_h + kh) * img_w + kw;
         u = *reinterpret_cast<const f32x4 *>(src);
         v = *reinterpret_cast<const f32x4 *>(src + 4);
     } else {
@@ -974,7 +974,7 @@ __global__ void im2row_planes_kernel(const float *__restrict__ images, char *__r
             float x = 0.0f;
             if (k < K) {
                 const int ic = k / pp2, rem = k - ic * pp2, kh = rem / patch, kw = rem - kh * patch;
-                x = base[((size_t)ic * img + kh) * img + kw];
+                x = base[((size_t)ic * img_h + kh) * img_w + kw];
             }
             if (e < 4)
                 u[e] = x;
@@ -1026,13 +1026,13 @@ __device__ __forceinline__ void hwc_row8(const unsigned char *src, int ic, const
 }
 
 /* im2row_planes_kernel on 8-bit pixels, normalised as they are gathered: the same threads, the same planes.  Images
- * [n][img][img][chans] (HWC) or [n][chans][img][img] (CHW), chans <= 4, base 16-byte aligned.  With patch % 8 == 0 a
+ * [n][img_h][img_w][chans] (HWC) or [n][chans][img_h][img_w] (CHW), chans <= 4, base 16-byte aligned.  With patch % 8 == 0 a
  * lane's eight k lie in one image row of one channel (and the 32 k of a K step in one channel: ic is wave-uniform): one
  * dwordx2 (CHW) or chans dwordx2 (HWC) where the row offsets are multiples of 8 bytes, one byte per k elsewhere (patch 14,
  * K padding). */
 template <int NPL, int LAYOUT>
 __global__ void im2row_planes_u8_kernel(const unsigned char *__restrict__ images, PixelNorm nm, char *__restrict__ planes, int n_rows,
-                                        int chans, int img, int patch, int grid, int K, int Kp)
+                                        int chans, int img_h, int img_w, int patch, int grid, int np, int K, int Kp)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)n_rows * (Kp >> 3))
@@ -1041,21 +1041,21 @@ __global__ void im2row_planes_u8_kernel(const unsigned char *__restrict__ images
     const size_t rm = i >> 2;
     const int kt = (int)(rm / n_rows), m = (int)(rm - (size_t)kt * n_rows);
     const int k0 = 32 * kt + 8 * c;
-    const int np = grid * grid, b = m / np, pp = m - b * np, oh = pp / grid, ow = pp - oh * grid;
+    const int b = m / np, pp = m - b * np, oh = pp / grid, ow = pp - oh * grid;
     const unsigned char *base = LAYOUT == PIXELS_CHW
-                                    ? images + ((size_t)b * chans * img + (size_t)oh * patch) * img + (size_t)ow * patch
-                                    : images + (((size_t)b * img + (size_t)oh * patch) * img + (size_t)ow * patch) * chans;
+                                    ? images + ((size_t)b * chans * img_h + (size_t)oh * patch) * img_w + (size_t)ow * patch
+                                    : images + (((size_t)b * img_h + (size_t)oh * patch) * img_w + (size_t)ow * patch) * chans;
     const int pp2 = patch * patch;
     float x[8];
-    if ((patch & 7) == 0 && k0 + 8 <= K && (LAYOUT == PIXELS_CHW ? (img & 7) == 0 : ((img * chans) & 7) == 0)) {
+    if ((patch & 7) == 0 && k0 + 8 <= K && (LAYOUT == PIXELS_CHW ? (img_w & 7) == 0 : ((img_w * chans) & 7) == 0)) {
         const int ic = k0 / pp2, rem = k0 - ic * pp2, kh = rem / patch, kw = rem - kh * patch;
         if (LAYOUT == PIXELS_CHW) {
-            const uint2 d = *reinterpret_cast<const uint2 *>(base + ((size_t)ic * img + kh) * img + kw);
+            const uint2 d = *reinterpret_cast<const uint2 *>(base + ((size_t)ic * img_h + kh) * img_w + kw);
 #pragma unroll
             for (int e = 0; e < 8; ++e)
                 x[e] = norm_pixel(((e < 4 ? d.x : d.y) >> (8 * (e & 3))) & 255u, ic, nm);
         } else {
-            const unsigned char *src = base + ((size_t)kh * img + kw) * chans;
+            const unsigned char *src = base + ((size_t)kh * img_w + kw) * chans;
             switch (chans) {
             case 1: hwc_row8<1>(src, ic, nm, x); break;
             case 2: hwc_row8<2>(src, ic, nm, x); break;
@@ -1070,7 +1070,7 @@ __global__ void im2row_planes_u8_kernel(const unsigned char *__restrict__ images
             x[e] = 0.0f;
             if (k < K) {
                 const int ic = k / pp2, rem = k - ic * pp2, kh = rem / patch, kw = rem - kh * patch;
-                x[e] = norm_pixel(LAYOUT == PIXELS_CHW ? base[((size_t)ic * img + kh) * img + kw] : base[((size_t)kh * img + kw) * chans + ic],
+                x[e] = norm_pixel(LAYOUT == PIXELS_CHW ? base[((size_t)ic * img_h + kh) * img_w + kw] : base[((size_t)kh * img_w + kw) * chans + ic],
                                   ic, nm);
             }
         }
@@ -1079,11 +1079,11 @@ __global__ void im2row_planes_u8_kernel(const unsigned char *__restrict__ images
     store_parts8<NPL>(planes, (size_t)kt, n_rows, m, c, u, v);
 }
 
-/* 8-bit images -> normalised fp32 [n][chans][img][img], one output value per thread (the fp32-rows paths' input) */
+/* 8-bit images -> normalised fp32 [n][chans][img_h][img_w], one output value per thread (the fp32-rows paths' input) */
 template <int LAYOUT>
-__global__ void expand_u8_kernel(const unsigned char *__restrict__ images, PixelNorm nm, float *__restrict__ out, int n, int chans, int img)
+__global__ void expand_u8_kernel(const unsigned char *__restrict__ images, PixelNorm nm, float *__restrict__ out, int n, int chans, int img_h, int img_w)
 {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, hw = (size_t)img * img, chw = hw * chans;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, hw = (size_t)img_h * img_w, chw = hw * chans;
     if (i >= (size_t)n * chw)
         return;
     const size_t b = i / chw, r = i - b * chw;
@@ -1156,33 +1156,35 @@ struct PixelSrc
 };
 } // namespace
 
-static int launch_im2row_u8(hipStream_t st, const PixelSrc &src, char *planes, int parts, int M, int in_chans, int img_size,
-                            int patch_size, int grid, int K, int Kp)
+static int launch_im2row_u8(hipStream_t st, const PixelSrc &src, char *planes, int parts, int M, int in_chans, int img_h, int img_w,
+                            int patch_size, int grid, int np, int K, int Kp)
 {
     const dim3 blocks((unsigned)(((size_t)M * (Kp / 8) + 255) / 256));
     const bool chw = src.layout == PIXELS_CHW;
-    void (*kernel)(const unsigned char *, PixelNorm, char *, int, int, int, int, int, int, int) =
+    void (*kernel)(const unsigned char *, PixelNorm, char *, int, int, int, int, int, int, int, int, int) =
         parts == 3 ? (chw ? im2row_planes_u8_kernel<3, PIXELS_CHW> : im2row_planes_u8_kernel<3, PIXELS_HWC>)
                    : (chw ? im2row_planes_u8_kernel<1, PIXELS_CHW> : im2row_planes_u8_kernel<1, PIXELS_HWC>);
-    hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, st, src.u8, src.nm, planes, M, in_chans, img_size, patch_size, grid, K, Kp);
+    hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, st, src.u8, src.nm, planes, M, in_chans, img_h, img_w, patch_size, grid, np, K, Kp);
     VH_LAUNCH_CHECK("im2row_planes_u8_kernel");
     return 0;
 }
 
 static int patch_embed_planes(vh_stream_t s, const PixelSrc &src, const void *conv_w_planes, const float *conv_b,
                               const float *cls_token, const float *pos_embed, float *tokens, int n_images, int in_chans,
-                              int img_size, int patch_size, int embed_dim, void *workspace, size_t workspace_bytes,
+                              int img_h, int img_w, int patch_size, int embed_dim, void *workspace, size_t workspace_bytes,
                               void *operand_out, void *operand_scales_out, float *row_stats_out, int parts = 1)
 {
     const void *images = src.u8 ? (const void *)src.u8 : (const void *)src.f32;
     if (!images || !conv_w_planes || !conv_b || !cls_token || !pos_embed || !tokens || !workspace)
         return vh_fail(1, "vh_launch_patch_embed_planes: null pointer argument");
-    if (n_images <= 0 || in_chans <= 0 || img_size <= 0 || patch_size <= 0 || embed_dim <= 0 || img_size % patch_size != 0 ||
-        embed_dim % 128 != 0)
+    if (n_images <= 0 || in_chans <= 0 || img_h <= 0 || img_w <= 0 || patch_size <= 0 || embed_dim <= 0 || img_h % patch_size != 0 ||
+        img_w % patch_size != 0 || embed_dim % 128 != 0)
         return vh_fail(1, "vh_launch_patch_embed_planes: bad geometry (embed_dim %% 128 == 0)");
-    const int grid = img_size / patch_size, K = in_chans * patch_size * patch_size, Kp = vh_patch_planes_k(in_chans, patch_size);
-    const long M = (long)n_images * grid * grid;
-    const long c_rows = (long)n_images * (grid * grid + 1);
+    /* grid: patches per patch row; np: patches per image, row-major in its (img_h / patch) x grid grid */
+    const int grid = img_w / patch_size, np = (img_h / patch_size) * grid, K = in_chans * patch_size * patch_size;
+    const int Kp = vh_patch_planes_k(in_chans, patch_size);
+    const long M = (long)n_images * np;
+    const long c_rows = (long)n_images * (np + 1);
     if ((parts != 1 && parts != 3) || (parts == 3 && operand_scales_out))
         return vh_fail(1, "vh_launch_patch_embed_planes: parts must be 1 (bf16 operands) or 3 (exact fp32 split: planes operand only)");
     if (c_rows * 128 > 0xffffffffl || workspace_bytes < (size_t)M * Kp * 2 * parts ||
@@ -1196,25 +1198,25 @@ static int patch_embed_planes(vh_stream_t s, const PixelSrc &src, const void *co
         if (parts == 3)
             hipLaunchKernelGGL(cls_rows_operand_kernel<3>, dim3((n_images + 15) / 16, embed_dim / 128), dim3(64), 0, st, cls_token, pos_embed,
                                tokens, static_cast<char *>(operand_out), static_cast<unsigned char *>(operand_scales_out), row_stats_out,
-                               n_images, grid * grid + 1, embed_dim, (int)c_rows);
+                               n_images, np + 1, embed_dim, (int)c_rows);
         else
             hipLaunchKernelGGL(cls_rows_operand_kernel<1>, dim3((n_images + 15) / 16, embed_dim / 128), dim3(64), 0, st, cls_token, pos_embed,
                                tokens, static_cast<char *>(operand_out), static_cast<unsigned char *>(operand_scales_out), row_stats_out,
-                               n_images, grid * grid + 1, embed_dim, (int)c_rows);
+                               n_images, np + 1, embed_dim, (int)c_rows);
         VH_LAUNCH_CHECK("cls_rows_operand_kernel");
-    } else if (int rc = vh_cls_rows(st, cls_token, pos_embed, tokens, n_images, grid * grid + 1, embed_dim))
+    } else if (int rc = vh_cls_rows(st, cls_token, pos_embed, tokens, n_images, np + 1, embed_dim))
         return rc;
     const size_t threads = (size_t)M * (Kp / 8);
     if (src.u8) {
-        if (int rc = launch_im2row_u8(st, src, static_cast<char *>(workspace), parts, (int)M, in_chans, img_size, patch_size, grid, K, Kp))
+        if (int rc = launch_im2row_u8(st, src, static_cast<char *>(workspace), parts, (int)M, in_chans, img_h, img_w, patch_size, grid, np, K, Kp))
             return rc;
     } else {
         if (parts == 3)
             hipLaunchKernelGGL(im2row_planes_kernel<3>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, src.f32,
-                               static_cast<char *>(workspace), (int)M, in_chans, img_size, patch_size, grid, K, Kp);
+                               static_cast<char *>(workspace), (int)M, in_chans, img_h, img_w, patch_size, grid, np, K, Kp);
         else
             hipLaunchKernelGGL(im2row_planes_kernel<1>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, src.f32,
-                               static_cast<char *>(workspace), (int)M, in_chans, img_size, patch_size, grid, K, Kp);
+                               static_cast<char *>(workspace), (int)M, in_chans, img_h, img_w, patch_size, grid, np, K, Kp);
         VH_LAUNCH_CHECK("im2row_planes_kernel");
     }
     P3Params p = {};
@@ -1223,7 +1225,7 @@ static int patch_embed_planes(vh_stream_t s, const PixelSrc &src, const void *co
     p.bias = conv_b; p.C = tokens; p.pos = pos_embed;
     p.row_begin = 0; p.row_end = (int)M; p.a_rows = (int)M; p.c_rows = (int)c_rows;
     p.N = embed_dim; p.K = Kp;
-    p.np = grid * grid; p.tokens = grid * grid + 1;
+    p.np = np; p.tokens = np + 1;
     p.oper = operand_out; p.oper_scales = operand_scales_out; p.stats_out = row_stats_out;
     const int small_only = Kp < 2048;   /* the shape of the output projection: small tiles (measured there) */
     if (parts == 3)
@@ -1238,7 +1240,7 @@ extern "C" int vh_launch_patch_embed_planes(vh_stream_t s, const float *images, 
                                             int in_chans, int img_size, int patch_size, int embed_dim, void *workspace,
                                             size_t workspace_bytes)
 {
-    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, nullptr, nullptr, nullptr);
 }
 
@@ -1250,7 +1252,7 @@ extern "C" int vh_launch_patch_embed_planes3(vh_stream_t s, const float *images,
                                              int in_chans, int img_size, int patch_size, int embed_dim, void *workspace,
                                              size_t workspace_bytes)
 {
-    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes3, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes3, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, nullptr, nullptr, nullptr, 3);
 }
 
@@ -1262,7 +1264,7 @@ extern "C" int vh_launch_patch_embed_planes3_norm(vh_stream_t s, const float *im
 {
     if (!operand_planes3_out || !row_stats_out)
         return vh_fail(1, "vh_launch_patch_embed_planes3_norm: null pointer argument");
-    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes3, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes3, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, operand_planes3_out, nullptr, row_stats_out, 3);
 }
 
@@ -1277,7 +1279,7 @@ extern "C" int vh_launch_patch_embed_planes_norm(vh_stream_t s, const float *ima
 {
     if (!operand_out || !row_stats_out)
         return vh_fail(1, "vh_launch_patch_embed_planes_norm: null pointer argument");
-    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, PixelSrc{images, nullptr, 0, {}}, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, operand_out, operand_scales_out, row_stats_out);
 }
 
@@ -1315,23 +1317,50 @@ extern "C" int vh_launch_patch_embed_planes_u8(vh_stream_t s, const unsigned cha
         return rc;
     if ((operand_out != nullptr) != (row_stats_out != nullptr))
         return vh_fail(1, "vh_launch_patch_embed_planes_u8: operand and row statistics go together");
-    return patch_embed_planes(s, src, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, patch_size,
+    return patch_embed_planes(s, src, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_size, img_size, patch_size,
                               embed_dim, workspace, workspace_bytes, operand_out, operand_scales_out, row_stats_out, parts);
+}
+
+/* Every planes variant on an img_h x img_w image: fp32 pixels (images_f32) or 8-bit ones (images_u8 in `layout` with scale and
+ * bias), exactly one of the two; parts, operand_out, operand_scales_out and row_stats_out as vh_launch_patch_embed_planes_u8 */
+extern "C" int vh_launch_patch_embed_planes_hw(vh_stream_t s, const float *images_f32, const unsigned char *images_u8, int layout,
+                                               const float *scale, const float *bias, const void *conv_w_planes, const float *conv_b,
+                                               const float *cls_token, const float *pos_embed, float *tokens, int n_images, int in_chans,
+                                               int img_h, int img_w, int patch_size, int embed_dim, void *workspace,
+                                               size_t workspace_bytes, int parts, void *operand_out, void *operand_scales_out,
+                                               float *row_stats_out)
+{
+    PixelSrc src = {images_f32, nullptr, 0, {}};
+    if ((images_f32 != nullptr) == (images_u8 != nullptr))
+        return vh_fail(1, "vh_launch_patch_embed_planes_hw: exactly one of the fp32 and the 8-bit images");
+    if (images_u8)
+        if (int rc = pixel_source("vh_launch_patch_embed_planes_hw", images_u8, layout, scale, bias, in_chans, &src))
+            return rc;
+    if ((operand_out != nullptr) != (row_stats_out != nullptr))
+        return vh_fail(1, "vh_launch_patch_embed_planes_hw: operand and row statistics go together");
+    return patch_embed_planes(s, src, conv_w_planes, conv_b, cls_token, pos_embed, tokens, n_images, in_chans, img_h, img_w, patch_size,
+                              embed_dim, workspace, workspace_bytes, operand_out, operand_scales_out, row_stats_out, parts);
+}
+
+extern "C" int vh_launch_expand_u8_hw(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias,
+                                      float *out, int n_images, int in_chans, int img_h, int img_w)
+{
+    PixelSrc src;
+    if (int rc = pixel_source("vh_launch_expand_u8", images, layout, scale, bias, in_chans, &src))
+        return rc;
+    if (!out || n_images <= 0 || img_h <= 0 || img_w <= 0)
+        return vh_fail(1, "vh_launch_expand_u8: bad argument");
+    const size_t total = (size_t)n_images * in_chans * img_h * img_w;
+    const dim3 blocks((unsigned)((total + 255) / 256));
+    void (*kernel)(const unsigned char *, PixelNorm, float *, int, int, int, int) =
+        layout == PIXELS_CHW ? expand_u8_kernel<PIXELS_CHW> : expand_u8_kernel<PIXELS_HWC>;
+    hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, (hipStream_t)s, images, src.nm, out, n_images, in_chans, img_h, img_w);
+    VH_LAUNCH_CHECK("expand_u8_kernel");
+    return 0;
 }
 
 extern "C" int vh_launch_expand_u8(vh_stream_t s, const unsigned char *images, int layout, const float *scale, const float *bias,
                                    float *out, int n_images, int in_chans, int img_size)
 {
-    PixelSrc src;
-    if (int rc = pixel_source("vh_launch_expand_u8", images, layout, scale, bias, in_chans, &src))
-        return rc;
-    if (!out || n_images <= 0 || img_size <= 0)
-        return vh_fail(1, "vh_launch_expand_u8: bad argument");
-    const size_t total = (size_t)n_images * in_chans * img_size * img_size;
-    const dim3 blocks((unsigned)((total + 255) / 256));
-    void (*kernel)(const unsigned char *, PixelNorm, float *, int, int, int) =
-        layout == PIXELS_CHW ? expand_u8_kernel<PIXELS_CHW> : expand_u8_kernel<PIXELS_HWC>;
-    hipLaunchKernelGGL(kernel, blocks, dim3(256), 0, (hipStream_t)s, images, src.nm, out, n_images, in_chans, img_size);
-    VH_LAUNCH_CHECK("expand_u8_kernel");
-    return 0;
+    return vh_launch_expand_u8_hw(s, images, layout, scale, bias, out, n_images, in_chans, img_size, img_size);
 }

@@ -16,6 +16,7 @@ int vit_config_preset(vit_config *cfg, const char *name)
     if (!cfg || !name)
         return -1;
     cfg->img_size = 224;
+    cfg->img_width = 0;
     cfg->in_chans = 3;
     cfg->num_classes = 1000;
     cfg->eps = 1e-6;
@@ -45,10 +46,23 @@ int vit_config_preset(vit_config *cfg, const char *name)
     return 0;
 }
 
+int vit_config_sizeof(void) { return (int)sizeof(vit_config); }
+
+static int width_of(const vit_config *cfg) { return cfg->img_width ? cfg->img_width : cfg->img_size; }
+
+void vit_config_grid(const vit_config *cfg, int *grid_h, int *grid_w)
+{
+    if (grid_h)
+        *grid_h = cfg->img_size / cfg->patch_size;
+    if (grid_w)
+        *grid_w = width_of(cfg) / cfg->patch_size;
+}
+
 int vit_config_tokens(const vit_config *cfg)
 {
-    int g = cfg->img_size / cfg->patch_size;
-    return g * g + 1;
+    int gh, gw;
+    vit_config_grid(cfg, &gh, &gw);
+    return gh * gw + 1;
 }
 
 int vit_config_num_tensors(const vit_config *cfg)
@@ -94,36 +108,117 @@ extern int vh_set_error(int code, const char *message) __attribute__((weak));
 
 static int resample_refuse(const char *fmt, int a, int b)
 {
-    char msg[192];
+    char msg[256];
     snprintf(msg, sizeof msg, fmt, a, b);
     return vh_set_error ? vh_set_error(1, msg) : 1;
 }
 
-/* The argument checks of vit_hip_create_at_resolution that need no context: the target config of a source config at
- * another img_size, and the resampling of its position grid (vh_launch_resample_pos_embed's limits). */
-int vit_resample_check(const vit_config *src, int img_size, const vit_pos_resample *how, vit_config *out_cfg)
+/* The one form of a config inside the library: every byte of *out written (the padding zero, so two equal configs compare
+ * equal as memory), img_width == img_size stored as 0.  out may be in. */
+static void canonical(vit_config *out, const vit_config *in)
+{
+    const vit_config c = *in;
+    memset(out, 0, sizeof *out);
+    out->img_size = c.img_size; out->patch_size = c.patch_size; out->in_chans = c.in_chans; out->num_classes = c.num_classes;
+    out->embed_dim = c.embed_dim; out->depth = c.depth; out->num_heads = c.num_heads; out->mlp_hidden = c.mlp_hidden;
+    out->eps = c.eps;
+    out->img_width = c.img_width == c.img_size ? 0 : c.img_width;
+}
+
+int vit_config_canonical(const vit_config *cfg, vit_config *out, const char *who)
+{
+    enum { MAX_GRID = 512, MAX_SIDE = 4096 };
+    char fmt[256];
+    if (!who)
+        who = "vit_config_canonical";
+    if (!cfg || !out) {
+        snprintf(fmt, sizeof fmt, "%s: null argument (cfg, out)", who);
+        return resample_refuse(fmt, 0, 0);
+    }
+    vit_config c;
+    canonical(&c, cfg);
+    if (c.img_width != 0) {   /* a square config is refused where it always was (plan_make) */
+        if (c.patch_size <= 0 || c.img_width < 0 || c.img_width % c.patch_size != 0) {
+            snprintf(fmt, sizeof fmt, "%s: img_width=%%d must be a positive multiple of patch_size=%%d (0: img_size)", who);
+            return resample_refuse(fmt, c.img_width, c.patch_size);
+        }
+        if (c.img_width > MAX_SIDE) {
+            snprintf(fmt, sizeof fmt, "%s: img_width=%%d is above %%d", who);
+            return resample_refuse(fmt, c.img_width, MAX_SIDE);
+        }
+        if (c.img_width / c.patch_size > MAX_GRID || c.img_size / c.patch_size > MAX_GRID) {
+            snprintf(fmt, sizeof fmt, "%s: img_size=%%d by img_width=%%d: a side of the patch grid is above 512", who);
+            return resample_refuse(fmt, c.img_size, c.img_width);
+        }
+    }
+    *out = c;
+    return 0;
+}
+
+/* The argument checks of vit_hip_create_at_size that need no context: the target config of a source config at another
+ * img_height x img_width, and the resampling of its position grid (vh_launch_resample_pos_embed's limits).  `who` and
+ * `what` word the messages: vit_resample_check keeps the text it has always had. */
+static int resample_side_check(const char *who, const char *what, const vit_config *src, int side)
 {
     enum { MAX_GRID = 512 };
-    if (!src || !out_cfg)
-        return resample_refuse("vit_resample_check: null argument (src, out_cfg)", 0, 0);
-    if (src->patch_size <= 0 || src->img_size <= 0 || src->img_size % src->patch_size != 0 ||
-        src->img_size / src->patch_size > MAX_GRID)
-        return resample_refuse("vit_resample_check: the source's img_size=%d must be a positive multiple of its patch_size=%d, "
-                               "at most 512 patches a side", src->img_size, src->patch_size);
-    if (img_size <= 0 || img_size % src->patch_size != 0)
-        return resample_refuse("vit_resample_check: img_size=%d must be a positive multiple of patch_size=%d", img_size,
-                               src->patch_size);
-    if (img_size / src->patch_size > MAX_GRID)
-        return resample_refuse("vit_resample_check: img_size=%d gives %d patches a side, the position grid takes at most 512",
-                               img_size, img_size / src->patch_size);
-    if (how && how->mode != VIT_POS_BICUBIC && how->mode != VIT_POS_BILINEAR)
-        return resample_refuse("vit_resample_check: mode=%d must be VIT_POS_BICUBIC (%d) or VIT_POS_BILINEAR (1)", how->mode,
-                               VIT_POS_BICUBIC);
-    if (how && how->align_corners != 0 && how->align_corners != 1)
-        return resample_refuse("vit_resample_check: align_corners=%d must be %d or 1", how->align_corners, 0);
-    *out_cfg = *src;
-    out_cfg->img_size = img_size;
+    char fmt[256];
+    if (side <= 0 || side % src->patch_size != 0) {
+        snprintf(fmt, sizeof fmt, "%s: %s=%%d must be a positive multiple of patch_size=%%d", who, what);
+        return resample_refuse(fmt, side, src->patch_size);
+    }
+    if (side / src->patch_size > MAX_GRID) {
+        snprintf(fmt, sizeof fmt, "%s: %s=%%d gives %%d patches a side, the position grid takes at most 512", who, what);
+        return resample_refuse(fmt, side, side / src->patch_size);
+    }
     return 0;
+}
+
+static int resample_check_hw(const char *who, const char *h_name, const char *w_name, const vit_config *src, int img_height,
+                             int img_width, const vit_pos_resample *how, vit_config *out_cfg)
+{
+    enum { MAX_GRID = 512 };
+    char fmt[256];
+    if (!src || !out_cfg) {
+        snprintf(fmt, sizeof fmt, "%s: null argument (src, out_cfg)", who);
+        return resample_refuse(fmt, 0, 0);
+    }
+    const int src_w = src->img_width ? src->img_width : src->img_size;
+    if (src->patch_size <= 0 || src->img_size <= 0 || src->img_size % src->patch_size != 0 ||
+        src->img_size / src->patch_size > MAX_GRID) {
+        snprintf(fmt, sizeof fmt, "%s: the source's img_size=%%d must be a positive multiple of its patch_size=%%d, "
+                                  "at most 512 patches a side", who);
+        return resample_refuse(fmt, src->img_size, src->patch_size);
+    }
+    if (src_w <= 0 || src_w % src->patch_size != 0 || src_w / src->patch_size > MAX_GRID) {
+        snprintf(fmt, sizeof fmt, "%s: the source's img_width=%%d must be a positive multiple of its patch_size=%%d, "
+                                  "at most 512 patches a side", who);
+        return resample_refuse(fmt, src_w, src->patch_size);
+    }
+    if (resample_side_check(who, h_name, src, img_height) || resample_side_check(who, w_name, src, img_width))
+        return 1;
+    if (how && how->mode != VIT_POS_BICUBIC && how->mode != VIT_POS_BILINEAR) {
+        snprintf(fmt, sizeof fmt, "%s: mode=%%d must be VIT_POS_BICUBIC (%%d) or VIT_POS_BILINEAR (1)", who);
+        return resample_refuse(fmt, how->mode, VIT_POS_BICUBIC);
+    }
+    if (how && how->align_corners != 0 && how->align_corners != 1) {
+        snprintf(fmt, sizeof fmt, "%s: align_corners=%%d must be %%d or 1", who);
+        return resample_refuse(fmt, how->align_corners, 0);
+    }
+    vit_config c = *src;
+    c.img_size = img_height;
+    c.img_width = img_width;
+    canonical(out_cfg, &c);
+    return 0;
+}
+
+int vit_resample_check_hw(const vit_config *src, int img_height, int img_width, const vit_pos_resample *how, vit_config *out_cfg)
+{
+    return resample_check_hw("vit_resample_check_hw", "img_height", "img_width", src, img_height, img_width, how, out_cfg);
+}
+
+int vit_resample_check(const vit_config *src, int img_size, const vit_pos_resample *how, vit_config *out_cfg)
+{
+    return resample_check_hw("vit_resample_check", "img_size", "img_size", src, img_size, img_size, how, out_cfg);
 }
 
 /* splitmix64 finaliser used as a counter-based generator: value i of stream
@@ -184,6 +279,6 @@ void vit_synth_tensor(const vit_config *cfg, int idx, unsigned long long seed_ba
 
 void vit_synth_image(const vit_config *cfg, int image_index, float *dst)
 {
-    const size_t n = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
+    const size_t n = (size_t)cfg->in_chans * cfg->img_size * width_of(cfg);
     vit_synth_fill(dst, n, 1000ull + (unsigned long long)image_index, 2.0f, 0.0f);
 }

@@ -207,11 +207,13 @@ int ingest_check(const char *who, const struct ingest_model *model, const struct
     const int null = !model || !pixels || (kind == INGEST_U8_RESIZED && !src->rc) || (kind == INGEST_U8_BOXES && !src->boxes) ||
                      (src->crops_only ? !src->crops : !src->norm);
     const int filter = null || !sized ? 0 : ingest_filter(src);
-    /* One chain in the order every form had.  The u8 forms: NULL, n, max_batch (device), layout, channels, alignment (device).
+    /* One chain in the order every form had (a non-square model refuses the sized kinds first: their crops are square).  The u8 forms: NULL, n, max_batch (device), layout, channels, alignment (device).
      * The resized forms: NULL, n, max_batch (device), layout, filter, channels, crop row, resize_short.  The box forms: NULL,
      * n, n_images, max_batch (device), layout, filter, channels, crop row.  An arm that is not a form's own is guarded by
      * `sized` (resized and boxes) or by the kind, so it cannot fire for another form. */
     const char *why = null                                                                     ? (sized ? "NULL argument" : "NULL context, images or norm")
+                      : sized && model->img_width != 0
+                          ? "the context's input is non-square: the resize and box forms make square crops"
                       : n <= 0                                                                 ? "n must be positive"
                       : kind == INGEST_U8_BOXES && src->n_images <= 0                          ? "n_images must be positive"
                       : !host && n > model->max_batch                                          ? "n exceeds the context's max_batch"

@@ -58,6 +58,8 @@ struct ingest_src
 struct ingest_model
 {
     int max_batch, in_chans, img_size;
+    int img_width;                   /* 0: square.  Otherwise img_size rows by img_width columns: the resized and the box kinds,
+                                      * whose crops are img_size x img_size, are refused */
     size_t slot_bytes;               /* of one staging slot: what a chunk of a host form may pack */
 };
 

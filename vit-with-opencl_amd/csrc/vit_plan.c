@@ -5,6 +5,7 @@
  */
 #include "vit_plan.h"
 #include "vit_ingest.h"
+#include "patch_geometry.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -87,8 +88,9 @@ void plan_layout(const struct vit_plan *plan, const vit_config *cfg, void *const
 static void plan_arena(struct vit_plan *plan, const vit_config *cfg, int max_batch)
 {
     const size_t E = (size_t)cfg->embed_dim, F = (size_t)cfg->mlp_hidden, act = (size_t)plan->act_bytes, n = (size_t)max_batch;
-    const size_t rows = n * (size_t)plan->tokens, grid = (size_t)(cfg->img_size / cfg->patch_size);
-    const size_t img = (size_t)cfg->in_chans * cfg->img_size * cfg->img_size;
+    const size_t rows = n * (size_t)plan->tokens, patches = (size_t)plan->tokens - 1;
+    const int width = cfg->img_width ? cfg->img_width : cfg->img_size;
+    const size_t img = (size_t)cfg->in_chans * cfg->img_size * width;
     const int fp8 = plan->precision == VIT_PRECISION_FP8_GEMM, resizes = cfg->in_chans <= 4;
     const int planes_path = plan->use_p3 || plan->precision == VIT_PRECISION_BF16_GEMM || fp8;
     size_t b;
@@ -119,10 +121,13 @@ static void plan_arena(struct vit_plan *plan, const vit_config *cfg, int max_bat
         plan->hid_scales_off = align_up(rows * F, 256);
         b = max_of(b, plan->hid_scales_off + vh_mx_act_scale_bytes((int)rows, cfg->mlp_hidden));
     }
-    /* the gathered patch rows of geometries such as H/14 */
-    b = max_of(b, vh_patch_embed_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->patch_size, cfg->embed_dim));
+    /* the gathered patch rows of geometries such as H/14: a square input through the shim's own sizing function, a
+     * rectangle through the arithmetic both share (csrc/patch_geometry.h) */
+    b = max_of(b, width == cfg->img_size
+                      ? vh_patch_embed_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->patch_size, cfg->embed_dim)
+                      : vh_patch_rows_workspace_hw(max_batch, cfg->in_chans, cfg->img_size, width, cfg->patch_size, cfg->embed_dim));
     /* the im2row producer's planes: patches x Kp x 2 bytes x parts (a small MLP can be smaller than that) */
-    b = max_of(b, n * grid * grid * (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * 2 * (size_t)plan->conv_parts);
+    b = max_of(b, n * patches * (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * 2 * (size_t)plan->conv_parts);
     if (resizes)
         b = max_of(b, n * ingest_max_table_bytes(cfg->img_size));   /* the resize's coefficient tables at the steepest downscale */
     if (planes_path && (plan->attn_form == ATTN_STREAMING || plan->attn_form == ATTN_LONG))
@@ -157,6 +162,9 @@ int plan_make(struct vit_plan *plan, const vit_config *cfg, int n_tensors, int m
     if (n_tensors != vit_config_num_tensors(cfg))
         return 2;
     if (cfg->embed_dim % cfg->num_heads != 0 || cfg->img_size % cfg->patch_size != 0)
+        return 2;
+    /* img_width: 0 or img_size is the square input; vit_config_canonical words the refusals of another width for the callers */
+    if (cfg->img_width < 0 || cfg->img_width > 4096 || cfg->img_width % cfg->patch_size != 0)
         return 2;
 
     const int E = cfg->embed_dim, F = cfg->mlp_hidden, H = cfg->num_heads, T = vit_config_tokens(cfg);

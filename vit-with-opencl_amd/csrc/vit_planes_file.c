@@ -152,8 +152,11 @@ int planes_file_open(struct planes_file *pf, const char *path, int max_batch)
         rc = vh_set_error(124, "vit_hip_create_from_planes: not a planes file of this library version (magic, header size or operand-layout version)");
         goto fail;
     }
-    pf->cfg = (vit_config){h.cfg_ints[0], h.cfg_ints[1], h.cfg_ints[2], h.cfg_ints[3], h.cfg_ints[4], h.cfg_ints[5], h.cfg_ints[6],
-                           h.cfg_ints[7], h.eps};
+    /* the header holds one image side: a file's context is square (img_width 0), every byte of the config written */
+    const vit_config from_header = {h.cfg_ints[0], h.cfg_ints[1], h.cfg_ints[2], h.cfg_ints[3], h.cfg_ints[4], h.cfg_ints[5], h.cfg_ints[6],
+                                    h.cfg_ints[7], h.eps, 0};
+    memset(&pf->cfg, 0, sizeof pf->cfg);
+    (void)vit_config_canonical(&from_header, &pf->cfg, NULL);   /* a square config is never refused there: plan_make judges it */
     pf->n_tensors = h.n_tensors;
     /* plan_make bounds every dimension and checks the fold flag (n_tensors is tied to depth) */
     plan_env_read(&env);

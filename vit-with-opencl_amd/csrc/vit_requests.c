@@ -398,38 +398,43 @@ int requests_set_gallery(const char *who, const struct request_model *m, struct 
 }
 
 /* spec against cfg, pointers aside; tap resolved to a layer index, the grid, the output size */
-static int dense_spec_check(const char *who, const vit_config *cfg, const vit_dense_spec *spec, int *layer, int *grid, int *out_h, int *out_w)
+static int dense_spec_check(const char *who, const vit_config *cfg, const vit_dense_spec *spec, int *layer, int *grid_h, int *grid_w,
+                            int *out_h, int *out_w)
 {
-    const int g = cfg && cfg->patch_size > 0 ? cfg->img_size / cfg->patch_size : 0;
+    int gh = 0, gw = 0;
+    if (cfg && cfg->patch_size > 0)
+        vit_config_grid(cfg, &gh, &gw);
+    const int width = cfg ? gw * cfg->patch_size : 0;
     const char *why = !cfg || !spec ? "NULL argument"
                       : cfg->depth <= 0 || cfg->embed_dim <= 0 || cfg->patch_size <= 0 || cfg->img_size < cfg->patch_size ? "bad model config"
                       : spec->tap < -cfg->depth || spec->tap >= cfg->depth ? "tap lies outside [-depth, depth)"
-                      : vit_config_tokens(cfg) < 2 || vit_config_tokens(cfg) - 1 != g * g ? "the model needs a square grid of at least one patch token"
-                      : g > VH_DENSE_MAX_GRID ? "the patch grid must be at most 64 x 64"
+                      : vit_config_tokens(cfg) < 2 ? "the model needs a grid of at least one patch token"
+                      : gh > VH_DENSE_MAX_GRID || gw > VH_DENSE_MAX_GRID ? "the patch grid must be at most 64 x 64"
                       : cfg->embed_dim % 4 != 0 || cfg->embed_dim > 2048 ? "embed_dim must be a multiple of 4, at most 2048"
                       : spec->n_labels < 2 || spec->n_labels > VH_DENSE_MAX_LABELS ? "n_labels must be in 2..256"
                       : spec->out_h < 0 || spec->out_h > 4096 || spec->out_w < 0 || spec->out_w > 4096 ||
-                        (spec->out_h == 0 && cfg->img_size > 4096) || (spec->out_w == 0 && cfg->img_size > 4096)
-                          ? "out_h and out_w must be in 1..4096 (0: the model's img_size)"
+                        (spec->out_h == 0 && cfg->img_size > 4096) || (spec->out_w == 0 && width > 4096)
+                          ? "out_h and out_w must be in 1..4096 (0: the model's img_size and width)"
                       : spec->weight_stride < cfg->embed_dim || spec->weight_stride > (1L << 40) || spec->weight_stride % 4 != 0
                           ? "weight_stride must be at least embed_dim, and a multiple of 4"
                       : NULL;
     if (why)
         return ingest_refuse(who, why);
     *layer = spec->tap < 0 ? spec->tap + cfg->depth : spec->tap;
-    *grid = g;
+    *grid_h = gh;
+    *grid_w = gw;
     *out_h = spec->out_h ? spec->out_h : cfg->img_size;
-    *out_w = spec->out_w ? spec->out_w : cfg->img_size;
+    *out_w = spec->out_w ? spec->out_w : width;
     return 0;
 }
 
 int vit_dense_sizes(const vit_config *cfg, const vit_dense_spec *spec, size_t *labels_bytes, size_t *scores_elems,
                     size_t *patch_logits_elems, size_t *scratch_bytes_per_image)
 {
-    int layer, grid, out_h, out_w;
-    if (dense_spec_check("vit_dense_sizes", cfg, spec, &layer, &grid, &out_h, &out_w))
+    int layer, grid_h, grid_w, out_h, out_w;
+    if (dense_spec_check("vit_dense_sizes", cfg, spec, &layer, &grid_h, &grid_w, &out_h, &out_w))
         return 1;
-    const size_t P = (size_t)grid * grid;
+    const size_t P = (size_t)grid_h * grid_w;
     if (labels_bytes)
         *labels_bytes = (size_t)out_h * out_w;
     if (scores_elems)
@@ -449,7 +454,7 @@ int requests_set_dense(const char *who, const struct request_model *m, struct re
     char oom[160] = "";
     memset(&de, 0, sizeof de);
     if (spec) {
-        if (dense_spec_check(who, m->cfg, spec, &de.layer, &de.grid, &de.out_h, &de.out_w))
+        if (dense_spec_check(who, m->cfg, spec, &de.layer, &de.grid_h, &de.grid_w, &de.out_h, &de.out_w))
             return 1;
         const char *why = !spec->d_weight ? "no head weight"
                           : ((uintptr_t)spec->d_weight | (uintptr_t)spec->d_bias) & 15 ? "the head's weight and bias must be 16-byte aligned"

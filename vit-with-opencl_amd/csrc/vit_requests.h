@@ -97,8 +97,8 @@ struct dense_req
     struct request head;         /* st: labels, none; scratch: [0] the patch logits, when the caller gives no buffer, [1] the
                                   * normalised tokens, when final_norm is set and the MLP buffer does not hold them */
     vit_dense_spec spec;
-    int layer, grid;             /* spec.tap resolved; img_size / patch_size */
-    int out_h, out_w;            /* spec's, 0 resolved to img_size */
+    int layer, grid_h, grid_w;   /* spec.tap resolved; the patch grid (vit_config_grid) */
+    int out_h, out_w;            /* spec's, 0 resolved to img_size and to the width */
     vit_dense_buffers out;       /* FEAT_HOST: labels = st[0].dev */
 };
 

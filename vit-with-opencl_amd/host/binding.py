@@ -75,6 +75,8 @@ EXPORTS = [
     "vit_hip_set_gallery", "vit_hip_set_gallery_host",
     "vh_launch_dense_logits", "vh_launch_dense_labels", "vit_dense_sizes", "vit_hip_set_dense", "vit_hip_set_dense_host",
     "vh_launch_resample_pos_embed", "vit_resample_check", "vit_hip_create_at_resolution",
+    "vit_config_canonical", "vit_config_grid", "vit_config_sizeof", "vit_resample_check_hw", "vit_hip_create_at_size",
+    "vh_launch_patch_embed_planes_hw", "vh_patch_embed_workspace_hw", "vh_launch_patch_embed_rows_hw", "vh_launch_expand_u8_hw",
 ]
 
 # include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
@@ -91,7 +93,25 @@ class VitConfig(C.Structure):
         ("img_size", C.c_int), ("patch_size", C.c_int), ("in_chans", C.c_int),
         ("num_classes", C.c_int), ("embed_dim", C.c_int), ("depth", C.c_int),
         ("num_heads", C.c_int), ("mlp_hidden", C.c_int), ("eps", C.c_double),
+        ("img_width", C.c_int),   # 0: img_size (square); otherwise the input is img_size rows by img_width columns
     ]
+
+    @property
+    def width(self) -> int:
+        """columns of an input image (its rows are img_size)"""
+        return self.img_width or self.img_size
+
+    @property
+    def grid(self) -> tuple:
+        """(gh, gw): the patch grid, row-major (vit_config_grid)"""
+        gh, gw = C.c_int(), C.c_int()
+        lib().vit_config_grid(C.byref(self), C.byref(gh), C.byref(gw))
+        return gh.value, gw.value
+
+    def image_shape(self, n: int, layout: str = "chw") -> tuple:
+        """the shape of n input images: [n][C][H][W] (fp32, and bytes in layout "chw") or [n][H][W][C] (bytes, "hwc")"""
+        h, w, ch = self.img_size, self.width, self.in_chans
+        return (n, h, w, ch) if layout == "hwc" else (n, ch, h, w)
 
 
 class PixelNorm(C.Structure):
@@ -348,10 +368,22 @@ def _pos_mode(mode) -> int:
     return POS_MODES[mode] if isinstance(mode, str) else int(mode)
 
 
-def resample_check(cfg: "VitConfig", img_size: int, mode="bicubic", align_corners=False) -> "VitConfig":
-    """vit_resample_check -> cfg at img_size; raises VitHipError with the library's message"""
+def resample_check(cfg: "VitConfig", img_size, mode="bicubic", align_corners=False) -> "VitConfig":
+    """vit_resample_check -> cfg at img_size, or with img_size a (height, width) pair vit_resample_check_hw -> cfg at that
+    size; raises VitHipError with the library's message"""
     how, out = PosResampleC(_pos_mode(mode), int(align_corners)), VitConfig()
-    check(lib().vit_resample_check(C.byref(cfg), int(img_size), C.byref(how), C.byref(out)), "vit_resample_check")
+    if isinstance(img_size, (tuple, list)):
+        h, w = img_size
+        check(lib().vit_resample_check_hw(C.byref(cfg), int(h), int(w), C.byref(how), C.byref(out)), "vit_resample_check_hw")
+    else:
+        check(lib().vit_resample_check(C.byref(cfg), int(img_size), C.byref(how), C.byref(out)), "vit_resample_check")
+    return out
+
+
+def canonical_config(cfg: "VitConfig") -> "VitConfig":
+    """vit_config_canonical: cfg as the library stores it (img_width == img_size as 0); raises VitHipError for a bad width"""
+    out = VitConfig()
+    check(lib().vit_config_canonical(C.byref(cfg), C.byref(out), None), "vit_config_canonical")
     return out
 
 
@@ -730,6 +762,17 @@ def lib() -> C.CDLL:
     L.vh_launch_resample_pos_embed.argtypes = [voidp, voidp, voidp] + [i] * 8
     L.vit_resample_check.argtypes = [C.POINTER(VitConfig), i, prp, C.POINTER(VitConfig)]
     L.vit_hip_create_at_resolution.argtypes = [C.POINTER(voidp), voidp, i, i, prp]
+    L.vit_resample_check_hw.argtypes = [C.POINTER(VitConfig), i, i, prp, C.POINTER(VitConfig)]
+    L.vit_hip_create_at_size.argtypes = [C.POINTER(voidp), voidp, i, i, i, prp]
+    L.vit_config_canonical.argtypes = [C.POINTER(VitConfig), C.POINTER(VitConfig), C.c_char_p]
+    L.vit_config_grid.argtypes = [C.POINTER(VitConfig), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.vit_config_grid.restype = None
+    L.vit_config_sizeof.argtypes = []
+    L.vh_launch_patch_embed_planes_hw.argtypes = [voidp, voidp, voidp, i, f32p, f32p] + [voidp] * 5 + [i] * 6 + [voidp, sz, i] + [voidp] * 3
+    L.vh_patch_embed_workspace_hw.argtypes = [i] * 6
+    L.vh_patch_embed_workspace_hw.restype = sz
+    L.vh_launch_patch_embed_rows_hw.argtypes = [voidp] + [voidp] * 6 + [i] * 6 + [voidp, sz, i]
+    L.vh_launch_expand_u8_hw.argtypes = [voidp, voidp, i, f32p, f32p, voidp, i, i, i, i]
     L.vit_hip_config.argtypes = [voidp]
     L.vit_hip_config.restype = C.POINTER(VitConfig)
     _lib = L
@@ -769,7 +812,7 @@ def synth_weights(cfg: VitConfig, seed_base: int = 0) -> list[np.ndarray]:
 
 def synth_images(cfg: VitConfig, first: int, count: int) -> np.ndarray:
     L = lib()
-    a = np.empty((count, cfg.in_chans, cfg.img_size, cfg.img_size), dtype=np.float32)
+    a = np.empty(cfg.image_shape(count), dtype=np.float32)
     for i in range(count):
         L.vit_synth_image(C.byref(cfg), first + i, fptr(a[i]))
     return a
@@ -889,10 +932,30 @@ class ViTHip:
         how = PosResampleC(_pos_mode(mode), int(align_corners))
         check(self.L.vit_hip_create_at_resolution(C.byref(new.ctx), self.ctx, int(img_size), int(max_batch or 0), C.byref(how)),
               "vit_hip_create_at_resolution")
+        return self._derived(new)
+
+    def _derived(self, new: "ViTHip") -> "ViTHip":
         new.cfg = VitConfig.from_buffer_copy(self.L.vit_hip_config(new.ctx).contents)
         new.precision = self.precision
         new.max_batch, new.tokens = self.L.vit_hip_max_batch(new.ctx), tokens(new.cfg)
         return new
+
+    def at_size(self, height: int, width: int, max_batch=None, mode="bicubic", align_corners=False) -> "ViTHip":
+        """at_resolution for an input of height rows by width columns (vit_hip_create_at_size); this context may itself be
+        non-square."""
+        new = type(self).__new__(type(self))
+        new.L, new._weights, new.ctx = self.L, None, voidp()
+        how = PosResampleC(_pos_mode(mode), int(align_corners))
+        check(self.L.vit_hip_create_at_size(C.byref(new.ctx), self.ctx, int(height), int(width), int(max_batch or 0), C.byref(how)),
+              "vit_hip_create_at_size")
+        return self._derived(new)
+
+    def check_images(self, images: np.ndarray, layout: str = "chw", who: str = "forward") -> None:
+        """ValueError unless images is [n][C][H][W] ("chw": fp32, or bytes) or [n][H][W][C] ("hwc": bytes) of this context's
+        H = img_size rows, W = width columns and C = in_chans"""
+        want = self.cfg.image_shape(images.shape[0] if images.ndim else 0, layout)
+        if images.shape != want:
+            raise ValueError(f"{who}: images of shape {images.shape}, the context's config takes {want} ({layout})")
 
     def weight(self, idx: int) -> np.ndarray:
         """Tensor idx as the context holds it in fp32 (vit_hip_weight), read back to the host."""
@@ -915,6 +978,7 @@ class ViTHip:
     def forward(self, images: np.ndarray):
         """Host-pointer path: [n][C][H][W] -> (logits[n][classes], probs[n][classes])."""
         images = np.ascontiguousarray(images, dtype=np.float32)
+        self.check_images(images, "chw", "forward")
         n, nc = images.shape[0], self.cfg.num_classes
         logits = np.empty((n, nc), dtype=np.float32)
         probs = np.empty((n, nc), dtype=np.float32)
@@ -938,10 +1002,8 @@ class ViTHip:
         None in that place."""
         cfg = self.cfg
         images = np.ascontiguousarray(images, dtype=np.uint8)
-        n, S, Ch = images.shape[0], cfg.img_size, cfg.in_chans
-        want = (n, S, S, Ch) if layout == "hwc" else (n, Ch, S, S)
-        if images.shape != want:
-            raise ValueError(f"forward_u8: images of shape {images.shape}, the context's config takes {want} ({layout})")
+        self.check_images(images, layout, "forward_u8")
+        n = images.shape[0]
         norm, out_l, out_p, lp, rows = self._u8_outputs(mean, std, n, logits, probs)
         check(self.L.vit_hip_forward_u8(self.ctx, images.ctypes.data_as(C.POINTER(C.c_ubyte)), n, PIXEL_LAYOUTS[layout],
                                         C.byref(norm), lp, rows), "vit_hip_forward_u8")
@@ -1219,7 +1281,7 @@ class ViTHip:
         img_size), the host form armed for this one call."""
         images = np.ascontiguousarray(images, dtype=np.float32)
         n = images.shape[0]
-        h, w = (size, size) if isinstance(size, int) else size if size is not None else (self.cfg.img_size, self.cfg.img_size)
+        h, w = (size, size) if isinstance(size, int) else size if size is not None else (self.cfg.img_size, self.cfg.width)
         labels = np.empty((n, h, w), dtype=np.uint8)
         self.set_dense_host(DenseSpec(0, h, w, tap, final_norm), weight, bias, labels=labels)
         try:
