@@ -347,11 +347,21 @@ vh_stream_t vit_hip_stream(const vit_hip_ctx *ctx);
 int vit_hip_max_batch(const vit_hip_ctx *ctx);
 /* Device pointer of weight tensor idx (same index map as `networks`). */
 const float *vit_hip_weight(const vit_hip_ctx *ctx, int idx);
-/* Opt-in (default off; $VIT_HIP_LAST_LAYER=cls turns it on at creation): evaluate the last encoder layer's output
- * projection, LayerNorm and MLP for the class-token rows only -- the only rows the classifier reads (ViT_seq.c:511).
- * Logits and probabilities are identical bit for bit; the last layer then does not update the other rows of the
- * residual stream (vit_hip_read_tokens).  fp32 path on planes only (ignored elsewhere).  Returns the previous setting,
- * -1 for a NULL context. */
+/* The last encoder layer behind its attention.  The classifier reads the class-token row of every image only
+ * (ViT_seq.c:511) and behind the last attention no operator mixes rows, so on the fp32 path on planes a forward evaluates
+ * the last layer's output projection, LayerNorm and MLP for the class-token rows only, with the same kernels and the same
+ * k order: logits and probabilities are those of the full evaluation bit for bit.  The other rows stay computable: the
+ * forward leaves the pre-projection residual and the attention output in place, and vit_hip_read_tokens runs the full
+ * layer's launches on them before it copies, so nothing a caller can read differs from the full evaluation.  An armed
+ * request that needs patch rows of the last layer makes its forward run the layer on all rows.  With the resident
+ * three-part attention such a forward also runs the last layer's Q projection and attention for the class-token query alone
+ * (K and V on all rows; csrc/attention_p3.hip, CLSQ), unless an armed attention-map tap on the last layer or a rollout
+ * reads its Q|K|V; vit_hip_read_tokens then runs the QKV projection and the attention again as well.
+ * $VIT_HIP_LAST_LAYER at creation: "full" = every forward runs the last layer on all rows (the A/B of tests and benchmarks);
+ * "all_queries" = the class-rows path with Q and the attention on all rows.
+ * vit_hip_set_last_layer_cls_only is the older switch for the same path ($VIT_HIP_LAST_LAYER=cls sets it at creation): a
+ * forward takes the class-rows path when either it or the default asks for it.  It returns the previous setting of its
+ * own flag, -1 for a NULL context; fp32 path on planes only (ignored elsewhere). */
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on);
 
 /* ---- feature outputs: class, pooled and patch-token embeddings (the model as a backbone) ----
@@ -381,9 +391,9 @@ int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on);
  * 1..4, a tap outside [-depth, depth), taps not ascending and distinct, an unknown dtype or token_layout, all three
  * buffers NULL, a misaligned device buffer, T < 2 with pooled or tokens asked for.  A refused call leaves the previous
  * request armed.
- * vit_hip_set_last_layer_cls_only: a forward whose armed request needs patch rows of the last layer (pooled or tokens
- * with the last layer among the taps) runs the last layer on all rows; one that needs only cls there uses the compacted
- * class-token rows.  Logits are bit-identical either way.
+ * The class-rows last layer (vit_hip_set_last_layer_cls_only above): a forward whose armed request needs patch rows of the
+ * last layer (pooled or tokens with the last layer among the taps) runs the last layer on all rows; one that needs only cls
+ * there uses the compacted class-token rows.  Logits are bit-identical either way.
  * vit_hip_multi: a context from vit_hip_multi_ctx may be armed for the device forms like any other;
  * vit_hip_forward_multi and vit_hip_forward_device_multi neither write features nor refuse. */
 enum { VIT_FEATURE_F32 = 0, VIT_FEATURE_BF16 = 1 };
@@ -573,7 +583,7 @@ int vit_hip_set_rollout_host(vit_hip_ctx *ctx, const vit_rollout_spec *spec, con
  * dtype, n_rows or row_stride outside the above, an embed_dim the search does not take, POOLED on a model without patch
  * tokens, NULL or misaligned d_rows, no indices buffer, a misaligned device buffer, scratch that cannot be allocated -- all
  * when the request is armed, not at the first forward.  A refused call leaves the previous request armed.
- * Under vit_hip_set_last_layer_cls_only: cls of the last layer reads the compacted class rows; pooled of the last layer
+ * The class-rows last layer (vit_hip_set_last_layer_cls_only): cls of the last layer reads the compacted class rows; pooled of the last layer
  * makes that forward run the last layer on all rows, as a feature request for pooled does; logits are bit-identical either
  * way.
  * vit_hip_multi: a context from vit_hip_multi_ctx may be armed for the device forms like any other; vit_hip_forward_multi
@@ -632,7 +642,7 @@ int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, con
  * out_h, out_w or weight_stride outside the above, a model the head does not take, NULL or misaligned d_weight, misaligned
  * d_bias, no labels buffer, a misaligned device buffer, scratch that cannot be allocated -- all when the request is armed,
  * not at the first forward.  A refused call leaves the previous request armed.
- * Under vit_hip_set_last_layer_cls_only: a tap on the last layer makes that forward run the last layer on all rows, as a
+ * The class-rows last layer (vit_hip_set_last_layer_cls_only): a tap on the last layer makes that forward run the last layer on all rows, as a
  * feature request for pooled does; logits are bit-identical either way.
  * vit_hip_multi: vit_hip_forward_multi and vit_hip_forward_device_multi neither write labels nor refuse.
  * Out of scope: per-pixel probabilities, multi-layer or non-linear decode heads, antialiased or bicubic upsampling, more
@@ -652,10 +662,13 @@ int vit_dense_sizes(const vit_config *cfg, const vit_dense_spec *spec, size_t *l
 int vit_hip_set_dense(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *d_bufs);
 int vit_hip_set_dense_host(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *h_bufs);
 
-/* Debug hook: copy the residual stream left by the last forward ([n*tokens][embed], un-normalised; rows other than the
- * class tokens are stale under vit_hip_set_last_layer_cls_only) to the host.  The supported interface to the encoder's
- * output is vit_hip_set_features above. */
+/* Debug hook: copy the residual stream of the last forward ([n*tokens][embed], un-normalised) to the host.  Where that
+ * forward ran the last layer behind its attention on the class-token rows only, the full layer's launches run on all rows of
+ * its images first, on the context's stream: the rows are those of the full evaluation, bit for bit; a second read runs
+ * nothing.  As for the copy itself, a forward the caller put on a stream of its own must have completed.  The supported interface to the encoder's output is vit_hip_set_features above. */
 int vit_hip_read_tokens(vit_hip_ctx *ctx, int n, float *host_out);
+/* Images of the last forward whose last layer still waits to be finished on all rows (0: none; -1: NULL context) */
+int vit_hip_last_layer_pending(const vit_hip_ctx *ctx);
 
 /* Per-operator timing with HIP events recorded on the launch stream (the capability
  * behind the reference's dead profileEvents/printEventProfile, ViT_opencl.c:988-1048).
@@ -673,6 +686,11 @@ enum vit_op_class
     VIT_OP_FC2,             /* MLP fc2 + residual */
     VIT_OP_HEAD,            /* classifier GEMM */
     VIT_OP_SOFTMAX,         /* class softmax */
+    /* the last layer on the class-token rows only: n-row launches, kept apart so that the means of the classes above stay
+     * those of full-size launches (that layer's LayerNorm is timed with the LayerNorms, like the final one) */
+    VIT_OP_OUT_PROJ_CLS,    /* two row gathers + output projection + residual */
+    VIT_OP_FC1_CLS,
+    VIT_OP_FC2_CLS,
     VIT_OP_COUNT
 };
 int vit_hip_profile_enable(vit_hip_ctx *ctx, int max_forwards);

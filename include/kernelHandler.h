@@ -234,6 +234,19 @@ int vh_launch_attention_long(vh_stream_t s, const void *qkv_planes, int parts, f
 int vh_launch_linear_p3(vh_stream_t s, void *output, int output_planes, const void *weight_planes,
                         const void *input_planes, const float *bias, int rowA, int colA, int colB,
                         int doGelu, const float *residual);
+/* colB consecutive output features of a projection that has w_features of them (no GELU, no residual): weight_planes points
+ * at the first of them inside the whole matrix's planes [colA/32][3][w_features][32] (64 bytes per feature), bias at its
+ * entry; output is these columns' own, fp32 [rowA][colB] or planes [colB/32][3][rowA][32].  The kernels and the k order of
+ * vh_launch_linear_p3 on the whole matrix: the same bits in these columns.  w_features >= colB. */
+int vh_launch_linear_p3_cols(vh_stream_t s, void *output, int output_planes, const void *weight_planes, int w_features,
+                             const void *input_planes, const float *bias, int rowA, int colA, int colB);
+/* vh_launch_attention_planes for the class-token query (row 0) of every image alone, as the last layer needs it:
+ * qkv_planes as there, of which only K and V are read; q_cls_planes [embed_dim/32][3][n_images][32], the Q planes of the
+ * n_images class rows; out_cls_planes [embed_dim/32][3][n_images][32].  One wave computes the query tile that holds the
+ * class query, its other 31 columns loaded as zeros, with the products, the key mapping, the softmax and the P.V order of
+ * the full kernel: row i of the output is row i * tokens of vh_launch_attention_planes' on the same Q|K|V, bit for bit. */
+int vh_launch_attention_planes_cls(vh_stream_t s, const void *qkv_planes, const void *q_cls_planes, void *out_cls_planes,
+                                   int n_images, int tokens, int embed_dim, int num_heads);
 
 /* fp32 emulation with two fp16 parts per operand and three products (the "3 x TF32" scheme on
  * fp16: a = a0 + a1 + eps, |eps| <= 2^-22 |a|; a.w ~ a0w0 + a0w1 + a1w0, fp32 accumulation).  NOT

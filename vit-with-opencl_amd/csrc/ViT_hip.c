@@ -95,6 +95,12 @@ struct vit_hip_ctx
     struct requests req;
     const struct serving *serving;
 
+    /* images of the last forward whose last layer ran behind its attention for the class-token rows only
+     * (plan.last_layer_lazy or plan.cls_only_last): x, attn and y still hold what the other rows need, and
+     * finish_last_layer evaluates them for whoever reads those rows afterwards.  0: nothing is pending */
+    int last_pending;
+    int last_pending_attention;   /* ... and Q and the attention ran for the class query alone (plan.cls_query) */
+
     /* optional per-operator timing with HIP events on the launch stream */
     vh_event_t *prof_ev;   /* 2 events per recorded launch */
     int *prof_class;       /* operator class per recorded launch */
@@ -121,13 +127,14 @@ static void prof_end(vit_hip_ctx *ctx, vh_stream_t s, int slot)
         vh_event_record(ctx->prof_ev[2 * slot + 1], s);
 }
 
-/* Launch `call` bracketed by two events when profiling is enabled. */
-#define OP(op_class, call)                                  \
-    do {                                                    \
-        const int op_slot_ = prof_begin(ctx, s, op_class);  \
-        TRY(call);                                          \
-        prof_end(ctx, s, op_slot_);                         \
+/* Launch `call` bracketed by two events when profiling is enabled and the launch is `timed` (part of a forward). */
+#define OP_T(timed, op_class, call)                                        \
+    do {                                                                   \
+        const int op_slot_ = (timed) ? prof_begin(ctx, s, op_class) : -1;  \
+        TRY(call);                                                         \
+        prof_end(ctx, s, op_slot_);                                        \
     } while (0)
+#define OP(op_class, call) OP_T(1, op_class, call)
 
 static void prof_release(vit_hip_ctx *ctx)
 {
@@ -684,10 +691,88 @@ fail:
     return rc;
 }
 
+/* Layer l of the fp32 path on planes from LN1's output in y to the attention's in attn, on all rows: the QKV projection, the
+ * armed attention taps, the attention.  ATTN_HD64, ATTN_LONG: Q, K, V too travel as planes (only the probabilities are split
+ * inside the attention kernel); otherwise the streaming kernel, fp32 rows in.  Both but the resident kernel write fp32 rows
+ * (into the idle MLP buffer), then split.  timed: the launches of a forward; 0 when finish_last_layer runs them afterwards,
+ * outside every forward's operator times and with nothing armed to serve. */
+static int layer_f32_planes_attention(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int timed)
+{
+    int rc = 0;
+    const vit_config *c = &ctx->cfg;
+    const int E = c->embed_dim, T = ctx->plan.tokens, rows = n * T, fold = ctx->plan.ln_fold;
+    float **lw = layer_tensors(ctx, l);
+    const struct operand *op = ctx->op + 4 * l;
+    const int planes_attn = ctx->plan.qkv_form == VH_QKV_PLANES3;
+    OP_T(timed, VIT_OP_QKV, fold ? vh_launch_linear_p3_norm(s, ctx->qkv, planes_attn, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
+                                 : vh_launch_linear_p3(s, ctx->qkv, planes_attn, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
+    if (timed)
+        TRY(attention_tap(ctx, s, n, l));
+    OP_T(timed, VIT_OP_ATTENTION, ctx->plan.attn_form == ATTN_HD64 ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
+                                  : (rc = ctx->plan.attn_form == ATTN_LONG ? vh_launch_attention_long(s, ctx->qkv, 3, ctx->hid, n, T, E, c->num_heads)
+                                                                      : attention_rows(ctx, s, ctx->hid, VH_ATTN_SPLIT3, n)) != 0 ? rc
+                                  : vh_launch_split3_rows(s, ctx->hid, ctx->attn, rows, E));
+    return 0;
+fail:
+    return rc;
+}
+
+/* ... and behind its attention, on all rows: output projection, LayerNorm, MLP */
+static int layer_f32_planes_tail(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int timed)
+{
+    int rc = 0;
+    const vit_config *c = &ctx->cfg;
+    const int E = c->embed_dim, F = c->mlp_hidden, rows = n * ctx->plan.tokens, fold = ctx->plan.ln_fold, last = l == c->depth - 1;
+    float **lw = layer_tensors(ctx, l);
+    const struct operand *op = ctx->op + 4 * l;
+    OP_T(timed, VIT_OP_OUT_PROJ, fold ? vh_launch_linear_p3_resid_norm(s, ctx->x, op[1].w, ctx->attn, lw[5], ctx->x, rows, E, E, ctx->y, ctx->stats)
+                                      : vh_launch_linear_p3(s, ctx->x, 0, op[1].w, ctx->attn, lw[5], rows, E, E, 0, ctx->x));
+    if (!fold)
+        OP_T(timed, VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, c->eps));
+    OP_T(timed, VIT_OP_FC1, fold ? vh_launch_linear_p3_norm(s, ctx->hid, 1, op[2].w, ctx->y, ctx->stats, op[2].colsum, op[2].bias_folded, c->eps, rows, E, F, 1)
+                                 : vh_launch_linear_p3(s, ctx->hid, 1, op[2].w, ctx->y, lw[9], rows, E, F, 1, NULL));
+    OP_T(timed, VIT_OP_FC2, fold && !last ? vh_launch_linear_p3_resid_norm(s, ctx->x, op[3].w, ctx->hid, lw[11], ctx->x, rows, F, E, ctx->y, ctx->stats)
+                                          : vh_launch_linear_p3(s, ctx->x, 0, op[3].w, ctx->hid, lw[11], rows, F, E, 0, ctx->x));
+    return 0;
+fail:
+    return rc;
+}
+
+/* What a forward on the class-rows path left pending: the last layer on all rows of those images, from what that forward
+ * left untouched -- the pre-projection residual in x and the attention output in attn; where it ran Q and the attention for
+ * the class query alone (last_pending_attention), from LN1's planes in y through the QKV projection and the attention
+ * again.  The launches of the full layer on the same operands, on the context's stream: the residual stream is then the
+ * full evaluation's, bit for bit (y holds LN2's output and hid the MLP's, as behind a full layer). */
+static int finish_last_layer(vit_hip_ctx *ctx)
+{
+    int rc = 0;
+    const int n = ctx->last_pending, l = ctx->cfg.depth - 1;
+    if (!n)
+        return 0;
+    if (ctx->last_pending_attention)
+        TRY(layer_f32_planes_attention(ctx, ctx->stream, n, l, 0));
+    TRY(layer_f32_planes_tail(ctx, ctx->stream, n, l, 0));
+    ctx->last_pending = ctx->last_pending_attention = 0;
+fail:
+    return rc;
+}
+
+/* An armed attention-map tap on layer l, or the rollout from a layer up to l: they read all of Q|K|V behind l's projection */
+static int attention_tap_reads(const vit_hip_ctx *ctx, int l)
+{
+    const struct attn_req *ar = ctx->serving->ar;
+    const struct rollout_req *ro = ctx->serving->ro;
+    for (int k = 0; ar && k < ar->spec.n_taps; ++k)
+        if (ar->layer[k] == l)
+            return 1;
+    return ro && l >= ro->first;
+}
+
 /* F32, the default: GEMM inputs as exact three-part planes written by LayerNorm, attention and the fc1 epilogue.  ln_fold
  * here is the LAB VARIANT ($VIT_HIP_LN_FOLD=1, docs/LABBOOK.md R4.6): ctx->y then holds the split of x itself.
- * cls_only: this forward runs the last layer on the class-token rows only (opt-in); *cls_rows is set when it did: the final
- * LayerNorm then reads them compacted at the start of the Q|K|V buffer. */
+ * cls_only: this forward runs the last layer behind its attention on the class-token rows only (the default where the plan
+ * allows it); *cls_rows is set when it did (2: Q and the attention too ran for the class query alone): the final LayerNorm
+ * then reads them compacted at the start of the Q|K|V buffer. */
 static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int cls_only, int *cls_rows)
 {
     int rc = 0;
@@ -695,48 +780,46 @@ static int layer_f32_planes(vit_hip_ctx *ctx, vh_stream_t s, int n, int l, int c
     const int E = c->embed_dim, F = c->mlp_hidden, T = ctx->plan.tokens, rows = n * T, fold = ctx->plan.ln_fold, last = l == c->depth - 1;
     float **lw = layer_tensors(ctx, l);
     const struct operand *op = ctx->op + 4 * l;
-    /* ATTN_HD64, ATTN_LONG: Q, K, V too travel as planes (only the probabilities are split inside the attention kernel);
-     * otherwise the streaming kernel, fp32 rows in.  Both but the resident kernel write fp32 rows (into the idle MLP
-     * buffer), then split */
-    const int planes_attn = ctx->plan.qkv_form == VH_QKV_PLANES3;
     if (!fold)
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, ctx->x, lw[0], lw[1], ctx->y, rows, E, E, c->eps));
-    OP(VIT_OP_QKV, fold ? vh_launch_linear_p3_norm(s, ctx->qkv, planes_attn, op[0].w, ctx->y, ctx->stats, op[0].colsum, op[0].bias_folded, c->eps, rows, E, 3 * E, 0)
-                        : vh_launch_linear_p3(s, ctx->qkv, planes_attn, op[0].w, ctx->y, lw[3], rows, E, 3 * E, 0, NULL));
-    TRY(attention_tap(ctx, s, n, l));
-    OP(VIT_OP_ATTENTION, ctx->plan.attn_form == ATTN_HD64 ? vh_launch_attention_planes(s, ctx->qkv, ctx->attn, n, T, E, c->num_heads)
-                         : (rc = ctx->plan.attn_form == ATTN_LONG ? vh_launch_attention_long(s, ctx->qkv, 3, ctx->hid, n, T, E, c->num_heads)
-                                                             : attention_rows(ctx, s, ctx->hid, VH_ATTN_SPLIT3, n)) != 0 ? rc
-                         : vh_launch_split3_rows(s, ctx->hid, ctx->attn, rows, E));
     if (last && cls_only) {
-        /* Opt-in (vit_hip_set_last_layer_cls_only / $VIT_HIP_LAST_LAYER=cls).  The classifier reads row 0 of every
-         * image only (ViT_seq.c:511), and behind the last attention no operator mixes rows: the output projection,
-         * LayerNorm and MLP of the last layer are evaluated for the n class-token rows instead of n * T, in the
-         * Q|K|V buffer the attention has just released.  Same kernels, same k order: identical logits, bit for
-         * bit; the residual stream of the other rows (vit_hip_read_tokens) is NOT updated by this layer. */
-        size_t off[3];
+        /* The classifier reads row 0 of every image only (ViT_seq.c:511), and behind the last attention no operator
+         * mixes rows: the output projection, LayerNorm and MLP of the last layer are evaluated for the n class-token
+         * rows instead of n * T, in the Q|K|V buffer the attention has just released.  Same kernels, same k order:
+         * identical logits, bit for bit.  x, attn and y are left as they are: the other rows stay computable
+         * (finish_last_layer).  The three projections are timed under operator names of their own, so that the full-size
+         * operators' means stay those of full-size launches. */
+        size_t off[3], q_off;
         plan_cls_only_scratch(c, n, off);   /* cls_only_ok: it fits for max_batch rows */
+        plan_cls_query_scratch(c, n, &q_off);
         char *scratch = (char *)ctx->qkv;
         float *x_cls = (float *)scratch;
-        char *attn_cls = scratch + off[0], *y_cls = scratch + off[1], *hid_cls = scratch + off[2];
-        OP(VIT_OP_OUT_PROJ, (rc = vh_launch_gather_rows(s, ctx->attn, attn_cls, 3 * (E / 32), rows, n, 64, T)) != 0 ? rc :
-                            (rc = vh_launch_gather_rows(s, ctx->x, x_cls, 1, rows, n, 4 * E, T)) != 0 ? rc :
-                            vh_launch_linear_p3(s, x_cls, 0, op[1].w, attn_cls, lw[5], n, E, E, 0, x_cls));
+        char *attn_cls = scratch + off[0], *y_cls = scratch + off[1], *hid_cls = scratch + off[2], *q_cls = scratch + q_off;
+        const int cls_query = ctx->plan.cls_query && !attention_tap_reads(ctx, l);
+        if (cls_query) {
+            /* The rows that are skipped are all that Q and the attention output of the patch rows feed: K and V on all rows,
+             * into their place in Q|K|V; Q for the gathered class rows of LN1's planes, by the same kernels column range by
+             * column range; the attention for the class query alone, straight into attn_cls.  The scratch lies in the place
+             * of the Q planes (plan.cls_query: it fits there at every n).  Timed with the QKV projections and the attentions. */
+            char *kv = scratch + (size_t)rows * E * 6;
+            OP(VIT_OP_QKV, (rc = vh_launch_linear_p3_cols(s, kv, 1, (const char *)op[0].w + (size_t)E * 64, 3 * E, ctx->y, lw[3] + E, rows, E, 2 * E)) != 0 ? rc :
+                           (rc = vh_launch_gather_rows(s, ctx->y, y_cls, 3 * (E / 32), rows, n, 64, T)) != 0 ? rc :
+                           vh_launch_linear_p3_cols(s, q_cls, 1, op[0].w, 3 * E, y_cls, lw[3], n, E, E));
+            OP(VIT_OP_ATTENTION, vh_launch_attention_planes_cls(s, ctx->qkv, q_cls, attn_cls, n, T, E, c->num_heads));
+        } else {
+            TRY(layer_f32_planes_attention(ctx, s, n, l, 1));
+        }
+        OP(VIT_OP_OUT_PROJ_CLS, (rc = cls_query ? 0 : vh_launch_gather_rows(s, ctx->attn, attn_cls, 3 * (E / 32), rows, n, 64, T)) != 0 ? rc :
+                                (rc = vh_launch_gather_rows(s, ctx->x, x_cls, 1, rows, n, 4 * E, T)) != 0 ? rc :
+                                vh_launch_linear_p3(s, x_cls, 0, op[1].w, attn_cls, lw[5], n, E, E, 0, x_cls));
         OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, x_cls, lw[6], lw[7], y_cls, n, E, E, c->eps));
-        OP(VIT_OP_FC1, vh_launch_linear_p3(s, hid_cls, 1, op[2].w, y_cls, lw[9], n, E, F, 1, NULL));
-        OP(VIT_OP_FC2, vh_launch_linear_p3(s, x_cls, 0, op[3].w, hid_cls, lw[11], n, F, E, 0, x_cls));
-        *cls_rows = 1;
+        OP(VIT_OP_FC1_CLS, vh_launch_linear_p3(s, hid_cls, 1, op[2].w, y_cls, lw[9], n, E, F, 1, NULL));
+        OP(VIT_OP_FC2_CLS, vh_launch_linear_p3(s, x_cls, 0, op[3].w, hid_cls, lw[11], n, F, E, 0, x_cls));
+        *cls_rows = cls_query ? 2 : 1;
         return 0;
     }
-    OP(VIT_OP_OUT_PROJ, fold ? vh_launch_linear_p3_resid_norm(s, ctx->x, op[1].w, ctx->attn, lw[5], ctx->x, rows, E, E, ctx->y, ctx->stats)
-                             : vh_launch_linear_p3(s, ctx->x, 0, op[1].w, ctx->attn, lw[5], rows, E, E, 0, ctx->x));
-    if (!fold)
-        OP(VIT_OP_LAYER_NORM, vh_launch_layer_norm_p3(s, ctx->x, lw[6], lw[7], ctx->y, rows, E, E, c->eps));
-    OP(VIT_OP_FC1, fold ? vh_launch_linear_p3_norm(s, ctx->hid, 1, op[2].w, ctx->y, ctx->stats, op[2].colsum, op[2].bias_folded, c->eps, rows, E, F, 1)
-                        : vh_launch_linear_p3(s, ctx->hid, 1, op[2].w, ctx->y, lw[9], rows, E, F, 1, NULL));
-    OP(VIT_OP_FC2, fold && !last ? vh_launch_linear_p3_resid_norm(s, ctx->x, op[3].w, ctx->hid, lw[11], ctx->x, rows, F, E, ctx->y, ctx->stats)
-                                 : vh_launch_linear_p3(s, ctx->x, 0, op[3].w, ctx->hid, lw[11], rows, F, E, 0, ctx->x));
-    return 0;
+    TRY(layer_f32_planes_attention(ctx, s, n, l, 1));
+    return layer_f32_planes_tail(ctx, s, n, l, 1);
 fail:
     return rc;
 }
@@ -919,9 +1002,11 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         src = &crops;
     }
     OP(VIT_OP_PATCH_EMBED, patch_embed_launches(ctx, s, src, n));
-    int cls_rows = 0;   /* the last layer ran on the class-token rows only (opt-in, fp32 path on planes) */
+    int cls_rows = 0;   /* the last layer ran behind its attention on the class-token rows only (fp32 path on planes) */
     /* a request for patch rows of the last layer makes this forward run the last layer on all rows */
-    const int cls_only = ctx->plan.cls_only_last && ctx->plan.cls_only_ok && !serving_needs_last_layer_rows(sv, c->depth);
+    const int cls_only = (ctx->plan.last_layer_lazy || ctx->plan.cls_only_last) && ctx->plan.cls_only_ok &&
+                         !serving_needs_last_layer_rows(sv, c->depth);
+    ctx->last_pending = ctx->last_pending_attention = 0;   /* this forward overwrites what a pending last layer would read */
     for (int l = 0, k = 0; l < c->depth; ++l) {
         switch (ctx->plan.precision) {
         case VIT_PRECISION_FP8_GEMM: TRY(layer_fp8(ctx, s, n, l)); break;
@@ -956,6 +1041,10 @@ static int forward_device(vit_hip_ctx *ctx, const struct ingest_src *src, int n,
         OP(VIT_OP_SOFTMAX, vh_launch_softmax(s, logits, d_probs, n, NC));
     if (tk)   /* the k best of every row of the fp32 logits: one launch, whatever the precision mode */
         OP(VIT_OP_SOFTMAX, vh_launch_topk(s, logits, n, NC, tk->spec.k, tk->spec.score_kind, tk->out.labels, tk->out.scores));
+    if (cls_rows) {
+        ctx->last_pending = n;
+        ctx->last_pending_attention = cls_rows == 2;
+    }
 fail:
     ctx->serving = NULL;
     return rc;
@@ -1080,6 +1169,9 @@ SETTER(vit_hip_set_dense, dense, vit_dense_spec, vit_dense_buffers, 0)
 SETTER(vit_hip_set_dense_host, dense, vit_dense_spec, vit_dense_buffers, 1)
 #undef SETTER
 
+/* images whose last layer is pending behind the last forward (finish_last_layer); tests */
+int vit_hip_last_layer_pending(const vit_hip_ctx *ctx) { return ctx ? ctx->last_pending : -1; }
+
 int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
 {
     if (!ctx)
@@ -1089,12 +1181,15 @@ int vit_hip_set_last_layer_cls_only(vit_hip_ctx *ctx, int on)
     return before;
 }
 
-/* Debug/test hook: copy the residual stream ([n*tokens][E], un-normalised) to the host.  The supported interface to the
- * encoder's output is vit_hip_set_features. */
+/* Debug/test hook: copy the residual stream ([n*tokens][E], un-normalised) to the host, behind the last layer on all rows
+ * of the last forward's images (finish_last_layer; a second read runs nothing).  The supported interface to the encoder's
+ * output is vit_hip_set_features. */
 int vit_hip_read_tokens(vit_hip_ctx *ctx, int n, float *host_out)
 {
     int rc = vh_set_device(ctx->device);
     if (rc)
+        return rc;
+    if ((rc = finish_last_layer(ctx)) != 0)
         return rc;
     rc = vh_d2h(host_out, ctx->x, (size_t)n * ctx->plan.tokens * ctx->cfg.embed_dim * sizeof(float),
                     ctx->stream);

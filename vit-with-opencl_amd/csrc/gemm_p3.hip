@@ -68,12 +68,14 @@ enum { OUT_F32 = 0, OUT_PLANES = 1, OUT_PLANES_H = 2, OUT_F32_OPER = 3, OUT_F32_
 
 struct P3Params {
     const char *A;            /* activation planes [K/32][NPL][a_rows][32] bf16 */
-    const char *W;            /* weight planes     [K/32][NPL][N][32] bf16 */
+    const char *W;            /* weight planes     [K/32][NPL][w_rows][32] bf16, from the first of the N output features */
     const float *bias;        /* [N] */
     const float *R;           /* residual [a_rows][N] fp32 (EPI_RESID) */
     void *C;                  /* fp32 [a_rows][N], or planes [N/32][NPL][a_rows][32] */
     int row_begin, row_end;   /* rows of the activation matrix this launch covers */
     int N, K;
+    int w_rows;               /* output features of the whole weight matrix = its planes' row count (0: N; more where a
+                               * launch covers a range of its columns, vh_launch_linear_p3_cols) */
     int a_rows;               /* rows of the whole activation matrix = the planes' row count */
     int mtiles, ntiles;
     /* EPI_PATCH (patch embedding): GEMM row m = patch (m / np, m % np) lands in token row image * tokens + 1 + patch,
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(64 * NW, 2) void gemm_p3_kernel(const P3Params p)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
         aoff[i] = (unsigned)min(m0 + 32 * wave + 16 * i + l15, p.row_end - 1) * 64u + 16u * q;
-    const size_t a_plane = (size_t)p.a_rows * 64, w_plane = (size_t)p.N * 64;
+    const size_t a_plane = (size_t)p.a_rows * 64, w_plane = (size_t)p.w_rows * 64;
 
     /* W DMA piece pc = 16 rows x 64 B of one part: lane fills physical chunk (lane & 3) of row
      * 16*rb + (lane >> 2) with logical chunk phys ^ f(row >> 2). */
@@ -436,6 +438,8 @@ int launch_p3_tile(hipStream_t st, P3Params p)
     VH_SET_LDS_ONCE((gemm_p3_kernel<NW, BN, EPI, OUTK, NPL>), LDS);
     p.mtiles = (p.row_end - p.row_begin + 32 * NW - 1) / (32 * NW);
     p.ntiles = p.N / BN;
+    if (p.w_rows == 0)
+        p.w_rows = p.N;
     hipLaunchKernelGGL((gemm_p3_kernel<NW, BN, EPI, OUTK, NPL>), dim3(p.mtiles * p.ntiles), dim3(64 * NW), LDS, st, p);
     VH_LAUNCH_CHECK("gemm_p3_kernel");
     return 0;
@@ -607,9 +611,10 @@ extern "C" int vh_launch_merge3_rows(vh_stream_t s, const void *planes, float *o
     return vh_launch_merge_rows(s, planes, output, rows, cols, 3);
 }
 
-extern "C" int vh_launch_linear_planes(vh_stream_t s, void *output, int output_planes, const void *weight_planes,
-                                       const void *input_planes, int parts, const float *bias, int rowA, int colA,
-                                       int colB, int doGelu, const float *residual)
+/* w_rows: the planes' row count of the weight matrix; colB of them from weight_planes on are this launch's */
+static int linear_planes(vh_stream_t s, void *output, int output_planes, const void *weight_planes, int w_rows,
+                         const void *input_planes, int parts, const float *bias, int rowA, int colA,
+                         int colB, int doGelu, const float *residual)
 {
     if (!output || !weight_planes || !input_planes || !bias)
         return vh_fail(1, "vh_launch_linear_planes: null pointer argument");
@@ -630,7 +635,7 @@ extern "C" int vh_launch_linear_planes(vh_stream_t s, void *output, int output_p
     p.W = static_cast<const char *>(weight_planes);
     p.bias = bias; p.R = residual; p.C = output;
     p.row_begin = 0; p.row_end = rowA; p.a_rows = rowA;
-    p.N = colB; p.K = colA;
+    p.N = colB; p.K = colA; p.w_rows = w_rows;
     hipStream_t st = (hipStream_t)s;
     const int small_only = residual && colA < 2048;   /* the N = K = E output projection: measured */
 #define VH_P3_DISPATCH(NPL)                                                                                          \
@@ -649,6 +654,25 @@ extern "C" int vh_launch_linear_planes(vh_stream_t s, void *output, int output_p
         return launch_p3<EPI_NONE, OUT_PLANES_H, 1>(st, p, small_only);
     VH_P3_DISPATCH(1);
 #undef VH_P3_DISPATCH
+}
+
+extern "C" int vh_launch_linear_planes(vh_stream_t s, void *output, int output_planes, const void *weight_planes,
+                                       const void *input_planes, int parts, const float *bias, int rowA, int colA,
+                                       int colB, int doGelu, const float *residual)
+{
+    return linear_planes(s, output, output_planes, weight_planes, colB, input_planes, parts, bias, rowA, colA, colB, doGelu, residual);
+}
+
+/* colB consecutive output features of a projection with w_features of them, on three-part planes: weight_planes3 points at
+ * the first of them in the whole matrix's planes [colA/32][3][w_features][32] (64 bytes per feature), bias at its entry; the
+ * output is these columns' own -- planes [colB/32][3][rowA][32] or fp32 rows [rowA][colB].  Every element sums the products
+ * vh_launch_linear_p3 on the whole matrix sums, in the same order: the same bits. */
+extern "C" int vh_launch_linear_p3_cols(vh_stream_t s, void *output, int output_planes, const void *weight_planes3, int w_features,
+                                        const void *input_planes, const float *bias, int rowA, int colA, int colB)
+{
+    if (w_features < colB || w_features % 16 != 0)
+        return vh_fail(1, "vh_launch_linear_p3_cols: w_features=%d must hold colB=%d columns", w_features, colB);
+    return linear_planes(s, output, output_planes, weight_planes3, w_features, input_planes, 3, bias, rowA, colA, colB, 0, nullptr);
 }
 
 extern "C" int vh_launch_linear_p3(vh_stream_t s, void *output, int output_planes, const void *weight_planes,

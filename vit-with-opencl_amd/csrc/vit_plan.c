@@ -21,6 +21,8 @@ void plan_env_parse(struct plan_env *env, const char *const v[PLAN_ENV_COUNT])
     env->fp32_native = v[PLAN_ENV_GEMM_FP32] && v[PLAN_ENV_GEMM_FP32][0] == 'n';
     env->ln_fold = (fold && fold[0] == '0') ? 0 : (fold && fold[0] == '1') ? 1 : -1;
     env->last_layer_cls = v[PLAN_ENV_LAST_LAYER] && strcmp(v[PLAN_ENV_LAST_LAYER], "cls") == 0;
+    env->last_layer_full = v[PLAN_ENV_LAST_LAYER] && strcmp(v[PLAN_ENV_LAST_LAYER], "full") == 0;
+    env->last_layer_all_queries = v[PLAN_ENV_LAST_LAYER] && strcmp(v[PLAN_ENV_LAST_LAYER], "all_queries") == 0;
     env->attn_long = attn && strcmp(attn, "long") == 0;
     env->attn_tiled = attn && attn[0] == 't';
 }
@@ -44,6 +46,14 @@ size_t plan_cls_only_scratch(const vit_config *cfg, int n, size_t off[3])
     if (off)
         memcpy(off, o, sizeof o);
     return o[2] + rows * F * 6;
+}
+
+size_t plan_cls_query_scratch(const vit_config *cfg, int n, size_t *q_off)
+{
+    const size_t at = align_up(plan_cls_only_scratch(cfg, n, NULL), 256);
+    if (q_off)
+        *q_off = at;
+    return at + (size_t)n * (size_t)cfg->embed_dim * 6;
 }
 
 /* The next 256-byte aligned piece of a slab: its address once the slab exists, NULL while only sizing. */
@@ -235,5 +245,12 @@ int plan_make(struct vit_plan *plan, const vit_config *cfg, int n_tensors, int m
     plan_layout(plan, cfg, NULL, NULL, NULL, plan->slab_bytes);
     plan_arena(plan, cfg, max_batch);
     plan->cls_only_ok = use_p3 && !ln_fold && T >= 4 && plan_cls_only_scratch(cfg, max_batch, NULL) <= plan->qkv_bytes;
+    plan->last_layer_lazy = plan->cls_only_ok && !env->last_layer_full;
+    /* the class query's scratch lies where the Q planes of the forward's n images would, in front of K: n * T * E * 6 bytes.
+     * Per class row it takes 22 E + 6 F bytes and at most 5 * 256 of alignment in all, so it fits at every n if it fits so
+     * at n = 1 */
+    plan->cls_query = plan->last_layer_lazy && !env->last_layer_all_queries && plan->attn_form == ATTN_HD64 &&
+                      plan->qkv_form == VH_QKV_PLANES3 &&
+                      22 * (size_t)E + 6 * (size_t)F + 5 * 256 <= (size_t)T * (size_t)E * 6;
     return 0;
 }

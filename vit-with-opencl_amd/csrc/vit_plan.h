@@ -56,6 +56,8 @@ struct plan_env
     int fp32_native;      /* $VIT_HIP_GEMM_FP32=native */
     int ln_fold;          /* $VIT_HIP_LN_FOLD: 0, 1, or -1 when it says neither */
     int last_layer_cls;   /* $VIT_HIP_LAST_LAYER=cls */
+    int last_layer_full;  /* $VIT_HIP_LAST_LAYER=full */
+    int last_layer_all_queries;   /* $VIT_HIP_LAST_LAYER=all_queries */
     int attn_long;        /* $VIT_HIP_ATTN=long */
     int attn_tiled;       /* $VIT_HIP_ATTN=tiled */
 };
@@ -87,8 +89,16 @@ struct vit_plan
     int conv_parts;     /* of conv_proj's planes: 1 (bf16; BF16_GEMM, FP8_GEMM), 3 (the exact split; weight_planes) or 0 (none) */
     int planes_patch_embed;   /* the patch embedding runs on planes (an im2row producer); 0 on the fp32-rows paths */
     int act_bytes;      /* the arena holds this many bytes per GEMM-input value in y, attn, Q|K|V and hid */
-    int cls_only_ok;    /* the class-only last layer may be switched on: planes path, no fold, T >= 4, and its scratch for
+    int cls_only_ok;    /* the class-only last layer may run: planes path, no fold, T >= 4, and its scratch for
                          * max_batch class rows (plan_cls_only_scratch) fits Q|K|V */
+    int last_layer_lazy; /* where cls_only_ok, unless $VIT_HIP_LAST_LAYER=full: a forward evaluates the last layer behind its
+                         * attention for the class-token rows only and leaves the other rows pending; whoever reads them
+                         * afterwards (vit_hip_read_tokens) runs the same launches on all rows first */
+    int cls_query;      /* such a forward also runs the last layer's Q projection and attention for the class-token query
+                         * alone (K and V on all rows): last_layer_lazy with the resident three-part attention, where the
+                         * scratch with the class rows of LN1 and Q behind it (plan_cls_query_scratch) fits the place of Q
+                         * in Q|K|V at every batch, unless $VIT_HIP_LAST_LAYER=all_queries.  Otherwise Q|K|V and the attention
+                         * run on all rows, never an allocation in the forward */
     size_t slab_bytes[N_SLABS];
     /* the arena (plan_make states each buffer's borrowers).  hid doubles as the workspace of the patch embedding, the resize
      * and the feature readout, which are told ws_bytes */
@@ -114,5 +124,8 @@ void plan_layout(const struct vit_plan *plan, const vit_config *cfg, void *const
 /* The class-only last layer's scratch for n class rows, laid into Q|K|V: x_cls at 0, then attn_cls, y_cls and hid_cls at
  * off[0..2]; returns its bytes */
 size_t plan_cls_only_scratch(const vit_config *cfg, int n, size_t off[3]);
+/* ... with the class query's planes (n class rows of Q, [E/32][3][n][32]) behind it at *q_off; returns the bytes of both.
+ * The class rows of LN1's planes, the Q projection's input, lie in y_cls until LN2 writes it. */
+size_t plan_cls_query_scratch(const vit_config *cfg, int n, size_t *q_off);
 
 #endif

@@ -77,6 +77,7 @@ EXPORTS = [
     "vh_launch_resample_pos_embed", "vit_resample_check", "vit_hip_create_at_resolution",
     "vit_config_canonical", "vit_config_grid", "vit_config_sizeof", "vit_resample_check_hw", "vit_hip_create_at_size",
     "vh_launch_patch_embed_planes_hw", "vh_patch_embed_workspace_hw", "vh_launch_patch_embed_rows_hw", "vh_launch_expand_u8_hw",
+    "vh_launch_linear_p3_cols", "vh_launch_attention_planes_cls", "vit_hip_last_layer_pending",
 ]
 
 # include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
@@ -607,6 +608,7 @@ def lib() -> C.CDLL:
     L.vh_launch_attention_planes.argtypes = [voidp, voidp, voidp, i, i, i, i]
     L.vh_launch_gather_rows.argtypes = [voidp, voidp, voidp, i, i, i, i, i]
     L.vit_hip_set_last_layer_cls_only.argtypes = [voidp, i]
+    L.vit_hip_last_layer_pending.argtypes = [voidp]
     L.vh_launch_attention_planes_f16.argtypes = [voidp, voidp, voidp, i, i, i, i, i]
     L.vh_launch_attention_planes_f16_mx.argtypes = [voidp, voidp, voidp, voidp, i, i, i, i]
     L.vh_launch_attention_planes_f16_hd80.argtypes = [voidp, voidp, voidp, i, i, i, i]
@@ -1296,12 +1298,16 @@ class ViTHip:
         return out
 
     OP_NAMES = ["patch_embed", "layer_norm", "qkv_gemm", "attention", "out_proj_gemm", "fc1_gemm",
-                "fc2_gemm", "head_gemm", "softmax"]
+                "fc2_gemm", "head_gemm", "softmax", "out_proj_gemm_cls", "fc1_gemm_cls", "fc2_gemm_cls"]
 
     def set_last_layer_cls_only(self, on: bool) -> bool:
-        """Opt-in: the last layer's output projection and MLP on the class-token rows only (identical logits).
-        Returns the previous setting."""
+        """The older switch for the last layer's output projection and MLP on the class-token rows only (identical logits;
+        the default where the plan allows it).  Returns the previous setting of this flag."""
         return bool(self.L.vit_hip_set_last_layer_cls_only(self.ctx, 1 if on else 0))
+
+    def last_layer_pending(self) -> int:
+        """Images of the last forward whose last layer ran on the class-token rows only and waits for read_tokens to finish it."""
+        return int(self.L.vit_hip_last_layer_pending(self.ctx))
 
     def profile_enable(self, max_forwards: int):
         check(self.L.vit_hip_profile_enable(self.ctx, max_forwards), "vit_hip_profile_enable")
