@@ -32,6 +32,7 @@ class VitConfig(C.Structure):
         ("img_size", C.c_int), ("patch_size", C.c_int), ("in_chans", C.c_int),
         ("num_classes", C.c_int), ("embed_dim", C.c_int), ("depth", C.c_int),
         ("num_heads", C.c_int), ("mlp_hidden", C.c_int), ("eps", C.c_double),
+        ("img_width", C.c_int),   # 0: img_size (square); otherwise the input is img_size rows by img_width columns
     ]
 
 

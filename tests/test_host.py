@@ -296,7 +296,6 @@ def test_planes_file_header_is_checked_before_anything_is_allocated(pkg, tmp_pat
     or planes path cannot honour."""
     import struct
     L, b = pkg.lib(), pkg.binding
-    L.vit_hip_create_from_planes.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_int]
     FMT = "<8sIii8i4xd4QQiiQ"
     assert struct.calcsize(FMT) == 120
 

@@ -51,29 +51,18 @@ def main():
         d_q = pkg.DeviceBuffer.from_numpy(planes.ravel().view(np.float32))
         d_o = pkg.DeviceBuffer(rows * E)
     d_s = pkg.DeviceBuffer(rows * E // 32 + 64)
-    voidp, i = C.c_void_p, C.c_int
     handles = []
     for name, path in libs:
-        L = C.CDLL(path)
-        L.vh_init.argtypes = [i]
-        L.vh_last_error.restype = C.c_char_p
+        L = pkg.binding.declare(C.CDLL(path))
         assert L.vh_init(0) == 0, L.vh_last_error()
         if f32:
-            f0 = L.vh_launch_attention_planes
-            f0.argtypes = [voidp, voidp, voidp, i, i, i, i]
-
-            def f(st, q, o, sc, knd, n_, t_, e_, h_, f0=f0):
+            def f(st, q, o, sc, knd, n_, t_, e_, h_, f0=L.vh_launch_attention_planes):
                 return f0(st, q, o, n_, t_, e_, h_)
         elif b16:
-            f1, f2 = L.vh_launch_attention_planes_f16, L.vh_launch_attention_planes_f16_mx
-            f1.argtypes = [voidp, voidp, voidp, i, i, i, i, i]
-            f2.argtypes = [voidp, voidp, voidp, voidp, i, i, i, i]
-
-            def f(st, q, o, sc, knd, n_, t_, e_, h_, f1=f1, f2=f2):
+            def f(st, q, o, sc, knd, n_, t_, e_, h_, f1=L.vh_launch_attention_planes_f16, f2=L.vh_launch_attention_planes_f16_mx):
                 return f1(st, q, o, 1, n_, t_, e_, h_) if knd == 1 else f2(st, q, o, sc, n_, t_, e_, h_)
         else:
             f = L.vh_launch_attention_planes_f16_hd80_operand
-            f.argtypes = [voidp, voidp, voidp, voidp, i, i, i, i, i]
         handles.append((name, L, f))
     outs = {}
     for name, L, f in handles:      # warm-up + the bytes each variant writes

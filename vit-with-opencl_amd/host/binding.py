@@ -1,7 +1,8 @@
 """ctypes binding of libvit_hip.so -- test / bench plumbing over the C ABI.
 
-The product is the C library (include/*.h); this module only loads it, mirrors
-its structs, and turns non-zero status codes into exceptions.  There is no
+The product is the C library (include/*.h); this module only loads it, wraps
+its calls, and turns non-zero status codes into exceptions.  What the ABI is --
+prototypes, struct mirrors, enum mirrors -- is stated in abi.py.  There is no
 Python or CPU implementation of any operator here: if the library or a gfx950
 device is missing, calls fail loudly.
 """
@@ -14,152 +15,18 @@ from pathlib import Path
 
 import numpy as np
 
+from .abi import (  # noqa: F401
+    ATTN_ARITH, ATTN_KERNEL, DENSE_MAX_GRID, DENSE_MAX_LABELS, DENSE_TOKEN_TILE, ENUMS, EXPORTS, FEATURE_DTYPES, FP32_MATH,
+    GALLERY_DTYPES, GALLERY_MAX_SPLITS, GALLERY_ROW_TILE, GALLERY_SOURCES, OP_NAMES, PIXEL_LAYOUTS, POS_MODES, PRECISIONS,
+    PROTOTYPES, QKV_FORMS, RESIZE_FILTERS, SHARD_FN, STRUCTS, TOKEN_LAYOUTS, TOPK_SCORES,
+    AttnBuffers, AttnSpecC, Box, CompareReport, DenseBuffers, DenseSpecC, FeatureBuffers, FeatureSpecC, GalleryBuffers,
+    GallerySpecC, ImageData, ImageU8, Network, PixelNorm, PosResampleC, ResizeCrop, RolloutBuffers, RolloutSpecC, TopKBuffers,
+    TopKSpecC, VitConfig, declare, f32p, voidp,
+)
+
 PKG_DIR = Path(__file__).resolve().parent.parent
 LIB_PATH = PKG_DIR / "libvit_hip.so"
 CSRC = PKG_DIR / "csrc"
-
-f32p = C.POINTER(C.c_float)
-voidp = C.c_void_p
-
-# Every symbol include/kernelHandler.h, include/ViT_opencl.h and include/Network.h declare.
-EXPORTS = [
-    "vh_device_count", "vh_init", "vh_last_error", "vh_device_name",
-    "vh_stream_create", "vh_stream_destroy", "vh_stream_sync", "vh_device_sync",
-    "vh_event_create", "vh_event_destroy", "vh_event_record", "vh_stream_wait_event", "vh_event_sync",
-    "vh_event_elapsed_ms",
-    "vh_malloc", "vh_free", "vh_host_alloc", "vh_host_free", "vh_memset", "vh_h2d", "vh_d2h", "vh_d2d",
-    "vh_launch_patch_embed", "vh_launch_layer_norm", "vh_launch_linear", "vh_launch_attention",
-    "vh_launch_softmax",
-    "vit_config_preset", "vit_config_tokens", "vit_config_num_tensors", "vit_config_tensor_size",
-    "ViT_opencl", "vit_hip_last_call_seconds", "vit_hip_create", "vit_hip_destroy", "vit_hip_forward", "vit_hip_forward_device",
-    "vit_hip_config", "vit_hip_stream", "vit_hip_max_batch", "vit_hip_weight", "vit_hip_read_tokens",
-    "vit_hip_profile_enable", "vit_hip_profile_read", "vit_hip_profile_select", "vit_hip_create_ex", "vit_hip_precision",
-    "vit_hip_export_planes", "vit_hip_create_from_planes",
-    "vh_patch_embed_workspace", "vh_launch_patch_embed_ws", "vh_patch_planes_k", "vh_launch_conv_weight_planes",
-    "vh_launch_patch_embed_planes", "vh_launch_split3_planes", "vh_launch_linear_w3",
-    "vh_launch_split2h_planes", "vh_launch_linear_h2", "vh_launch_attention_h2", "vh_launch_attention_f16",
-    "vh_launch_absmax",
-    "vh_launch_split3_rows", "vh_launch_merge3_rows", "vh_launch_layer_norm_p3", "vh_launch_attention_p3",
-    "vh_launch_linear_p3", "vh_launch_split_rows", "vh_launch_merge_rows", "vh_launch_layer_norm_planes", "vh_layer_norm_planes_max_embed",
-    "vh_launch_attention_planes_bf16", "vh_launch_linear_planes", "vh_launch_attention_planes",
-    "vh_launch_quantize_mx_rows", "vh_launch_quantize_mx_act", "vh_mx_act_scale_bytes", "vh_gemm_tile_class", "vh_launch_linear_mx", "vh_launch_layer_norm_mx",
-    "vh_launch_attention_planes_f16", "vh_launch_linear_mx_planes_f16", "vh_launch_attention_planes_f16_mx",
-    "vh_launch_attention_planes_f16_hd80", "vh_launch_attention_planes_f16_hd80_operand", "vh_launch_attention_long",
-    "vh_launch_gather_rows", "vit_hip_set_last_layer_cls_only",
-    "vh_launch_conv_weight_planes_parts", "vh_launch_patch_embed_planes3",
-    "vh_launch_colsum_planes3", "vh_launch_patch_embed_planes3_norm", "vh_launch_linear_p3_norm", "vh_launch_linear_p3_resid_norm",
-    "vh_launch_fold_gamma", "vh_launch_fold_bias", "vh_launch_colsum_operand", "vh_launch_patch_embed_planes_norm",
-    "vh_launch_linear_planes_norm", "vh_launch_linear_planes_resid_norm", "vh_launch_linear_mx_norm",
-    "vh_launch_linear_mx_resid_norm", "vit_hip_ln_fold",
-    "vh_set_device", "vit_hip_create_multi", "vit_hip_forward_multi", "vit_hip_destroy_multi", "vit_hip_multi_devices",
-    "vit_hip_multi_ctx", "vit_shard_range", "vit_shard_run", "vit_shard_run_timed", "vit_hip_multi_last_enqueue_ms",
-    "vit_hip_forward_device_multi", "vit_hip_device", "vh_set_error",
-    "vit_synth_fill", "vit_synth_tensor", "vit_synth_image",
-    "load_image_data", "load_weights", "vit_write_image_file", "vit_write_weight_file",
-    "vit_write_result_file", "vit_compare_rows",
-    "vh_launch_patch_embed_planes_u8", "vh_launch_expand_u8", "vit_pixel_norm_from_mean_std", "vit_hip_forward_device_u8",
-    "vit_hip_forward_u8",
-    "vh_launch_resize_crop_u8", "vit_resize_crop_geometry", "vit_hip_resize_crop_u8", "vit_hip_forward_device_u8_resized",
-    "vit_hip_forward_u8_resized",
-    "vit_box_check", "vit_box_rows", "vit_tile_boxes", "vit_hip_crop_boxes_u8", "vit_hip_forward_device_u8_boxes",
-    "vit_hip_forward_u8_boxes",
-    "vh_feature_readout_scratch", "vh_launch_feature_readout", "vit_feature_sizes", "vit_hip_set_features",
-    "vit_hip_set_features_host",
-    "vh_launch_linear_math", "vh_launch_patch_embed_ws_math", "vh_launch_attention_rows",
-    "vh_launch_topk", "vit_topk_check", "vit_hip_set_topk", "vit_hip_set_topk_host", "vit_write_result_file_topk",
-    "vh_cls_attention_head_dim_ok", "vh_launch_cls_attention", "vit_attn_sizes", "vit_hip_set_attention",
-    "vit_hip_set_attention_host",
-    "vh_rollout_workspace", "vh_rollout_max_tokens", "vh_launch_rollout_step", "vh_launch_rollout_read", "vit_rollout_sizes",
-    "vit_hip_set_rollout", "vit_hip_set_rollout_host",
-    "vh_gallery_query_tile", "vh_gallery_splits", "vh_gallery_workspace", "vh_launch_gallery_topk", "vit_gallery_check",
-    "vit_hip_set_gallery", "vit_hip_set_gallery_host",
-    "vh_launch_dense_logits", "vh_launch_dense_labels", "vit_dense_sizes", "vit_hip_set_dense", "vit_hip_set_dense_host",
-    "vh_launch_resample_pos_embed", "vit_resample_check", "vit_hip_create_at_resolution",
-    "vit_config_canonical", "vit_config_grid", "vit_config_sizeof", "vit_resample_check_hw", "vit_hip_create_at_size",
-    "vh_launch_patch_embed_planes_hw", "vh_patch_embed_workspace_hw", "vh_launch_patch_embed_rows_hw", "vh_launch_expand_u8_hw",
-    "vh_launch_linear_p3_cols", "vh_launch_attention_planes_cls", "vit_hip_last_layer_pending",
-]
-
-# include/kernelHandler.h: fp32_math of vh_launch_linear_math / vh_launch_patch_embed_ws_math; arith and kernel of
-# vh_launch_attention_rows
-FP32_MATH = {"split3": 0, "native": 1}
-ATTN_ARITH = {"native": 0, "fp16": 1, "fp16x2": 2, "split3": 3}
-ATTN_KERNEL = {"auto": 0, "streaming": 1}
-
-
-class VitConfig(C.Structure):
-    """`vit_config` (include/ViT_opencl.h)."""
-
-    _fields_ = [
-        ("img_size", C.c_int), ("patch_size", C.c_int), ("in_chans", C.c_int),
-        ("num_classes", C.c_int), ("embed_dim", C.c_int), ("depth", C.c_int),
-        ("num_heads", C.c_int), ("mlp_hidden", C.c_int), ("eps", C.c_double),
-        ("img_width", C.c_int),   # 0: img_size (square); otherwise the input is img_size rows by img_width columns
-    ]
-
-    @property
-    def width(self) -> int:
-        """columns of an input image (its rows are img_size)"""
-        return self.img_width or self.img_size
-
-    @property
-    def grid(self) -> tuple:
-        """(gh, gw): the patch grid, row-major (vit_config_grid)"""
-        gh, gw = C.c_int(), C.c_int()
-        lib().vit_config_grid(C.byref(self), C.byref(gh), C.byref(gw))
-        return gh.value, gw.value
-
-    def image_shape(self, n: int, layout: str = "chw") -> tuple:
-        """the shape of n input images: [n][C][H][W] (fp32, and bytes in layout "chw") or [n][H][W][C] (bytes, "hwc")"""
-        h, w, ch = self.img_size, self.width, self.in_chans
-        return (n, h, w, ch) if layout == "hwc" else (n, ch, h, w)
-
-
-class PixelNorm(C.Structure):
-    """`vit_pixel_norm` (include/ViT_opencl.h): x = (float)u * scale[c] + bias[c], each step rounded to fp32."""
-
-    _fields_ = [("scale", C.c_float * 4), ("bias", C.c_float * 4)]
-
-
-PIXEL_LAYOUTS = {"hwc": 0, "chw": 1}
-
-
-class ImageU8(C.Structure):
-    """`vit_image_u8` (include/ViT_opencl.h): one 8-bit image of any size; data is a host or device pointer."""
-
-    _fields_ = [("data", C.c_void_p), ("height", C.c_int), ("width", C.c_int), ("row_stride", C.c_long)]
-
-
-class ResizeCrop(C.Structure):
-    """`vit_resize_crop` (include/ViT_opencl.h): shorter side resized to resize_short, then the centre crop."""
-
-    _fields_ = [("resize_short", C.c_int), ("filter", C.c_int)]
-
-
-RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}
-
-
-class Box(C.Structure):
-    """`vit_box_u8` (include/ViT_opencl.h): a region (left, top, right, bottom) of image `image` of an images array."""
-
-    _fields_ = [("image", C.c_int), ("box", C.c_float * 4)]
-
-
-class FeatureSpecC(C.Structure):
-    """`vit_feature_spec` (include/ViT_opencl.h)."""
-
-    _fields_ = [("n_taps", C.c_int), ("taps", C.c_int * 4), ("final_norm", C.c_int), ("l2_normalize", C.c_int),
-                ("dtype", C.c_int), ("token_layout", C.c_int)]
-
-
-class FeatureBuffers(C.Structure):
-    """`vit_feature_buffers` (include/ViT_opencl.h): device or host pointers, each may be NULL."""
-
-    _fields_ = [("cls", C.c_void_p), ("pooled", C.c_void_p), ("tokens", C.c_void_p)]
-
-
-FEATURE_DTYPES = {"f32": 0, "bf16": 1}
-TOKEN_LAYOUTS = {"nlc": 0, "nchw": 1}
 
 
 class FeatureSpec:
@@ -182,21 +49,6 @@ class FeatureSpec:
                             FEATURE_DTYPES[self.dtype], TOKEN_LAYOUTS[self.token_layout])
 
 
-class TopKSpecC(C.Structure):
-    """`vit_topk_spec` (include/ViT_opencl.h)."""
-
-    _fields_ = [("k", C.c_int), ("score_kind", C.c_int)]
-
-
-class TopKBuffers(C.Structure):
-    """`vit_topk_buffers` (include/ViT_opencl.h): device or host pointers; scores may be NULL."""
-
-    _fields_ = [("labels", C.c_void_p), ("scores", C.c_void_p)]
-
-
-TOPK_SCORES = {"probs": 0, "logits": 1}
-
-
 class TopKSpec:
     """A top-k request: the k best classes per image (1..32) with their scores ("probs" | "logits")."""
 
@@ -205,22 +57,6 @@ class TopKSpec:
 
     def c_struct(self) -> TopKSpecC:
         return TopKSpecC(self.k, TOPK_SCORES[self.scores])
-
-
-class AttnSpecC(C.Structure):
-    """`vit_attn_spec` (include/ViT_opencl.h)."""
-
-    _fields_ = [("n_taps", C.c_int), ("taps", C.c_int * 4)]
-
-
-class AttnBuffers(C.Structure):
-    """`vit_attn_buffers` (include/ViT_opencl.h): device or host pointers; each may be NULL, not both."""
-
-    _fields_ = [("heads", C.c_void_p), ("mean", C.c_void_p)]
-
-
-# include/kernelHandler.h: qkv_form of vh_launch_cls_attention
-QKV_FORMS = {"rows_f32": 0, "planes3": 1, "planes_f16": 2}
 
 
 class AttentionSpec:
@@ -242,18 +78,6 @@ def attention_sizes(cfg: "VitConfig", spec: AttentionSpec):
     return tuple(o.value for o in out)
 
 
-class RolloutSpecC(C.Structure):
-    """`vit_rollout_spec` (include/ViT_opencl.h)."""
-
-    _fields_ = [("first_layer", C.c_int)]
-
-
-class RolloutBuffers(C.Structure):
-    """`vit_rollout_buffers` (include/ViT_opencl.h): a device or host pointer."""
-
-    _fields_ = [("rollout", C.c_void_p)]
-
-
 class RolloutSpec:
     """A rollout request: the first layer of the product (0-based or negative from the end; 0 is the standard rollout)."""
 
@@ -270,24 +94,6 @@ def rollout_sizes(cfg: "VitConfig", spec: RolloutSpec):
     cs = spec.c_struct()
     check(lib().vit_rollout_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_rollout_sizes")
     return tuple(o.value for o in out)
-
-
-class GallerySpecC(C.Structure):
-    """`vit_gallery_spec` (include/ViT_opencl.h)."""
-
-    _fields_ = [("source", C.c_int), ("tap", C.c_int), ("final_norm", C.c_int), ("l2_normalize", C.c_int), ("k", C.c_int),
-                ("dtype", C.c_int), ("n_rows", C.c_long), ("row_stride", C.c_long), ("d_rows", C.c_void_p)]
-
-
-class GalleryBuffers(C.Structure):
-    """`vit_gallery_buffers` (include/ViT_opencl.h): device or host pointers; scores may be NULL."""
-
-    _fields_ = [("indices", C.c_void_p), ("scores", C.c_void_p)]
-
-
-GALLERY_SOURCES = {"cls": 0, "pooled": 1}
-GALLERY_DTYPES = {"f32": 0, "bf16": 1}
-GALLERY_MAX_SPLITS, GALLERY_ROW_TILE = 1024, 128   # VH_GALLERY_MAX_SPLITS, VH_GALLERY_ROW_TILE (include/kernelHandler.h)
 
 
 class GallerySpec:
@@ -314,22 +120,6 @@ def gallery_check(cfg: "VitConfig", spec: GallerySpec) -> int:
     return out.value
 
 
-class DenseSpecC(C.Structure):
-    """`vit_dense_spec` (include/ViT_opencl.h)."""
-
-    _fields_ = [("tap", C.c_int), ("final_norm", C.c_int), ("n_labels", C.c_int), ("out_h", C.c_int), ("out_w", C.c_int),
-                ("weight_stride", C.c_long), ("d_weight", C.c_void_p), ("d_bias", C.c_void_p)]
-
-
-class DenseBuffers(C.Structure):
-    """`vit_dense_buffers` (include/ViT_opencl.h): device or host pointers; scores and patch_logits may be NULL."""
-
-    _fields_ = [("labels", C.c_void_p), ("scores", C.c_void_p), ("patch_logits", C.c_void_p)]
-
-
-DENSE_MAX_LABELS, DENSE_MAX_GRID, DENSE_TOKEN_TILE = 256, 64, 128   # VH_DENSE_* (include/kernelHandler.h)
-
-
 class DenseSpec:
     """A dense request: a label per pixel of an out_h x out_w map (0: the model's img_size) from a linear head of n_labels
     (2..256) rows over the patch tokens behind layer `tap`, read as a FeatureSpec((tap,), final_norm) would give them.  The
@@ -353,15 +143,6 @@ def dense_sizes(cfg: "VitConfig", spec: DenseSpec):
     cs = spec.c_struct()
     check(lib().vit_dense_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_dense_sizes")
     return tuple(o.value for o in out)
-
-
-class PosResampleC(C.Structure):
-    """`vit_pos_resample` (include/ViT_opencl.h)."""
-
-    _fields_ = [("mode", C.c_int), ("align_corners", C.c_int)]
-
-
-POS_MODES = {"bicubic": 0, "bilinear": 1}   # VIT_POS_* / VH_POS_*
 
 
 def _pos_mode(mode) -> int:
@@ -494,29 +275,6 @@ def host_image_descs(images, layout: str):
     return arr, keep
 
 
-class CompareReport(C.Structure):
-    """`vit_compare_report` (include/ViT_opencl.h)."""
-    _fields_ = [("rows", C.c_int), ("classes", C.c_int), ("max_abs_diff", C.c_double), ("mean_abs_diff", C.c_double),
-                ("top1_equal", C.c_int), ("top1_equal_or_near_tie", C.c_int), ("top5_overlap", C.c_double),
-                ("nonfinite", C.c_int)]
-
-
-class ImageData(C.Structure):
-    """`ImageData` (include/Network.h; reference Network.h:7-14)."""
-
-    _fields_ = [("n", C.c_int), ("c", C.c_int), ("h", C.c_int), ("w", C.c_int), ("data", f32p)]
-
-
-class Network(C.Structure):
-    """`Network` (include/Network.h; reference Network.h:19-23)."""
-
-    _fields_ = [("data", f32p), ("size", C.c_size_t)]
-
-
-# int fn(void *arg, int shard, int lo, int hi) -- the callback type of vit_shard_run
-SHARD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int)
-
-
 class VitHipError(RuntimeError):
     pass
 
@@ -553,232 +311,8 @@ def lib() -> C.CDLL:
         except ImportError:
             pass
     # VIT_HIP_LIB: a differently built copy of the same library (kernel tuning experiments only)
-    L = C.CDLL(os.environ.get("VIT_HIP_LIB") or str(LIB_PATH))
-    i, sz = C.c_int, C.c_size_t
-    L.vh_last_error.restype = C.c_char_p
-    L.vh_device_name.restype = C.c_char_p
-    L.vh_init.argtypes = [i]
-    L.vh_stream_create.argtypes = [C.POINTER(voidp)]
-    L.vh_stream_destroy.argtypes = [voidp]
-    L.vh_stream_sync.argtypes = [voidp]
-    L.vh_event_create.argtypes = [C.POINTER(voidp)]
-    L.vh_event_destroy.argtypes = [voidp]
-    L.vh_event_record.argtypes = [voidp, voidp]
-    L.vh_stream_wait_event.argtypes = [voidp, voidp]
-    L.vh_event_sync.argtypes = [voidp]
-    L.vh_event_elapsed_ms.argtypes = [C.POINTER(C.c_float), voidp, voidp]
-    L.vh_malloc.argtypes = [C.POINTER(voidp), sz]
-    L.vh_free.argtypes = [voidp]
-    L.vh_host_alloc.argtypes = [C.POINTER(voidp), sz]
-    L.vh_host_free.argtypes = [voidp]
-    L.vh_memset.argtypes = [voidp, i, sz, voidp]
-    L.vh_h2d.argtypes = [voidp, voidp, sz, voidp]
-    L.vh_d2h.argtypes = [voidp, voidp, sz, voidp]
-    L.vh_d2d.argtypes = [voidp, voidp, sz, voidp]
-    L.vh_launch_patch_embed.argtypes = [voidp] + [voidp] * 6 + [i] * 5
-    L.vh_launch_patch_embed_ws.argtypes = [voidp] + [voidp] * 6 + [i] * 5 + [voidp, sz]
-    L.vh_launch_patch_embed_ws_math.argtypes = [voidp] + [voidp] * 6 + [i] * 5 + [voidp, sz, i]
-    L.vh_patch_embed_workspace.argtypes = [i] * 5
-    L.vh_patch_planes_k.argtypes = [i, i]
-    L.vh_launch_conv_weight_planes.argtypes = [voidp, voidp, voidp, i, i, i]
-    L.vh_launch_patch_embed_planes.argtypes = [voidp] + [voidp] * 6 + [i] * 5 + [voidp, sz]
-    L.vh_patch_embed_workspace.restype = sz
-    L.vh_launch_layer_norm.argtypes = [voidp] + [voidp] * 4 + [i, i, C.c_long, C.c_long, C.c_double]
-    L.vh_launch_linear.argtypes = [voidp] + [voidp] * 4 + [i, i, i, i, voidp]
-    L.vh_launch_linear_math.argtypes = [voidp] + [voidp] * 4 + [i, i, i, i, voidp, i]
-    L.vh_launch_attention.argtypes = [voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_attention_rows.argtypes = [voidp, voidp, voidp, i, i, i, i, i, i, i]
-    L.vh_launch_attention_h2.argtypes = [voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_attention_f16.argtypes = [voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_split3_planes.argtypes = [voidp, voidp, voidp, i, i]
-    L.vh_launch_linear_w3.argtypes = [voidp] + [voidp] * 4 + [i, i, i, i, voidp]
-    L.vh_launch_split2h_planes.argtypes = [voidp, voidp, voidp, i, i, C.c_float]
-    L.vh_launch_linear_h2.argtypes = [voidp, voidp, voidp, C.c_float, voidp, voidp, i, i, i, i, voidp]
-    L.vh_launch_softmax.argtypes = [voidp, voidp, voidp, i, i]
-    L.vh_launch_split3_rows.argtypes = [voidp, voidp, voidp, i, i]
-    L.vh_launch_merge3_rows.argtypes = [voidp, voidp, voidp, i, i]
-    L.vh_launch_layer_norm_p3.argtypes = [voidp] + [voidp] * 4 + [i, i, C.c_long, C.c_double]
-    L.vh_launch_attention_p3.argtypes = [voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_linear_p3.argtypes = [voidp, voidp, i, voidp, voidp, voidp, i, i, i, i, voidp]
-    L.vh_launch_split_rows.argtypes = [voidp, voidp, voidp, i, i, i]
-    L.vh_launch_merge_rows.argtypes = [voidp, voidp, voidp, i, i, i]
-    L.vh_launch_layer_norm_planes.argtypes = [voidp] + [voidp] * 4 + [i, i, i, C.c_long, C.c_double]
-    L.vh_layer_norm_planes_max_embed.argtypes = [i]
-    L.vh_launch_attention_planes_bf16.argtypes = [voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_attention_planes.argtypes = [voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_gather_rows.argtypes = [voidp, voidp, voidp, i, i, i, i, i]
-    L.vit_hip_set_last_layer_cls_only.argtypes = [voidp, i]
-    L.vit_hip_last_layer_pending.argtypes = [voidp]
-    L.vh_launch_attention_planes_f16.argtypes = [voidp, voidp, voidp, i, i, i, i, i]
-    L.vh_launch_attention_planes_f16_mx.argtypes = [voidp, voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_attention_planes_f16_hd80.argtypes = [voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_attention_planes_f16_hd80_operand.argtypes = [voidp, voidp, voidp, voidp, i, i, i, i, i]
-    L.vh_launch_attention_long.argtypes = [voidp, voidp, i, voidp, i, i, i, i]
-    L.vh_launch_linear_mx_planes_f16.argtypes = [voidp, voidp, voidp, voidp, voidp, voidp, voidp, i, i, i]
-    L.vh_launch_quantize_mx_rows.argtypes = [voidp, voidp, voidp, voidp, i, i]
-    L.vh_launch_layer_norm_mx.argtypes = [voidp] + [voidp] * 5 + [i, i, C.c_long, C.c_double]
-    L.vh_launch_linear_mx.argtypes = [voidp, voidp, voidp, voidp, voidp, voidp, voidp, voidp, i, i, i, i, voidp]
-    L.vh_launch_linear_planes.argtypes = [voidp, voidp, i, voidp, voidp, i, voidp, i, i, i, i, voidp]
-    L.vh_launch_conv_weight_planes_parts.argtypes = [voidp, voidp, voidp, i, i, i, i]
-    L.vh_launch_patch_embed_planes3.argtypes = [voidp] + [voidp] * 6 + [i] * 5 + [voidp, sz]
-    L.vh_launch_colsum_planes3.argtypes = [voidp, voidp, voidp, i, i]
-    L.vh_launch_patch_embed_planes3_norm.argtypes = [voidp] + [voidp] * 6 + [i] * 5 + [voidp, sz, voidp, voidp]
-    L.vh_launch_linear_p3_norm.argtypes = [voidp, voidp, i, voidp, voidp, voidp, voidp, voidp, C.c_double, i, i, i, i]
-    L.vh_launch_linear_p3_resid_norm.argtypes = [voidp, voidp, voidp, voidp, voidp, voidp, i, i, i, voidp, voidp]
-    L.vh_launch_quantize_mx_act.argtypes = [voidp, voidp, voidp, voidp, i, i]
-    L.vh_mx_act_scale_bytes.argtypes = [i, i]
-    L.vh_mx_act_scale_bytes.restype = sz
-    L.vh_gemm_tile_class.argtypes = [i, i, i, i, i, i, i, C.POINTER(C.c_int)]
-    L.vh_launch_fold_gamma.argtypes = [voidp, voidp, voidp, voidp, i, i]
-    L.vh_launch_fold_bias.argtypes = [voidp, voidp, voidp, voidp, voidp, i, i]
-    L.vh_launch_colsum_operand.argtypes = [voidp, voidp, voidp, voidp, i, i]
-    L.vh_launch_patch_embed_planes_norm.argtypes = [voidp] + [voidp] * 6 + [i] * 5 + [voidp, sz, voidp, voidp, voidp]
-    L.vh_launch_linear_planes_norm.argtypes = [voidp, voidp, i, voidp, voidp, voidp, voidp, voidp, C.c_double, i, i, i, i]
-    L.vh_launch_linear_planes_resid_norm.argtypes = [voidp, voidp, voidp, voidp, voidp, voidp, i, i, i, voidp, voidp, voidp]
-    L.vh_launch_linear_mx_norm.argtypes = [voidp, voidp, voidp, i, voidp, voidp, voidp, voidp, voidp, voidp, voidp, C.c_double, i, i, i, i]
-    L.vh_launch_linear_mx_resid_norm.argtypes = [voidp, voidp, voidp, voidp, voidp, voidp, voidp, voidp, i, i, i, voidp, voidp, voidp]
-    L.vit_hip_ln_fold.argtypes = [voidp]
-    L.vit_config_preset.argtypes = [C.POINTER(VitConfig), C.c_char_p]
-    L.vit_config_tokens.argtypes = [C.POINTER(VitConfig)]
-    L.vit_config_num_tensors.argtypes = [C.POINTER(VitConfig)]
-    L.vit_config_tensor_size.argtypes = [C.POINTER(VitConfig), i]
-    L.vit_config_tensor_size.restype = sz
-    L.ViT_opencl.argtypes = [C.POINTER(ImageData), C.POINTER(Network), C.POINTER(f32p)]
-    L.ViT_opencl.restype = None
-    L.vit_hip_last_call_seconds.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.vit_hip_last_call_seconds.restype = None
-    L.vit_hip_create.argtypes = [C.POINTER(voidp), C.POINTER(VitConfig), C.POINTER(Network), i, i, i]
-    L.vit_hip_create_ex.argtypes = [C.POINTER(voidp), C.POINTER(VitConfig), C.POINTER(Network), i, i, i, i]
-    L.vit_hip_precision.argtypes = [voidp]
-    L.vit_hip_export_planes.argtypes = [voidp, C.c_char_p]
-    L.vit_hip_create_from_planes.argtypes = [C.POINTER(voidp), C.c_char_p, i, i]
-    f = C.c_float
-    L.vh_launch_absmax.argtypes = [voidp, voidp, sz, voidp]
-    L.vit_hip_destroy.argtypes = [voidp]
-    L.vit_hip_destroy.restype = None
-    L.vh_set_device.argtypes = [i]
-    L.vit_hip_create_multi.argtypes = [C.POINTER(voidp), C.POINTER(VitConfig), C.POINTER(Network), i, C.POINTER(i), i, i, i]
-    L.vit_hip_forward_multi.argtypes = [voidp, C.POINTER(ImageData), i, f32p, C.POINTER(f32p)]
-    L.vit_hip_destroy_multi.argtypes = [voidp]
-    L.vit_hip_destroy_multi.restype = None
-    L.vit_hip_multi_devices.argtypes = [voidp]
-    L.vit_hip_multi_ctx.argtypes = [voidp, i]
-    L.vit_hip_multi_ctx.restype = voidp
-    L.vit_hip_device.argtypes = [voidp]
-    L.vit_hip_forward_device_multi.argtypes = [voidp, C.POINTER(voidp), C.POINTER(i), voidp, voidp]
-    L.vh_set_error.argtypes = [i, C.c_char_p]
-    L.vit_shard_range.argtypes = [i, i, i, C.POINTER(i), C.POINTER(i)]
-    L.vit_shard_range.restype = None
-    L.vit_shard_run.argtypes = [i, i, SHARD_FN, voidp]
-    L.vit_shard_run_timed.argtypes = [i, i, SHARD_FN, voidp, C.POINTER(C.c_double)]
-    L.vit_hip_multi_last_enqueue_ms.argtypes = [voidp, C.POINTER(C.c_double), i]
-    L.vit_hip_forward.argtypes = [voidp, C.POINTER(ImageData), i, f32p, C.POINTER(f32p)]
-    L.vit_hip_forward_device.argtypes = [voidp, voidp, i, voidp, voidp, voidp]
-    L.vit_hip_stream.argtypes = [voidp]
-    L.vit_hip_stream.restype = voidp
-    L.vit_hip_max_batch.argtypes = [voidp]
-    L.vit_hip_weight.argtypes = [voidp, i]
-    L.vit_hip_weight.restype = voidp
-    L.vit_hip_read_tokens.argtypes = [voidp, i, f32p]
-    L.vit_hip_profile_enable.argtypes = [voidp, i]
-    L.vit_hip_profile_select.argtypes = [voidp, C.c_uint]
-    L.vit_hip_profile_read.argtypes = [voidp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
-    L.vit_synth_fill.argtypes = [f32p, sz, C.c_ulonglong, C.c_float, C.c_float]
-    L.vit_synth_fill.restype = None
-    L.vit_synth_tensor.argtypes = [C.POINTER(VitConfig), i, C.c_ulonglong, f32p]
-    L.vit_synth_tensor.restype = None
-    L.vit_synth_image.argtypes = [C.POINTER(VitConfig), i, f32p]
-    L.vit_synth_image.restype = None
-    L.load_image_data.argtypes = [C.c_char_p]
-    L.load_image_data.restype = C.POINTER(ImageData)
-    L.load_weights.argtypes = [C.c_char_p, C.POINTER(Network), i]
-    L.load_weights.restype = None
-    L.vit_write_image_file.argtypes = [C.c_char_p, C.POINTER(ImageData), i]
-    L.vit_write_weight_file.argtypes = [C.c_char_p, i, C.c_char_p, f32p, sz]
-    L.vit_write_result_file.argtypes = [C.c_char_p, C.POINTER(f32p), i, i]
-    L.vit_compare_rows.argtypes = [f32p, f32p, i, i, C.c_double, C.POINTER(CompareReport)]
-    u8p = C.POINTER(C.c_ubyte)
-    L.vh_launch_patch_embed_planes_u8.argtypes = [voidp, voidp, i, f32p, f32p] + [voidp] * 5 + [i] * 5 + [voidp, sz, i] + [voidp] * 3
-    L.vh_launch_expand_u8.argtypes = [voidp, voidp, i, f32p, f32p, voidp, i, i, i]
-    L.vit_pixel_norm_from_mean_std.argtypes = [C.POINTER(PixelNorm), f32p, f32p, i]
-    L.vit_hip_forward_device_u8.argtypes = [voidp, voidp, i, i, C.POINTER(PixelNorm), voidp, voidp, voidp]
-    L.vit_hip_forward_u8.argtypes = [voidp, u8p, i, i, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
-    imgp, rcp, ip = C.POINTER(ImageU8), C.POINTER(ResizeCrop), C.POINTER(C.c_int)
-    L.vh_launch_resize_crop_u8.argtypes = [voidp, voidp, i, i, i, i, i, voidp, sz, voidp]
-    L.vit_resize_crop_geometry.argtypes = [i, i, rcp, i, ip, ip, ip, ip]
-    L.vit_hip_resize_crop_u8.argtypes = [voidp, imgp, i, i, rcp, voidp, voidp]
-    L.vit_hip_forward_device_u8_resized.argtypes = [voidp, imgp, i, i, rcp, C.POINTER(PixelNorm), voidp, voidp, voidp]
-    L.vit_hip_forward_u8_resized.argtypes = [voidp, imgp, i, i, rcp, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
-    boxp = C.POINTER(Box)
-    L.vit_box_check.argtypes = [i, i, C.POINTER(C.c_float)]
-    L.vit_box_rows.argtypes = [i, C.c_float, C.c_float, i, i, ip, ip]
-    L.vit_tile_boxes.argtypes = [i, i, i, i, i, boxp, i]
-    L.vit_hip_crop_boxes_u8.argtypes = [voidp, imgp, i, boxp, i, i, i, voidp, voidp]
-    L.vit_hip_forward_device_u8_boxes.argtypes = [voidp, imgp, i, boxp, i, i, i, C.POINTER(PixelNorm), voidp, voidp, voidp]
-    L.vit_hip_forward_u8_boxes.argtypes = [voidp, imgp, i, boxp, i, i, i, C.POINTER(PixelNorm), f32p, C.POINTER(f32p)]
-    L.vh_feature_readout_scratch.argtypes = [i, i, i]
-    L.vh_feature_readout_scratch.restype = sz
-    L.vh_launch_feature_readout.argtypes = [voidp, voidp, voidp, C.c_long, voidp, voidp, C.c_double] + [i] * 9 + [voidp] * 4 + [sz]
-    specp, bufp, szp = C.POINTER(FeatureSpecC), C.POINTER(FeatureBuffers), C.POINTER(sz)
-    L.vit_feature_sizes.argtypes = [C.POINTER(VitConfig), specp, szp, szp, szp]
-    L.vit_hip_set_features.argtypes = [voidp, specp, bufp]
-    L.vit_hip_set_features_host.argtypes = [voidp, specp, bufp]
-    ip32 = C.POINTER(C.c_int)
-    L.vh_launch_topk.argtypes = [voidp, voidp, i, i, i, i, voidp, voidp]
-    tkp, tbp = C.POINTER(TopKSpecC), C.POINTER(TopKBuffers)
-    L.vit_topk_check.argtypes = [C.POINTER(VitConfig), tkp]
-    L.vit_hip_set_topk.argtypes = [voidp, tkp, tbp]
-    L.vit_hip_set_topk_host.argtypes = [voidp, tkp, tbp]
-    L.vit_write_result_file_topk.argtypes = [C.c_char_p, ip32, f32p, i, i]
-    L.vh_cls_attention_head_dim_ok.argtypes = [i]
-    L.vh_launch_cls_attention.argtypes = [voidp, voidp] + [i] * 7 + [voidp, voidp]
-    asp, abp = C.POINTER(AttnSpecC), C.POINTER(AttnBuffers)
-    L.vit_attn_sizes.argtypes = [C.POINTER(VitConfig), asp, szp, szp]
-    L.vit_hip_set_attention.argtypes = [voidp, asp, abp]
-    L.vit_hip_set_attention_host.argtypes = [voidp, asp, abp]
-    L.vh_rollout_workspace.argtypes = [i, i]
-    L.vh_rollout_workspace.restype = sz
-    L.vh_rollout_max_tokens.argtypes = [i]
-    L.vh_launch_rollout_step.argtypes = [voidp, voidp] + [i] * 5 + [voidp, voidp, voidp]
-    L.vh_launch_rollout_read.argtypes = [voidp, voidp, i, i, voidp]
-    rsp, rbp = C.POINTER(RolloutSpecC), C.POINTER(RolloutBuffers)
-    L.vit_rollout_sizes.argtypes = [C.POINTER(VitConfig), rsp, szp, szp]
-    L.vit_hip_set_rollout.argtypes = [voidp, rsp, rbp]
-    L.vit_hip_set_rollout_host.argtypes = [voidp, rsp, rbp]
-    L.vh_gallery_query_tile.argtypes = [i]
-    L.vh_gallery_splits.argtypes = [i, C.c_long]
-    L.vh_gallery_workspace.argtypes = [i, C.c_long, i, i]
-    L.vh_gallery_workspace.restype = sz
-    L.vh_launch_gallery_topk.argtypes = [voidp, voidp, i, i, voidp, i, C.c_long, C.c_long, i, i, voidp, voidp, voidp]
-    gsp, gbp = C.POINTER(GallerySpecC), C.POINTER(GalleryBuffers)
-    L.vit_gallery_check.argtypes = [C.POINTER(VitConfig), gsp, szp]
-    L.vit_hip_set_gallery.argtypes = [voidp, gsp, gbp]
-    L.vit_hip_set_gallery_host.argtypes = [voidp, gsp, gbp]
-    L.vh_launch_dense_logits.argtypes = [voidp, voidp, C.c_long, C.c_long, i, i, i, voidp, C.c_long, voidp, i, voidp]
-    L.vh_launch_dense_labels.argtypes = [voidp, voidp, i, i, i, i, i, i, voidp, voidp]
-    dsp, dbp = C.POINTER(DenseSpecC), C.POINTER(DenseBuffers)
-    L.vit_dense_sizes.argtypes = [C.POINTER(VitConfig), dsp, szp, szp, szp, szp]
-    L.vit_hip_set_dense.argtypes = [voidp, dsp, dbp]
-    L.vit_hip_set_dense_host.argtypes = [voidp, dsp, dbp]
-    prp = C.POINTER(PosResampleC)
-    L.vh_launch_resample_pos_embed.argtypes = [voidp, voidp, voidp] + [i] * 8
-    L.vit_resample_check.argtypes = [C.POINTER(VitConfig), i, prp, C.POINTER(VitConfig)]
-    L.vit_hip_create_at_resolution.argtypes = [C.POINTER(voidp), voidp, i, i, prp]
-    L.vit_resample_check_hw.argtypes = [C.POINTER(VitConfig), i, i, prp, C.POINTER(VitConfig)]
-    L.vit_hip_create_at_size.argtypes = [C.POINTER(voidp), voidp, i, i, i, prp]
-    L.vit_config_canonical.argtypes = [C.POINTER(VitConfig), C.POINTER(VitConfig), C.c_char_p]
-    L.vit_config_grid.argtypes = [C.POINTER(VitConfig), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.vit_config_grid.restype = None
-    L.vit_config_sizeof.argtypes = []
-    L.vh_launch_patch_embed_planes_hw.argtypes = [voidp, voidp, voidp, i, f32p, f32p] + [voidp] * 5 + [i] * 6 + [voidp, sz, i] + [voidp] * 3
-    L.vh_patch_embed_workspace_hw.argtypes = [i] * 6
-    L.vh_patch_embed_workspace_hw.restype = sz
-    L.vh_launch_patch_embed_rows_hw.argtypes = [voidp] + [voidp] * 6 + [i] * 6 + [voidp, sz, i]
-    L.vh_launch_expand_u8_hw.argtypes = [voidp, voidp, i, f32p, f32p, voidp, i, i, i, i]
-    L.vit_hip_config.argtypes = [voidp]
-    L.vit_hip_config.restype = C.POINTER(VitConfig)
-    _lib = L
-    return L
+    _lib = declare(C.CDLL(os.environ.get("VIT_HIP_LIB") or str(LIB_PATH)))
+    return _lib
 
 
 def check(rc: int, what: str = "") -> None:
@@ -896,7 +430,7 @@ def _host_ptr(a):
 class ViTHip:
     """Resident-weights context (vit_hip_create / forward / destroy)."""
 
-    PRECISIONS = {"f32": 0, "bf16": 1, "fp8": 2, "f32_fp16x2": 3}
+    PRECISIONS, OP_NAMES = PRECISIONS, OP_NAMES     # abi.py's, under the names callers know
 
     def __init__(self, cfg: VitConfig, weights: list[np.ndarray], device: int = 0, max_batch: int = 64,
                  precision: str = "f32"):
@@ -918,8 +452,6 @@ class ViTHip:
         self.L, self._weights, self.ctx = lib(), None, voidp()
         check(self.L.vit_hip_create_from_planes(C.byref(self.ctx), str(path).encode(), device, max_batch),
               "vit_hip_create_from_planes")
-        self.L.vit_hip_config.restype = C.POINTER(VitConfig)
-        self.L.vit_hip_config.argtypes = [voidp]
         self.cfg = VitConfig.from_buffer_copy(self.L.vit_hip_config(self.ctx).contents)
         self.precision = {v: k for k, v in cls.PRECISIONS.items()}[self.L.vit_hip_precision(self.ctx)]
         self.max_batch, self.tokens = max_batch, tokens(self.cfg)
@@ -1297,9 +829,6 @@ class ViTHip:
         check(self.L.vit_hip_read_tokens(self.ctx, n, fptr(out)), "vit_hip_read_tokens")
         return out
 
-    OP_NAMES = ["patch_embed", "layer_norm", "qkv_gemm", "attention", "out_proj_gemm", "fc1_gemm",
-                "fc2_gemm", "head_gemm", "softmax", "out_proj_gemm_cls", "fc1_gemm_cls", "fc2_gemm_cls"]
-
     def set_last_layer_cls_only(self, on: bool) -> bool:
         """The older switch for the last layer's output projection and MLP on the class-token rows only (identical logits;
         the default where the plan allows it).  Returns the previous setting of this flag."""
@@ -1346,7 +875,7 @@ class ViTHipMulti:
         devs = (C.c_int * len(devices))(*devices)
         check(self.L.vit_hip_create_multi(C.byref(self.handle), C.byref(cfg), networks(weights), len(weights), devs,
                                           len(devices), max_batch_per_device,
-                                          {"f32": 0, "bf16": 1, "fp8": 2, "f32_fp16x2": 3}[precision]), "vit_hip_create_multi")
+                                          PRECISIONS[precision]), "vit_hip_create_multi")
 
     def forward(self, images: np.ndarray):
         images = np.ascontiguousarray(images, dtype=np.float32)
