@@ -662,6 +662,62 @@ int vit_dense_sizes(const vit_config *cfg, const vit_dense_spec *spec, size_t *l
 int vit_hip_set_dense(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *d_bufs);
 int vit_hip_set_dense_host(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *h_bufs);
 
+/* ---- whole frames: overlapping windows of one large 8-bit image, their logits blended into one label per frame pixel ----
+ * The sliding-window protocol of semantic segmentation (mmseg's mode="slide") in one call: the windows (vit_box_u8 boxes of
+ * ONE frame, e.g. from vit_tile_boxes; `image` must be 0) are cut and resized as vit_hip_forward_device_u8_boxes does, run
+ * through the model with the dense head `spec->head`, and their patch logits are upsampled to their boxes, averaged where
+ * boxes overlap and ranked per frame pixel by vh_launch_dense_stitch (include/kernelHandler.h, which states the definition
+ * bit for bit and its error bound): labels u8 [H][W] (required), scores fp32 [H][W] (the winning mean logit; may be NULL),
+ * cover u8 [H][W] (how many windows cover the pixel, at most 255; may be NULL); a pixel that no window covers gets
+ * fill_label.  Neither the windows' tokens nor any [C][H][W] logits leave the GPU or exist.
+ * A call: everything is validated before anything is queued; scratch is allocated (the patch logits of all windows
+ * [n_windows][T - 1][n_labels] fp32, one chunk's patch logits, the boxes and the block index; refused with code 1 when that
+ * fails); a device-form dense request of the call's own is armed with out_h = out_w = 1 (the per-window label maps that
+ * nobody reads shrink to one byte each); the windows run in chunks of at most max_batch through
+ * vit_hip_forward_device_u8_boxes on the context's stream, each chunk's patch logits copied device to device to their place
+ * behind it (one request armed once: re-arming per chunk would allocate and free the request's scratch per chunk, and a
+ * chunk's offset in the frame's buffer is not 16-byte aligned for every T - 1 and n_labels); the request is disarmed, the
+ * stitch launched, the stream waited for, the scratch freed.  Both calls are complete on return, and on return -- success or
+ * failure -- the context has no dense request armed and holds no allocation of the call's.
+ * Requests of the other five kinds armed in device form are served per chunk, as by any forward: their buffers hold the
+ * last chunk's outputs afterwards.
+ * Device form: d_frame->data and the three output buffers are device memory of the context's device, the outputs 16-byte
+ * aligned.  Host form: host memory; the frame is uploaded once, whole (the row packing of vit_hip_forward_u8_boxes is not
+ * needed for one frame), the device form runs, and the buffers asked for are copied back.
+ * Code 1 with a message, nothing launched: a NULL argument (norm as for the u8 forwards); a dense request of the caller's
+ * armed in either form; any request armed in host form; a non-square context; a model or a head vit_hip_set_dense does not
+ * take; head.out_h or head.out_w not 0; fill_label outside 0..255; n_windows < 1 or n_windows * (T - 1) >= 2^31 - 128; a frame
+ * outside vit_image_u8's limits; a window outside the frame (vit_stitch_check) or with image != 0; an unknown layout or filter;
+ * no labels buffer or a misaligned device buffer.
+ * Out of scope: tapered blend weights, per-pixel probabilities, several frames per call, non-square contexts, vit_hip_multi. */
+typedef struct vit_frame_spec {
+    vit_dense_spec head;   /* tap, final_norm, n_labels, weight_stride, d_weight, d_bias; out_h and out_w must be 0 */
+    int fill_label;        /* 0..255: the label of pixels no window covers */
+} vit_frame_spec;
+typedef struct vit_frame_buffers { unsigned char *labels; float *scores; unsigned char *cover; } vit_frame_buffers; /* [H][W]; labels required */
+/* host only, no device: validates spec (everything but the pointers), the frame size and n_windows against cfg; bytes of
+ * labels (= of cover; scores are as many floats) and the device scratch of a call without the ids of its block index (4
+ * bytes each, vit_stitch_index) and without one chunk's patch logits (max_batch windows'); either pointer may be NULL; 0, or
+ * 1 with a message */
+int vit_frame_sizes(const vit_config *cfg, const vit_frame_spec *spec, int frame_h, int frame_w, int n_windows,
+                    size_t *labels_bytes, size_t *scratch_bytes);
+/* host only: every one of the n boxes (l, t, r, b: 4 floats each) is a box of a frame_h x frame_w frame -- vit_box_check's
+ * domain, 1 <= frame_h, frame_w <= 16384, n >= 1; 0, or 1 with a message that starts with `who` */
+int vit_stitch_check(int frame_h, int frame_w, const float *boxes, int n, const char *who);
+/* host only: the block index of vh_launch_dense_stitch.  Blocks of block x block pixels, row-major, blocks_x = ceil(frame_w
+ * / block); offsets [blocks_y * blocks_x + 1] and the ids of block k at ids[offsets[k] .. offsets[k + 1]), strictly ascending
+ * window indices.  EXACT: a window is listed for a block iff it covers at least one pixel centre of the block (its covered
+ * columns and rows are ranges, found with the kernel's own fp32 comparisons).  Returns the number of ids; ids == NULL only
+ * sizes (offsets, when given, are still written); more ids than `capacity`, a bad argument or a count of 2^31 or more: -1
+ * with a message. */
+long vit_stitch_index(int frame_h, int frame_w, int block, const float *boxes, int n, int *offsets, int *ids, long capacity);
+int vit_hip_segment_frame_device_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_frame, const vit_box_u8 *windows, int n_windows,
+                                    int layout, int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec,
+                                    const vit_frame_buffers *d_out);
+int vit_hip_segment_frame_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const vit_box_u8 *windows, int n_windows,
+                             int layout, int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec,
+                             const vit_frame_buffers *h_out);
+
 /* Debug hook: copy the residual stream of the last forward ([n*tokens][embed], un-normalised) to the host.  Where that
  * forward ran the last layer behind its attention on the class-token rows only, the full layer's launches run on all rows of
  * its images first, on the context's stream: the rows are those of the full evaluation, bit for bit; a second read runs

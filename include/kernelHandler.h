@@ -627,6 +627,74 @@ int vh_launch_dense_labels(vh_stream_t s, const float *patch_logits /* [n][grid_
                            int grid_h, int grid_w, int n_labels, int out_h, int out_w,
                            unsigned char *labels /* u8 [n][out_h][out_w] */, float *scores /* fp32, may be NULL */);
 
+/* Dense stitch (csrc/dense_stitch.hip; the kernel under vit_hip_segment_frame_u8, include/ViT_opencl.h): one label per pixel
+ * of a frame_h x frame_w frame from the patch logits of n_windows overlapping windows of it -- the sliding-window protocol
+ * (upsample every window's logits to its box, average where boxes overlap, take the best class) as a GATHER: per pixel the
+ * windows that cover it are found, each window's patch logits are interpolated at that pixel and averaged; no frame-sized
+ * logits buffer exists.  u = 2^-24 below.
+ * Inputs.  patch_logits [n_windows][GH * GW][C] fp32 in device memory, as vh_launch_dense_logits writes them.  windows:
+ * n_windows boxes (l, t, r, b), 4 floats each, in frame pixel coordinates, in HOST memory; offsets / ids: the block index of
+ * vit_stitch_index(frame_h, frame_w, VH_STITCH_BLOCK, windows, n_windows, ..) (include/ViT_opencl.h), in HOST memory:
+ * offsets [blocks_y * blocks_x + 1], the ids of block k at ids[offsets[k] .. offsets[k + 1]), strictly ascending window
+ * indices; a block's list must hold every window that covers a pixel centre of the block and may hold more.
+ * Definition, in these fp32 expressions, each operation rounded once, fmaf fused.
+ * Coverage: window w covers pixel (X, Y) iff l <= cx < r and t <= cy < b, cx = (float)X + 0.5f, cy = (float)Y + 0.5f (exact
+ * values, exact comparisons).
+ * Coordinates of the pixel in w:
+ *   bw = r - l;  rx = (float)GW / bw;  tx = cx - l;  sx = fmaxf(fmaf(tx, rx, -0.5f), 0.0f);  c0 = min((int)sx, GW - 1);
+ *   c1 = min(c0 + 1, GW - 1);  wx = sx - (float)c0;  ux = 1.0f - wx;   and bh, ry, ty, sy, r0, r1, wy, uy from cy, t, b, GH alike.
+ * Value of class c in w, the three lerps of vh_launch_dense_labels on w's logits L (horizontal first, then vertical):
+ *   top = fmaf(wx, L[r0,c1][c], ux * L[r0,c0][c]);  bot = fmaf(wx, L[r1,c1][c], ux * L[r1,c0][c]);  v_w[c] = fmaf(wy, bot, uy * top)
+ * Consequence: for a box of integer corners with r - l = out_w and b - t = out_h, v_w at (X, Y) has the bits
+ * vh_launch_dense_labels gives at (X - l, Y - t) for that out_h x out_w: bw and (X + 0.5) - l are exact there, so rx, sx and
+ * all that follows are that launcher's own values.
+ * Blend: over the windows that cover the pixel, in ascending window index, acc = v_first, then acc = acc + v_next (fp32 adds);
+ * m[c] = acc / (float)count, one correctly rounded fp32 division: the plain mean of the slide protocol.
+ * labels[Y][X] = the c that vh_launch_topk's rule ranks first among m[0..C): the largest, equal values (-0 == +0) to the lowest
+ * c, NaN below -inf (all NaN: 0).  scores[Y][X] (may be NULL) = that m[c]'s bits, a NaN as 0x7FC00000.  cover[Y][X] (may be
+ * NULL) = min(count, 255).  Asking for scores or cover changes no label.  A pixel that no window covers: labels = fill_label,
+ * scores = 0x7FC00000, cover = 0.
+ * The bits of a pixel depend on that pixel, the windows that cover it with the order of their indices, and those windows'
+ * logits: not on the frame size, on other windows, on what else a block's list names or on any tiling.  No atomics: the same
+ * output on every run.
+ * Error bound, against this definition evaluated in float64 (coverage is exact in both) on the same fp32 logits and boxes,
+ * per (pixel, class), for count <= 2^22:
+ *   |m - m64| <= (1 + A) max_w B_w + A max_w |v64_w|,      A = (count + 1) (1 + 2 count u) u,
+ * B_w = the interpolation part of vh_launch_dense_labels' bound on window w with the coordinate constant doubled:
+ *   B_w = k'(GH, GW) u M_w,   k' = 8 (GH + GW) + 16,   M_w as M there (|L| over rows r0 - 1 .. r0 + 2, columns c0 - 1 .. c0 + 2 of w);
+ * where the logits themselves come from vh_launch_dense_logits, that launcher's corner term (E + 8) u (sum |x w| + |b|), its
+ * maximum over the four corners, is added to B_w.  Derivation.  The coordinate: bw, rx, tx and the fmaf round once each where
+ * vh_launch_dense_labels has two roundings: rx = (GW / (r - l)) (1 + e1)(1 + e2), tx = (cx - l)(1 + e3), sx = (tx rx - 0.5)(1 +
+ * e4), |e| <= u, tx / (r - l) < 1 and |tx rx - 0.5| < GW give |sx - sx64| < 4 GW u (there: 2 GW u); the surface argument is
+ * that launcher's, hence 8 GH u M + 8 GW u M; the three lerps and the slack are unchanged (7 + 9).  The blend: count - 1 adds
+ * err by at most g sum_w |v_w|, g = (count - 1) u / (1 - (count - 1) u) <= (count - 1)(1 + 2 count u) u, which after the
+ * division is g max_w |v_w|; the division adds u |m| <= u (1 + g) max |v_w|; together at most A max |v_w|, and |v_w| <=
+ * |v64_w| + B_w.  The windows' own errors reach the mean with at most their maximum.
+ * One workgroup of VH_STITCH_BLOCK^2 threads per block of VH_STITCH_BLOCK x VH_STITCH_BLOCK pixels, one pixel per thread;
+ * classes in chunks of 16 whose running sums stay in registers; inside a chunk the block's list in ascending order; corner
+ * logits are read from global memory, 16 bytes at a time (a frame's patch logits are some tens of MB: L2 and MALL traffic).
+ * Staging each window's rectangle of patches in LDS was built and measured: the same bits, 10-18 % slower.
+ * The boxes and the index are copied into d_scratch (vh_dense_stitch_scratch bytes, the CALLER'S device memory, 16-byte
+ * aligned) with synchronous copies before the launch: the three host arrays may be freed when the launcher returns; the
+ * kernel itself is asynchronous on s and reads d_scratch when it runs.  Until it has run, d_scratch must neither be freed
+ * nor written, nor handed to another call of this launcher: that call's copies do not wait for s and would replace the index
+ * under the queued kernel.  One scratch per launch in flight (the frame calls allocate theirs per call and wait for s).
+ * Limits: 2 <= n_labels <= VH_DENSE_MAX_LABELS; 1 <= grid_h, grid_w <= VH_DENSE_MAX_GRID; 1 <= frame_h, frame_w <=
+ * VH_STITCH_MAX_SIDE; n_windows >= 1, n_windows * grid_h * grid_w < 2^31 - 128; every box finite with 0 <= l, r <= frame_w,
+ * 0 <= t, b <= frame_h, r - l >= 1, b - t >= 1 (vit_stitch_check); offsets[0] = 0, offsets non-decreasing, offsets[blocks] =
+ * n_ids < 2^31, the ids of a block strictly ascending in [0, n_windows); 0 <= fill_label <= 255; scratch_bytes >=
+ * vh_dense_stitch_scratch; every device pointer 16-byte aligned.  Anything else: code 1 with a message that starts with the
+ * launcher's name, no launch, nothing written.  No cap on how many windows cover a pixel or fall into a block.  No reference
+ * counterpart. */
+#define VH_STITCH_BLOCK 16
+#define VH_STITCH_MAX_SIDE 16384
+size_t vh_dense_stitch_scratch(int n_windows, int frame_h, int frame_w, long n_ids);   /* bytes; 0 for arguments out of range */
+int vh_launch_dense_stitch(vh_stream_t s, const float *patch_logits /* device [n_windows][grid_h * grid_w][n_labels] */,
+                           int n_windows, int grid_h, int grid_w, int n_labels, const float *windows /* host [n_windows][4] */,
+                           int frame_h, int frame_w, const int *offsets /* host [blocks + 1] */, const int *ids /* host */,
+                           int fill_label, void *d_scratch, size_t scratch_bytes, unsigned char *labels /* u8 [frame_h][frame_w] */,
+                           float *scores /* fp32, may be NULL */, unsigned char *cover /* u8, may be NULL */);
+
 /* Position embedding resampled to another patch grid (csrc/pos_resample.hip; the kernel under vit_hip_create_at_resolution,
  * include/ViT_opencl.h).  src [prefix + in_h * in_w][E] fp32 -> dst [prefix + out_h * out_w][E] fp32, both contiguous.
  * Definition.  The first `prefix` rows (the class token's) are copied bit for bit.  The remaining rows are a row-major

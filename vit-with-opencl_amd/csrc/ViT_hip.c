@@ -1169,6 +1169,218 @@ SETTER(vit_hip_set_dense, dense, vit_dense_spec, vit_dense_buffers, 0)
 SETTER(vit_hip_set_dense_host, dense, vit_dense_spec, vit_dense_buffers, 1)
 #undef SETTER
 
+/* ---- whole frames (include/ViT_opencl.h): windows through the box forward with a dense request of the call's own, their
+ * patch logits blended per frame pixel by vh_launch_dense_stitch.  Public pieces composed; nothing of a forward changes ---- */
+
+/* spec's head as the call arms it: one label per window, which nobody reads */
+static vit_dense_spec frame_head(const vit_frame_spec *spec)
+{
+    vit_dense_spec head = spec->head;
+    head.out_h = head.out_w = 1;
+    return head;
+}
+
+/* What needs no context: spec, frame size and window count against cfg; P and C of the patch logits */
+static int frame_spec_check(const char *who, const vit_config *cfg, const vit_frame_spec *spec, int frame_h, int frame_w, int n_windows,
+                            size_t *patch_elems)
+{
+    if (!cfg || !spec)
+        return ingest_refuse(who, "NULL argument");
+    if (cfg->img_width != 0 && cfg->img_width != cfg->img_size)
+        return ingest_refuse(who, "the context's input is non-square: the box forms make square crops");
+    if (spec->head.out_h != 0 || spec->head.out_w != 0)
+        return ingest_refuse(who, "head.out_h and head.out_w must be 0: the output is the frame");
+    if (spec->fill_label < 0 || spec->fill_label > 255)
+        return ingest_refuse(who, "fill_label must be in 0..255");
+    if (frame_h < 1 || frame_w < 1 || frame_h > VH_STITCH_MAX_SIDE || frame_w > VH_STITCH_MAX_SIDE)
+        return ingest_refuse(who, "the frame's height and width must be in 1..16384");
+    const vit_dense_spec head = frame_head(spec);
+    if (vit_dense_sizes(cfg, &head, NULL, NULL, patch_elems, NULL))
+        return 1;
+    if (n_windows < 1 || (size_t)n_windows * (*patch_elems / (size_t)head.n_labels) >= 2147483647u - 128u)
+        return ingest_refuse(who, "n_windows must be positive, n_windows * (T - 1) below 2^31 - 128");
+    return 0;
+}
+
+int vit_frame_sizes(const vit_config *cfg, const vit_frame_spec *spec, int frame_h, int frame_w, int n_windows, size_t *labels_bytes,
+                    size_t *scratch_bytes)
+{
+    size_t patch_elems = 0;
+    if (frame_spec_check("vit_frame_sizes", cfg, spec, frame_h, frame_w, n_windows, &patch_elems))
+        return 1;
+    if (labels_bytes)
+        *labels_bytes = (size_t)frame_h * frame_w;
+    if (scratch_bytes)   /* all windows' patch logits, the boxes and the offsets; not the ids (4 bytes each) nor one chunk's patch
+                          * logits, which depend on the boxes and on max_batch */
+        *scratch_bytes = align_up((size_t)n_windows * patch_elems * sizeof(float), 16) + vh_dense_stitch_scratch(n_windows, frame_h, frame_w, 0);
+    return 0;
+}
+
+/* Everything both forms refuse, before anything is queued or allocated; *patch_elems: a window's patch logits, (T - 1) * n_labels */
+static int frame_check(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *frame, const vit_box_u8 *windows, int n_windows, int layout,
+                       int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_frame_buffers *out, int on_device,
+                       size_t *patch_elems)
+{
+    if (!ctx || !frame || !windows || !norm || !spec || !out || !frame->data)
+        return ingest_refuse(who, "NULL argument");
+    if (frame_spec_check(who, &ctx->cfg, spec, frame->height, frame->width, n_windows, patch_elems))
+        return 1;
+    if (ctx->req.dense.head.form != FEAT_NONE)
+        return ingest_refuse(who, "a dense request is armed (vit_hip_set_dense / _host): the call arms its own; disarm it first");
+    struct serving sv;
+    if (requests_serving(&ctx->req, who, FEAT_DEVICE, &sv))   /* a request armed in host form: the call forwards in device form */
+        return 1;
+    if (!spec->head.d_weight || (((uintptr_t)spec->head.d_weight | (uintptr_t)spec->head.d_bias) & 15))
+        return ingest_refuse(who, "the head's weight must be given, weight and bias 16-byte aligned");
+    if (!out->labels)
+        return ingest_refuse(who, "no labels buffer");
+    if (on_device && (((uintptr_t)out->labels | (uintptr_t)out->scores | (uintptr_t)out->cover) & 15))
+        return ingest_refuse(who, "device output buffers must be 16-byte aligned");
+    for (int i = 0; i < n_windows; ++i) {
+        char why[120];
+        if (windows[i].image != 0)
+            return ingest_refuse(who, "every window's image must be 0: a call takes one frame");
+        if (vit_box_check(frame->height, frame->width, windows[i].box)) {   /* vit_stitch_check's rule, window by window */
+            snprintf(why, sizeof why, "window %d is not a box of the frame (finite, inside it, at least 1 px each way)", i);
+            return ingest_refuse(who, why);
+        }
+    }
+    /* the frame, layout, filter and channels as the box forward will check them, chunk by chunk */
+    for (int first = 0; first < n_windows; first += ctx->max_batch) {
+        const int m = n_windows - first < ctx->max_batch ? n_windows - first : ctx->max_batch;
+        const struct ingest_src src = {.kind = INGEST_U8_BOXES, .on_device = 1, .images = frame, .n_images = 1, .boxes = windows + first,
+                                       .filter = filter, .layout = layout, .norm = norm};
+        if (source_check(who, ctx, &src, m))
+            return 1;
+    }
+    return 0;
+}
+
+/* The device form behind its checks */
+static int frame_run(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *d_frame, const vit_box_u8 *windows, int n_windows, int layout,
+                     int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_frame_buffers *d_out, size_t patch_elems)
+{
+    int rc = 0, armed = 0;
+    const int H = d_frame->height, W = d_frame->width, mb = ctx->max_batch;
+    const int C = spec->head.n_labels;
+    int grid_h, grid_w;
+    vit_config_grid(&ctx->cfg, &grid_h, &grid_w);
+    float *boxes4 = malloc((size_t)n_windows * 4 * sizeof(float));
+    int *offsets = NULL, *ids = NULL;
+    void *d_all = NULL, *d_chunk = NULL, *d_lab = NULL, *d_index = NULL;
+    if (!boxes4) {
+        rc = ingest_refuse(who, "out of host memory");
+        goto fail;
+    }
+    for (int i = 0; i < n_windows; ++i)
+        memcpy(boxes4 + 4 * (size_t)i, windows[i].box, 4 * sizeof(float));
+    const long blocks = (long)((H + VH_STITCH_BLOCK - 1) / VH_STITCH_BLOCK) * ((W + VH_STITCH_BLOCK - 1) / VH_STITCH_BLOCK);
+    const long n_ids = vit_stitch_index(H, W, VH_STITCH_BLOCK, boxes4, n_windows, NULL, NULL, 0);
+    if (n_ids < 0) {
+        rc = 1;
+        goto fail;
+    }
+    offsets = malloc((size_t)(blocks + 1) * sizeof(int));
+    ids = malloc((size_t)(n_ids > 0 ? n_ids : 1) * sizeof(int));
+    if (!offsets || !ids) {
+        rc = ingest_refuse(who, "out of host memory");
+        goto fail;
+    }
+    if (vit_stitch_index(H, W, VH_STITCH_BLOCK, boxes4, n_windows, offsets, ids, n_ids) != n_ids) {
+        rc = 1;
+        goto fail;
+    }
+    const size_t index_bytes = vh_dense_stitch_scratch(n_windows, H, W, n_ids);
+    TRY(vh_set_device(ctx->device));
+    if (vh_malloc(&d_all, align_up((size_t)n_windows * patch_elems * sizeof(float), 16)) || vh_malloc(&d_chunk, align_up((size_t)mb * patch_elems * sizeof(float), 16)) ||
+        vh_malloc(&d_lab, align_up((size_t)mb, 16)) || vh_malloc(&d_index, index_bytes)) {
+        rc = ingest_refuse(who, "the scratch of the call (patch logits of all windows, block index) cannot be allocated");
+        goto fail;
+    }
+    const vit_dense_spec head = frame_head(spec);
+    const vit_dense_buffers bufs = {.labels = d_lab, .scores = NULL, .patch_logits = d_chunk};
+    TRY(vit_hip_set_dense(ctx, &head, &bufs));
+    armed = 1;
+    for (int first = 0; first < n_windows; first += mb) {
+        const int m = n_windows - first < mb ? n_windows - first : mb;
+        TRY(vit_hip_forward_device_u8_boxes(ctx, d_frame, 1, windows + first, m, layout, filter, norm, NULL, NULL, 0));
+        TRY(vh_d2d((float *)d_all + (size_t)first * patch_elems, d_chunk, (size_t)m * patch_elems * sizeof(float), ctx->stream));
+    }
+    armed = 0;
+    TRY(vit_hip_set_dense(ctx, NULL, NULL));
+    TRY(vh_launch_dense_stitch(ctx->stream, d_all, n_windows, grid_h, grid_w, C, boxes4, H, W, offsets, ids, spec->fill_label, d_index,
+                               index_bytes, d_out->labels, d_out->scores, d_out->cover));
+    TRY(vh_stream_sync(ctx->stream));
+fail:
+    if (armed) {   /* keep the failure's message over the disarming's */
+        char kept[512];
+        snprintf(kept, sizeof kept, "%s", vh_last_error());
+        vit_hip_set_dense(ctx, NULL, NULL);
+        vh_set_error(rc, kept);
+    }
+    if (d_all || d_chunk || d_lab || d_index) {
+        if (rc)
+            vh_stream_sync(ctx->stream);
+        void *dev[] = {d_all, d_chunk, d_lab, d_index};
+        for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); ++i)
+            if (dev[i])
+                vh_free(dev[i]);
+    }
+    free(boxes4);
+    free(offsets);
+    free(ids);
+    return rc;
+}
+
+int vit_hip_segment_frame_device_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_frame, const vit_box_u8 *windows, int n_windows, int layout,
+                                    int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_frame_buffers *d_out)
+{
+    static const char who[] = "vit_hip_segment_frame_device_u8";
+    size_t patch_elems = 0;
+    if (frame_check(who, ctx, d_frame, windows, n_windows, layout, filter, norm, spec, d_out, 1, &patch_elems))
+        return 1;
+    return frame_run(who, ctx, d_frame, windows, n_windows, layout, filter, norm, spec, d_out, patch_elems);
+}
+
+int vit_hip_segment_frame_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const vit_box_u8 *windows, int n_windows, int layout, int filter,
+                             const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_frame_buffers *h_out)
+{
+    static const char who[] = "vit_hip_segment_frame_u8";
+    int rc = 0;
+    size_t patch_elems = 0;
+    if (frame_check(who, ctx, frame, windows, n_windows, layout, filter, norm, spec, h_out, 0, &patch_elems))
+        return 1;
+    /* what the caller's image owns: rows of `row` bytes, row_stride apart -- the last row of the last plane ends with its pixels,
+     * not with its stride (a column band of a larger array), so that is where the upload ends */
+    const size_t planes = layout == VIT_PIXELS_HWC ? 1 : (size_t)ctx->cfg.in_chans;
+    const size_t row = (size_t)frame->width * (layout == VIT_PIXELS_HWC ? (size_t)ctx->cfg.in_chans : 1);
+    const size_t frame_bytes = (planes * (size_t)frame->height - 1) * (size_t)frame->row_stride + row;
+    const size_t px = (size_t)frame->height * frame->width;
+    void *d_data = NULL, *d_lab = NULL, *d_sc = NULL, *d_cov = NULL;
+    TRY(vh_set_device(ctx->device));
+    if (vh_malloc(&d_data, align_up(frame_bytes, 16)) || vh_malloc(&d_lab, align_up(px, 16)) ||
+        (h_out->scores && vh_malloc(&d_sc, px * sizeof(float))) || (h_out->cover && vh_malloc(&d_cov, align_up(px, 16)))) {
+        rc = ingest_refuse(who, "the frame and its outputs cannot be allocated on the device");
+        goto fail;
+    }
+    TRY(vh_h2d(d_data, frame->data, frame_bytes, ctx->stream));
+    const vit_image_u8 d_frame = {.data = d_data, .height = frame->height, .width = frame->width, .row_stride = frame->row_stride};
+    const vit_frame_buffers d_out = {.labels = d_lab, .scores = d_sc, .cover = d_cov};
+    TRY(frame_run(who, ctx, &d_frame, windows, n_windows, layout, filter, norm, spec, &d_out, patch_elems));
+    TRY(vh_d2h(h_out->labels, d_lab, px, ctx->stream));
+    if (d_sc)
+        TRY(vh_d2h(h_out->scores, d_sc, px * sizeof(float), ctx->stream));
+    if (d_cov)
+        TRY(vh_d2h(h_out->cover, d_cov, px, ctx->stream));
+fail:
+    vh_stream_sync(ctx->stream);
+    void *dev[] = {d_data, d_lab, d_sc, d_cov};
+    for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); ++i)
+        if (dev[i])
+            vh_free(dev[i]);
+    return rc;
+}
+
 /* images whose last layer is pending behind the last forward (finish_last_layer); tests */
 int vit_hip_last_layer_pending(const vit_hip_ctx *ctx) { return ctx ? ctx->last_pending : -1; }
 

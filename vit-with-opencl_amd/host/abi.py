@@ -42,6 +42,8 @@ GALLERY_MAX_SPLITS, GALLERY_ROW_TILE = 1024, 128
 enum("VH_GALLERY_", {"max_splits": GALLERY_MAX_SPLITS, "row_tile": GALLERY_ROW_TILE})
 DENSE_MAX_LABELS, DENSE_MAX_GRID, DENSE_TOKEN_TILE = 256, 64, 128
 enum("VH_DENSE_", {"max_labels": DENSE_MAX_LABELS, "max_grid": DENSE_MAX_GRID, "token_tile": DENSE_TOKEN_TILE})
+STITCH_BLOCK, STITCH_MAX_SIDE = 16, 16384
+enum("VH_STITCH_", {"block": STITCH_BLOCK, "max_side": STITCH_MAX_SIDE})
 POS_MODES = enum("VH_POS_", {"bicubic": 0, "bilinear": 1})
 enum("VIT_POS_", POS_MODES)
 
@@ -184,6 +186,18 @@ class DenseBuffers(C.Structure):
     _fields_ = [("labels", p), ("scores", p), ("patch_logits", p)]
 
 
+@mirrors("vit_frame_spec")
+class FrameSpecC(C.Structure):
+    """head: a vit_dense_spec whose out_h and out_w are 0; fill_label for pixels no window covers."""
+    _fields_ = [("head", DenseSpecC), ("fill_label", i)]
+
+
+@mirrors("vit_frame_buffers")
+class FrameBuffers(C.Structure):
+    """device or host pointers, [H][W]; scores and cover may be NULL."""
+    _fields_ = [("labels", p), ("scores", p), ("cover", p)]
+
+
 @mirrors("vit_compare_report")
 class CompareReport(C.Structure):
     _fields_ = [("rows", i), ("classes", i), ("max_abs_diff", d), ("mean_abs_diff", d), ("top1_equal", i),
@@ -321,6 +335,8 @@ PROTOTYPES = {
         _fn("vh_launch_gallery_topk", p, p, i, i, p, i, l, l, i, i, p, p, p),
         _fn("vh_launch_dense_logits", p, p, l, l, i, i, i, p, l, p, i, p),
         _fn("vh_launch_dense_labels", p, p, i, i, i, i, i, i, p, p),
+        _fn("vh_dense_stitch_scratch", i, i, i, l, ret=sz),
+        _fn("vh_launch_dense_stitch", p, p, i, i, i, i, fp, i, i, ip, ip, i, p, sz, p, p, p),
         _fn("vh_launch_resample_pos_embed", p, p, p, i, i, i, i, i, i, i, i),
     ],
     "ViT_opencl.h": [
@@ -393,6 +409,11 @@ PROTOTYPES = {
         _fn("vit_dense_sizes", P(VitConfig), P(DenseSpecC), szp, szp, szp, szp),
         _fn("vit_hip_set_dense", p, P(DenseSpecC), P(DenseBuffers)),
         _fn("vit_hip_set_dense_host", p, P(DenseSpecC), P(DenseBuffers)),
+        _fn("vit_frame_sizes", P(VitConfig), P(FrameSpecC), i, i, i, szp, szp),
+        _fn("vit_stitch_check", i, i, fp, i, s),
+        _fn("vit_stitch_index", i, i, i, fp, i, ip, ip, l, ret=l),
+        _fn("vit_hip_segment_frame_device_u8", p, P(ImageU8), P(Box), i, i, i, P(PixelNorm), P(FrameSpecC), P(FrameBuffers)),
+        _fn("vit_hip_segment_frame_u8", p, P(ImageU8), P(Box), i, i, i, P(PixelNorm), P(FrameSpecC), P(FrameBuffers)),
         _fn("vit_hip_read_tokens", p, i, fp),
         _fn("vit_hip_last_layer_pending", p),
         _fn("vit_hip_profile_enable", p, i),

@@ -18,8 +18,9 @@ import numpy as np
 from .abi import (  # noqa: F401
     ATTN_ARITH, ATTN_KERNEL, DENSE_MAX_GRID, DENSE_MAX_LABELS, DENSE_TOKEN_TILE, ENUMS, EXPORTS, FEATURE_DTYPES, FP32_MATH,
     GALLERY_DTYPES, GALLERY_MAX_SPLITS, GALLERY_ROW_TILE, GALLERY_SOURCES, OP_NAMES, PIXEL_LAYOUTS, POS_MODES, PRECISIONS,
-    PROTOTYPES, QKV_FORMS, RESIZE_FILTERS, SHARD_FN, STRUCTS, TOKEN_LAYOUTS, TOPK_SCORES,
-    AttnBuffers, AttnSpecC, Box, CompareReport, DenseBuffers, DenseSpecC, FeatureBuffers, FeatureSpecC, GalleryBuffers,
+    PROTOTYPES, QKV_FORMS, RESIZE_FILTERS, SHARD_FN, STITCH_BLOCK, STITCH_MAX_SIDE, STRUCTS, TOKEN_LAYOUTS, TOPK_SCORES,
+    AttnBuffers, AttnSpecC, Box, CompareReport, DenseBuffers, DenseSpecC, FeatureBuffers, FeatureSpecC, FrameBuffers, FrameSpecC,
+    GalleryBuffers,
     GallerySpecC, ImageData, ImageU8, Network, PixelNorm, PosResampleC, ResizeCrop, RolloutBuffers, RolloutSpecC, TopKBuffers,
     TopKSpecC, VitConfig, declare, f32p, voidp,
 )
@@ -243,6 +244,36 @@ def tile_boxes(h: int, w: int, tile: int, stride: int, image: int = 0):
     if lib().vit_tile_boxes(h, w, tile, stride, image, arr, n) != n:
         check(1, "vit_tile_boxes")
     return [(b.image, tuple(b.box)) for b in arr]
+
+
+def _boxes4(boxes) -> np.ndarray:
+    """[n][4] float32 (left, top, right, bottom) from an array of that shape or from (image, box) pairs"""
+    if len(boxes) and isinstance(boxes[0], (tuple, list)) and len(boxes[0]) == 2 and not np.isscalar(boxes[0][1]):
+        boxes = [b[1] for b in boxes]
+    return np.ascontiguousarray(np.asarray(boxes, dtype=np.float32).reshape(-1, 4))
+
+
+def stitch_check(frame_h: int, frame_w: int, boxes) -> None:
+    """vit_stitch_check: raises VitHipError unless every box is a window of a frame_h x frame_w frame"""
+    b = _boxes4(boxes)
+    check(lib().vit_stitch_check(frame_h, frame_w, fptr(b), len(b), b"vit_stitch_check"), "vit_stitch_check")
+
+
+def stitch_index(frame_h: int, frame_w: int, boxes, block: int = STITCH_BLOCK):
+    """vit_stitch_index -> (offsets int32 [blocks_y * blocks_x + 1], ids int32): per block of block x block frame pixels,
+    row-major, the strictly ascending indices of the windows (boxes: [n][4] left, top, right, bottom, or (image, box) pairs)
+    that cover at least one pixel centre of the block -- what vh_launch_dense_stitch takes for block = STITCH_BLOCK"""
+    b = _boxes4(boxes)
+    L = lib()
+    n = L.vit_stitch_index(frame_h, frame_w, block, fptr(b), len(b), None, None, 0)
+    if n < 0:
+        check(1, "vit_stitch_index")
+    blocks = -(-frame_h // block) * -(-frame_w // block)
+    offsets, ids = np.zeros(blocks + 1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    if L.vit_stitch_index(frame_h, frame_w, block, fptr(b), len(b), offsets.ctypes.data_as(ip), ids.ctypes.data_as(ip), n) != n:
+        check(1, "vit_stitch_index")
+    return offsets, ids[:n]
 
 
 def image_descs(images) -> C.Array:
@@ -823,6 +854,53 @@ class ViTHip:
         finally:
             self.set_dense_host(None)
         return labels
+
+    def _frame_spec(self, weight, bias, tap, final_norm, fill_label, n_labels=0, weight_stride=0):
+        """(FrameSpecC, what keeps the head's device arrays alive) for the frame calls: the head as _dense_head makes it"""
+        spec = self._dense_head(DenseSpec(n_labels, 0, 0, tap, final_norm, weight_stride), weight, bias)
+        return FrameSpecC(spec.c_struct(), int(fill_label)), (spec.d_weight, spec.d_bias)
+
+    def segment_frame_device(self, d_frame, windows, norm: PixelNorm, weight, bias=None, labels=None, scores=None, cover=None,
+                             filter: str = "bilinear", layout: str = "hwc", tap: int = -1, final_norm: bool = True,
+                             fill_label: int = 255, n_labels: int = 0, weight_stride: int = 0):
+        """vit_hip_segment_frame_device_u8: d_frame is (device pointer, height, width, row_stride), windows a list of (0,
+        (left, top, right, bottom)); labels (uint8 [H][W]), scores (float32, may be None) and cover (uint8, may be None)
+        are DeviceBuffers or device pointers; a head given as DeviceBuffers has n_labels rows weight_stride elements apart
+        (0: embed_dim, and as many rows as the buffer holds).  Complete on return."""
+        fs, keep = self._frame_spec(weight, bias, tap, final_norm, fill_label, n_labels, weight_stride)
+        bufs = FrameBuffers(_device_ptr(labels), _device_ptr(scores), _device_ptr(cover))
+        check(self.L.vit_hip_segment_frame_device_u8(self.ctx, image_descs([d_frame]), box_array(windows), len(windows),
+                                                     PIXEL_LAYOUTS[layout], RESIZE_FILTERS[filter], C.byref(norm), C.byref(fs),
+                                                     C.byref(bufs)), "vit_hip_segment_frame_device_u8")
+        del keep
+
+    def segment_frame(self, frame, weight, bias=None, tile=None, stride=None, windows=None, filter: str = "bilinear", mean=None,
+                      std=None, layout: str = "hwc", tap: int = -1, final_norm: bool = True, fill_label: int = 255,
+                      scores: bool = False, cover: bool = False):
+        """A whole 8-bit frame ([H][W][C] uint8, or [C][H][W] with layout "chw") -> labels [H][W] uint8: the sliding-window
+        protocol on the GPU.  The windows (a list of (0, (left, top, right, bottom)); None: tile_boxes(H, W, tile or the
+        model's img_size, stride or 2 * tile // 3)) are resized as forward_u8_boxes resizes them, normalised with
+        pixel_norm(mean, std) (or a PixelNorm as `mean`) and run through the model; a linear head (weight [C][E], bias [C]
+        or None, as segment takes them) gives every patch its logits, which are upsampled to the window's box, averaged
+        where windows overlap and ranked per frame pixel.  A pixel no window covers gets fill_label.  scores=True / cover=True:
+        returns (labels, scores float32 [H][W] or None, cover uint8 [H][W] or None) -- the winning mean logit and the number
+        of windows over the pixel."""
+        descs, keep = host_image_descs([frame], layout)
+        H, W = descs[0].height, descs[0].width
+        if windows is None:
+            tile = int(tile or self.cfg.img_size)
+            windows = tile_boxes(H, W, tile, int(stride or 2 * tile // 3))
+        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
+        fs, head_keep = self._frame_spec(weight, bias, tap, final_norm, fill_label)
+        out_l = np.empty((H, W), dtype=np.uint8)
+        out_s = np.empty((H, W), dtype=np.float32) if scores else None
+        out_c = np.empty((H, W), dtype=np.uint8) if cover else None
+        bufs = FrameBuffers(*[None if a is None else _host_ptr(a) for a in (out_l, out_s, out_c)])
+        check(self.L.vit_hip_segment_frame_u8(self.ctx, descs, box_array(windows), len(windows), PIXEL_LAYOUTS[layout],
+                                              RESIZE_FILTERS[filter], C.byref(norm), C.byref(fs), C.byref(bufs)),
+              "vit_hip_segment_frame_u8")
+        del keep, head_keep
+        return (out_l, out_s, out_c) if scores or cover else out_l
 
     def read_tokens(self, n: int) -> np.ndarray:
         out = np.empty((n * self.tokens, self.cfg.embed_dim), dtype=np.float32)
