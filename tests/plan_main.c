@@ -5,11 +5,13 @@
  * tensor and operand 256-byte aligned, inside its slab and clear of the others; and every borrower of an arena buffer must
  * fit it.  Built and run by tests/test_plan_host.py under ASan + UBSan; exit status 0 = every check held.
  *   plan_main TABLE          the checks
- *   plan_main TABLE stubs    print what the four sizing stand-ins below return for every shape (held against the library)
+ *   plan_main TABLE limits   print what the sizing functions of csrc/kernel_limits.h, which the plan calls, return for every
+ *                            shape (the library's exported entries are held against them)
  *   plan_main TABLE record   print the table as this code plans it, the inputs kept: how a change that alters a plan cell on
  *                            purpose re-records it
  */
 #include "vit_plan.h"
+#include "kernel_limits.h"
 #include "vit_ingest.h"
 
 #include <stdint.h>
@@ -22,36 +24,6 @@ int vh_set_error(int code, const char *message)
 {
     snprintf(last_error, sizeof last_error, "%s", message);
     return code ? code : 1;
-}
-
-/* The shim's four pure sizing functions restated in plain C (csrc/rowops.hip, gemm_p3.hip, gemm_mfma.hip, gemm_mx.hip) */
-int vh_layer_norm_planes_max_embed(int parts)
-{
-    if (parts != 1 && parts != 3)
-        return 0;
-    const int by_lds = 160 * 1024 / (parts * 16 * 64) * 32;
-    return by_lds < 2048 ? by_lds : 2048;
-}
-
-int vh_patch_planes_k(int in_chans, int patch_size)
-{
-    const int K = in_chans * patch_size * patch_size;
-    return (K + 127) / 128 * 128;
-}
-
-size_t vh_patch_embed_workspace(int n_images, int in_chans, int img_size, int patch_size, int embed_dim)
-{
-    const int K = in_chans * patch_size * patch_size;
-    if (n_images <= 0 || in_chans <= 0 || img_size <= 0 || patch_size <= 0 || embed_dim <= 0 || img_size % patch_size != 0 ||
-        (patch_size % 4 == 0 && K % 32 == 0 && img_size % 4 == 0))
-        return 0;
-    const size_t grid = (size_t)(img_size / patch_size), Kp = ((size_t)K + 31) / 32 * 32;
-    return ((size_t)n_images * grid * grid + (size_t)embed_dim) * Kp * sizeof(float);
-}
-
-size_t vh_mx_act_scale_bytes(int rows, int cols)
-{
-    return rows > 0 && cols > 0 ? (size_t)((cols / 128 + 3) / 4) * 16 * (size_t)rows : 0;
 }
 
 static char context[1200];   /* the line under test, for a failure's message */
@@ -117,7 +89,7 @@ static void check_layout(const struct vit_plan *plan, const vit_config *cfg)
         CHECK(i == 0 || pc[i - 1].at + pc[i - 1].bytes <= pc[i].at, "pieces %d and %d overlap", i - 1, i);
     }
     /* conv_proj's planes are the whole of their slab */
-    CHECK(bytes[SLAB_CONV] == (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * (size_t)cfg->embed_dim * 2 * (size_t)plan->conv_parts,
+    CHECK(bytes[SLAB_CONV] == (size_t)kl_patch_planes_k(cfg->in_chans, cfg->patch_size) * (size_t)cfg->embed_dim * 2 * (size_t)plan->conv_parts,
           "conv slab");
     free(pc);
     free(op);
@@ -142,9 +114,9 @@ static void check_invariants(const struct vit_plan *plan, const vit_config *cfg,
           plan->attn_bytes == plan->y_bytes && rows * 3 * E * (size_t)plan->act_bytes <= plan->qkv_bytes, "activations");
     if (p == VIT_PRECISION_FP8_GEMM) {   /* MX scales behind the values */
         CHECK(plan->e_scales_off >= rows * E && plan->e_scales_off % 256 == 0 &&
-              plan->e_scales_off + vh_mx_act_scale_bytes((int)rows, cfg->embed_dim) <= plan->y_bytes, "scales in y and attn");
+              plan->e_scales_off + kl_mx_act_scale_bytes((int)rows, cfg->embed_dim) <= plan->y_bytes, "scales in y and attn");
         CHECK(plan->hid_scales_off >= rows * F && plan->hid_scales_off % 256 == 0 &&
-              plan->hid_scales_off + vh_mx_act_scale_bytes((int)rows, cfg->mlp_hidden) <= plan->ws_bytes, "scales in hid");
+              plan->hid_scales_off + kl_mx_act_scale_bytes((int)rows, cfg->mlp_hidden) <= plan->ws_bytes, "scales in hid");
     }
     if (plan->cls_only_ok) {   /* x_cls fp32, then attn_cls, y_cls, hid_cls as three-part planes, each 256-byte aligned */
         size_t off[3];
@@ -162,7 +134,8 @@ static void check_invariants(const struct vit_plan *plan, const vit_config *cfg,
         CHECK(plan->crop_off % 256 == 0 && plan->crop_off + n * img <= plan->qkv_bytes, "crops");
         CHECK(n * ingest_max_table_bytes(cfg->img_size) <= plan->ws_bytes, "resize tables");
     }
-    CHECK(vh_patch_embed_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->patch_size, cfg->embed_dim) <= plan->ws_bytes, "patch workspace");
+    CHECK(kl_patch_rows_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->img_size, cfg->patch_size, cfg->embed_dim) <= plan->ws_bytes,
+          "patch workspace");
     CHECK((plan->stats_bytes != 0) == plan->ln_fold, "stats");
 }
 
@@ -170,7 +143,7 @@ int main(int argc, char **argv)
 {
     if (argc < 2)
         return 2;
-    const int stubs = argc > 2 && strcmp(argv[2], "stubs") == 0, record = argc > 2 && strcmp(argv[2], "record") == 0;
+    const int limits = argc > 2 && strcmp(argv[2], "limits") == 0, record = argc > 2 && strcmp(argv[2], "record") == 0;
     FILE *fp = fopen(argv[1], "r");
     if (!fp)
         return 2;
@@ -215,11 +188,11 @@ int main(int argc, char **argv)
                 CHECK(strcmp(want, line) == 0, "plan_make gives\n  %s", want);
             continue;
         }
-        if (stubs) {
+        if (limits) {
             const int rows = mb * plan.tokens;
-            printf("%d %d %d %d %d %d %d : %d %d %zu %zu %zu\n", chans, patch, img, E, F, mb, rows, vh_layer_norm_planes_max_embed(3),
-                   vh_patch_planes_k(chans, patch), vh_patch_embed_workspace(mb, chans, img, patch, E), vh_mx_act_scale_bytes(rows, E),
-                   vh_mx_act_scale_bytes(rows, F));
+            printf("%d %d %d %d %d %d %d : %d %d %zu %zu %zu\n", chans, patch, img, E, F, mb, rows, kl_layer_norm_planes_max_embed(3),
+                   kl_patch_planes_k(chans, patch), kl_patch_rows_workspace(mb, chans, img, img, patch, E), kl_mx_act_scale_bytes(rows, E),
+                   kl_mx_act_scale_bytes(rows, F));
             continue;
         }
         snprintf(want, sizeof want, "%.*s => 0 p=%d fold=%d p3=%d cls=%d attn=%d native=%d tiled=%d T=%d form=%d wp=%d ob=%d os=%d cp=%d ppe=%d "
@@ -239,7 +212,7 @@ int main(int argc, char **argv)
         ++plans;
     }
     fclose(fp);
-    if (!stubs && !record)
+    if (!limits && !record)
         printf("plan table: ok (%d lines, %d plans, %d hand-edited)\n", lines, plans, edited);
     return 0;
 }

@@ -41,37 +41,6 @@ int vh_set_error(int code, const char *message)
     return code ? code : 1;
 }
 
-/* The shim's four pure sizing functions restated in plain C, as tests/plan_main.c restates them (held against the library
- * by tests/test_plan_host.py) */
-int vh_layer_norm_planes_max_embed(int parts)
-{
-    if (parts != 1 && parts != 3)
-        return 0;
-    const int by_lds = 160 * 1024 / (parts * 16 * 64) * 32;
-    return by_lds < 2048 ? by_lds : 2048;
-}
-
-int vh_patch_planes_k(int in_chans, int patch_size)
-{
-    const int K = in_chans * patch_size * patch_size;
-    return (K + 127) / 128 * 128;
-}
-
-size_t vh_patch_embed_workspace(int n_images, int in_chans, int img_size, int patch_size, int embed_dim)
-{
-    const int K = in_chans * patch_size * patch_size;
-    if (n_images <= 0 || in_chans <= 0 || img_size <= 0 || patch_size <= 0 || embed_dim <= 0 || img_size % patch_size != 0 ||
-        (patch_size % 4 == 0 && K % 32 == 0 && img_size % 4 == 0))
-        return 0;
-    const size_t grid = (size_t)(img_size / patch_size), Kp = ((size_t)K + 31) / 32 * 32;
-    return ((size_t)n_images * grid * grid + (size_t)embed_dim) * Kp * sizeof(float);
-}
-
-size_t vh_mx_act_scale_bytes(int rows, int cols)
-{
-    return rows > 0 && cols > 0 ? (size_t)((cols / 128 + 3) / 4) * 16 * (size_t)rows : 0;
-}
-
 /* ---- the six vh_* of the unit: call number fail_in[kind] from now fails with FAIL_STATUS + kind ------------------------- */
 enum { HOST_ALLOC, H2D, D2H, SYNC, N_KINDS, FAIL_STATUS = 700 };
 static const char *const kind_name[N_KINDS] = {"vh_host_alloc", "vh_h2d", "vh_d2h", "vh_stream_sync"};

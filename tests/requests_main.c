@@ -5,9 +5,11 @@
  * predicate and the release of everything.  Built and run by tests/test_requests_host.py under ASan + UBSan; exit status
  * 0 = every check held.
  *   requests_main          the checks
- *   requests_main stubs    print what the four sizing stand-ins below return (held against the library)
+ *   requests_main limits   print what the sizing functions of csrc/kernel_limits.h, which the unit calls, return (the
+ *                          library's exported entries are held against them)
  */
 #include "vit_requests.h"
+#include "kernel_limits.h"
 
 #include <stdint.h>
 #include <stdio.h>
@@ -82,34 +84,6 @@ int vh_malloc(void **out, size_t bytes) { return block_alloc(out, bytes, DEVICE_
 int vh_free(void *p) { return block_free(p, DEVICE_BLOCK); }
 int vh_host_alloc(void **out, size_t bytes) { return block_alloc(out, bytes, PINNED_BLOCK); }
 int vh_host_free(void *p) { return block_free(p, PINNED_BLOCK); }
-
-/* ---- the shim's four pure sizing functions restated in plain C (csrc/attn_map.hip, rollout.hip, gallery.hip) ---------- */
-int vh_cls_attention_head_dim_ok(int head_dim) { return head_dim > 0 && head_dim % 16 == 0 && head_dim <= 128; }
-
-size_t vh_rollout_workspace(int n_images, int tokens)
-{
-    return n_images > 0 && tokens > 0 ? (size_t)n_images * (size_t)tokens * (size_t)tokens * sizeof(float) : 0;
-}
-
-/* 16 score rows of T keys rounded up to 64, + 20, and 16 + 64 staged rows of head_dim + 4, fp32, within 160 KB of LDS */
-int vh_rollout_max_tokens(int head_dim)
-{
-    int T = 0;
-    while (((size_t)16 * (size_t)(T + 64 + 20) + (size_t)80 * (size_t)(head_dim + 4)) * sizeof(float) <= (size_t)160 * 1024)
-        T += 64;
-    return T;
-}
-
-size_t vh_gallery_workspace(int n_queries, long n_rows, int k, int splits)
-{
-    if (n_queries < 1 || n_rows < 1 || k < 1 || splits < 0)
-        return 0;
-    if (splits == 0) {
-        const long tiles = (n_rows + 127) / 128;
-        splits = tiles < 1024 ? (int)tiles : 1024;
-    }
-    return (size_t)n_queries * (size_t)splits * (size_t)k * 8;
-}
 
 /* ---- the context the requests are armed on: all six take it ----------------------------------------------------------- */
 static const vit_config cfg = {32, 8, 3, 10, 64, 2, 4, 128, 1e-6};
@@ -443,16 +417,16 @@ static void check_release_all(void)
 
 int main(int argc, char **argv)
 {
-    if (argc > 1 && strcmp(argv[1], "stubs") == 0) {
+    if (argc > 1 && strcmp(argv[1], "limits") == 0) {
         const int dims[] = {0, 16, 24, 64, 80, 128, 144}, toks[] = {0, 1, 17, 197, 1370};
         const long n_rows[] = {0, 1, 128, 129, 1000, 200000, 2147483647L};
         for (size_t i = 0; i < sizeof dims / sizeof dims[0]; ++i)
-            printf("head_dim %d : %d %d\n", dims[i], vh_cls_attention_head_dim_ok(dims[i]), vh_rollout_max_tokens(dims[i]));
+            printf("head_dim %d : %d %d\n", dims[i], kl_cls_attention_head_dim_ok(dims[i]), kl_rollout_max_tokens(dims[i]));
         for (size_t i = 0; i < sizeof toks / sizeof toks[0]; ++i)
-            printf("rollout %d %d : %zu\n", MAX_BATCH, toks[i], vh_rollout_workspace(MAX_BATCH, toks[i]));
+            printf("rollout %d %d : %zu\n", MAX_BATCH, toks[i], kl_rollout_workspace(MAX_BATCH, toks[i]));
         for (size_t i = 0; i < sizeof n_rows / sizeof n_rows[0]; ++i)
             for (int k = 1; k <= 32; k += k < 4 ? 1 : 28)
-                printf("gallery %ld %d : %zu %zu\n", n_rows[i], k, vh_gallery_workspace(1, n_rows[i], k, 0), vh_gallery_workspace(3, n_rows[i], k, 7));
+                printf("gallery %ld %d : %zu %zu\n", n_rows[i], k, kl_gallery_workspace(1, n_rows[i], k, 0), kl_gallery_workspace(3, n_rows[i], k, 7));
         return 0;
     }
     check_failure_at_every_allocation();

@@ -46,11 +46,11 @@ def test_the_plan_reproduces_the_table_and_every_borrower_fits(plan_main):
 
 
 def test_the_programs_sizing_functions_are_the_librarys(plan_main, pkg):
-    """plan_main.c restates the shim's four pure sizing functions; the loaded library's (no device is touched) must agree
-    at every shape of the table."""
+    """plan_main.c prints what the sizing functions of csrc/kernel_limits.h, which the plan calls, return; the loaded
+    library's exported entries (no device is touched) must agree at every shape of the table: each still forwards."""
     L = pkg.lib()
     seen = 0
-    for ln in run(plan_main, "stubs").splitlines():
+    for ln in run(plan_main, "limits").splitlines():
         args, got = ln.split(" : ")
         chans, patch, img, E, F, mb, rows = map(int, args.split())
         want = [L.vh_layer_norm_planes_max_embed(3), L.vh_patch_planes_k(chans, patch), L.vh_patch_embed_workspace(mb, chans, img, patch, E),

@@ -41,11 +41,12 @@ def test_arming_fails_clean_at_every_allocation_and_serves_what_is_armed(request
 
 
 def test_the_programs_sizing_functions_are_the_librarys(requests_main, pkg):
-    """requests_main.c restates the shim's four pure sizing functions; the loaded library's (no device is touched) must
-    agree at the shapes the program arms at and around the functions' thresholds."""
+    """requests_main.c prints what the sizing functions of csrc/kernel_limits.h, which the unit calls, return; the loaded
+    library's exported entries (no device is touched) must agree at the shapes the program arms at and around the
+    functions' thresholds: each still forwards."""
     L = pkg.lib()
     seen = set()
-    for ln in run(requests_main, "stubs").splitlines():
+    for ln in run(requests_main, "limits").splitlines():
         args, got = ln.split(" : ")
         kind, *args = args.split()
         args, got = list(map(int, args)), list(map(int, got.split()))

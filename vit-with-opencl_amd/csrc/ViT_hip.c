@@ -22,7 +22,9 @@
  *
  * What a context will run -- the kernels of a forward, the layout of the weight slabs, the size of every arena buffer -- is one
  * struct vit_plan (csrc/vit_plan.h), made by plan_make before anything is allocated; this file allocates what it says and
- * branches on its fields.
+ * branches on its fields.  What the plan, the requests and the frame sizing here know about the kernels -- the shapes each
+ * takes, the bytes of scratch each needs -- is stated once in csrc/kernel_limits.h, plain C that the launchers read too; none
+ * of them asks the shim for a size or a limit.
  *
  * What is left here is the context (both ways of making one end in ctx_finish), the layer functions, the forwards and the
  * drop-in ViT_opencl().  The repacked-weights file -- format, writer, reader and every refusal of a header -- is
@@ -34,6 +36,7 @@
  *   y = LN2(x); h = gelu(y W1^T + b1); x = x + (h W2^T + b2)
  */
 #include "ViT_opencl.h"
+#include "kernel_limits.h"
 #include "vit_ingest.h"
 #include "vit_multi.h"
 #include "vit_pipeline.h"
@@ -1212,7 +1215,7 @@ int vit_frame_sizes(const vit_config *cfg, const vit_frame_spec *spec, int frame
         *labels_bytes = (size_t)frame_h * frame_w;
     if (scratch_bytes)   /* all windows' patch logits, the boxes and the offsets; not the ids (4 bytes each) nor one chunk's patch
                           * logits, which depend on the boxes and on max_batch */
-        *scratch_bytes = align_up((size_t)n_windows * patch_elems * sizeof(float), 16) + vh_dense_stitch_scratch(n_windows, frame_h, frame_w, 0);
+        *scratch_bytes = align_up((size_t)n_windows * patch_elems * sizeof(float), 16) + kl_dense_stitch_scratch(n_windows, frame_h, frame_w, 0);
     return 0;
 }
 
@@ -1290,7 +1293,7 @@ static int frame_run(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *d_fr
         rc = 1;
         goto fail;
     }
-    const size_t index_bytes = vh_dense_stitch_scratch(n_windows, H, W, n_ids);
+    const size_t index_bytes = kl_dense_stitch_scratch(n_windows, H, W, n_ids);
     TRY(vh_set_device(ctx->device));
     if (vh_malloc(&d_all, align_up((size_t)n_windows * patch_elems * sizeof(float), 16)) || vh_malloc(&d_chunk, align_up((size_t)mb * patch_elems * sizeof(float), 16)) ||
         vh_malloc(&d_lab, align_up((size_t)mb, 16)) || vh_malloc(&d_index, index_bytes)) {

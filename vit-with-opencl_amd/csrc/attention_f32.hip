@@ -40,17 +40,19 @@
  * [n_images*T][E] with heads concatenated (ViT_seq.c:252-258).
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "fp32_split.h"
 
 namespace {
 
 constexpr int HD = 64;                    /* head dim this kernel is specialised for */
-constexpr int MAX_LDS = 160 * 1024;
+constexpr int MAX_LDS = KL_LDS_BYTES;
 #ifndef LATE_SCALE
 #define LATE_SCALE 100   /* per cent of the default hold-back of a SIMD's second wave (tuning) */
 #endif
 constexpr int MAX_ROWS = (MAX_LDS - 64) / (3 * HD * 4) / 8 * 8; /* rows per buffer with 3 buffers: 208 */
+static_assert(MAX_ROWS == KL_ATTN_HD64_MAX_TOKENS, "csrc/kernel_limits.h restates the resident kernel's rows");
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;

@@ -36,6 +36,7 @@
  * every output value through HBM.
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "fp32_split.h"
 #include "gemm_common.h"
@@ -47,7 +48,9 @@ typedef __attribute__((address_space(3))) void *lptr_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int MAX_LDS = 160 * 1024;
+constexpr int MAX_LDS = KL_LDS_BYTES;
+constexpr int HD80_NJ = 17, HD80_NW = 9;   /* the head_dim-80 instantiation: 17 key tiles of 16, 9 waves */
+static_assert(16 * HD80_NJ == KL_ATTN_HD80_MAX_TOKENS, "csrc/kernel_limits.h restates the key tiles");
 
 template <int HD, int NJ, int NW, int OUTK> /* NJ 16-key tiles (T <= 16 NJ), NW waves; two rounds of NW 16-query tiles cover T <= 32 NW */
 __global__ __launch_bounds__(64 * NW) void attention_h16_kernel(const char *__restrict__ qkvh, float *__restrict__ out,
@@ -298,13 +301,14 @@ extern "C" int vh_launch_attention_planes_f16_hd80(vh_stream_t s, const void *qk
 {
     if (!qkv_planes_f16 || !output)
         return vh_fail(1, "vh_launch_attention_planes_f16_hd80: null pointer argument");
-    if (n_images <= 0 || tokens <= 0 || num_heads <= 0 || embed_dim != num_heads * 80 || tokens > 272 || embed_dim % 32 != 0)
-        return vh_fail(1, "vh_launch_attention_planes_f16_hd80: needs head_dim 80 and 1 <= tokens <= 272 (n=%d tokens=%d embed=%d heads=%d)",
-                       n_images, tokens, embed_dim, num_heads);
+    if (n_images <= 0 || tokens <= 0 || num_heads <= 0 || embed_dim != num_heads * 80 || tokens > KL_ATTN_HD80_MAX_TOKENS ||
+        embed_dim % 32 != 0)
+        return vh_fail(1, "vh_launch_attention_planes_f16_hd80: needs head_dim 80 and 1 <= tokens <= %d (n=%d tokens=%d embed=%d heads=%d)",
+                       KL_ATTN_HD80_MAX_TOKENS, n_images, tokens, embed_dim, num_heads);
     if ((((uintptr_t)qkv_planes_f16 | (uintptr_t)output) & 15) != 0)
         return vh_fail(1, "vh_launch_attention_planes_f16_hd80: pointers must be 16-byte aligned");
-    return launch_h16<80, 17, 9, 0>((hipStream_t)s, static_cast<const char *>(qkv_planes_f16), output, nullptr, n_images, tokens,
-                                    embed_dim, num_heads);
+    return launch_h16<80, HD80_NJ, HD80_NW, 0>((hipStream_t)s, static_cast<const char *>(qkv_planes_f16), output, nullptr, n_images,
+                                               tokens, embed_dim, num_heads);
 }
 
 /* The same attention writing the output projection's operand directly: output_kind 1 = one-part bf16 planes
@@ -316,13 +320,14 @@ extern "C" int vh_launch_attention_planes_f16_hd80_operand(vh_stream_t s, const 
 {
     if (!qkv_planes_f16 || !output || (output_kind == 2 && !out_scales))
         return vh_fail(1, "vh_launch_attention_planes_f16_hd80_operand: null pointer argument");
-    if (n_images <= 0 || tokens <= 0 || num_heads <= 0 || (num_heads & 1) || embed_dim != num_heads * 80 || tokens > 272 ||
-        (output_kind != 1 && output_kind != 2) || (output_kind == 2 && embed_dim % 128 != 0))
-        return vh_fail(1, "vh_launch_attention_planes_f16_hd80_operand: needs head_dim 80, an even number of heads, 1 <= tokens <= 272, "
-                          "output_kind 1 or 2 (n=%d tokens=%d embed=%d heads=%d kind=%d)", n_images, tokens, embed_dim, num_heads, output_kind);
+    if (n_images <= 0 || tokens <= 0 || num_heads <= 0 || (num_heads & 1) || embed_dim != num_heads * 80 ||
+        tokens > KL_ATTN_HD80_MAX_TOKENS || (output_kind != 1 && output_kind != 2) || (output_kind == 2 && embed_dim % 128 != 0))
+        return vh_fail(1, "vh_launch_attention_planes_f16_hd80_operand: needs head_dim 80, an even number of heads, 1 <= tokens <= %d, "
+                          "output_kind 1 or 2 (n=%d tokens=%d embed=%d heads=%d kind=%d)", KL_ATTN_HD80_MAX_TOKENS, n_images, tokens, embed_dim,
+                       num_heads, output_kind);
     if ((((uintptr_t)qkv_planes_f16 | (uintptr_t)output) & 15) != 0)
         return vh_fail(1, "vh_launch_attention_planes_f16_hd80_operand: pointers must be 16-byte aligned");
     const char *in = static_cast<const char *>(qkv_planes_f16);
-    return output_kind == 1 ? launch_h16<80, 17, 9, 4>((hipStream_t)s, in, output, nullptr, n_images, tokens, embed_dim, num_heads)
-                            : launch_h16<80, 17, 9, 8>((hipStream_t)s, in, output, out_scales, n_images, tokens, embed_dim, num_heads);
+    return output_kind == 1 ? launch_h16<80, HD80_NJ, HD80_NW, 4>((hipStream_t)s, in, output, nullptr, n_images, tokens, embed_dim, num_heads)
+                            : launch_h16<80, HD80_NJ, HD80_NW, 8>((hipStream_t)s, in, output, out_scales, n_images, tokens, embed_dim, num_heads);
 }

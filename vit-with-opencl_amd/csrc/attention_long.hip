@@ -30,6 +30,7 @@
  * Output: fp32 rows [rows][E], heads concatenated.
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "fp32_split.h"
 #include "gemm_common.h"
@@ -43,7 +44,7 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int KC = 64;        /* keys per chunk */
 constexpr int NW = 8;         /* waves per workgroup: 128 queries */
-constexpr int MAX_LDS = 160 * 1024;
+constexpr int MAX_LDS = KL_LDS_BYTES;
 
 template <int HD> constexpr int planes_staged() { return HD % 32 == 0 ? HD / 32 : (HD + 16 + 31) / 32; }
 template <int HD, int NPL> constexpr size_t lds_bytes() { return (size_t)2 * 2 * planes_staged<HD>() * NPL * KC * 64; }
@@ -261,7 +262,7 @@ extern "C" int vh_launch_attention_long(vh_stream_t s, const void *qkv_planes, i
         return vh_fail(1, "vh_launch_attention_long: bad arguments (n=%d tokens=%d embed=%d heads=%d parts=%d)", n_images, tokens,
                        embed_dim, num_heads, parts);
     const int D = embed_dim / num_heads;
-    if ((D != 64 && D != 80) || embed_dim % 32 != 0)
+    if (!kl_attn_long_head_dim_ok(D) || embed_dim % 32 != 0)
         return vh_fail(1, "vh_launch_attention_long: head_dim %d (embed=%d heads=%d) not built: head_dim 64 or 80", D, embed_dim,
                        num_heads);
     const size_t rows = (size_t)n_images * (size_t)tokens;

@@ -32,6 +32,7 @@
  *    v_permlane32_swap per dword), as attention_f32.hip's planes epilogue does.
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "fp32_split.h"
 #include "gemm_common.h"
@@ -39,8 +40,9 @@
 namespace {
 
 constexpr int HD = 64;
-constexpr int MAX_LDS = 160 * 1024;
-constexpr int MAX_ROWS = 208;            /* 2 buffers x 6 planes x 208 rows x 64 B = 159 744 B */
+constexpr int MAX_LDS = KL_LDS_BYTES;
+constexpr int MAX_ROWS = KL_ATTN_HD64_MAX_TOKENS;   /* 2 buffers x 6 planes x 208 rows x 64 B = 159 744 B */
+static_assert(2 * 2 * 3 * MAX_ROWS * 64 <= MAX_LDS && MAX_ROWS % 16 == 0 && MAX_ROWS <= 32 * 7, "the rows of launch_k and launch_t");
 
 typedef const __attribute__((address_space(1))) void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;

@@ -26,6 +26,7 @@
  * [n_images*T][E] with heads concatenated (ViT_seq.c:252-258).
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "fp32_split.h"
 
@@ -257,6 +258,7 @@ int launch_d(hipStream_t st, const float *qkv, float *out, int lowp, int n_image
         return launch_nj<D, 8>(st, qkv, out, lowp, n_images, T, E, H);
     if (T <= 272)
         return launch_nj<D, 17>(st, qkv, out, lowp, n_images, T, E, H);
+    static_assert(16 * 32 == KL_ATTN_STREAMING_MAX_TOKENS, "csrc/kernel_limits.h restates the largest class: 32 key tiles of 16");
     return launch_nj<D, 32>(st, qkv, out, lowp, n_images, T, E, H);
 }
 
@@ -270,9 +272,10 @@ int vh_attention_tiled(vh_stream_t s, const float *qkv, float *output, int lowp,
                        int num_heads)
 {
     const int D = embed_dim / num_heads;
-    if (D * num_heads != embed_dim || tokens > 512 || ((size_t)n_images * num_heads * ((tokens + QB_MIN - 1) / QB_MIN)) >> 31)
+    if (D * num_heads != embed_dim || tokens > KL_ATTN_STREAMING_MAX_TOKENS ||
+        ((size_t)n_images * num_heads * ((tokens + QB_MIN - 1) / QB_MIN)) >> 31)
         return vh_fail(1, "vh_launch_attention: embed=%d heads=%d tokens=%d outside the supported range "
-                          "(head_dim 64 | 80 | 128, tokens <= 512)", embed_dim, num_heads, tokens);
+                          "(head_dim 64 | 80 | 128, tokens <= %d)", embed_dim, num_heads, tokens, KL_ATTN_STREAMING_MAX_TOKENS);
     if ((((uintptr_t)qkv | (uintptr_t)output) & 15) != 0 || embed_dim % 4 != 0)
         return vh_fail(1, "vh_launch_attention: qkv / output must be 16-byte aligned");
     hipStream_t st = (hipStream_t)s;

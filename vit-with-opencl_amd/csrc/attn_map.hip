@@ -201,10 +201,7 @@ int launch_cls_attn(hipStream_t st, const void *qkv, int n, int T, int E, int H,
 
 } // namespace
 
-extern "C" int vh_cls_attention_head_dim_ok(int head_dim)
-{
-    return head_dim > 0 && head_dim % 16 == 0 && head_dim <= AM_MAX_HEAD_DIM;
-}
+extern "C" int vh_cls_attention_head_dim_ok(int head_dim) { return kl_cls_attention_head_dim_ok(head_dim); }
 
 extern "C" int vh_launch_cls_attention(vh_stream_t s, const void *qkv, int qkv_form, int n_images, int tokens, int embed_dim,
                                        int num_heads, int tap_index, int n_taps, float *heads, float *mean)
@@ -216,9 +213,9 @@ extern "C" int vh_launch_cls_attention(vh_stream_t s, const void *qkv, int qkv_f
     if (n_images <= 0 || tokens < 1 || num_heads <= 0 || embed_dim <= 0 || embed_dim % num_heads != 0)
         return vh_fail(1, "vh_launch_cls_attention: bad arguments (n=%d tokens=%d embed=%d heads=%d)", n_images, tokens, embed_dim,
                        num_heads);
-    if (!vh_cls_attention_head_dim_ok(embed_dim / num_heads))
+    if (!kl_cls_attention_head_dim_ok(embed_dim / num_heads))
         return vh_fail(1, "vh_launch_cls_attention: head_dim=%d must be a multiple of 16, at most %d", embed_dim / num_heads,
-                       AM_MAX_HEAD_DIM);
+                       KL_CLS_ATTN_MAX_HEAD_DIM);
     if (qkv_form != VH_QKV_ROWS_F32 && embed_dim % 32 != 0)
         return vh_fail(1, "vh_launch_cls_attention: embed_dim=%d: the planes forms need a multiple of 32", embed_dim);
     if ((((uintptr_t)qkv | (uintptr_t)heads | (uintptr_t)mean) & 15) != 0)

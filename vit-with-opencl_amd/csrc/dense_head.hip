@@ -28,6 +28,7 @@
  * ragged ends.  No atomics at all.
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include <type_traits>
 
@@ -37,7 +38,7 @@ constexpr int DH_THREADS = 256;
 constexpr int DH_TT = VH_DENSE_TOKEN_TILE;   /* token rows per tile: 32 per wave */
 constexpr int DH_KC = 32;                  /* columns per stage */
 constexpr int DH_LS = DH_KC + 4;           /* LDS row stride in floats, as gallery.hip's */
-constexpr int DH_MAX_C = VH_DENSE_MAX_LABELS, DH_MAX_E = 2048, DH_MAX_OUT = 4096;
+constexpr int DH_MAX_C = VH_DENSE_MAX_LABELS, DH_MAX_E = KL_DENSE_MAX_EMBED, DH_MAX_OUT = 4096;
 constexpr int DH_T_PIECES = DH_TT * (DH_KC / 4) / DH_THREADS;   /* 4-column pieces of a token stage per thread */
 constexpr int DH_CS_SMALL = 4;             /* 16-label tiles per workgroup when the token tiles are few */
 constexpr int DH_RB = 16;                  /* output rows a thread carries at a time */

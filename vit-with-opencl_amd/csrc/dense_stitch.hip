@@ -16,6 +16,7 @@
  * classes are all -inf or NaN.
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "ViT_opencl.h"
 
@@ -135,17 +136,11 @@ __global__ __launch_bounds__(ST_THREADS) void dense_stitch_kernel(const float *_
         cover[at] = (unsigned char)(count < 255 ? count : 255);
 }
 
-inline size_t st_round16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 } // namespace
 
 extern "C" size_t vh_dense_stitch_scratch(int n_windows, int frame_h, int frame_w, long n_ids)
 {
-    if (n_windows < 1 || frame_h < 1 || frame_w < 1 || frame_h > VH_STITCH_MAX_SIDE || frame_w > VH_STITCH_MAX_SIDE || n_ids < 0 ||
-        n_ids > 2147483647L)
-        return 0;
-    const size_t blocks = (size_t)((frame_h + ST_B - 1) / ST_B) * (size_t)((frame_w + ST_B - 1) / ST_B);
-    return st_round16((size_t)n_windows * 16) + st_round16((blocks + 1) * sizeof(int)) + st_round16((size_t)n_ids * sizeof(int)) + 16;
+    return kl_dense_stitch_scratch(n_windows, frame_h, frame_w, n_ids);
 }
 
 extern "C" int vh_launch_dense_stitch(vh_stream_t s, const float *patch_logits, int n_windows, int grid_h, int grid_w, int n_labels,
@@ -182,15 +177,15 @@ extern "C" int vh_launch_dense_stitch(vh_stream_t s, const float *patch_logits, 
         for (long j = offsets[k]; j < offsets[k + 1]; ++j)
             if (ids[j] < 0 || ids[j] >= n_windows || (j > offsets[k] && ids[j] <= ids[j - 1]))
                 return vh_fail(1, "%s: the ids of block %ld must be strictly ascending window indices in 0..%d", who, k, n_windows - 1);
-    const size_t need = vh_dense_stitch_scratch(n_windows, frame_h, frame_w, n_ids);
+    const size_t need = kl_dense_stitch_scratch(n_windows, frame_h, frame_w, n_ids);
     if (scratch_bytes < need)
         return vh_fail(1, "%s: scratch_bytes=%zu, %zu needed (vh_dense_stitch_scratch)", who, scratch_bytes, need);
     if ((((uintptr_t)patch_logits | (uintptr_t)d_scratch | (uintptr_t)labels | (uintptr_t)scores | (uintptr_t)cover) & 15) != 0)
         return vh_fail(1, "%s: device pointers must be 16-byte aligned", who);
     hipStream_t st = (hipStream_t)s;
     char *const d_boxes = (char *)d_scratch;
-    char *const d_offsets = d_boxes + st_round16((size_t)n_windows * 16);
-    char *const d_ids = d_offsets + st_round16((size_t)(blocks + 1) * sizeof(int));
+    char *const d_offsets = d_boxes + kl_round16((size_t)n_windows * 16);
+    char *const d_ids = d_offsets + kl_round16((size_t)(blocks + 1) * sizeof(int));
     VH_TRY(hipMemcpy(d_boxes, windows, (size_t)n_windows * 16, hipMemcpyHostToDevice));
     VH_TRY(hipMemcpy(d_offsets, offsets, (size_t)(blocks + 1) * sizeof(int), hipMemcpyHostToDevice));
     if (n_ids > 0)

@@ -17,6 +17,7 @@
  * in a fixed order (row w + row w + 16 in the wave, waves 0..15, slab entries 0..chunks-1); no atomics.
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "fp32_split.h"
 
@@ -24,6 +25,7 @@ namespace {
 
 constexpr int RD_WAVES = 16;              /* waves per workgroup of readout_rows_kernel */
 constexpr int RD_ROWS = 2 * RD_WAVES;     /* patch rows per workgroup */
+static_assert(RD_ROWS == KL_READOUT_ROWS, "csrc/kernel_limits.h restates the rows per workgroup");
 constexpr int RD_TILE_STRIDE = 257;       /* dwords per row of the transposition tile: 256 columns + 1 */
 
 /* The row in x[], normalised in place: the arithmetic and summation order of layernorm_kernel (rowops.hip) */
@@ -276,9 +278,7 @@ __global__ __launch_bounds__(256) void readout_pool_kernel(const float *__restri
 
 extern "C" size_t vh_feature_readout_scratch(int n_images, int tokens, int embed_dim)
 {
-    if (n_images <= 0 || tokens < 2 || embed_dim <= 0)
-        return 0;
-    return (size_t)n_images * ((tokens - 1 + RD_ROWS - 1) / RD_ROWS) * embed_dim * sizeof(float);
+    return kl_feature_readout_scratch(n_images, tokens, embed_dim);
 }
 
 extern "C" int vh_launch_feature_readout(vh_stream_t s, const float *x, const float *cls_rows, long cls_row_stride,
@@ -308,8 +308,8 @@ extern "C" int vh_launch_feature_readout(vh_stream_t s, const float *x, const fl
     const int chunks = T >= 2 ? (T - 1 + RD_ROWS - 1) / RD_ROWS : 0;
     if ((size_t)n * (size_t)(chunks > 0 ? chunks : 1) > 0x7fffffffull)
         return vh_fail(1, "vh_launch_feature_readout: too many images");
-    if (pooled && (!scratch || scratch_bytes < vh_feature_readout_scratch(n, T, E)))
-        return vh_fail(1, "vh_launch_feature_readout: pooled needs %zu bytes of scratch", vh_feature_readout_scratch(n, T, E));
+    if (pooled && (!scratch || scratch_bytes < kl_feature_readout_scratch(n, T, E)))
+        return vh_fail(1, "vh_launch_feature_readout: pooled needs %zu bytes of scratch", kl_feature_readout_scratch(n, T, E));
     hipStream_t st = (hipStream_t)s;
     const int nv = (E / 4 + 63) / 64, bf16 = dtype == 1;
 
@@ -335,7 +335,7 @@ extern "C" int vh_launch_feature_readout(vh_stream_t s, const float *x, const fl
         float *partial = pooled ? static_cast<float *>(scratch) : nullptr;
 #define VH_RD_ROWS_F(NV, FULL)                                                                                     \
     do {                                                                                                           \
-        VH_SET_LDS_ONCE((readout_rows_kernel<NV, FULL>), 160 * 1024);                                              \
+        VH_SET_LDS_ONCE((readout_rows_kernel<NV, FULL>), KL_LDS_BYTES);                                            \
         hipLaunchKernelGGL((readout_rows_kernel<NV, FULL>), grid, block, lds, st, x, gamma, beta, eps, final_norm, \
                            bf16, token_layout, T, E, tap_index, n_taps, chunks, tokens, partial);                  \
     } while (0)

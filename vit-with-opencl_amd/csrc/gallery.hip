@@ -32,6 +32,7 @@
  * 0x7FC00000).
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 
 namespace {
@@ -39,11 +40,11 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int GA_THREADS = 256;
-constexpr int GA_RT = 128;                 /* gallery rows per tile: 32 per wave */
+constexpr int GA_RT = KL_GALLERY_ROW_TILE;   /* gallery rows per tile: 32 per wave */
 constexpr int GA_KC = 32;                  /* columns per stage */
 constexpr int GA_LS = GA_KC + 4;           /* LDS row stride in floats: the 16 rows of an operand read start 4 banks apart */
 constexpr int GA_QT_SMALL = 16, GA_QT_LARGE = 128;
-constexpr int GA_MAX_K = 32, GA_MAX_E = 2048;
+constexpr int GA_MAX_K = 32, GA_MAX_E = KL_GALLERY_MAX_EMBED;
 constexpr int GA_ROW_PIECES = GA_RT * (GA_KC / 4) / GA_THREADS;   /* 4-column pieces of a row stage per thread */
 
 inline int ga_query_tile(int n_queries) { return n_queries <= GA_QT_SMALL ? GA_QT_SMALL : GA_QT_LARGE; }
@@ -268,13 +269,8 @@ extern "C" int vh_gallery_splits(int n_queries, long n_rows)
 
 extern "C" size_t vh_gallery_workspace(int n_queries, long n_rows, int k, int splits)
 {
-    if (n_queries < 1 || n_rows < 1 || k < 1 || splits < 0)
-        return 0;
-    if (splits == 0) {   /* whatever the launcher chooses is at most this */
-        const long tiles = ga_row_tiles(n_rows);
-        splits = tiles < VH_GALLERY_MAX_SPLITS ? (int)tiles : VH_GALLERY_MAX_SPLITS;
-    }
-    return (size_t)n_queries * (size_t)splits * (size_t)k * sizeof(u64);
+    static_assert(sizeof(u64) == 8, "csrc/kernel_limits.h sizes the (score, index) pairs");
+    return kl_gallery_workspace(n_queries, n_rows, k, splits);   /* splits = 0: whatever ga_choose_splits chooses is at most this */
 }
 
 extern "C" int vh_launch_gallery_topk(vh_stream_t s, const float *queries, int n_queries, int embed_dim, const void *rows, int dtype,

@@ -44,7 +44,7 @@
 #include "vit_kernels.h"
 #include "fp32_split.h"
 #include "gemm_common.h"
-#include "patch_geometry.h"
+#include "kernel_limits.h"
 
 #include <cstdint>
 
@@ -78,10 +78,10 @@ struct Tile {
     static constexpr int stage_f(int npl) { return npl ? BM * BK + npl * BN * 16 : STAGE_F; }
     static constexpr size_t lds(int npl) { return sizeof(float) * 2 * stage_f(npl); }
     static constexpr int chw(int npl) { return npl ? npl * BN / 16 / NW : CHW; }   /* W DMA pieces per wave */
-    static constexpr int WG_PER_CU = (2 * LDS <= 160 * 1024) ? 2 : 1;
+    static constexpr int WG_PER_CU = (2 * LDS <= KL_LDS_BYTES) ? 2 : 1;
     static constexpr int MIN_WAVES_PER_SIMD = WG_PER_CU * NW / 4;
     static_assert(BM % (8 * NW) == 0 && BN % (8 * NW) == 0, "DMA pieces must divide evenly over waves");
-    static_assert(IT >= 1 && JT >= 1 && LDS <= 160 * 1024, "tile does not fit");
+    static_assert(IT >= 1 && JT >= 1 && LDS <= KL_LDS_BYTES, "tile does not fit");
 };
 
 struct GemmParams {
@@ -933,8 +933,8 @@ int vh_cls_rows(hipStream_t st, const float *cls_token, const float *pos_embed, 
 
 extern "C" size_t vh_patch_embed_workspace_hw(int n_images, int in_chans, int img_h, int img_w, int patch_size, int embed_dim)
 {
-    static_assert(VH_PATCH_ROWS_K_STEP == BK, "csrc/patch_geometry.h restates the K step");
-    return vh_patch_rows_workspace_hw(n_images, in_chans, img_h, img_w, patch_size, embed_dim);
+    static_assert(KL_PATCH_ROWS_K_STEP == BK, "csrc/kernel_limits.h restates the K step");
+    return kl_patch_rows_workspace(n_images, in_chans, img_h, img_w, patch_size, embed_dim);
 }
 
 extern "C" size_t vh_patch_embed_workspace(int n_images, int in_chans, int img_size, int patch_size, int embed_dim)
@@ -958,8 +958,8 @@ extern "C" int vh_launch_patch_embed_rows_hw(vh_stream_t s, const float *images,
         return vh_fail(1, "vh_launch_patch_embed: bad geometry");
     const int K = in_chans * patch_size * patch_size;
     const int grid = img_w / patch_size, np = (img_h / patch_size) * grid;
-    const bool direct = vh_patch_direct_hw(in_chans, img_w, patch_size);
-    const size_t need = vh_patch_embed_workspace_hw(n_images, in_chans, img_h, img_w, patch_size, embed_dim);
+    const bool direct = kl_patch_direct(in_chans, img_w, patch_size);
+    const size_t need = kl_patch_rows_workspace(n_images, in_chans, img_h, img_w, patch_size, embed_dim);
     if (!direct && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)))
         return vh_fail(1, "vh_launch_patch_embed: patch=%d (K=%d) is not a multiple of 4 / %d: this geometry needs "
                           "vh_launch_patch_embed_ws with %zu bytes of workspace", patch_size, K, BK, need);

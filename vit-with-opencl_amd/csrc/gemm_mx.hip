@@ -419,7 +419,7 @@ extern "C" int vh_launch_quantize_mx_act(vh_stream_t s, const float *input, void
 
 extern "C" size_t vh_mx_act_scale_bytes(int rows, int cols)
 {
-    return rows > 0 && cols > 0 ? (size_t)((cols / 128 + 3) / 4) * 16 * (size_t)rows : 0;
+    return kl_mx_act_scale_bytes(rows, cols);
 }
 
 extern "C" int vh_launch_linear_mx(vh_stream_t s, void *output, void *output_scales, const void *weight_values,
@@ -481,7 +481,7 @@ extern "C" int vh_launch_linear_mx_norm(vh_stream_t s, void *output, void *outpu
         return vh_fail(1, "vh_launch_linear_mx_norm: needs colA %% 256 == 0 and colB %% 128 == 0 (%d,%d,%d)", rowA, colA, colB);
     if (output_kind < 0 || output_kind > 2 || (doGelu && output_kind != 1))
         return vh_fail(1, "vh_launch_linear_mx_norm: unsupported epilogue combination");
-    if (colA > 16 * 128)
+    if (colA > KL_FOLD_MAX_GROUPS * KL_FOLD_GROUP)
         return vh_fail(1, "vh_launch_linear_mx_norm: colA=%d: at most 16 partial sums per row (colA <= 2048)", colA);
     if ((((uintptr_t)output | (uintptr_t)weight_values | (uintptr_t)input_values | (uintptr_t)colsum | (uintptr_t)bias_folded |
           (uintptr_t)weight_scales) & 15) != 0 || ((uintptr_t)row_stats & 7) != 0)

@@ -699,7 +699,7 @@ static int linear_planes_norm(vh_stream_t s, void *output, int output_planes, co
         return vh_fail(1, "vh_launch_linear_planes_norm: needs colA %% %d == 0 and colB %% 128 == 0 (%d,%d,%d)", kstep, rowA, colA, colB);
     if (output_planes < 0 || output_planes > 2 || (output_planes == 2 && (doGelu || parts == 3)) || (output_planes == 0 && doGelu))
         return vh_fail(1, "vh_launch_linear_planes_norm: unsupported epilogue combination");
-    if (colA > 16 * 128 || colA % 128 != 0)
+    if (colA > KL_FOLD_MAX_GROUPS * KL_FOLD_GROUP || colA % KL_FOLD_GROUP != 0)
         return vh_fail(1, "vh_launch_linear_planes_norm: colA=%d: one partial sum per 128 columns, at most 16 per row", colA);
     if ((((uintptr_t)output | (uintptr_t)weight_planes | (uintptr_t)input_planes | (uintptr_t)colsum | (uintptr_t)bias_folded) & 15) != 0 ||
         ((uintptr_t)row_stats & 7) != 0)
@@ -1143,8 +1143,8 @@ __global__ void pad_rows_planes_kernel(const float *__restrict__ in, char *__res
 
 extern "C" int vh_patch_planes_k(int in_chans, int patch_size)
 {
-    const int K = in_chans * patch_size * patch_size, step = 64 * P1_KG;
-    return (K + step - 1) / step * step;
+    static_assert(KL_PATCH_PLANES_K_STEP == 64 * P1_KG, "csrc/kernel_limits.h restates the one-part K step");
+    return kl_patch_planes_k(in_chans, patch_size);
 }
 
 extern "C" int vh_launch_conv_weight_planes_parts(vh_stream_t s, const float *conv_w, void *planes, int embed_dim, int in_chans,

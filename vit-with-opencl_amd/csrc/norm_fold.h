@@ -24,8 +24,11 @@
 #ifndef VIT_HIP_NORM_FOLD_H
 #define VIT_HIP_NORM_FOLD_H
 
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "gemm_common.h"
+
+static_assert(KL_FOLD_MAX_GROUPS == 4 * 4, "row_norm_terms: four lanes hold a row, each adds four partials");
 
 /* 1/std and -mean/std of row `row` from its producer's partial sums (groups = K / 128 <= 16).  Called by all four lanes
  * (q = lane >> 4) that hold the row in the GEMM epilogue's layout: lane q takes partials q, q + 4, q + 8, q + 12 (four

@@ -15,9 +15,10 @@
 #define VIT_HIP_QKV_FORMS_H
 
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 
-constexpr int AM_MAX_HEAD_DIM = 128;
+constexpr int AM_MAX_HEAD_DIM = KL_CLS_ATTN_MAX_HEAD_DIM;
 
 typedef _Float16 am_half8 __attribute__((ext_vector_type(8)));
 typedef __bf16 am_bf16x8 __attribute__((ext_vector_type(8)));

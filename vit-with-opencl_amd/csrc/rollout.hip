@@ -25,22 +25,19 @@
  * an image's rows are the same bits wherever it sits.
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "qkv_forms.h"
 #include "vit_kernels.h"
 
 namespace {
 
 constexpr int RO_THREADS = 256;
-constexpr int RO_QT = 16;            /* query rows per workgroup */
-constexpr int RO_KC = 64;            /* keys per chunk: 16 per wave */
-constexpr int RO_MAX_LDS = 160 * 1024;
+constexpr int RO_QT = KL_ROLLOUT_QUERY_ROWS;   /* query rows per workgroup */
+constexpr int RO_KC = KL_ROLLOUT_KEY_CHUNK;    /* keys per chunk: 16 per wave */
+static_assert(RO_KC == 16 * RO_THREADS / 64, "a chunk is 16 keys per wave");
 constexpr int RP_TILE = 64, RP_KC = 16;
 constexpr int RP_AS = RP_KC + 4;     /* row strides in floats: the 16 rows of an A-operand read start in 16 distinct bank quads, */
 constexpr int RP_RS = RP_TILE + 16;  /* the 4 rows of a B-operand read 16 banks apart */
-
-/* row stride of the score tile: whole key chunks, and the 4 row groups of a matrix result 16 banks apart */
-__host__ __device__ inline int ro_score_stride(int T) { return (T + RO_KC - 1) / RO_KC * RO_KC + 20; }
-inline size_t ro_lds_bytes(int T, int D) { return ((size_t)RO_QT * ro_score_stride(T) + (size_t)(RO_QT + RO_KC) * (D + 4)) * sizeof(float); }
 
 /* Rows [first, first + count) of one image's Q|K|V, columns [col0, col0 + D), decoded to fp32 into dst[count][DS]; rows
  * >= T become zeros.  LPK lanes per row as in attn_map.hip, so a wave reads whole 256-byte / 64-byte segments. */
@@ -78,7 +75,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_attn_kernel(const char *__
                                                                   float scale, float *a_out, float *r_first)
 {
     extern __shared__ __attribute__((aligned(16))) float ro_lds[];
-    const int D = E / H, DS = D + 4, nj = D / 16, TP = ro_score_stride(T);
+    const int D = E / H, DS = D + 4, nj = D / 16, TP = kl_rollout_score_stride(T);
     float *const p_s = ro_lds, *const q_s = p_s + RO_QT * TP, *const k_s = q_s + RO_QT * DS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lg = lane >> 4;
     const int img = blockIdx.x / tiles, u0 = (blockIdx.x % tiles) * RO_QT;
@@ -212,8 +209,8 @@ template <int FORM>
 int launch_rollout_attn(hipStream_t st, const void *qkv, int n, int T, int E, int H, float *a_out, float *r_first)
 {
     const int tiles = (T + RO_QT - 1) / RO_QT;
-    const size_t lds = ro_lds_bytes(T, E / H);
-    VH_SET_LDS_ONCE((rollout_attn_kernel<FORM>), RO_MAX_LDS);
+    const size_t lds = kl_rollout_lds_bytes(T, E / H);
+    VH_SET_LDS_ONCE((rollout_attn_kernel<FORM>), KL_LDS_BYTES);
     hipLaunchKernelGGL(rollout_attn_kernel<FORM>, dim3((unsigned)((size_t)n * tiles)), dim3(RO_THREADS), lds, st,
                        static_cast<const char *>(qkv), n, T, E, H, tiles, 1.0f / sqrtf((float)(E / H)), a_out, r_first);
     VH_LAUNCH_CHECK("rollout_attn_kernel");
@@ -224,16 +221,10 @@ int launch_rollout_attn(hipStream_t st, const void *qkv, int n, int T, int E, in
 
 extern "C" size_t vh_rollout_workspace(int n_images, int tokens)
 {
-    return n_images > 0 && tokens > 0 ? (size_t)n_images * (size_t)tokens * (size_t)tokens * sizeof(float) : 0;
+    return kl_rollout_workspace(n_images, tokens);
 }
 
-extern "C" int vh_rollout_max_tokens(int head_dim)
-{
-    int T = 0;
-    while (ro_lds_bytes(T + RO_KC, head_dim) <= (size_t)RO_MAX_LDS)
-        T += RO_KC;
-    return T;
-}
+extern "C" int vh_rollout_max_tokens(int head_dim) { return kl_rollout_max_tokens(head_dim); }
 
 extern "C" int vh_launch_rollout_step(vh_stream_t s, const void *qkv, int qkv_form, int n_images, int tokens, int embed_dim, int num_heads,
                                       const float *r_prev, float *r_next, void *workspace)
@@ -245,17 +236,17 @@ extern "C" int vh_launch_rollout_step(vh_stream_t s, const void *qkv, int qkv_fo
     if (n_images <= 0 || tokens < 1 || num_heads <= 0 || embed_dim <= 0 || embed_dim % num_heads != 0)
         return vh_fail(1, "vh_launch_rollout_step: bad arguments (n=%d tokens=%d embed=%d heads=%d)", n_images, tokens, embed_dim, num_heads);
     const int D = embed_dim / num_heads;
-    if (!vh_cls_attention_head_dim_ok(D))
-        return vh_fail(1, "vh_launch_rollout_step: head_dim=%d must be a multiple of 16, at most %d", D, AM_MAX_HEAD_DIM);
+    if (!kl_cls_attention_head_dim_ok(D))
+        return vh_fail(1, "vh_launch_rollout_step: head_dim=%d must be a multiple of 16, at most %d", D, KL_CLS_ATTN_MAX_HEAD_DIM);
     if (qkv_form != VH_QKV_ROWS_F32 && embed_dim % 32 != 0)
         return vh_fail(1, "vh_launch_rollout_step: embed_dim=%d: the planes forms need a multiple of 32", embed_dim);
     if ((((uintptr_t)qkv | (uintptr_t)r_prev | (uintptr_t)r_next | (uintptr_t)workspace) & 15) != 0)
         return vh_fail(1, "vh_launch_rollout_step: pointers must be 16-byte aligned");
     if (r_prev == r_next || (const void *)r_prev == workspace || (void *)r_next == workspace)
         return vh_fail(1, "vh_launch_rollout_step: r_prev, r_next and workspace must be three different buffers");
-    if (ro_lds_bytes(tokens, D) > (size_t)RO_MAX_LDS)
+    if (kl_rollout_lds_bytes(tokens, D) > (size_t)KL_LDS_BYTES)
         return vh_fail(1, "vh_launch_rollout_step: tokens=%d: at most %d at head_dim %d (the score rows of 16 queries stay in LDS)", tokens,
-                       vh_rollout_max_tokens(D), D);
+                       kl_rollout_max_tokens(D), D);
     const size_t q_tiles = ((size_t)tokens + RO_QT - 1) / RO_QT, p_tiles = ((size_t)tokens + RP_TILE - 1) / RP_TILE;
     if (((size_t)n_images * q_tiles) >> 31 || ((size_t)n_images * p_tiles * p_tiles) >> 31 || ((size_t)n_images * tokens) >> 31)
         return vh_fail(1, "vh_launch_rollout_step: n=%d x tokens=%d too large for one launch", n_images, tokens);

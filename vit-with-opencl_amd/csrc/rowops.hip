@@ -14,6 +14,7 @@
  * ViT_seq.c:372-397.
  */
 #include "kernelHandler.h"
+#include "kernel_limits.h"
 #include "vit_kernels.h"
 #include "fp32_split.h"
 
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
  * summation order: identical values), 16 rows per workgroup; the parts go through an LDS image of the
  * planes' own order, [K step][part][16 rows][64 B], so that every global store instruction writes one
  * contiguous, aligned KiB (16 rows x 64 B of one K step and part) instead of eight 64-byte pieces 19 MB apart. */
-constexpr int LN3_ROWS = 16;
+constexpr int LN3_ROWS = KL_LN_PLANES_ROWS;
 
 /* Persistent: a workgroup walks row groups blockIdx.x, blockIdx.x + gridDim.x, ... and loads the rows of the next
  * group before it normalises, stages and stores the current one -- with one group per workgroup the loads of a
@@ -391,17 +392,11 @@ extern "C" int vh_launch_layer_norm(vh_stream_t s, const float *input, const flo
                              out_row_stride, eps);
 }
 
-/* The planes kernel stages 16 rows of every part in LDS, 32 * parts * embed_dim bytes, and a CU has LN3_LDS_LIMIT of it:
+/* The planes kernel stages 16 rows of every part in LDS, 32 * parts * embed_dim bytes, and a CU has KL_LDS_BYTES of it:
  * the registers hold rows of up to 2048 values, the LDS image with three parts only 1696 (162 816 of 163 840 bytes). */
-constexpr int LN3_LDS_LIMIT = 160 * 1024;
+static_assert(kl_layer_norm_planes_max_embed(1) == 2048 && kl_layer_norm_planes_max_embed(3) == 1696, "the widths the messages below name");
 
-extern "C" int vh_layer_norm_planes_max_embed(int parts)
-{
-    if (parts != 1 && parts != 3)
-        return 0;
-    const int by_lds = LN3_LDS_LIMIT / (parts * LN3_ROWS * 64) * 32;
-    return by_lds < 2048 ? by_lds : 2048;
-}
+extern "C" int vh_layer_norm_planes_max_embed(int parts) { return kl_layer_norm_planes_max_embed(parts); }
 
 extern "C" int vh_launch_layer_norm_planes(vh_stream_t s, const float *input, const float *weight, const float *bias,
                                            void *out_planes, int parts, int rows, int embed_dim, long in_row_stride,
@@ -409,26 +404,26 @@ extern "C" int vh_launch_layer_norm_planes(vh_stream_t s, const float *input, co
 {
     if (!input || !weight || !bias || !out_planes)
         return vh_fail(1, "vh_launch_layer_norm_planes: null pointer argument");
-    if (rows <= 0 || embed_dim <= 0 || embed_dim % 32 != 0 || embed_dim > 2048 || ((uintptr_t)out_planes & 15) ||
+    if (rows <= 0 || embed_dim <= 0 || embed_dim % 32 != 0 || embed_dim > KL_LN_PLANES_MAX_EMBED || ((uintptr_t)out_planes & 15) ||
         (parts != 1 && parts != 3))
         return vh_fail(1, "vh_launch_layer_norm_planes: embed_dim=%d must be a multiple of 32, <= 2048 with one part and "
                           "<= 1696 with three, planes 16-byte aligned, parts 1 or 3", embed_dim);
-    if (embed_dim > vh_layer_norm_planes_max_embed(parts))
+    if (embed_dim > kl_layer_norm_planes_max_embed(parts))
         return vh_fail(1, "vh_launch_layer_norm_planes: embed_dim=%d with %d parts needs %d bytes of LDS for its 16-row image, "
                           "a CU has %d: the largest embed_dim with %d parts is %d", embed_dim, parts,
-                       32 * parts * embed_dim, LN3_LDS_LIMIT, parts, vh_layer_norm_planes_max_embed(parts));
+                       32 * parts * embed_dim, KL_LDS_BYTES, parts, kl_layer_norm_planes_max_embed(parts));
     if (in_row_stride % 4 != 0 || in_row_stride < embed_dim)
         return vh_fail(1, "vh_launch_layer_norm_planes: row stride must be a multiple of 4 floats and >= embed_dim");
     const int nv = (embed_dim / 4 + 63) / 64;
     const size_t lds = (size_t)(embed_dim / 32) * parts * LN3_ROWS * 64;
     const int ngroups = (rows + LN3_ROWS - 1) / LN3_ROWS;
-    const int resident = LN3_LDS_LIMIT / (int)lds < 2 ? 1 : 2;           /* workgroups of 1024 threads per CU */
+    const int resident = KL_LDS_BYTES / (int)lds < 2 ? 1 : 2;           /* workgroups of 1024 threads per CU */
     const int cap = resident * vh_device_cus(vh_current_device());
     const dim3 grid(ngroups < cap ? ngroups : cap), block(64 * LN3_ROWS);
     hipStream_t st = (hipStream_t)s;
 #define VH_LN3_F(NV, NPL, FULL)                                                                           \
     do {                                                                                                  \
-        VH_SET_LDS_ONCE((layernorm_p3_kernel<NV, NPL, FULL>), LN3_LDS_LIMIT);                             \
+        VH_SET_LDS_ONCE((layernorm_p3_kernel<NV, NPL, FULL>), KL_LDS_BYTES);                              \
         hipLaunchKernelGGL((layernorm_p3_kernel<NV, NPL, FULL>), grid, block, lds, st, input, weight, bias, \
                            static_cast<char *>(out_planes), rows, embed_dim, in_row_stride, eps);         \
     } while (0)

@@ -1,11 +1,12 @@
 /*
  * vit_plan.c -- the plan of a context (csrc/vit_plan.h): the switches of the environment, the argument checks, which
  * kernels a forward takes, where every weight lies in its slab and how large every arena buffer must be for all that
- * borrow it.  Host arithmetic only; nothing here allocates or touches a device.
+ * borrow it.  Host arithmetic only; nothing here allocates or touches a device.  What it knows about the kernels -- the
+ * shapes each one takes, the bytes each one needs -- it reads from csrc/kernel_limits.h, as the launchers do.
  */
 #include "vit_plan.h"
 #include "vit_ingest.h"
-#include "patch_geometry.h"
+#include "kernel_limits.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -89,7 +90,7 @@ void plan_layout(const struct vit_plan *plan, const vit_config *cfg, void *const
         }
     }
     place(slab[SLAB_CONV], &off[SLAB_CONV],   /* E % 128 == 0 wherever there are parts: already 256-byte aligned */
-          (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * (size_t)cfg->embed_dim * 2 * (size_t)plan->conv_parts);
+          (size_t)kl_patch_planes_k(cfg->in_chans, cfg->patch_size) * (size_t)cfg->embed_dim * 2 * (size_t)plan->conv_parts);
     if (bytes)
         memcpy(bytes, off, sizeof(off));
 }
@@ -111,7 +112,7 @@ static void plan_arena(struct vit_plan *plan, const vit_config *cfg, int max_bat
     b = rows * E * act;
     if (fp8) {   /* ... as MX tensors: a byte per value, then the scales (rows that overflow an int run no forward either) */
         plan->e_scales_off = align_up(rows * E, 256);
-        b = max_of(b, plan->e_scales_off + vh_mx_act_scale_bytes((int)rows, cfg->embed_dim));
+        b = max_of(b, plan->e_scales_off + kl_mx_act_scale_bytes((int)rows, cfg->embed_dim));
     }
     plan->y_bytes = plan->attn_bytes = b;
 
@@ -129,15 +130,12 @@ static void plan_arena(struct vit_plan *plan, const vit_config *cfg, int max_bat
     b = rows * F * act;                           /* the MLP's hidden activations */
     if (fp8) {                                    /* ... as an MX tensor */
         plan->hid_scales_off = align_up(rows * F, 256);
-        b = max_of(b, plan->hid_scales_off + vh_mx_act_scale_bytes((int)rows, cfg->mlp_hidden));
+        b = max_of(b, plan->hid_scales_off + kl_mx_act_scale_bytes((int)rows, cfg->mlp_hidden));
     }
-    /* the gathered patch rows of geometries such as H/14: a square input through the shim's own sizing function, a
-     * rectangle through the arithmetic both share (csrc/patch_geometry.h) */
-    b = max_of(b, width == cfg->img_size
-                      ? vh_patch_embed_workspace(max_batch, cfg->in_chans, cfg->img_size, cfg->patch_size, cfg->embed_dim)
-                      : vh_patch_rows_workspace_hw(max_batch, cfg->in_chans, cfg->img_size, width, cfg->patch_size, cfg->embed_dim));
+    /* the gathered patch rows of geometries such as H/14, square or not */
+    b = max_of(b, kl_patch_rows_workspace(max_batch, cfg->in_chans, cfg->img_size, width, cfg->patch_size, cfg->embed_dim));
     /* the im2row producer's planes: patches x Kp x 2 bytes x parts (a small MLP can be smaller than that) */
-    b = max_of(b, n * patches * (size_t)vh_patch_planes_k(cfg->in_chans, cfg->patch_size) * 2 * (size_t)plan->conv_parts);
+    b = max_of(b, n * patches * (size_t)kl_patch_planes_k(cfg->in_chans, cfg->patch_size) * 2 * (size_t)plan->conv_parts);
     if (resizes)
         b = max_of(b, n * ingest_max_table_bytes(cfg->img_size));   /* the resize's coefficient tables at the steepest downscale */
     if (planes_path && (plan->attn_form == ATTN_STREAMING || plan->attn_form == ATTN_LONG))
@@ -145,7 +143,7 @@ static void plan_arena(struct vit_plan *plan, const vit_config *cfg, int max_bat
                                                    * rounded into attn */
     plan->ws_bytes = b;
 
-    plan->stats_bytes = plan->ln_fold ? rows * (E / 128) * 2 * sizeof(float) : 0;   /* partial (sum, sum of squares) per row */
+    plan->stats_bytes = plan->ln_fold ? rows * (E / KL_FOLD_GROUP) * 2 * sizeof(float) : 0;   /* partial (sum, sum of squares) per row */
 }
 
 int plan_make(struct vit_plan *plan, const vit_config *cfg, int n_tensors, int max_batch, int precision, int ln_fold,
@@ -185,8 +183,9 @@ int plan_make(struct vit_plan *plan, const vit_config *cfg, int n_tensors, int m
     const int planes_wanted = !env->p3_off && !env->fp32_native;
     const int weight_planes = precision == VIT_PRECISION_F32 && E % 128 == 0 && F % 128 == 0;
     const int use_p3 = weight_planes && planes_wanted && (size_t)max_batch * (size_t)T * 64 <= 0xffffffffull;
-    /* the fold's row terms take at most 16 partial sums per row (row_norm_terms); on F32 it needs the planes path */
-    const int fold_fits = E % 128 == 0 && E / 128 <= 16 && (reduced || weight_planes);
+    /* the fold's row terms take at most KL_FOLD_MAX_GROUPS partial sums per row (row_norm_terms); on F32 it needs the planes
+     * path */
+    const int fold_fits = E % KL_FOLD_GROUP == 0 && E / KL_FOLD_GROUP <= KL_FOLD_MAX_GROUPS && (reduced || weight_planes);
     if (ln_fold < 0)
         /* the reduced modes fold unless $VIT_HIP_LN_FOLD=0 (the separate LayerNorm launches of rounds 1-3: the A/B of tests
          * and bench).  On F32 the fold is a LAB VARIANT, off unless $VIT_HIP_LN_FOLD=1: the same fold on the exact
@@ -197,26 +196,27 @@ int plan_make(struct vit_plan *plan, const vit_config *cfg, int n_tensors, int m
         return vh_set_error(2, "vit_hip_create: this shape, precision and batch cannot fold the LayerNorms (the fp32 path "
                                "needs the planes path)");
     /* the planes path's LayerNorms write three parts per value through an LDS image that ends at embed_dim 1696
-     * (vh_layer_norm_planes_max_embed, csrc/rowops.hip); the lab fold launches none of them */
-    if (use_p3 && !ln_fold && E > vh_layer_norm_planes_max_embed(3)) {
+     * (kl_layer_norm_planes_max_embed; csrc/rowops.hip); the lab fold launches none of them */
+    if (use_p3 && !ln_fold && E > kl_layer_norm_planes_max_embed(3)) {
         char msg[320];
         snprintf(msg, sizeof msg, "vit_hip_create: embed_dim=%d: the fp32 planes path's LayerNorm (three-part planes, 96 bytes of "
                  "LDS per column) takes a LayerNorm width of at most %d",
-                 E, vh_layer_norm_planes_max_embed(3));
+                 E, kl_layer_norm_planes_max_embed(3));
         return vh_set_error(2, msg);
     }
-    /* attention: ATTN_LONG is the only kernel past STREAMING_MAX_TOKENS, and it reads the planes paths' Q|K|V with head_dim
-     * 64 or 80; $VIT_HIP_ATTN=long forces it at any T (tests, A/B), $VIT_HIP_ATTN=tiled the streaming kernel wherever
+    /* attention: ATTN_LONG is the only kernel past KL_ATTN_STREAMING_MAX_TOKENS, and it reads the planes paths' Q|K|V with
+     * head_dim 64 or 80; $VIT_HIP_ATTN=long forces it at any T (tests, A/B), $VIT_HIP_ATTN=tiled the streaming kernel wherever
      * attention reads fp32 rows (the planes paths' resident kernels are not rows kernels and stay).  Shapes no kernel runs are
      * refused here, not at every forward. */
-    const int long_hd = E == 64 * H || E == 80 * H;
-    const int long_wanted = T > STREAMING_MAX_TOKENS || env->attn_long;
-    if (T > STREAMING_MAX_TOKENS && (precision == VIT_PRECISION_F32_FP16X2 || (precision == VIT_PRECISION_F32 && !use_p3) || !long_hd)) {
+    const int long_hd = kl_attn_long_head_dim_ok(E / H);   /* E % H == 0 here */
+    const int long_wanted = T > KL_ATTN_STREAMING_MAX_TOKENS || env->attn_long;
+    if (T > KL_ATTN_STREAMING_MAX_TOKENS &&
+        (precision == VIT_PRECISION_F32_FP16X2 || (precision == VIT_PRECISION_F32 && !use_p3) || !long_hd)) {
         char msg[320];
         snprintf(msg, sizeof msg, "vit_hip_create: %d tokens: above %d tokens attention runs on the planes paths (F32 with "
                  "embed_dim and mlp_hidden multiples of 128 and neither $VIT_HIP_P3=0 nor $VIT_HIP_GEMM_FP32=native, BF16_GEMM, "
                  "FP8_GEMM; not F32_FP16X2) with head_dim 64 or 80 (precision %d, head_dim %d)",
-                 T, STREAMING_MAX_TOKENS, precision, E / H);
+                 T, KL_ATTN_STREAMING_MAX_TOKENS, precision, E / H);
         return vh_set_error(2, msg);
     }
 
@@ -227,8 +227,8 @@ int plan_make(struct vit_plan *plan, const vit_config *cfg, int n_tensors, int m
     plan->cls_only_last = use_p3 && !ln_fold && env->last_layer_cls;
     plan->attn_form = !(use_p3 || reduced) ? ATTN_STREAMING
                     : (long_wanted && long_hd) ? ATTN_LONG
-                    : (E == 64 * H && T <= 208) ? ATTN_HD64
-                    : (reduced && E == 80 * H && T <= 272) ? ATTN_HD80 : ATTN_STREAMING;
+                    : (E == 64 * H && T <= KL_ATTN_HD64_MAX_TOKENS) ? ATTN_HD64
+                    : (reduced && E == 80 * H && T <= KL_ATTN_HD80_MAX_TOKENS) ? ATTN_HD80 : ATTN_STREAMING;
     plan->fp32_native = env->fp32_native;
     plan->attn_rows_streaming = env->attn_tiled;
     plan->tokens = T;

@@ -2,8 +2,8 @@
  * vit_plan.h -- what a context will run, decided once before anything is allocated: the kernels a forward takes, the
  * layout of the weight slabs and the size of every arena buffer with the borrowers it has to hold.  Internal to the
  * library: ViT_hip.c makes one plan per context and only reads it afterwards.  vit_plan.c is plain C and needs no device:
- * its outside symbols are vh_set_error, four pure sizing functions of the shim (vh_layer_norm_planes_max_embed,
- * vh_patch_planes_k, vh_patch_embed_workspace, vh_mx_act_scale_bytes) and ingest_max_table_bytes.
+ * its outside symbols are vh_set_error and ingest_max_table_bytes, and what it knows about the kernels' shape limits and
+ * scratch sizes is the arithmetic of csrc/kernel_limits.h.
  * tests/plan_main.c runs it against tests/golden/plan_table.txt.
  */
 #ifndef VIT_PLAN_H
@@ -34,9 +34,6 @@ enum { SLAB_F32, SLAB_OPERAND, SLAB_CONV, SLAB_FOLD, N_SLABS };
  * flash-style kernel (csrc/attention_long.hip; any T, head_dim 64 or 80), fp32 rows out into the idle MLP buffer, then
  * rounded / split like the streaming kernel's -- every T > 512, and any T under $VIT_HIP_ATTN=long */
 enum { ATTN_STREAMING, ATTN_HD64, ATTN_HD80, ATTN_LONG };
-
-/* the largest T the streaming kernel (attention_tiled.hip) takes; beyond it only ATTN_LONG runs */
-enum { STREAMING_MAX_TOKENS = 512 };
 
 enum { MAX_DEPTH = 256, MAX_TENSORS = 4 + 12 * MAX_DEPTH + 4 };
 

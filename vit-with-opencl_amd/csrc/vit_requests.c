@@ -4,6 +4,7 @@
  * and what a forward serves.  Plain C; nothing here launches a kernel or reads a context.
  */
 #include "vit_requests.h"
+#include "kernel_limits.h"
 #include "vit_ingest.h"
 
 #include <stdint.h>
@@ -244,7 +245,7 @@ int requests_set_attention(const char *who, const struct request_model *m, struc
             return 1;
         const vit_config *c = m->cfg;
         const char *why = !bufs || (!bufs->heads && !bufs->mean) ? "no output buffer"
-                          : !vh_cls_attention_head_dim_ok(c->embed_dim / c->num_heads) ? "head_dim must be a multiple of 16, at most 128"
+                          : !kl_cls_attention_head_dim_ok(c->embed_dim / c->num_heads) ? "head_dim must be a multiple of 16, at most 128"
                           : !host && (((uintptr_t)bufs->heads | (uintptr_t)bufs->mean) & 15) ? "device buffers must be 16-byte aligned"
                           : NULL;
         if (why)
@@ -306,9 +307,9 @@ int requests_set_rollout(const char *who, const struct request_model *m, struct 
         const vit_config *c = m->cfg;
         const int D = c->embed_dim / c->num_heads;
         const char *why = !bufs || !bufs->rollout ? "no output buffer"
-                          : !vh_cls_attention_head_dim_ok(D) ? "head_dim must be a multiple of 16, at most 128"
+                          : !kl_cls_attention_head_dim_ok(D) ? "head_dim must be a multiple of 16, at most 128"
                           : m->qkv_form != VH_QKV_ROWS_F32 && c->embed_dim % 32 != 0 ? "embed_dim must be a multiple of 32 where Q|K|V is stored as planes"
-                          : m->tokens > vh_rollout_max_tokens(D) ? "too many tokens for the rollout kernel at this head_dim (vh_rollout_max_tokens)"
+                          : m->tokens > kl_rollout_max_tokens(D) ? "too many tokens for the rollout kernel at this head_dim (vh_rollout_max_tokens)"
                           : !host && ((uintptr_t)bufs->rollout & 15) ? "device buffers must be 16-byte aligned"
                           : NULL;
         if (why)
@@ -318,7 +319,7 @@ int requests_set_rollout(const char *who, const struct request_model *m, struct 
         ro.out = *bufs;
         if (host)
             ro.head.st[0] = (struct staged){.host = (char *)bufs->rollout, .per_image = (size_t)m->tokens * sizeof(float)};
-        scratch[0] = scratch[1] = scratch[2] = vh_rollout_workspace(m->max_batch, m->tokens);
+        scratch[0] = scratch[1] = scratch[2] = kl_rollout_workspace(m->max_batch, m->tokens);
         snprintf(oom, sizeof oom, "3 x %zu bytes of device scratch (max_batch x T x T x 4 each) cannot be allocated", scratch[0]);
     }
     const int rc = request_arm(who, m, &rq->roll.head, &ro.head, sizeof ro, scratch, 1, oom);
@@ -336,7 +337,7 @@ static int gallery_spec_check(const char *who, const vit_config *cfg, const vit_
                       : spec->tap < -cfg->depth || spec->tap >= cfg->depth ? "tap lies outside [-depth, depth)"
                       : spec->source == VIT_GALLERY_POOLED && vit_config_tokens(cfg) < 2 ? "pooled needs at least one patch token"
                       : spec->dtype != VH_GALLERY_F32 && spec->dtype != VH_GALLERY_BF16 ? "dtype must be VH_GALLERY_F32 or VH_GALLERY_BF16"
-                      : cfg->embed_dim % 4 != 0 || cfg->embed_dim > 2048 ? "embed_dim must be a multiple of 4, at most 2048"
+                      : cfg->embed_dim % 4 != 0 || cfg->embed_dim > KL_GALLERY_MAX_EMBED ? "embed_dim must be a multiple of 4, at most 2048"
                       : spec->k < 1 || spec->k > 32 ? "k must be in 1..32"
                       : spec->n_rows < spec->k || spec->n_rows > 2147483647L ? "n_rows must be in k..2^31 - 1"
                       : spec->row_stride < cfg->embed_dim || spec->row_stride > (1L << 40) ||
@@ -346,7 +347,7 @@ static int gallery_spec_check(const char *who, const vit_config *cfg, const vit_
     if (why)
         return ingest_refuse(who, why);
     *layer = spec->tap < 0 ? spec->tap + cfg->depth : spec->tap;
-    *per_image = (size_t)cfg->embed_dim * sizeof(float) + vh_gallery_workspace(1, spec->n_rows, spec->k, 0);
+    *per_image = (size_t)cfg->embed_dim * sizeof(float) + kl_gallery_workspace(1, spec->n_rows, spec->k, 0);
     return 0;
 }
 
@@ -410,7 +411,7 @@ static int dense_spec_check(const char *who, const vit_config *cfg, const vit_de
                       : spec->tap < -cfg->depth || spec->tap >= cfg->depth ? "tap lies outside [-depth, depth)"
                       : vit_config_tokens(cfg) < 2 ? "the model needs a grid of at least one patch token"
                       : gh > VH_DENSE_MAX_GRID || gw > VH_DENSE_MAX_GRID ? "the patch grid must be at most 64 x 64"
-                      : cfg->embed_dim % 4 != 0 || cfg->embed_dim > 2048 ? "embed_dim must be a multiple of 4, at most 2048"
+                      : cfg->embed_dim % 4 != 0 || cfg->embed_dim > KL_DENSE_MAX_EMBED ? "embed_dim must be a multiple of 4, at most 2048"
                       : spec->n_labels < 2 || spec->n_labels > VH_DENSE_MAX_LABELS ? "n_labels must be in 2..256"
                       : spec->out_h < 0 || spec->out_h > 4096 || spec->out_w < 0 || spec->out_w > 4096 ||
                         (spec->out_h == 0 && cfg->img_size > 4096) || (spec->out_w == 0 && width > 4096)

@@ -3,8 +3,8 @@
  * is armed, the one way of arming it, and what a forward serves.  Internal to the library: ViT_hip.c holds one struct
  * requests per context and launches what it names.  vit_requests.c is plain C, knows nothing of the context but a struct
  * request_model and launches nothing: its outside symbols are vh_set_error and ingest_refuse, vh_set_device and
- * vh_stream_sync, the allocators vh_malloc, vh_free, vh_host_alloc and vh_host_free, and four pure sizing functions of the
- * shim (vh_cls_attention_head_dim_ok, vh_rollout_max_tokens, vh_rollout_workspace, vh_gallery_workspace).
+ * vh_stream_sync and the allocators vh_malloc, vh_free, vh_host_alloc and vh_host_free; the kernels' shape limits and
+ * scratch sizes it checks against are the arithmetic of csrc/kernel_limits.h.
  * tests/requests_main.c runs it over a counting allocator that fails on demand.
  */
 #ifndef VIT_REQUESTS_H
