@@ -381,6 +381,29 @@ size_t vh_mx_act_scale_bytes(int rows, int cols);
 enum { VH_GEMM_PLANES = 0, VH_GEMM_MX = 1 };
 enum { VH_TILES_128x256 = 0, VH_TILES_128x128 = 1, VH_TILES_256x256 = 2, VH_TILES_256x256_TAIL = 3 };
 int vh_gemm_tile_class(int family, int parts, int resid_or_patch, int small_only, int rows, int N, int num_cus, int *rows_big);
+/* The same for the GEMMs on fp32 activation rows (csrc/gemm_mfma.hip): which kernel and tile a launch of `rows` x N over K
+ * runs -- pure, touches no device; vh_launch_linear / _math and vh_launch_patch_embed* on fp32 rows (VH_ROWS_INLOOP: both
+ * operands split inside the K loop, or the native fp32 instruction), vh_launch_linear_w3 (VH_ROWS_W3) and vh_launch_linear_h2
+ * (VH_ROWS_H2) decide by it.  epilogue: what follows the sum; fp32_math: VH_FP32_SPLIT3 or VH_FP32_NATIVE (read by
+ * VH_ROWS_INLOOP only); out_aligned16: the output, bias, residual and position-embedding pointers are all 16-byte aligned.
+ *  - colB % 128 != 0 (the classifier): guarded tiles on the native instruction under either fp32_math, 32x64 while
+ *    2 * ceil(rows / 128) * ceil(N / 128) < num_cus, 128x128 from there on;
+ *  - 256x256 tiles where N % 256 == 0 and rows >= 4096, except with a residual over K < 2048; 128x128 otherwise;
+ *  - VH_ROWS_INLOOP runs the split kernel under VH_FP32_SPLIT3 with aligned pointers, the native one otherwise;
+ *  - the planes families hand the last, partly filled round of 256x256 tiles (at most 3/4 of the CUs) to a 128x128 launch
+ *    from row *rows_big (may be NULL) on; every other class is one launch and leaves 0 there.
+ * -1 for what the launchers refuse: a size <= 0, an unknown family, epilogue or fp32_math, and for the planes families
+ * N % 128 != 0, the patch epilogue or a misaligned pointer.  Within one arithmetic (split and planes W3 / native / H2)
+ * results never depend on the class: every tile sums the same products in the same order. */
+enum { VH_ROWS_INLOOP = 0, VH_ROWS_W3 = 1, VH_ROWS_H2 = 2 };
+enum { VH_EPI_NONE = 0, VH_EPI_GELU = 1, VH_EPI_RESID = 2, VH_EPI_PATCH = 3 };
+enum {
+    VH_ROWS_32x64_NATIVE_GUARDED = 0, VH_ROWS_128x128_NATIVE_GUARDED = 1, VH_ROWS_128x128_NATIVE = 2, VH_ROWS_256x256_NATIVE = 3,
+    VH_ROWS_128x128_SPLIT = 4, VH_ROWS_256x256_SPLIT = 5, VH_ROWS_128x128_PLANES = 6, VH_ROWS_256x256_PLANES = 7,
+    VH_ROWS_256x256_PLANES_TAIL = 8
+};
+int vh_gemm_rows_tile_class(int family, int epilogue, int fp32_math, int out_aligned16, int rows, int K, int N, int num_cus,
+                            int *rows_big);
 /* vh_launch_layer_norm writing its result as an MX tensor (embed_dim % 128 == 0) */
 int vh_launch_layer_norm_mx(vh_stream_t s, const float *input, const float *weight, const float *bias,
                             void *out_values, void *out_scales, int rows, int embed_dim, long in_row_stride, double eps);

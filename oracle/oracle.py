@@ -80,6 +80,7 @@ class Oracle:
         L.port_softmax.argtypes = [f32p, f32p, C.c_int]
         L.port_gelu.argtypes = [C.c_float]
         L.port_gelu.restype = C.c_float
+        L.port_gelu_rows.argtypes = [f32p, f32p, C.c_size_t]
         self.cfg = VitConfig()
         if L.vit_config_preset(C.byref(self.cfg), preset.encode()) != 0:
             raise ValueError(f"unknown preset {preset}")
@@ -192,7 +193,10 @@ class Oracle:
         return out
 
     def gelu(self, xs):
-        return np.array([self.lib.port_gelu(float(v)) for v in xs], dtype=np.float32)
+        xs = np.ascontiguousarray(xs, dtype=np.float32)
+        out = np.empty_like(xs)
+        self.lib.port_gelu_rows(_ptr(xs), _ptr(out), xs.size)
+        return out
 
 
 # ---- the real reference, where its build is present -----------------------------

@@ -163,6 +163,13 @@ float port_gelu(float x)
     return 0.5f * x * (1.0f + erff(x / sqrtf(2.0f)));
 }
 
+/* port_gelu over an array, as mlp_block_seq applies it (ViT_seq.c:318-320): the same bits per element. */
+void port_gelu_rows(const float *input, float *output, size_t count)
+{
+    for (size_t i = 0; i < count; ++i)
+        output[i] = port_gelu(input[i]);
+}
+
 /* ViT_seq.c:310-327. */
 void port_mlp(const vit_config *c, const float *input, float *output, const float *fc1_w,
               const float *fc1_b, const float *fc2_w, const float *fc2_b, int tokens)

@@ -21,6 +21,22 @@ __device__ __forceinline__ int xcd_tile(int bid, int nwg)
     return start + idx;
 }
 
+/* Two measured facts that every tile rule of these units reads (vh_gemm_tile_class in gemm_p3.hip, vh_gemm_rows_tile_class in
+ * gemm_mfma.hip), stated here once; pure host arithmetic.
+ *  - a projection that adds a residual and contracts over fewer than 2048 values (the N = K = E output projection) is
+ *    faster on small tiles at every row count: its launchers never give it a 256x256 tile; */
+inline bool tile_rule_short_k(int K) { return K < 2048; }
+/*  - a grid of r.f scheduling rounds of 256x256 tiles (one workgroup per CU) costs ceil(r.f) rounds, its remainder rows as
+ *    quarter-size tiles about f/2: the last, partly filled round is handed to a 128x128 launch where it fills at most 3/4
+ *    of the CUs.  `tiles` = mtiles * ntiles of 256x256 over `rows` rows.  -> the row where the 128x128 launch takes over,
+ *    0 where the big tiles run alone (whole rounds, a remainder above 3/4, or no whole round of whole tile rows). */
+inline int tile_rule_tail_row(long tiles, int ntiles, int num_cus, int rows)
+{
+    const long full = tiles / num_cus, rem = tiles % num_cus;
+    const int rb = (int)(full * num_cus / ntiles) * 256;
+    return (rem == 0 || 4 * rem > 3 * (long)num_cus || rb <= 0 || rb >= rows) ? 0 : rb;
+}
+
 /* GELU for the fc1 epilogue: 0.5*x*(1+erf(x/sqrt(2))), ViT_seq.c:285 / ll.cl:4.
  * The scalar loop calls libm erff; a device libm erff is two divergent branches of
  * ~50 VALU instructions each, which made this epilogue a third of the fc1 kernel

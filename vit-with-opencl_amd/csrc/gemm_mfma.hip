@@ -653,25 +653,72 @@ bool aligned16(const GemmParams &p)
     return (((uintptr_t)p.C | (uintptr_t)p.bias | (uintptr_t)p.R | (uintptr_t)p.pos) & 15) == 0;
 }
 
-/* fp32 operands, both split inside the K loop (vh_launch_linear on raw fp32 weights, and the patch
- * embedding): 256x256 tiles where N allows and there is enough work, else 128x128.  fp32_math: the exact
- * 3-way bf16 split on the bf16 cores (VH_FP32_SPLIT3), or the native fp32 MFMA (VH_FP32_NATIVE).  Both give
- * fp32-level results (same measured logit parity); the split is ~1.4x faster end to end. */
+static_assert(EPI_NONE == VH_EPI_NONE && EPI_GELU == VH_EPI_GELU && EPI_RESID == VH_EPI_RESID && EPI_PATCH == VH_EPI_PATCH,
+              "include/kernelHandler.h names the epilogues for vh_gemm_rows_tile_class");
+
+} // namespace
+
+/* The tile rule of every launcher of this file: pure, no device -- include/kernelHandler.h states it, tests/gemm_tiles_ref.py
+ * restates it branch by branch.
+ *  - Ragged N (the classifier) runs the guarded tiles on the native fp32 MFMA.  A skinny problem (M = batch, N = 1000: 32
+ *    tiles of 128x128 on 256 CUs, 53 us) goes to 32x64 tiles, one 32x32 block per wave -- 256 workgroups for 512 x 1000,
+ *    same k order, same bits.
+ *  - 256x256 tiles where N allows and there is enough work, else 128x128.  fp32_math: the exact 3-way bf16 split on the
+ *    bf16 cores (VH_FP32_SPLIT3), or the native fp32 MFMA (VH_FP32_NATIVE).  Both give fp32-level results (same measured
+ *    logit parity); the split is ~1.4x faster end to end.  The split kernels read and write 16 bytes at a time.
+ *  - Pre-split weights: the last, partly filled scheduling round of 256x256 tiles goes to 128x128 tiles instead
+ *    (tile_rule_tail_row, gemm_common.h). */
+extern "C" int vh_gemm_rows_tile_class(int family, int epilogue, int fp32_math, int out_aligned16, int rows, int K, int N,
+                                       int num_cus, int *rows_big)
+{
+    if (rows_big)
+        *rows_big = 0;
+    if (rows <= 0 || K <= 0 || N <= 0 || num_cus <= 0 || family < VH_ROWS_INLOOP || family > VH_ROWS_H2 ||
+        epilogue < VH_EPI_NONE || epilogue > VH_EPI_PATCH)
+        return -1;
+    const bool big = N % 256 == 0 && rows >= 4096 && !(epilogue == VH_EPI_RESID && tile_rule_short_k(K));
+    if (family != VH_ROWS_INLOOP) {
+        if (epilogue == VH_EPI_PATCH || N % 128 != 0 || !out_aligned16)
+            return -1;
+        if (!big)
+            return VH_ROWS_128x128_PLANES;
+        const int ntiles = N / 256, mtiles = (rows + 255) / 256;
+        const int rb = tile_rule_tail_row((long)mtiles * ntiles, ntiles, num_cus, rows);
+        if (rb == 0)
+            return VH_ROWS_256x256_PLANES;
+        if (rows_big)
+            *rows_big = rb;
+        return VH_ROWS_256x256_PLANES_TAIL;
+    }
+    if (fp32_math != VH_FP32_SPLIT3 && fp32_math != VH_FP32_NATIVE)
+        return -1;
+    if (N % 128 != 0) {
+        const long tiles128 = (long)((rows + 127) / 128) * ((N + 127) / 128);
+        return 2 * tiles128 < num_cus ? VH_ROWS_32x64_NATIVE_GUARDED : VH_ROWS_128x128_NATIVE_GUARDED;
+    }
+    if (fp32_math == VH_FP32_SPLIT3 && out_aligned16)
+        return big ? VH_ROWS_256x256_SPLIT : VH_ROWS_128x128_SPLIT;
+    return big ? VH_ROWS_256x256_NATIVE : VH_ROWS_128x128_NATIVE;
+}
+
+namespace {
+
+/* fp32 operands, both split inside the K loop (vh_launch_linear on raw fp32 weights, and the patch embedding), or on the
+ * native fp32 MFMA: one kernel per class of the rule above. */
 template <int AMODE, int EPI>
 int launch(hipStream_t st, const GemmParams &p, int fp32_math)
 {
-    const bool big = p.N % 256 == 0 && p.M >= 4096 && !(EPI == EPI_RESID && p.K < 2048);
-    if (p.N % 128 != 0) {                    /* ragged N (the classifier): the guarded tiles on the native fp32 MFMA */
-        /* a skinny problem (M = batch, N = 1000: 32 tiles of 128x128 on 256 CUs, 53 us) goes to 32x64 tiles,
-         * one 32x32 block per wave -- 256 workgroups for 512 x 1000, same k order, same bits */
-        const long tiles128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-        if (2 * tiles128 < vh_device_cus(vh_current_device()))
-            return launch_tile<TileS, AMODE, EPI, true>(st, p);
-        return launch_tile<Tile0, AMODE, EPI, true>(st, p);
+    const int cls = vh_gemm_rows_tile_class(VH_ROWS_INLOOP, EPI, fp32_math, aligned16(p), p.M, p.K, p.N,
+                                            vh_device_cus(vh_current_device()), nullptr);
+    switch (cls) {
+    case VH_ROWS_32x64_NATIVE_GUARDED:   return launch_tile<TileS, AMODE, EPI, true>(st, p);
+    case VH_ROWS_128x128_NATIVE_GUARDED: return launch_tile<Tile0, AMODE, EPI, true>(st, p);
+    case VH_ROWS_128x128_NATIVE:         return launch_tile<Tile0, AMODE, EPI, false>(st, p);
+    case VH_ROWS_256x256_NATIVE:         return launch_tile<Tile4, AMODE, EPI, false>(st, p);
+    case VH_ROWS_128x128_SPLIT:          return launch_mf16<Tile1, AMODE, EPI>(st, p);
+    case VH_ROWS_256x256_SPLIT:          return launch_mf16<Tile3, AMODE, EPI>(st, p);
     }
-    if (fp32_math == VH_FP32_SPLIT3 && aligned16(p))
-        return big ? launch_mf16<Tile3, AMODE, EPI>(st, p) : launch_mf16<Tile1, AMODE, EPI>(st, p);
-    return big ? launch_tile<Tile4, AMODE, EPI, false>(st, p) : launch_tile<Tile0, AMODE, EPI, false>(st, p);
+    return vh_fail(1, "gemm_mfma: no tile class for rows=%d K=%d N=%d fp32_math=%d (class %d)", p.M, p.K, p.N, fp32_math, cls);
 }
 
 /* Argument checks and GemmParams shared by the rows launchers.  planes: the weights come pre-split
@@ -772,21 +819,20 @@ __global__ void split3_planes_kernel(const float *__restrict__ in, __bf16 *__res
     out[o + 2 * plane] = (__bf16)r2;
 }
 
-/* Pre-split-weight GEMM on the tile the shape wants, with the last, partly filled scheduling round
- * of 256x256 tiles handed to 128x128 tiles instead: with one
- * workgroup per CU a grid of r.f rounds costs ceil(r.f) rounds; the remainder rows as quarter-size
- * tiles cost about f/2. */
+/* Pre-split-weight GEMM on the class vh_gemm_rows_tile_class names; with a tail, rows [rows_big, M) are a second launch of
+ * 128x128 tiles whose operand, output and residual rows all start at rows_big. */
 template <int EPI, int NPL>
-int launch_planes(hipStream_t st, GemmParams p, bool prefer_small)
+int launch_planes(hipStream_t st, GemmParams p)
 {
-    if (!(p.N % 256 == 0 && p.M >= 4096 && !prefer_small))
+    int rows_big = 0;
+    const int cls = vh_gemm_rows_tile_class(NPL == 3 ? VH_ROWS_W3 : VH_ROWS_H2, EPI, VH_FP32_SPLIT3, aligned16(p), p.M, p.K, p.N,
+                                            vh_device_cus(vh_current_device()), &rows_big);
+    if (cls == VH_ROWS_128x128_PLANES)
         return launch_mf16<Tile9, A_ROWS, EPI, NPL>(st, p);
-    const int num_cus = vh_device_cus(vh_current_device());
-    const int ntiles = p.N / 256, mtiles = (p.M + 255) / 256;
-    const long tiles = (long)mtiles * ntiles, full = tiles / num_cus, rem = tiles % num_cus;
-    const int rows_big = (int)(full * num_cus / ntiles) * 256;
-    if (full < 1 || rem == 0 || 4 * rem > 3 * num_cus || rows_big <= 0 || rows_big >= p.M)
+    if (cls == VH_ROWS_256x256_PLANES)
         return launch_mf16<Tile8, A_ROWS, EPI, NPL>(st, p);
+    if (cls != VH_ROWS_256x256_PLANES_TAIL)
+        return vh_fail(1, "gemm_mfma: no planes tile class for rows=%d K=%d N=%d (class %d)", p.M, p.K, p.N, cls);
     GemmParams big = p, rest = p;
     big.M = rows_big;
     rest.M = p.M - rows_big;
@@ -803,12 +849,11 @@ template <int NPL>
 int launch_planes_epi(vh_stream_t s, const GemmParams &p, int doGelu)
 {
     hipStream_t st = (hipStream_t)s;
-    const bool prefer_small = p.R && p.K < 2048;   /* measured: the N = 768, K = 768 out-projection */
     if (doGelu)
-        return launch_planes<EPI_GELU, NPL>(st, p, prefer_small);
+        return launch_planes<EPI_GELU, NPL>(st, p);
     if (p.R)
-        return launch_planes<EPI_RESID, NPL>(st, p, prefer_small);
-    return launch_planes<EPI_NONE, NPL>(st, p, prefer_small);
+        return launch_planes<EPI_RESID, NPL>(st, p);
+    return launch_planes<EPI_NONE, NPL>(st, p);
 }
 
 } // namespace

@@ -443,7 +443,7 @@ extern "C" int vh_launch_linear_mx(vh_stream_t s, void *output, void *output_sca
     p.bias = bias; p.R = residual; p.C = output; p.Cs = output_scales;
     p.row_begin = 0; p.row_end = rowA; p.a_rows = rowA; p.N = colB; p.K = colA;
     hipStream_t st = (hipStream_t)s;
-    const int small_only = residual && colA < 2048;
+    const int small_only = residual && tile_rule_short_k(colA);
     if (doGelu)
         return output_scales ? launch_mx<EPI_GELU, OUT_MX>(st, p, small_only) : launch_mx<EPI_GELU, OUT_F32>(st, p, small_only);
     if (residual)
@@ -524,5 +524,5 @@ extern "C" int vh_launch_linear_mx_resid_norm(vh_stream_t s, float *output, cons
     p.bias = bias; p.R = residual; p.C = output;
     p.oper = operand_values; p.oper_scales = operand_scales; p.stats_out = row_stats_out;
     p.row_begin = 0; p.row_end = rowA; p.a_rows = rowA; p.N = colB; p.K = colA;
-    return launch_mx<EPI_RESID, OUT_F32_OPER_MX>((hipStream_t)s, p, colA < 2048);
+    return launch_mx<EPI_RESID, OUT_F32_OPER_MX>((hipStream_t)s, p, tile_rule_short_k(colA));
 }

@@ -467,9 +467,8 @@ extern "C" int vh_gemm_tile_class(int family, int parts, int resid_or_patch, int
         return VH_TILES_128x256;
     if (two_per_cu || N % 256 != 0 || small_only || 2 * tiles < 5 * (long)num_cus)
         return VH_TILES_128x128;
-    const long full = tiles / num_cus, rem = tiles % num_cus;
-    const int rb = (int)(full * num_cus / ntiles) * 256;
-    if (rem == 0 || 4 * rem > 3 * num_cus || rb <= 0 || rb >= rows)
+    const int rb = tile_rule_tail_row(tiles, ntiles, num_cus, rows);
+    if (rb == 0)
         return VH_TILES_256x256;
     if (rows_big)
         *rows_big = rb;
@@ -637,7 +636,7 @@ static int linear_planes(vh_stream_t s, void *output, int output_planes, const v
     p.row_begin = 0; p.row_end = rowA; p.a_rows = rowA;
     p.N = colB; p.K = colA; p.w_rows = w_rows;
     hipStream_t st = (hipStream_t)s;
-    const int small_only = residual && colA < 2048;   /* the N = K = E output projection: measured */
+    const int small_only = residual && tile_rule_short_k(colA);   /* the N = K = E output projection: measured */
 #define VH_P3_DISPATCH(NPL)                                                                                          \
     do {                                                                                                             \
         if (doGelu)                                                                                                  \
@@ -767,7 +766,7 @@ static int linear_planes_resid_norm(vh_stream_t s, float *output, const void *we
     p.row_begin = 0; p.row_end = rowA; p.a_rows = rowA; p.c_rows = rowA;
     p.N = colB; p.K = colA;
     hipStream_t st = (hipStream_t)s;
-    const int small_only = colA < 2048;   /* as vh_launch_linear_planes: the N = K = E output projection */
+    const int small_only = tile_rule_short_k(colA);   /* as vh_launch_linear_planes: the N = K = E output projection */
     if (parts == 3)
         return launch_p3<EPI_RESID, OUT_F32_OPER, 3>(st, p, small_only);
     return operand_scales_out ? launch_p3<EPI_RESID, OUT_F32_OPER_MX, 1>(st, p, small_only)
@@ -1251,7 +1250,7 @@ static int patch_embed_planes(vh_stream_t s, const PixelSrc &src, const void *co
     p.N = embed_dim; p.K = Kp;
     p.np = np; p.tokens = np + 1;
     p.oper = operand_out; p.oper_scales = operand_scales_out; p.stats_out = row_stats_out;
-    const int small_only = Kp < 2048;   /* the shape of the output projection: small tiles (measured there) */
+    const int small_only = tile_rule_short_k(Kp);   /* the shape of the output projection: small tiles (measured there) */
     if (parts == 3)
         return operand_out ? launch_p3<EPI_PATCH, OUT_F32_OPER, 3>(st, p, small_only) : launch_p3<EPI_PATCH, OUT_F32, 3>(st, p, small_only);
     if (!operand_out)

@@ -304,6 +304,7 @@ PROTOTYPES = {
         _fn("vh_launch_quantize_mx_act", p, p, p, p, i, i),
         _fn("vh_mx_act_scale_bytes", i, i, ret=sz),
         _fn("vh_gemm_tile_class", i, i, i, i, i, i, i, ip),
+        _fn("vh_gemm_rows_tile_class", i, i, i, i, i, i, i, i, ip),
         _fn("vh_launch_layer_norm_mx", p, p, p, p, p, p, i, i, l, d),
         _fn("vh_launch_linear_mx", p, p, p, p, p, p, p, p, i, i, i, i, p),
         _fn("vh_launch_attention_planes_f16_mx", p, p, p, p, i, i, i, i),
