@@ -645,8 +645,10 @@ int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, con
  * The class-rows last layer (vit_hip_set_last_layer_cls_only): a tap on the last layer makes that forward run the last layer on all rows, as a
  * feature request for pooled does; logits are bit-identical either way.
  * vit_hip_multi: vit_hip_forward_multi and vit_hip_forward_device_multi neither write labels nor refuse.
- * Out of scope: per-pixel probabilities, multi-layer or non-linear decode heads, antialiased or bicubic upsampling, more
- * than 256 labels. */
+ * Out of scope: the full [C][H][W] probability tensor (the per-pixel confidence, expected value and entropy maps are
+ * vit_hip_set_dense_soft, below), the soft maps for vit_hip_segment_frame_* (which needs a soft stitch: the natural
+ * follow-up), the "linear" (ReLU-normalised) bin strategy of depth heads, a host form of the soft maps, multi-layer or
+ * non-linear decode heads, antialiased or bicubic upsampling, more than 256 labels. */
 typedef struct vit_dense_spec {
     int tap, final_norm;          /* as vit_gallery_spec */
     int n_labels, out_h, out_w;   /* out_h 0 = the model's img_size, out_w 0 = its width */
@@ -661,6 +663,38 @@ int vit_dense_sizes(const vit_config *cfg, const vit_dense_spec *spec, size_t *l
                     size_t *patch_logits_elems, size_t *scratch_bytes_per_image);
 int vit_hip_set_dense(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *d_bufs);
 int vit_hip_set_dense_host(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_buffers *h_bufs);
+
+/* ---- dense head, soft maps: per-pixel confidence, expected value and entropy ----
+ * vit_hip_set_dense_soft arms THE dense request (not a seventh one), in device form, with soft outputs attached: per pixel
+ * prob = the softmax probability of the label the dense head writes (a confidence, to threshold or ignore uncertain pixels),
+ * expect = sum_c p_c * d_values[c] (dense regression by bins: depth as a linear head over C <= 256 depth bins read out at
+ * their centres, the linear depth protocol of DINOv2 and AdaBins' read-out) and entropy = -sum_c p_c ln p_c in nats, with p
+ * = softmax_c(logit_scale * v[c]) over the upsampled logits v the labels are ranked from.  vh_launch_dense_soft
+ * (include/kernelHandler.h) defines them to the operation and states their error bound.  fp32 [n][out_h][out_w] each.
+ * While armed, every vit_hip_forward_device* launches behind layer `tap`, in this order: the feature readout when final_norm
+ * is set, vh_launch_dense_logits, vh_launch_dense_labels -- only when a labels buffer was given -- and one
+ * vh_launch_dense_soft; all timed under VIT_OP_HEAD.  Class logits, probabilities and the other five requests' outputs are
+ * bit-identical to a forward without it; a context that is not soft-armed launches exactly what it launched before.
+ * spec: as vit_hip_set_dense takes it.  soft: logit_scale finite and > 0 (1 for a plain softmax; the inverse temperature);
+ * d_values [n_labels] fp32 in device memory, 16-byte aligned, the CALLER'S, valid and unchanged while armed -- given exactly
+ * when expect is asked for.  d_bufs: may be NULL, or its labels NULL: then no labels are written and vh_launch_dense_labels
+ * is not launched (scores then must be NULL too); patch_logits as for vit_hip_set_dense.  d_soft: device buffers for
+ * max_batch images, 16-byte aligned; each may be NULL, not all three.
+ * It is the dense request in every other respect: vit_hip_set_dense(ctx, NULL, NULL) and vit_hip_set_dense_soft(ctx, NULL,
+ * ...) disarm it, arming either form of vit_hip_set_dense replaces it, vit_hip_segment_frame_* refuses while it is armed, a
+ * host-form forward refuses, and a tap on the last layer runs all rows under vit_hip_set_last_layer_cls_only.
+ * Code 1 with a message that starts with "vit_hip_set_dense_soft: ", the previously armed request untouched and nothing of
+ * this call's left allocated: whatever vit_hip_set_dense refuses about spec, a NULL soft or d_soft, all three maps NULL,
+ * expect without d_values or the reverse, a logit_scale that is not finite and > 0, a misaligned pointer, scores without
+ * labels, scratch that cannot be allocated.
+ * There is no host form: fp32 maps are 200 KB per 224 x 224 image, and the host form of the dense request refuses `scores`
+ * for the same reason.  vit_dense_soft_check (host only, no device) validates spec against cfg and soft (everything above
+ * but the buffers) and gives the elements of one map per image. */
+typedef struct vit_dense_soft_spec { float logit_scale; const float *d_values; } vit_dense_soft_spec;
+typedef struct vit_dense_soft_buffers { float *prob, *expect, *entropy; } vit_dense_soft_buffers;
+int vit_dense_soft_check(const vit_config *cfg, const vit_dense_spec *spec, const vit_dense_soft_spec *soft, size_t *map_elems_per_image);
+int vit_hip_set_dense_soft(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_soft_spec *soft,
+                           const vit_dense_buffers *d_bufs, const vit_dense_soft_buffers *d_soft);
 
 /* ---- whole frames: overlapping windows of one large 8-bit image, their logits blended into one label per frame pixel ----
  * The sliding-window protocol of semantic segmentation (mmseg's mode="slide") in one call: the windows (vit_box_u8 boxes of

@@ -650,6 +650,49 @@ int vh_launch_dense_labels(vh_stream_t s, const float *patch_logits /* [n][grid_
                            int grid_h, int grid_w, int n_labels, int out_h, int out_w,
                            unsigned char *labels /* u8 [n][out_h][out_w] */, float *scores /* fp32, may be NULL */);
 
+/* Soft maps of the dense head (csrc/dense_soft.hip; the kernel under vit_hip_set_dense_soft, include/ViT_opencl.h): per pixel
+ * the softmax probability of the label vh_launch_dense_labels writes, the expected value of per-class `values` (depth by
+ * bins: sum_c p_c * centre_c) and the entropy of the softmax, from the same patch logits.  u = 2^-24 below.
+ * Definition.  Per pixel, v[c], c < C, are the fp32 values vh_launch_dense_labels defines above, by the same expressions:
+ * the same bits.  With s = logit_scale, finite and > 0:
+ *   m       = max_c v[c]                      (dense_labels' `scores` but for the sign of a zero, when no v is NaN)
+ *   z[c]    = s * (v[c] - m)  <= 0
+ *   S       = sum_c exp(z[c])  >= 1
+ *   prob    = 1 / S                           (the softmax probability of the label dense_labels writes)
+ *   expect  = (sum_c exp(z[c]) * values[c]) / S
+ *   entropy = log S - (sum_c exp(z[c]) * z[c]) / S      nats; a term whose exp(z) is 0 contributes 0
+ * Arithmetic, all fp32, each operation rounded once: k2 = s * fl(log2 e); t[c] = k2 * (v[c] - m); e[c] = v_exp_f32(t[c]) (the
+ * hardware's exp2, 1 ulp, a denormal result flushed to 0); S, X = sum e[c] values[c] and A = sum e[c] max(t[c], -FLT_MAX) are
+ * sequential sums over c = 0 .. C - 1 from +0, the two products as fmaf(e, ., sum): an order fixed by C alone.  prob =
+ * 1 / S, expect = X / S (IEEE divisions), entropy = fl(ln 2) * (v_log_f32(S) - A / S) (the hardware's log2, 1 ulp).  No
+ * atomics; an image's maps are the same bits wherever it sits in the batch and whatever n_images is, and a map's bits do not
+ * depend on which other maps are asked for.
+ * Special values: if any v[c] is NaN, or m is +-inf, all three outputs are written as 0x7FC00000.  A v[c] = -inf under a
+ * finite m contributes nothing.  (values are taken as finite.)
+ * Error bound, against this definition evaluated in float64 on the same fp32 v, s and values, K = 32:
+ *   |prob - prob64|       <= (C + K) u * prob64
+ *   |expect - expect64|   <= 2 (C + K) u * sum_c p64[c] |values[c]|
+ *   |entropy - entropy64| <= 2 (C + K) u * (1 + ln C)
+ * Derivation.  t is z / ln 2 with four roundings (the constant to half an ulp, k2, the difference, the product): a relative
+ * error of 3.5 u on every z, which moves S by at most 3.5 u E_p|z| S <= 3.5 u ln C * S, because E_p|z| = ln S - H <= ln C:
+ * 19.4 u at C = 256.  v_exp_f32 is good to 1 ulp = 2 u relative, a flushed term is below 2^-126 <= u S, the C-term sum costs at
+ * most C u relative, the division u: (C + 3.5 ln C + 4) u <= (C + 24) u on S and on prob.  X carries the same errors term by
+ * term and half an ulp more per fma, against sum e |values|; the quotient X / S adds S's: 2 (C + K) u sum p |values|.  A is X
+ * with the values t (each 3.5 u off itself, and E_p|t| ln 2 <= ln C), v_log_f32(S) is within 2 u log2 S + (C + 24) u / ln 2 of
+ * log2 S64, and the difference, the product with fl(ln 2) and that constant's own half ulp cost 2.5 u (1 + ln C) more: inside
+ * 2 (C + K) u (1 + ln C) with room.  Measured: tests/test_gpu_dense_soft.py prints the worst |error| / bound per map
+ * (profiles/dense_soft_errors.txt).
+ * One launch of one 256-thread workgroup per (image, patch row), as the labels kernel's, with its LDS (2 * grid_w * (C | 1) *
+ * 4 bytes); two passes over the classes, the first for m.
+ * Limits: those of vh_launch_dense_labels (n_labels, the grid, out_h, out_w, n_images; csrc/kernel_limits.h states them
+ * once); logit_scale finite and > 0; values given exactly when expect is; at least one of prob, expect, entropy; every pointer
+ * 16-byte aligned.  Anything else: code 1 with a message that starts with "vh_launch_dense_soft: ", no launch, nothing
+ * written.  No reference counterpart. */
+int vh_launch_dense_soft(vh_stream_t s, const float *patch_logits /* [n][grid_h * grid_w][n_labels] */, int n_images,
+                         int grid_h, int grid_w, int n_labels, int out_h, int out_w, float logit_scale,
+                         const float *values /* [n_labels] fp32, device; NULL iff expect is NULL */,
+                         float *prob, float *expect, float *entropy /* fp32 [n][out_h][out_w]; each may be NULL, not all three */);
+
 /* Dense stitch (csrc/dense_stitch.hip; the kernel under vit_hip_segment_frame_u8, include/ViT_opencl.h): one label per pixel
  * of a frame_h x frame_w frame from the patch logits of n_windows overlapping windows of it -- the sliding-window protocol
  * (upsample every window's logits to its box, average where boxes overlap, take the best class) as a GATHER: per pixel the

@@ -953,7 +953,7 @@ fail:
 
 /* The armed dense request behind its layer: the token rows (normalised by the feature readout into the MLP buffer, idle
  * behind fc2, or into the request's scratch; without final_norm the residual stream's patch rows in place), the patch
- * logits, the labels; timed with the classifier */
+ * logits, the labels, and the soft maps when the request was armed with them; timed with the classifier */
 static int dense_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct dense_req *de, int n)
 {
     int rc = 0;
@@ -972,8 +972,14 @@ static int dense_tap(vit_hip_ctx *ctx, vh_stream_t s, const struct dense_req *de
     float *pl = de->out.patch_logits ? de->out.patch_logits : (float *)de->head.scratch[0];
     OP(VIT_OP_HEAD, vh_launch_dense_logits(s, rows, image_stride, E, n, P, E, de->spec.d_weight, de->spec.weight_stride, de->spec.d_bias,
                                            de->spec.n_labels, pl));
-    OP(VIT_OP_HEAD, vh_launch_dense_labels(s, pl, n, de->grid_h, de->grid_w, de->spec.n_labels, de->out_h, de->out_w, de->out.labels,
-                                           de->out.scores));
+    const vit_dense_soft_buffers *so = &de->soft_out;
+    const int soft = so->prob || so->expect || so->entropy;   /* vit_hip_set_dense_soft; labels then are optional */
+    if (de->out.labels || !soft)
+        OP(VIT_OP_HEAD, vh_launch_dense_labels(s, pl, n, de->grid_h, de->grid_w, de->spec.n_labels, de->out_h, de->out_w, de->out.labels,
+                                               de->out.scores));
+    if (soft)
+        OP(VIT_OP_HEAD, vh_launch_dense_soft(s, pl, n, de->grid_h, de->grid_w, de->spec.n_labels, de->out_h, de->out_w, de->soft.logit_scale,
+                                             de->soft.d_values, so->prob, so->expect, so->entropy));
     return 0;
 fail:
     return rc;
@@ -1171,6 +1177,18 @@ SETTER(vit_hip_set_gallery_host, gallery, vit_gallery_spec, vit_gallery_buffers,
 SETTER(vit_hip_set_dense, dense, vit_dense_spec, vit_dense_buffers, 0)
 SETTER(vit_hip_set_dense_host, dense, vit_dense_spec, vit_dense_buffers, 1)
 #undef SETTER
+
+/* the dense request in device form with the soft maps attached (include/ViT_opencl.h) */
+int vit_hip_set_dense_soft(vit_hip_ctx *ctx, const vit_dense_spec *spec, const vit_dense_soft_spec *soft, const vit_dense_buffers *d_bufs,
+                           const vit_dense_soft_buffers *d_soft)
+{
+    static const char who[] = "vit_hip_set_dense_soft";
+    if (!ctx)
+        return ingest_refuse(who, "NULL context");
+    const struct request_model m = {.device = ctx->device, .max_batch = ctx->max_batch, .stream = ctx->stream, .cfg = &ctx->cfg,
+                                    .tokens = ctx->plan.tokens, .qkv_form = ctx->plan.qkv_form, .ws_bytes = ctx->plan.ws_bytes};
+    return requests_set_dense_soft(who, &m, &ctx->req, spec, soft, d_bufs, d_soft);
+}
 
 /* ---- whole frames (include/ViT_opencl.h): windows through the box forward with a dense request of the call's own, their
  * patch logits blended per frame pixel by vh_launch_dense_stitch.  Public pieces composed; nothing of a forward changes ---- */
@@ -1422,8 +1440,8 @@ int vit_hip_profile_enable(vit_hip_ctx *ctx, int max_forwards)
     if (max_forwards <= 0)
         return 0;
     /* + the readouts of an armed feature request + top-k + attention maps + the rollout's steps and read + the gallery's
-     * readout and search + the dense head's readout, logits and labels */
-    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4 + ctx->cfg.depth + 1 + 2 + 3;
+     * readout and search + the dense head's readout, logits, labels and soft maps */
+    const int per_forward = 1 + 7 * ctx->cfg.depth + 3 + 4 + 1 + 4 + ctx->cfg.depth + 1 + 2 + 4;
     ctx->prof_cap = per_forward * max_forwards;
     ctx->prof_ev = (vh_event_t *)calloc((size_t)2 * ctx->prof_cap, sizeof(vh_event_t));
     ctx->prof_class = (int *)calloc((size_t)ctx->prof_cap, sizeof(int));

@@ -30,6 +30,7 @@
 #include "kernelHandler.h"
 #include "kernel_limits.h"
 #include "vit_kernels.h"
+#include "dense_coords.h"
 #include <type_traits>
 
 namespace {
@@ -38,15 +39,14 @@ constexpr int DH_THREADS = 256;
 constexpr int DH_TT = VH_DENSE_TOKEN_TILE;   /* token rows per tile: 32 per wave */
 constexpr int DH_KC = 32;                  /* columns per stage */
 constexpr int DH_LS = DH_KC + 4;           /* LDS row stride in floats, as gallery.hip's */
-constexpr int DH_MAX_C = VH_DENSE_MAX_LABELS, DH_MAX_E = KL_DENSE_MAX_EMBED, DH_MAX_OUT = 4096;
+constexpr int DH_MAX_C = VH_DENSE_MAX_LABELS, DH_MAX_E = KL_DENSE_MAX_EMBED, DH_MAX_OUT = KL_DENSE_MAX_OUT;
 constexpr int DH_T_PIECES = DH_TT * (DH_KC / 4) / DH_THREADS;   /* 4-column pieces of a token stage per thread */
 constexpr int DH_CS_SMALL = 4;             /* 16-label tiles per workgroup when the token tiles are few */
 constexpr int DH_RB = 16;                  /* output rows a thread carries at a time */
 constexpr unsigned DH_NAN = 0x7FC00000u;   /* how a NaN score is written */
 
 inline size_t dh_logits_lds(int cs) { return (size_t)(DH_TT + 16 * cs) * DH_LS * sizeof(float); }
-inline int dh_label_stride(int C) { return C | 1; }
-inline size_t dh_labels_lds(int gw, int C) { return (size_t)2 * gw * dh_label_stride(C) * sizeof(float); }
+inline size_t dh_labels_lds(int gw, int C) { return kl_dense_labels_lds(gw, C); }
 
 template <int CS>
 __global__ __launch_bounds__(DH_THREADS, 2) void dense_logits_kernel(const float *__restrict__ rows, long image_stride, long row_stride,
@@ -148,29 +148,7 @@ __global__ __launch_bounds__(DH_THREADS, 2) void dense_logits_kernel(const float
     }
 }
 
-/* The source coordinate of output index i (include/kernelHandler.h): ratio = fl(G / out) */
-__device__ __forceinline__ float dh_src(int i, float ratio) { return fmaxf(fmaf((float)i + 0.5f, ratio, -0.5f), 0.0f); }
-__device__ __forceinline__ int dh_cell(float s, int G)
-{
-    const int r = (int)s;
-    return r < G - 1 ? r : G - 1;
-}
-
-/* the first output index whose cell is >= r (out when there is none): dh_cell(dh_src(.)) is non-decreasing */
-__device__ __forceinline__ int dh_band_start(int r, float ratio, int G, int out)
-{
-    if (r <= 0)
-        return 0;
-    if (r >= G)
-        return out;
-    const float guess = ((float)r + 0.5f) * (float)out / (float)G - 0.5f;
-    int y = guess < 0.0f ? 0 : guess > (float)out ? out : (int)guess;
-    while (y > 0 && dh_cell(dh_src(y - 1, ratio), G) >= r)
-        --y;
-    while (y < out && dh_cell(dh_src(y, ratio), G) < r)
-        ++y;
-    return y;
-}
+/* dh_src, dh_cell, dh_band_start: dense_coords.h, shared with dense_soft.hip */
 
 __global__ __launch_bounds__(DH_THREADS) void dense_labels_kernel(const float *__restrict__ logits, int GH, int GW, int C, int out_h,
                                                                  int out_w, unsigned char *__restrict__ labels, float *__restrict__ scores)

@@ -149,6 +149,21 @@ KL_FN size_t kl_feature_readout_scratch(int n_images, int tokens, int embed_dim)
 
 /* ---- dense head (dense_head.hip) -------------------------------------------------------------------------------------- */
 enum { KL_DENSE_MAX_EMBED = 2048 };
+/* ---- the per-pixel kernels of the dense head: labels (dense_head.hip) and the soft maps (dense_soft.hip) ------------- */
+enum { KL_DENSE_MAX_OUT = 4096 };   /* the largest out_h and out_w */
+/* patch rows r0 and r1 of one image x n_labels in LDS, label stride n_labels | 1 (odd: neighbouring patches on other banks) */
+KL_FN int kl_dense_label_stride(int n_labels) { return n_labels | 1; }
+KL_FN size_t kl_dense_labels_lds(int grid_w, int n_labels)
+{
+    return (size_t)2 * (size_t)grid_w * (size_t)kl_dense_label_stride(n_labels) * sizeof(float);
+}
+/* what vh_launch_dense_labels and vh_launch_dense_soft take besides their pointers: the shape of a launch */
+KL_FN int kl_dense_pixel_shape_ok(int n_images, int grid_h, int grid_w, int n_labels, int out_h, int out_w)
+{
+    return n_labels >= 2 && n_labels <= VH_DENSE_MAX_LABELS && grid_h >= 1 && grid_w >= 1 && grid_h <= VH_DENSE_MAX_GRID &&
+           grid_w <= VH_DENSE_MAX_GRID && out_h >= 1 && out_w >= 1 && out_h <= KL_DENSE_MAX_OUT && out_w <= KL_DENSE_MAX_OUT &&
+           n_images >= 1 && (long)n_images * grid_h <= 2147483647L;
+}
 
 /* ---- stitch (dense_stitch.hip) ---------------------------------------------------------------------------------------- */
 KL_FN size_t kl_round16(size_t v) { return (v + 15) & ~(size_t)15; }

@@ -1,7 +1,7 @@
 /*
  * vit_requests.c -- the armed outputs of a context (csrc/vit_requests.h): the six spec checks and the public size
- * functions, request_arm -- the one owner of every allocation and every free of a request -- the six setters around it,
- * and what a forward serves.  Plain C; nothing here launches a kernel or reads a context.
+ * functions, request_arm -- the one owner of every allocation and every free of a request -- the six setters around it
+ * (the dense request's has a second entry that attaches the soft maps), and what a forward serves.  Plain C; nothing here launches a kernel or reads a context.
  */
 #include "vit_requests.h"
 #include "kernel_limits.h"
@@ -447,9 +447,36 @@ int vit_dense_sizes(const vit_config *cfg, const vit_dense_spec *spec, size_t *l
     return 0;
 }
 
-int requests_set_dense(const char *who, const struct request_model *m, struct requests *rq, const vit_dense_spec *spec,
-                       const vit_dense_buffers *bufs, int host)
+/* soft against nothing but itself: NULL, or why not */
+static const char *dense_soft_spec_why(const vit_dense_soft_spec *soft)
 {
+    return !soft ? "NULL argument (soft)"
+           : !(soft->logit_scale > 0.0f) || !(soft->logit_scale <= 3.402823466e+38f) ? "logit_scale must be finite and > 0"
+           : (uintptr_t)soft->d_values & 15 ? "d_values must be 16-byte aligned"
+           : NULL;
+}
+
+int vit_dense_soft_check(const vit_config *cfg, const vit_dense_spec *spec, const vit_dense_soft_spec *soft, size_t *map_elems_per_image)
+{
+    static const char who[] = "vit_dense_soft_check";
+    int layer, grid_h, grid_w, out_h, out_w;
+    if (dense_spec_check(who, cfg, spec, &layer, &grid_h, &grid_w, &out_h, &out_w))
+        return 1;
+    const char *why = dense_soft_spec_why(soft);
+    if (why)
+        return ingest_refuse(who, why);
+    if (map_elems_per_image)
+        *map_elems_per_image = (size_t)out_h * out_w;
+    return 0;
+}
+
+/* Both setters of the dense request.  soft NULL: vit_hip_set_dense / _host.  Otherwise vit_hip_set_dense_soft: the device
+ * form with the soft maps attached; bufs may be NULL and labels need not be asked for. */
+static int dense_arm(const char *who, const struct request_model *m, struct requests *rq, const vit_dense_spec *spec,
+                     const vit_dense_buffers *bufs, int host, int with_soft, const vit_dense_soft_spec *soft,
+                     const vit_dense_soft_buffers *sbufs)
+{
+    static const vit_dense_buffers no_bufs;
     struct dense_req de;
     size_t scratch[3] = {0, 0, 0};
     char oom[160] = "";
@@ -457,18 +484,32 @@ int requests_set_dense(const char *who, const struct request_model *m, struct re
     if (spec) {
         if (dense_spec_check(who, m->cfg, spec, &de.layer, &de.grid_h, &de.grid_w, &de.out_h, &de.out_w))
             return 1;
+        if (with_soft && !bufs)
+            bufs = &no_bufs;
         const char *why = !spec->d_weight ? "no head weight"
                           : ((uintptr_t)spec->d_weight | (uintptr_t)spec->d_bias) & 15 ? "the head's weight and bias must be 16-byte aligned"
-                          : !bufs || !bufs->labels ? "no labels buffer"
-                          : host && (bufs->scores || bufs->patch_logits) ? "the host form takes labels only (scores, patch_logits: use the device form)"
-                          : !host && (((uintptr_t)bufs->labels | (uintptr_t)bufs->scores | (uintptr_t)bufs->patch_logits) & 15)
-                              ? "device buffers must be 16-byte aligned"
+                          : with_soft ? dense_soft_spec_why(soft)
                           : NULL;
+        why = why ? why
+              : with_soft && !sbufs ? "NULL argument (d_soft)"
+              : with_soft && !sbufs->prob && !sbufs->expect && !sbufs->entropy ? "no soft map asked for (prob, expect, entropy are all NULL)"
+              : with_soft && (sbufs->expect != NULL) != (soft->d_values != NULL) ? "d_values must be given exactly when expect is asked for"
+              : with_soft && (((uintptr_t)sbufs->prob | (uintptr_t)sbufs->expect | (uintptr_t)sbufs->entropy) & 15) ? "device buffers must be 16-byte aligned"
+              : with_soft && bufs->scores && !bufs->labels ? "scores need a labels buffer"
+              : !with_soft && (!bufs || !bufs->labels) ? "no labels buffer"
+              : host && (bufs->scores || bufs->patch_logits) ? "the host form takes labels only (scores, patch_logits: use the device form)"
+              : !host && (((uintptr_t)bufs->labels | (uintptr_t)bufs->scores | (uintptr_t)bufs->patch_logits) & 15)
+                  ? "device buffers must be 16-byte aligned"
+              : NULL;
         if (why)
             return ingest_refuse(who, why);
         de.head.form = host ? FEAT_HOST : FEAT_DEVICE;
         de.spec = *spec;
         de.out = *bufs;
+        if (with_soft) {
+            de.soft = *soft;
+            de.soft_out = *sbufs;
+        }
         if (host)
             de.head.st[0] = (struct staged){.host = (char *)bufs->labels, .per_image = (size_t)de.out_h * de.out_w};
         const size_t P = (size_t)m->tokens - 1;
@@ -483,6 +524,18 @@ int requests_set_dense(const char *who, const struct request_model *m, struct re
     if (rc == 0 && host && spec)
         rq->dense.out = (vit_dense_buffers){(unsigned char *)rq->dense.head.st[0].dev, NULL, NULL};
     return rc;
+}
+
+int requests_set_dense(const char *who, const struct request_model *m, struct requests *rq, const vit_dense_spec *spec,
+                       const vit_dense_buffers *bufs, int host)
+{
+    return dense_arm(who, m, rq, spec, bufs, host, 0, NULL, NULL);
+}
+
+int requests_set_dense_soft(const char *who, const struct request_model *m, struct requests *rq, const vit_dense_spec *spec,
+                            const vit_dense_soft_spec *soft, const vit_dense_buffers *bufs, const vit_dense_soft_buffers *sbufs)
+{
+    return dense_arm(who, m, rq, spec, bufs, 0, 1, soft, sbufs);
 }
 
 int requests_serving(const struct requests *rq, const char *who, int form, struct serving *sv)

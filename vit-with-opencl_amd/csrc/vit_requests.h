@@ -99,7 +99,9 @@ struct dense_req
     vit_dense_spec spec;
     int layer, grid_h, grid_w;   /* spec.tap resolved; the patch grid (vit_config_grid) */
     int out_h, out_w;            /* spec's, 0 resolved to img_size and to the width */
-    vit_dense_buffers out;       /* FEAT_HOST: labels = st[0].dev */
+    vit_dense_buffers out;       /* FEAT_HOST: labels = st[0].dev.  Soft-armed: labels may be NULL (no label launch) */
+    vit_dense_soft_spec soft;    /* vit_hip_set_dense_soft: the device form with soft maps attached ... */
+    vit_dense_soft_buffers soft_out;   /* ... the caller's device buffers; all NULL: not soft-armed */
 };
 
 /* The requests of a context, each armed independently of the others, in the order every walk over them takes */
@@ -123,6 +125,9 @@ int requests_set_attention(const char *who, const struct request_model *m, struc
 int requests_set_rollout(const char *who, const struct request_model *m, struct requests *rq, const vit_rollout_spec *spec, const vit_rollout_buffers *bufs, int host);
 int requests_set_gallery(const char *who, const struct request_model *m, struct requests *rq, const vit_gallery_spec *spec, const vit_gallery_buffers *bufs, int host);
 int requests_set_dense(const char *who, const struct request_model *m, struct requests *rq, const vit_dense_spec *spec, const vit_dense_buffers *bufs, int host);
+/* vit_hip_set_dense_soft: arms the dense request in device form with the soft maps attached; bufs may be NULL, or its labels */
+int requests_set_dense_soft(const char *who, const struct request_model *m, struct requests *rq, const vit_dense_spec *spec,
+                            const vit_dense_soft_spec *soft, const vit_dense_buffers *bufs, const vit_dense_soft_buffers *sbufs);
 
 /* Everything the six requests own; the caller has made sure that no forward still reads it */
 void requests_release(struct requests *rq);

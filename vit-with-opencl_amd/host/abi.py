@@ -186,6 +186,18 @@ class DenseBuffers(C.Structure):
     _fields_ = [("labels", p), ("scores", p), ("patch_logits", p)]
 
 
+@mirrors("vit_dense_soft_spec")
+class DenseSoftSpecC(C.Structure):
+    """logit_scale finite and > 0; d_values [n_labels] fp32 on the device, NULL without expect."""
+    _fields_ = [("logit_scale", f), ("d_values", p)]
+
+
+@mirrors("vit_dense_soft_buffers")
+class DenseSoftBuffers(C.Structure):
+    """device pointers, fp32 [max_batch][out_h][out_w]; each may be NULL, not all three."""
+    _fields_ = [("prob", p), ("expect", p), ("entropy", p)]
+
+
 @mirrors("vit_frame_spec")
 class FrameSpecC(C.Structure):
     """head: a vit_dense_spec whose out_h and out_w are 0; fill_label for pixels no window covers."""
@@ -336,6 +348,7 @@ PROTOTYPES = {
         _fn("vh_launch_gallery_topk", p, p, i, i, p, i, l, l, i, i, p, p, p),
         _fn("vh_launch_dense_logits", p, p, l, l, i, i, i, p, l, p, i, p),
         _fn("vh_launch_dense_labels", p, p, i, i, i, i, i, i, p, p),
+        _fn("vh_launch_dense_soft", p, p, i, i, i, i, i, i, f, p, p, p, p),
         _fn("vh_dense_stitch_scratch", i, i, i, l, ret=sz),
         _fn("vh_launch_dense_stitch", p, p, i, i, i, i, fp, i, i, ip, ip, i, p, sz, p, p, p),
         _fn("vh_launch_resample_pos_embed", p, p, p, i, i, i, i, i, i, i, i),
@@ -410,6 +423,8 @@ PROTOTYPES = {
         _fn("vit_dense_sizes", P(VitConfig), P(DenseSpecC), szp, szp, szp, szp),
         _fn("vit_hip_set_dense", p, P(DenseSpecC), P(DenseBuffers)),
         _fn("vit_hip_set_dense_host", p, P(DenseSpecC), P(DenseBuffers)),
+        _fn("vit_dense_soft_check", P(VitConfig), P(DenseSpecC), P(DenseSoftSpecC), szp),
+        _fn("vit_hip_set_dense_soft", p, P(DenseSpecC), P(DenseSoftSpecC), P(DenseBuffers), P(DenseSoftBuffers)),
         _fn("vit_frame_sizes", P(VitConfig), P(FrameSpecC), i, i, i, szp, szp),
         _fn("vit_stitch_check", i, i, fp, i, s),
         _fn("vit_stitch_index", i, i, i, fp, i, ip, ip, l, ret=l),

@@ -19,7 +19,7 @@ from .abi import (  # noqa: F401
     ATTN_ARITH, ATTN_KERNEL, DENSE_MAX_GRID, DENSE_MAX_LABELS, DENSE_TOKEN_TILE, ENUMS, EXPORTS, FEATURE_DTYPES, FP32_MATH,
     GALLERY_DTYPES, GALLERY_MAX_SPLITS, GALLERY_ROW_TILE, GALLERY_SOURCES, OP_NAMES, PIXEL_LAYOUTS, POS_MODES, PRECISIONS,
     PROTOTYPES, QKV_FORMS, RESIZE_FILTERS, SHARD_FN, STITCH_BLOCK, STITCH_MAX_SIDE, STRUCTS, TOKEN_LAYOUTS, TOPK_SCORES,
-    AttnBuffers, AttnSpecC, Box, CompareReport, DenseBuffers, DenseSpecC, FeatureBuffers, FeatureSpecC, FrameBuffers, FrameSpecC,
+    AttnBuffers, AttnSpecC, Box, CompareReport, DenseBuffers, DenseSoftBuffers, DenseSoftSpecC, DenseSpecC, FeatureBuffers, FeatureSpecC, FrameBuffers, FrameSpecC,
     GalleryBuffers,
     GallerySpecC, ImageData, ImageU8, Network, PixelNorm, PosResampleC, ResizeCrop, RolloutBuffers, RolloutSpecC, TopKBuffers,
     TopKSpecC, VitConfig, declare, f32p, voidp,
@@ -144,6 +144,14 @@ def dense_sizes(cfg: "VitConfig", spec: DenseSpec):
     cs = spec.c_struct()
     check(lib().vit_dense_sizes(C.byref(cfg), C.byref(cs), *[C.byref(o) for o in out]), "vit_dense_sizes")
     return tuple(o.value for o in out)
+
+
+def dense_soft_check(cfg: "VitConfig", spec: DenseSpec, logit_scale: float = 1.0, d_values=None) -> int:
+    """vit_dense_soft_check -> elements of one soft map per image; raises VitHipError with the library's message"""
+    out = C.c_size_t()
+    cs, soft = spec.c_struct(), DenseSoftSpecC(float(logit_scale), _device_ptr(d_values))
+    check(lib().vit_dense_soft_check(C.byref(cfg), C.byref(cs), C.byref(soft), C.byref(out)), "vit_dense_soft_check")
+    return out.value
 
 
 def _pos_mode(mode) -> int:
@@ -854,6 +862,58 @@ class ViTHip:
         finally:
             self.set_dense_host(None)
         return labels
+
+    def set_dense_soft(self, spec, weight=None, bias=None, soft_scale: float = 1.0, values=None, labels=None, prob=None, expect=None,
+                       entropy=None):
+        """Arm (spec=None: disarm) the dense request with soft maps attached, device form: prob / expect / entropy are float32
+        DeviceBuffers (or device pointers) of [max_batch][out_h][out_w], each may be None, not all; labels (uint8, the same
+        shape) may be None, then no labels are written.  soft_scale multiplies the logits before the softmax; values (a
+        [C] float32 array or DeviceBuffer: the bin centres) is given exactly when expect is.  weight, bias: see _dense_head."""
+        if spec is None:
+            check(self.L.vit_hip_set_dense_soft(self.ctx, None, None, None, None), "vit_hip_set_dense_soft")
+            self._dense_keep = self._dense_head_keep = None
+            return
+        spec = self._dense_head(spec, weight, bias)
+        if values is not None and not isinstance(values, (DeviceBuffer, int, C.c_void_p)):
+            values = DeviceBuffer.from_numpy(np.ascontiguousarray(values, dtype=np.float32))
+        soft = DenseSoftSpecC(float(soft_scale), _device_ptr(values))
+        bufs = DenseBuffers(_device_ptr(labels), None, None)
+        maps = DenseSoftBuffers(_device_ptr(prob), _device_ptr(expect), _device_ptr(entropy))
+        cs = spec.c_struct()
+        check(self.L.vit_hip_set_dense_soft(self.ctx, C.byref(cs), C.byref(soft), C.byref(bufs), C.byref(maps)), "vit_hip_set_dense_soft")
+        self._dense_keep = (labels, prob, expect, entropy)
+        self._dense_head_keep = (spec.d_weight, spec.d_bias, values)
+
+    def segment_soft(self, images: np.ndarray, weight, bias=None, values=None, logit_scale: float = 1.0, size=None, tap: int = -1,
+                     final_norm: bool = True, outputs=("labels", "prob")):
+        """fp32 images [n][C][H][W] -> {name: array [n][H][W]} for the names in `outputs`: "labels" (uint8), "prob" (the
+        softmax probability of that label), "expect" (sum_c p_c * values[c]; with values the bin centres of a depth head this
+        is the depth map) and "entropy" (nats), float32.  The softmax is over logit_scale times the upsampled logits of the
+        linear head (weight [C][E], bias [C] or None) at an output of `size` (an int or (height, width); None: the model's
+        img_size).  Chunks of at most max_batch images through the device form, armed for this one call."""
+        names = ("labels", "prob", "expect", "entropy")
+        outputs = tuple(outputs)
+        if not outputs or any(o not in names for o in outputs):
+            raise ValueError(f"segment_soft: outputs must be a non-empty subset of {names}")
+        images = np.ascontiguousarray(images, dtype=np.float32)
+        n, mb = images.shape[0], self.max_batch
+        h, w = (size, size) if isinstance(size, int) else size if size is not None else (self.cfg.img_size, self.cfg.width)
+        got = {o: np.empty((n, h, w), dtype=np.uint8 if o == "labels" else np.float32) for o in outputs}
+        dev = {o: DeviceBuffer(mb * h * w, np.uint8 if o == "labels" else np.float32) for o in outputs}
+        d_img = DeviceBuffer(mb * int(np.prod(images.shape[1:])))
+        self.set_dense_soft(DenseSpec(0, h, w, tap, final_norm), weight, bias, logit_scale, values, **dev)
+        try:
+            for a in range(0, n, mb):
+                m = min(mb, n - a)
+                chunk = images[a:a + m]
+                check(self.L.vh_h2d(d_img.ptr, chunk.ctypes.data_as(C.c_void_p), chunk.nbytes, self.stream), "vh_h2d")
+                self.forward_device(d_img.ptr, m)
+                self.sync()
+                for o in outputs:
+                    got[o][a:a + m] = dev[o].to_numpy((mb, h, w))[:m]
+        finally:
+            self.set_dense_soft(None)
+        return got
 
     def _frame_spec(self, weight, bias, tap, final_norm, fill_label, n_labels=0, weight_stride=0):
         """(FrameSpecC, what keeps the head's device arrays alive) for the frame calls: the head as _dense_head makes it"""
