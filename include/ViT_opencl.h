@@ -646,9 +646,9 @@ int vit_hip_set_gallery_host(vit_hip_ctx *ctx, const vit_gallery_spec *spec, con
  * feature request for pooled does; logits are bit-identical either way.
  * vit_hip_multi: vit_hip_forward_multi and vit_hip_forward_device_multi neither write labels nor refuse.
  * Out of scope: the full [C][H][W] probability tensor (the per-pixel confidence, expected value and entropy maps are
- * vit_hip_set_dense_soft, below), the soft maps for vit_hip_segment_frame_* (which needs a soft stitch: the natural
- * follow-up), the "linear" (ReLU-normalised) bin strategy of depth heads, a host form of the soft maps, multi-layer or
- * non-linear decode heads, antialiased or bicubic upsampling, more than 256 labels. */
+ * vit_hip_set_dense_soft, below; for whole frames vit_hip_segment_frame_soft_*), the "linear" (ReLU-normalised) bin
+ * strategy of depth heads, a host form of the soft maps, multi-layer or non-linear decode heads, antialiased or bicubic
+ * upsampling, more than 256 labels. */
 typedef struct vit_dense_spec {
     int tap, final_norm;          /* as vit_gallery_spec */
     int n_labels, out_h, out_w;   /* out_h 0 = the model's img_size, out_w 0 = its width */
@@ -723,7 +723,8 @@ int vit_hip_set_dense_soft(vit_hip_ctx *ctx, const vit_dense_spec *spec, const v
  * take; head.out_h or head.out_w not 0; fill_label outside 0..255; n_windows < 1 or n_windows * (T - 1) >= 2^31 - 128; a frame
  * outside vit_image_u8's limits; a window outside the frame (vit_stitch_check) or with image != 0; an unknown layout or filter;
  * no labels buffer or a misaligned device buffer.
- * Out of scope: tapered blend weights, per-pixel probabilities, several frames per call, non-square contexts, vit_hip_multi. */
+ * Out of scope: tapered blend weights, several frames per call, non-square contexts, vit_hip_multi.  Per-pixel confidence,
+ * expected value and entropy: vit_hip_segment_frame_soft_*, below. */
 typedef struct vit_frame_spec {
     vit_dense_spec head;   /* tap, final_norm, n_labels, weight_stride, d_weight, d_bias; out_h and out_w must be 0 */
     int fill_label;        /* 0..255: the label of pixels no window covers */
@@ -751,6 +752,38 @@ int vit_hip_segment_frame_device_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_fram
 int vit_hip_segment_frame_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const vit_box_u8 *windows, int n_windows,
                              int layout, int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec,
                              const vit_frame_buffers *h_out);
+
+/* ---- whole frames, soft maps: per-pixel confidence, expected value and entropy of a large frame ----
+ * The same protocol followed by its softmax -- average the windows' logits, then softmax: sliding-window depth by bins, or a
+ * mask of uncertain pixels, on a 4000 x 3000 frame.  vit_hip_segment_frame_soft_* run the windows exactly as
+ * vit_hip_segment_frame_* do and write, per frame pixel, prob / expect / entropy as vit_hip_set_dense_soft defines them on
+ * the blended mean logits (vh_launch_dense_stitch_soft, include/kernelHandler.h: the definition bit for bit and its error
+ * bound); fp32 [H][W] each, each may be NULL, not all three; a pixel that no window covers is 0x7FC00000 in every map.
+ * soft: logit_scale and d_values as vit_hip_set_dense_soft takes them; d_values is DEVICE memory in both forms, as the head's
+ * d_weight is.  d_out (h_out) may be NULL, or its labels NULL: then vh_launch_dense_stitch is not launched; scores and cover
+ * need labels.  Labels, scores and cover are vit_hip_segment_frame_*'s bits.
+ * A call: everything is validated; the scratch of vit_hip_segment_frame_* is allocated, with one block index per stitch
+ * launch (each launcher copies its index synchronously: one scratch per launch in flight); the windows run as there; the
+ * request is disarmed; vh_launch_dense_stitch where labels are asked for, then vh_launch_dense_stitch_soft, both timed under
+ * VIT_OP_HEAD; the stream is waited for and the scratch freed.  On return -- success or failure -- the context has no dense
+ * request armed and holds no allocation of the call's.  The host form uploads the frame once, runs the device form and
+ * copies back what was asked for.
+ * Code 1 with a message that starts with the entry point's name, nothing queued: whatever vit_hip_segment_frame_* refuse
+ * (but for the labels buffer), whatever vit_hip_set_dense_soft refuses about soft and the maps (a NULL soft or d_soft, all
+ * three maps NULL, expect without d_values or the reverse, a logit_scale that is not finite and > 0, a misaligned d_values or
+ * device map), scores or cover without labels.  vit_frame_soft_check (host only, no device) validates spec, soft, the frame
+ * size and n_windows against cfg and gives the elements of one map.
+ * Out of scope: the full [C][H][W] probabilities, tapered blend weights, several frames per call, vit_hip_multi. */
+int vit_frame_soft_check(const vit_config *cfg, const vit_frame_spec *spec, const vit_dense_soft_spec *soft, int frame_h,
+                         int frame_w, int n_windows, size_t *map_elems);
+int vit_hip_segment_frame_soft_device_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_frame, const vit_box_u8 *windows, int n_windows,
+                                         int layout, int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec,
+                                         const vit_dense_soft_spec *soft, const vit_frame_buffers *d_out,
+                                         const vit_dense_soft_buffers *d_soft);
+int vit_hip_segment_frame_soft_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const vit_box_u8 *windows, int n_windows,
+                                  int layout, int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec,
+                                  const vit_dense_soft_spec *soft, const vit_frame_buffers *h_out,
+                                  const vit_dense_soft_buffers *h_soft);
 
 /* Debug hook: copy the residual stream of the last forward ([n*tokens][embed], un-normalised) to the host.  Where that
  * forward ran the last layer behind its attention on the class-token rows only, the full layer's launches run on all rows of

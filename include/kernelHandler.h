@@ -761,6 +761,58 @@ int vh_launch_dense_stitch(vh_stream_t s, const float *patch_logits /* device [n
                            int fill_label, void *d_scratch, size_t scratch_bytes, unsigned char *labels /* u8 [frame_h][frame_w] */,
                            float *scores /* fp32, may be NULL */, unsigned char *cover /* u8, may be NULL */);
 
+/* Soft stitch (csrc/dense_stitch_soft.hip; the kernel under vit_hip_segment_frame_soft_u8, include/ViT_opencl.h): the soft
+ * maps of vh_launch_dense_soft per pixel of a frame, on the blended means of vh_launch_dense_stitch -- the slide protocol
+ * followed by its softmax (average the windows' logits, then softmax), as a gather: no [C][H][W] buffer.  u = 2^-24 below.
+ * Inputs.  patch_logits, windows, offsets, ids and d_scratch exactly as vh_launch_dense_stitch takes them (windows, offsets
+ * and ids in HOST memory, the index that of vit_stitch_index(.., VH_STITCH_BLOCK, ..), d_scratch of vh_dense_stitch_scratch
+ * bytes with that launcher's layout and that launcher's rule: one scratch per launch in flight); logit_scale, values (device
+ * [n_labels], given exactly when expect is) and the three maps, fp32 [frame_h][frame_w] each, as vh_launch_dense_soft takes
+ * them: each map may be NULL, not all three.
+ * Definition.  Per frame pixel, m[c], c < C, is the blended mean vh_launch_dense_stitch defines above -- coverage,
+ * coordinates, the three lerps per window, the adds in ascending window index with the first value replacing the zero, one
+ * fp32 division by (float)count -- by the same expressions: the same bits.  The three maps are vh_launch_dense_soft's
+ * definition with v[c] := m[c], operation for operation: M = max_c m[c], c ascending, a NaN never the maximum; k2 = s *
+ * fl(log2 e); t = k2 * (m[c] - M); e = v_exp_f32(t); S, X = sum fmaf(e, values[c], .) and A = sum fmaf(e, max(t, -FLT_MAX), .)
+ * sequential over c = 0 .. C - 1 from +0; prob = 1 / S, expect = X / S, entropy = fl(ln 2) * (v_log_f32(S) - A / S).
+ * Special values: a pixel that no window covers, a pixel with any NaN m[c] (a NaN corner under a non-zero or zero weight of
+ * a covering window, or +inf and -inf of one class in two covering windows) and a pixel whose M is +-inf get 0x7FC00000 in all
+ * three maps.  A -inf under a finite M contributes nothing.
+ * Consequences.  (1) For one window of integer corners with r - l = frame_w and b - t = frame_h the maps are
+ * vh_launch_dense_soft's bits at out_h x out_w = frame_h x frame_w: count = 1, m = v / 1.0f = v, and v is
+ * vh_launch_dense_labels' value by the consequence stated for the stitch.  (2) A pixel's bits depend on that pixel, on the
+ * windows that cover it with the order of their indices, and on their logits: not on the frame size, on other windows, on
+ * what else a block's list names, on which maps are asked for, nor on how the kernel keeps m between its two passes (below).
+ * (3) No atomics: the same output on every run.
+ * Error bound.  Against the definition evaluated in float64 on the same fp32 m: vh_launch_dense_soft's bound unchanged, (C
+ * + 32) u relative on prob and its companions on expect and entropy -- it is the same arithmetic on the same kind of input.
+ * Against float64 throughout (blend and softmax) on the same fp32 logits and boxes: m is within delta = max_c ((1 + A) max_w
+ * B_w + A max_w |v64_w|) of m64, the stitch's bound; softmax is invariant under a shift of all m, so every ln p_c moves by at
+ * most 2 s delta, and with g = expm1(2 s delta)
+ *   |prob - prob64| <= g prob64 + (C + 32) u prob64,   |expect - expect64| <= g sum p64 |values| + 2 (C + 32) u sum p64 |values|,
+ *   |entropy - entropy64| <= g (1 + ln C) + 2 (C + 32) u (1 + ln C)
+ * -- the combination tests/dense_soft_ref.py::combined_bounds makes of the interpolation bound, with the stitch's delta for it.
+ * Measured: tests/test_gpu_stitch_soft.py prints the worst |error| / bound per map (profiles/frame_soft_errors.txt).
+ * One workgroup of VH_STITCH_BLOCK^2 threads per block, one pixel per thread, classes in chunks of 16, the block's list in
+ * ascending order per chunk, corner logits as 16-byte global loads: the stitch's decomposition.  The softmax needs M before
+ * its sums: pass 1 blends every chunk for M, pass 2 needs every m[c] again.  Two ways are kept, which give the same bits
+ * because the definition fixes every operation: blend again (variant 1, any C), or keep the means of pass 1 in registers
+ * (variant 2, C <= 160: ten chunks).  vh_dense_stitch_soft_variant(n_labels) says which a launch takes -- by n_labels alone,
+ * from measurements (a third way, the means in LDS, was slower than either: docs/LABBOOK.md).  The tests and
+ * tools/frame_soft_rates.py reach either variant through an internal entry that takes it as an argument of the call
+ * (csrc/vit_kernels.h); the library keeps no switch.
+ * Limits: vh_launch_dense_stitch's (n_labels, the grid, the frame, n_windows, the boxes, the index -- validated on the host
+ * before any copy -- scratch_bytes, 16-byte alignment of every device pointer) and vh_launch_dense_soft's (logit_scale finite
+ * and > 0; values given exactly when expect is; at least one map).  Anything else: code 1 with a message that starts with
+ * "vh_launch_dense_stitch_soft: ", no launch, nothing written.  No reference counterpart. */
+int vh_dense_stitch_soft_variant(int n_labels);
+int vh_launch_dense_stitch_soft(vh_stream_t s, const float *patch_logits /* device [n_windows][grid_h * grid_w][n_labels] */,
+                                int n_windows, int grid_h, int grid_w, int n_labels, const float *windows /* host [n_windows][4] */,
+                                int frame_h, int frame_w, const int *offsets /* host [blocks + 1] */, const int *ids /* host */,
+                                void *d_scratch, size_t scratch_bytes, float logit_scale,
+                                const float *values /* [n_labels] fp32, device; NULL iff expect is NULL */,
+                                float *prob, float *expect, float *entropy /* fp32 [frame_h][frame_w]; each may be NULL, not all three */);
+
 /* Position embedding resampled to another patch grid (csrc/pos_resample.hip; the kernel under vit_hip_create_at_resolution,
  * include/ViT_opencl.h).  src [prefix + in_h * in_w][E] fp32 -> dst [prefix + out_h * out_w][E] fp32, both contiguous.
  * Definition.  The first `prefix` rows (the class token's) are copied bit for bit.  The remaining rows are a row-major

@@ -1237,11 +1237,20 @@ int vit_frame_sizes(const vit_config *cfg, const vit_frame_spec *spec, int frame
     return 0;
 }
 
+/* the soft side of a frame call: a NULL pointer to it for the labels calls, which then need their labels buffer */
+struct frame_soft {
+    const vit_dense_soft_spec *soft;
+    const vit_dense_soft_buffers *maps;
+};
+
 /* Everything both forms refuse, before anything is queued or allocated; *patch_elems: a window's patch logits, (T - 1) * n_labels */
 static int frame_check(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *frame, const vit_box_u8 *windows, int n_windows, int layout,
-                       int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_frame_buffers *out, int on_device,
-                       size_t *patch_elems)
+                       int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_frame_buffers *out,
+                       const struct frame_soft *fs, int on_device, size_t *patch_elems)
 {
+    static const vit_frame_buffers no_out;
+    if (fs && !out)
+        out = &no_out;
     if (!ctx || !frame || !windows || !norm || !spec || !out || !frame->data)
         return ingest_refuse(who, "NULL argument");
     if (frame_spec_check(who, &ctx->cfg, spec, frame->height, frame->width, n_windows, patch_elems))
@@ -1253,7 +1262,13 @@ static int frame_check(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *fr
         return 1;
     if (!spec->head.d_weight || (((uintptr_t)spec->head.d_weight | (uintptr_t)spec->head.d_bias) & 15))
         return ingest_refuse(who, "the head's weight must be given, weight and bias 16-byte aligned");
-    if (!out->labels)
+    if (fs) {
+        const char *why = requests_dense_soft_why(fs->soft, fs->maps, on_device);
+        if (why)
+            return ingest_refuse(who, why);
+        if (!out->labels && (out->scores || out->cover))
+            return ingest_refuse(who, "scores and cover need a labels buffer");
+    } else if (!out->labels)
         return ingest_refuse(who, "no labels buffer");
     if (on_device && (((uintptr_t)out->labels | (uintptr_t)out->scores | (uintptr_t)out->cover) & 15))
         return ingest_refuse(who, "device output buffers must be 16-byte aligned");
@@ -1277,18 +1292,24 @@ static int frame_check(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *fr
     return 0;
 }
 
-/* The device form behind its checks */
+/* The device form behind its checks.  fs NULL: the labels calls.  Otherwise the soft calls: the label stitch only where labels
+ * are asked for, then the soft stitch, each with an index of its own in device memory (the stitch launchers' rule: one scratch
+ * per launch in flight -- the second launcher's synchronous copies must not run over the queued kernel's index), both timed
+ * under VIT_OP_HEAD */
 static int frame_run(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *d_frame, const vit_box_u8 *windows, int n_windows, int layout,
-                     int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_frame_buffers *d_out, size_t patch_elems)
+                     int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_frame_buffers *d_out,
+                     const struct frame_soft *fs, size_t patch_elems)
 {
     int rc = 0, armed = 0;
+    const vh_stream_t s = ctx->stream;
+    const int want_labels = d_out && d_out->labels;
     const int H = d_frame->height, W = d_frame->width, mb = ctx->max_batch;
     const int C = spec->head.n_labels;
     int grid_h, grid_w;
     vit_config_grid(&ctx->cfg, &grid_h, &grid_w);
     float *boxes4 = malloc((size_t)n_windows * 4 * sizeof(float));
     int *offsets = NULL, *ids = NULL;
-    void *d_all = NULL, *d_chunk = NULL, *d_lab = NULL, *d_index = NULL;
+    void *d_all = NULL, *d_chunk = NULL, *d_lab = NULL, *d_index = NULL, *d_index_soft = NULL;
     if (!boxes4) {
         rc = ingest_refuse(who, "out of host memory");
         goto fail;
@@ -1314,7 +1335,8 @@ static int frame_run(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *d_fr
     const size_t index_bytes = kl_dense_stitch_scratch(n_windows, H, W, n_ids);
     TRY(vh_set_device(ctx->device));
     if (vh_malloc(&d_all, align_up((size_t)n_windows * patch_elems * sizeof(float), 16)) || vh_malloc(&d_chunk, align_up((size_t)mb * patch_elems * sizeof(float), 16)) ||
-        vh_malloc(&d_lab, align_up((size_t)mb, 16)) || vh_malloc(&d_index, index_bytes)) {
+        vh_malloc(&d_lab, align_up((size_t)mb, 16)) || (want_labels && vh_malloc(&d_index, index_bytes)) ||
+        (fs && vh_malloc(&d_index_soft, index_bytes))) {
         rc = ingest_refuse(who, "the scratch of the call (patch logits of all windows, block index) cannot be allocated");
         goto fail;
     }
@@ -1329,8 +1351,13 @@ static int frame_run(const char *who, vit_hip_ctx *ctx, const vit_image_u8 *d_fr
     }
     armed = 0;
     TRY(vit_hip_set_dense(ctx, NULL, NULL));
-    TRY(vh_launch_dense_stitch(ctx->stream, d_all, n_windows, grid_h, grid_w, C, boxes4, H, W, offsets, ids, spec->fill_label, d_index,
-                               index_bytes, d_out->labels, d_out->scores, d_out->cover));
+    if (want_labels)
+        OP_T(fs != NULL, VIT_OP_HEAD, vh_launch_dense_stitch(s, d_all, n_windows, grid_h, grid_w, C, boxes4, H, W, offsets, ids, spec->fill_label,
+                                                             d_index, index_bytes, d_out->labels, d_out->scores, d_out->cover));
+    if (fs)
+        OP(VIT_OP_HEAD, vh_launch_dense_stitch_soft(s, d_all, n_windows, grid_h, grid_w, C, boxes4, H, W, offsets, ids, d_index_soft, index_bytes,
+                                                    fs->soft->logit_scale, fs->soft->d_values, fs->maps->prob, fs->maps->expect,
+                                                    fs->maps->entropy));
     TRY(vh_stream_sync(ctx->stream));
 fail:
     if (armed) {   /* keep the failure's message over the disarming's */
@@ -1339,10 +1366,10 @@ fail:
         vit_hip_set_dense(ctx, NULL, NULL);
         vh_set_error(rc, kept);
     }
-    if (d_all || d_chunk || d_lab || d_index) {
+    if (d_all || d_chunk || d_lab || d_index || d_index_soft) {
         if (rc)
             vh_stream_sync(ctx->stream);
-        void *dev[] = {d_all, d_chunk, d_lab, d_index};
+        void *dev[] = {d_all, d_chunk, d_lab, d_index, d_index_soft};
         for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); ++i)
             if (dev[i])
                 vh_free(dev[i]);
@@ -1358,9 +1385,9 @@ int vit_hip_segment_frame_device_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_fram
 {
     static const char who[] = "vit_hip_segment_frame_device_u8";
     size_t patch_elems = 0;
-    if (frame_check(who, ctx, d_frame, windows, n_windows, layout, filter, norm, spec, d_out, 1, &patch_elems))
+    if (frame_check(who, ctx, d_frame, windows, n_windows, layout, filter, norm, spec, d_out, NULL, 1, &patch_elems))
         return 1;
-    return frame_run(who, ctx, d_frame, windows, n_windows, layout, filter, norm, spec, d_out, patch_elems);
+    return frame_run(who, ctx, d_frame, windows, n_windows, layout, filter, norm, spec, d_out, NULL, patch_elems);
 }
 
 int vit_hip_segment_frame_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const vit_box_u8 *windows, int n_windows, int layout, int filter,
@@ -1369,7 +1396,7 @@ int vit_hip_segment_frame_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const 
     static const char who[] = "vit_hip_segment_frame_u8";
     int rc = 0;
     size_t patch_elems = 0;
-    if (frame_check(who, ctx, frame, windows, n_windows, layout, filter, norm, spec, h_out, 0, &patch_elems))
+    if (frame_check(who, ctx, frame, windows, n_windows, layout, filter, norm, spec, h_out, NULL, 0, &patch_elems))
         return 1;
     /* what the caller's image owns: rows of `row` bytes, row_stride apart -- the last row of the last plane ends with its pixels,
      * not with its stride (a column band of a larger array), so that is where the upload ends */
@@ -1387,7 +1414,7 @@ int vit_hip_segment_frame_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const 
     TRY(vh_h2d(d_data, frame->data, frame_bytes, ctx->stream));
     const vit_image_u8 d_frame = {.data = d_data, .height = frame->height, .width = frame->width, .row_stride = frame->row_stride};
     const vit_frame_buffers d_out = {.labels = d_lab, .scores = d_sc, .cover = d_cov};
-    TRY(frame_run(who, ctx, &d_frame, windows, n_windows, layout, filter, norm, spec, &d_out, patch_elems));
+    TRY(frame_run(who, ctx, &d_frame, windows, n_windows, layout, filter, norm, spec, &d_out, NULL, patch_elems));
     TRY(vh_d2h(h_out->labels, d_lab, px, ctx->stream));
     if (d_sc)
         TRY(vh_d2h(h_out->scores, d_sc, px * sizeof(float), ctx->stream));
@@ -1396,6 +1423,89 @@ int vit_hip_segment_frame_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const 
 fail:
     vh_stream_sync(ctx->stream);
     void *dev[] = {d_data, d_lab, d_sc, d_cov};
+    for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); ++i)
+        if (dev[i])
+            vh_free(dev[i]);
+    return rc;
+}
+
+/* ---- whole frames, soft maps (include/ViT_opencl.h): frame_run with the soft stitch behind the windows ---- */
+
+int vit_frame_soft_check(const vit_config *cfg, const vit_frame_spec *spec, const vit_dense_soft_spec *soft, int frame_h, int frame_w,
+                         int n_windows, size_t *map_elems)
+{
+    static const char who[] = "vit_frame_soft_check";
+    size_t patch_elems = 0;
+    if (frame_spec_check(who, cfg, spec, frame_h, frame_w, n_windows, &patch_elems))
+        return 1;
+    float *const some = (float *)(uintptr_t)16;   /* the rules about soft alone: maps that fit it */
+    const vit_dense_soft_buffers with = {.prob = some, .expect = soft && soft->d_values ? some : NULL};
+    const char *why = requests_dense_soft_why(soft, &with, 0);
+    if (why)
+        return ingest_refuse(who, why);
+    if (map_elems)
+        *map_elems = (size_t)frame_h * frame_w;
+    return 0;
+}
+
+int vit_hip_segment_frame_soft_device_u8(vit_hip_ctx *ctx, const vit_image_u8 *d_frame, const vit_box_u8 *windows, int n_windows, int layout,
+                                         int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_dense_soft_spec *soft,
+                                         const vit_frame_buffers *d_out, const vit_dense_soft_buffers *d_soft)
+{
+    static const char who[] = "vit_hip_segment_frame_soft_device_u8";
+    const struct frame_soft fs = {.soft = soft, .maps = d_soft};
+    size_t patch_elems = 0;
+    if (frame_check(who, ctx, d_frame, windows, n_windows, layout, filter, norm, spec, d_out, &fs, 1, &patch_elems))
+        return 1;
+    return frame_run(who, ctx, d_frame, windows, n_windows, layout, filter, norm, spec, d_out, &fs, patch_elems);
+}
+
+int vit_hip_segment_frame_soft_u8(vit_hip_ctx *ctx, const vit_image_u8 *frame, const vit_box_u8 *windows, int n_windows, int layout,
+                                  int filter, const vit_pixel_norm *norm, const vit_frame_spec *spec, const vit_dense_soft_spec *soft,
+                                  const vit_frame_buffers *h_out, const vit_dense_soft_buffers *h_soft)
+{
+    static const char who[] = "vit_hip_segment_frame_soft_u8";
+    static const vit_frame_buffers no_out;
+    int rc = 0;
+    size_t patch_elems = 0;
+    const struct frame_soft h_fs = {.soft = soft, .maps = h_soft};
+    if (frame_check(who, ctx, frame, windows, n_windows, layout, filter, norm, spec, h_out, &h_fs, 0, &patch_elems))
+        return 1;
+    if (!h_out)
+        h_out = &no_out;
+    /* the upload ends with the last row's pixels (vit_hip_segment_frame_u8) */
+    const size_t planes = layout == VIT_PIXELS_HWC ? 1 : (size_t)ctx->cfg.in_chans;
+    const size_t row = (size_t)frame->width * (layout == VIT_PIXELS_HWC ? (size_t)ctx->cfg.in_chans : 1);
+    const size_t frame_bytes = (planes * (size_t)frame->height - 1) * (size_t)frame->row_stride + row;
+    const size_t px = (size_t)frame->height * frame->width;
+    void *d_data = NULL, *d_lab = NULL, *d_sc = NULL, *d_cov = NULL, *d_map[3] = {NULL, NULL, NULL};
+    float *const h_map[3] = {h_soft->prob, h_soft->expect, h_soft->entropy};
+    TRY(vh_set_device(ctx->device));
+    if (vh_malloc(&d_data, align_up(frame_bytes, 16)) || (h_out->labels && vh_malloc(&d_lab, align_up(px, 16))) ||
+        (h_out->scores && vh_malloc(&d_sc, px * sizeof(float))) || (h_out->cover && vh_malloc(&d_cov, align_up(px, 16))) ||
+        (h_map[0] && vh_malloc(&d_map[0], px * sizeof(float))) || (h_map[1] && vh_malloc(&d_map[1], px * sizeof(float))) ||
+        (h_map[2] && vh_malloc(&d_map[2], px * sizeof(float)))) {
+        rc = ingest_refuse(who, "the frame and its outputs cannot be allocated on the device");
+        goto fail;
+    }
+    TRY(vh_h2d(d_data, frame->data, frame_bytes, ctx->stream));
+    const vit_image_u8 d_frame = {.data = d_data, .height = frame->height, .width = frame->width, .row_stride = frame->row_stride};
+    const vit_frame_buffers d_out = {.labels = d_lab, .scores = d_sc, .cover = d_cov};
+    const vit_dense_soft_buffers d_soft = {.prob = d_map[0], .expect = d_map[1], .entropy = d_map[2]};
+    const struct frame_soft d_fs = {.soft = soft, .maps = &d_soft};
+    TRY(frame_run(who, ctx, &d_frame, windows, n_windows, layout, filter, norm, spec, &d_out, &d_fs, patch_elems));
+    if (d_lab)
+        TRY(vh_d2h(h_out->labels, d_lab, px, ctx->stream));
+    if (d_sc)
+        TRY(vh_d2h(h_out->scores, d_sc, px * sizeof(float), ctx->stream));
+    if (d_cov)
+        TRY(vh_d2h(h_out->cover, d_cov, px, ctx->stream));
+    for (int k = 0; k < 3; ++k)
+        if (d_map[k])
+            TRY(vh_d2h(h_map[k], d_map[k], px * sizeof(float), ctx->stream));
+fail:
+    vh_stream_sync(ctx->stream);
+    void *dev[] = {d_data, d_lab, d_sc, d_cov, d_map[0], d_map[1], d_map[2]};
     for (size_t i = 0; i < sizeof(dev) / sizeof(dev[0]); ++i)
         if (dev[i])
             vh_free(dev[i]);

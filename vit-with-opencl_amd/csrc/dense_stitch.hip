@@ -15,26 +15,9 @@
  * lower label and never lets a NaN win; the lowest label that is a number at all is kept beside it for the pixel whose
  * classes are all -inf or NaN.
  */
-#include "kernelHandler.h"
-#include "kernel_limits.h"
-#include "vit_kernels.h"
-#include "ViT_opencl.h"
+#include "stitch_common.h"   /* the constants, st_src and the launcher's host side, shared with dense_stitch_soft.hip */
 
 namespace {
-
-constexpr int ST_B = VH_STITCH_BLOCK, ST_THREADS = ST_B * ST_B;
-constexpr int ST_CH = 16;                  /* classes per chunk */
-constexpr unsigned ST_NAN = 0x7FC00000u;   /* how a NaN score is written */
-static_assert(ST_THREADS == 256, "a workgroup is four waves");
-
-struct __attribute__((packed, aligned(4))) f32x4_a4 { float v[4]; };   /* 16 bytes at a 4-byte aligned address */
-
-/* The source coordinate of the centre c (cx or cy) in a window side [lo, hi) over G patches (include/kernelHandler.h) */
-__device__ __forceinline__ float st_src(float c, float lo, float hi, int G)
-{
-    const float side = hi - lo, ratio = (float)G / side, t = c - lo;
-    return fmaxf(fmaf(t, ratio, -0.5f), 0.0f);
-}
 
 __global__ __launch_bounds__(ST_THREADS) void dense_stitch_kernel(const float *__restrict__ logits, const float4 *__restrict__ boxes,
                                                                  const int *__restrict__ offsets, const int *__restrict__ ids, int GH, int GW,
@@ -150,49 +133,26 @@ extern "C" int vh_launch_dense_stitch(vh_stream_t s, const float *patch_logits, 
     static const char who[] = "vh_launch_dense_stitch";
     if (!patch_logits || !windows || !offsets || !d_scratch || !labels)
         return vh_fail(1, "%s: null pointer argument (patch_logits, windows, offsets, d_scratch, labels)", who);
-    if (n_labels < 2 || n_labels > VH_DENSE_MAX_LABELS)
-        return vh_fail(1, "%s: n_labels=%d must be in 2..%d", who, n_labels, VH_DENSE_MAX_LABELS);
-    if (grid_h < 1 || grid_w < 1 || grid_h > VH_DENSE_MAX_GRID || grid_w > VH_DENSE_MAX_GRID)
-        return vh_fail(1, "%s: grid %d x %d must be in 1..%d each way", who, grid_h, grid_w, VH_DENSE_MAX_GRID);
-    if (frame_h < 1 || frame_w < 1 || frame_h > VH_STITCH_MAX_SIDE || frame_w > VH_STITCH_MAX_SIDE)
-        return vh_fail(1, "%s: frame %d x %d must be in 1..%d each way", who, frame_h, frame_w, VH_STITCH_MAX_SIDE);
-    if (n_windows < 1 || (long)n_windows * grid_h * grid_w >= 2147483647L - 128)
-        return vh_fail(1, "%s: n_windows=%d must be positive, n_windows * grid_h * grid_w below 2^31 - 128", who, n_windows);
+    if (st_check_shape(who, n_windows, grid_h, grid_w, n_labels, frame_h, frame_w))
+        return 1;
     if (fill_label < 0 || fill_label > 255)
         return vh_fail(1, "%s: fill_label=%d must be in 0..255", who, fill_label);
-    if (vit_stitch_check(frame_h, frame_w, windows, n_windows, who))
+    int blocks_x;
+    long blocks, n_ids;
+    if (st_check_index(who, n_windows, windows, frame_h, frame_w, offsets, ids, &blocks_x, &blocks, &n_ids))
         return 1;
-    const int blocks_x = (frame_w + ST_B - 1) / ST_B, blocks_y = (frame_h + ST_B - 1) / ST_B;
-    const long blocks = (long)blocks_x * blocks_y;
-    /* the index: every id the kernel will follow is looked at here */
-    if (offsets[0] != 0)
-        return vh_fail(1, "%s: offsets[0]=%d must be 0", who, offsets[0]);
-    for (long k = 0; k < blocks; ++k)
-        if (offsets[k + 1] < offsets[k])
-            return vh_fail(1, "%s: offsets must not decrease (block %ld)", who, k);
-    const long n_ids = offsets[blocks];
-    if (n_ids > 0 && !ids)
-        return vh_fail(1, "%s: null pointer argument (ids)", who);
-    for (long k = 0; k < blocks; ++k)
-        for (long j = offsets[k]; j < offsets[k + 1]; ++j)
-            if (ids[j] < 0 || ids[j] >= n_windows || (j > offsets[k] && ids[j] <= ids[j - 1]))
-                return vh_fail(1, "%s: the ids of block %ld must be strictly ascending window indices in 0..%d", who, k, n_windows - 1);
     const size_t need = kl_dense_stitch_scratch(n_windows, frame_h, frame_w, n_ids);
     if (scratch_bytes < need)
         return vh_fail(1, "%s: scratch_bytes=%zu, %zu needed (vh_dense_stitch_scratch)", who, scratch_bytes, need);
     if ((((uintptr_t)patch_logits | (uintptr_t)d_scratch | (uintptr_t)labels | (uintptr_t)scores | (uintptr_t)cover) & 15) != 0)
         return vh_fail(1, "%s: device pointers must be 16-byte aligned", who);
     hipStream_t st = (hipStream_t)s;
-    char *const d_boxes = (char *)d_scratch;
-    char *const d_offsets = d_boxes + kl_round16((size_t)n_windows * 16);
-    char *const d_ids = d_offsets + kl_round16((size_t)(blocks + 1) * sizeof(int));
-    VH_TRY(hipMemcpy(d_boxes, windows, (size_t)n_windows * 16, hipMemcpyHostToDevice));
-    VH_TRY(hipMemcpy(d_offsets, offsets, (size_t)(blocks + 1) * sizeof(int), hipMemcpyHostToDevice));
-    if (n_ids > 0)
-        VH_TRY(hipMemcpy(d_ids, ids, (size_t)n_ids * sizeof(int), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(dense_stitch_kernel, dim3((unsigned)blocks), dim3(ST_THREADS), 0, st, patch_logits, (const float4 *)d_boxes,
-                       (const int *)d_offsets, (const int *)d_ids, grid_h, grid_w, n_labels, frame_h, frame_w, blocks_x, fill_label, labels,
-                       scores, cover);
+    st_index_dev ix;
+    const int rc = st_upload_index(d_scratch, n_windows, windows, blocks, offsets, n_ids, ids, &ix);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(dense_stitch_kernel, dim3((unsigned)blocks), dim3(ST_THREADS), 0, st, patch_logits, ix.boxes, ix.offsets, ix.ids, grid_h,
+                       grid_w, n_labels, frame_h, frame_w, blocks_x, fill_label, labels, scores, cover);
     VH_LAUNCH_CHECK("dense_stitch_kernel");
     return 0;
 }

@@ -177,4 +177,24 @@ KL_FN size_t kl_dense_stitch_scratch(int n_windows, int frame_h, int frame_w, lo
     return kl_round16((size_t)n_windows * 16) + kl_round16((blocks + 1) * sizeof(int)) + kl_round16((size_t)n_ids * sizeof(int)) + 16;
 }
 
+/* ---- soft stitch (dense_stitch_soft.hip): its scratch is the stitch's, kl_dense_stitch_scratch ---------------------------- */
+/* How pass 2 comes by the means pass 1 formed (the same bits either way): blend again, or read them back from registers */
+enum { KL_STITCH_SOFT_RECOMPUTE = 1, KL_STITCH_SOFT_REGISTERS = 2 };
+enum { KL_STITCH_SOFT_CHUNK = 16, KL_STITCH_SOFT_REG_MAX_LABELS = 160 };   /* classes per chunk; ten chunks of means in registers */
+/* the chunks of the register variant's instance that holds n_labels: built for 2, 4, 7 and 10; 0 beyond */
+KL_FN int kl_dense_stitch_soft_reg_chunks(int n_labels)
+{
+    const int chunks = (n_labels + KL_STITCH_SOFT_CHUNK - 1) / KL_STITCH_SOFT_CHUNK;
+    return chunks <= 2 ? 2 : chunks <= 4 ? 4 : chunks <= 7 ? 7 : chunks <= 10 ? 10 : 0;
+}
+KL_FN int kl_dense_stitch_soft_variant_ok(int variant, int n_labels)
+{
+    return variant == KL_STITCH_SOFT_RECOMPUTE || (variant == KL_STITCH_SOFT_REGISTERS && n_labels <= KL_STITCH_SOFT_REG_MAX_LABELS);
+}
+/* what a launch takes, by n_labels alone (measured: DESIGN.md 7, docs/LABBOOK.md) */
+KL_FN int kl_dense_stitch_soft_variant(int n_labels)
+{
+    return n_labels <= KL_STITCH_SOFT_REG_MAX_LABELS ? KL_STITCH_SOFT_REGISTERS : KL_STITCH_SOFT_RECOMPUTE;
+}
+
 #endif

@@ -106,6 +106,18 @@ int vh_hip_status(hipError_t e, const char *what);
 int vh_attention_tiled(void *stream, const float *qkv, float *output, int lowp, int n_images, int tokens, int embed_dim,
                        int num_heads);
 
+/* dense_stitch_soft.hip: vh_launch_dense_stitch_soft (include/kernelHandler.h) with the variant as an argument of the call --
+ * 0: by n_labels, as the public launcher; 1: recompute; 2: registers (csrc/kernel_limits.h).  A variant that does not take
+ * n_labels, or an unknown one, is refused like any other bad argument.  For the tests that hold one variant against the
+ * other and for tools/frame_soft_rates.py; no state is kept between calls. */
+#ifdef __cplusplus
+extern "C"
+#endif
+int vh_launch_dense_stitch_soft_as(int as_variant, void *stream, const float *patch_logits, int n_windows, int grid_h, int grid_w,
+                                   int n_labels, const float *windows, int frame_h, int frame_w, const int *offsets, const int *ids,
+                                   void *d_scratch, size_t scratch_bytes, float logit_scale, const float *values, float *prob,
+                                   float *expect, float *entropy);
+
 /* gemm_mfma.hip: token 0 of every image = class token + pos_embed[0] (ViT_seq.c:90-93,114-117) */
 int vh_cls_rows(hipStream_t st, const float *cls_token, const float *pos_embed, float *tokens, int n_images,
                 int tokens_per_image, int embed_dim);

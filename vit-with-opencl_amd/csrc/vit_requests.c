@@ -456,6 +456,19 @@ static const char *dense_soft_spec_why(const vit_dense_soft_spec *soft)
            : NULL;
 }
 
+/* soft and the maps asked for, as both vit_hip_set_dense_soft and the soft frame calls take them (on_device: the maps are
+ * device buffers, 16-byte aligned): NULL, or why not */
+const char *requests_dense_soft_why(const vit_dense_soft_spec *soft, const vit_dense_soft_buffers *sbufs, int on_device)
+{
+    const char *why = dense_soft_spec_why(soft);
+    return why ? why
+           : !sbufs ? "NULL argument (d_soft)"
+           : !sbufs->prob && !sbufs->expect && !sbufs->entropy ? "no soft map asked for (prob, expect, entropy are all NULL)"
+           : (sbufs->expect != NULL) != (soft->d_values != NULL) ? "d_values must be given exactly when expect is asked for"
+           : on_device && (((uintptr_t)sbufs->prob | (uintptr_t)sbufs->expect | (uintptr_t)sbufs->entropy) & 15) ? "device buffers must be 16-byte aligned"
+           : NULL;
+}
+
 int vit_dense_soft_check(const vit_config *cfg, const vit_dense_spec *spec, const vit_dense_soft_spec *soft, size_t *map_elems_per_image)
 {
     static const char who[] = "vit_dense_soft_check";
@@ -488,13 +501,9 @@ static int dense_arm(const char *who, const struct request_model *m, struct requ
             bufs = &no_bufs;
         const char *why = !spec->d_weight ? "no head weight"
                           : ((uintptr_t)spec->d_weight | (uintptr_t)spec->d_bias) & 15 ? "the head's weight and bias must be 16-byte aligned"
-                          : with_soft ? dense_soft_spec_why(soft)
+                          : with_soft ? requests_dense_soft_why(soft, sbufs, 1)
                           : NULL;
         why = why ? why
-              : with_soft && !sbufs ? "NULL argument (d_soft)"
-              : with_soft && !sbufs->prob && !sbufs->expect && !sbufs->entropy ? "no soft map asked for (prob, expect, entropy are all NULL)"
-              : with_soft && (sbufs->expect != NULL) != (soft->d_values != NULL) ? "d_values must be given exactly when expect is asked for"
-              : with_soft && (((uintptr_t)sbufs->prob | (uintptr_t)sbufs->expect | (uintptr_t)sbufs->entropy) & 15) ? "device buffers must be 16-byte aligned"
               : with_soft && bufs->scores && !bufs->labels ? "scores need a labels buffer"
               : !with_soft && (!bufs || !bufs->labels) ? "no labels buffer"
               : host && (bufs->scores || bufs->patch_logits) ? "the host form takes labels only (scores, patch_logits: use the device form)"

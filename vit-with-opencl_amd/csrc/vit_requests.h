@@ -129,6 +129,9 @@ int requests_set_dense(const char *who, const struct request_model *m, struct re
 int requests_set_dense_soft(const char *who, const struct request_model *m, struct requests *rq, const vit_dense_spec *spec,
                             const vit_dense_soft_spec *soft, const vit_dense_buffers *bufs, const vit_dense_soft_buffers *sbufs);
 
+/* what vit_hip_set_dense_soft refuses about soft and the maps, for the soft frame calls to refuse in their own name: NULL, or why */
+const char *requests_dense_soft_why(const vit_dense_soft_spec *soft, const vit_dense_soft_buffers *sbufs, int on_device);
+
 /* Everything the six requests own; the caller has made sure that no forward still reads it */
 void requests_release(struct requests *rq);
 

@@ -351,6 +351,8 @@ PROTOTYPES = {
         _fn("vh_launch_dense_soft", p, p, i, i, i, i, i, i, f, p, p, p, p),
         _fn("vh_dense_stitch_scratch", i, i, i, l, ret=sz),
         _fn("vh_launch_dense_stitch", p, p, i, i, i, i, fp, i, i, ip, ip, i, p, sz, p, p, p),
+        _fn("vh_dense_stitch_soft_variant", i),
+        _fn("vh_launch_dense_stitch_soft", p, p, i, i, i, i, fp, i, i, ip, ip, p, sz, f, p, p, p, p),
         _fn("vh_launch_resample_pos_embed", p, p, p, i, i, i, i, i, i, i, i),
     ],
     "ViT_opencl.h": [
@@ -430,6 +432,11 @@ PROTOTYPES = {
         _fn("vit_stitch_index", i, i, i, fp, i, ip, ip, l, ret=l),
         _fn("vit_hip_segment_frame_device_u8", p, P(ImageU8), P(Box), i, i, i, P(PixelNorm), P(FrameSpecC), P(FrameBuffers)),
         _fn("vit_hip_segment_frame_u8", p, P(ImageU8), P(Box), i, i, i, P(PixelNorm), P(FrameSpecC), P(FrameBuffers)),
+        _fn("vit_frame_soft_check", P(VitConfig), P(FrameSpecC), P(DenseSoftSpecC), i, i, i, szp),
+        _fn("vit_hip_segment_frame_soft_device_u8", p, P(ImageU8), P(Box), i, i, i, P(PixelNorm), P(FrameSpecC), P(DenseSoftSpecC),
+            P(FrameBuffers), P(DenseSoftBuffers)),
+        _fn("vit_hip_segment_frame_soft_u8", p, P(ImageU8), P(Box), i, i, i, P(PixelNorm), P(FrameSpecC), P(DenseSoftSpecC), P(FrameBuffers),
+            P(DenseSoftBuffers)),
         _fn("vit_hip_read_tokens", p, i, fp),
         _fn("vit_hip_last_layer_pending", p),
         _fn("vit_hip_profile_enable", p, i),

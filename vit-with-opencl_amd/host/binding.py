@@ -154,6 +154,16 @@ def dense_soft_check(cfg: "VitConfig", spec: DenseSpec, logit_scale: float = 1.0
     return out.value
 
 
+def frame_soft_check(cfg: "VitConfig", spec: DenseSpec, frame_h: int, frame_w: int, n_windows: int, logit_scale: float = 1.0,
+                     d_values=None, fill_label: int = 255) -> int:
+    """vit_frame_soft_check -> elements of one soft map of the frame; raises VitHipError with the library's message"""
+    out = C.c_size_t()
+    fs, soft = FrameSpecC(spec.c_struct(), int(fill_label)), DenseSoftSpecC(float(logit_scale), _device_ptr(d_values))
+    check(lib().vit_frame_soft_check(C.byref(cfg), C.byref(fs), C.byref(soft), frame_h, frame_w, n_windows, C.byref(out)),
+          "vit_frame_soft_check")
+    return out.value
+
+
 def _pos_mode(mode) -> int:
     """a mode by name, or its number handed through (the refusals of unknown numbers are the library's)"""
     return POS_MODES[mode] if isinstance(mode, str) else int(mode)
@@ -961,6 +971,65 @@ class ViTHip:
               "vit_hip_segment_frame_u8")
         del keep, head_keep
         return (out_l, out_s, out_c) if scores or cover else out_l
+
+    def segment_frame_soft_device(self, d_frame, windows, norm: PixelNorm, weight, bias=None, values=None, logit_scale: float = 1.0,
+                                  prob=None, expect=None, entropy=None, labels=None, scores=None, cover=None, filter: str = "bilinear",
+                                  layout: str = "hwc", tap: int = -1, final_norm: bool = True, fill_label: int = 255, n_labels: int = 0,
+                                  weight_stride: int = 0):
+        """vit_hip_segment_frame_soft_device_u8: segment_frame_device's arguments, plus prob / expect / entropy (float32 [H][W]
+        DeviceBuffers or device pointers; each may be None, not all) and values (a [C] float32 array or DeviceBuffer, given
+        exactly when expect is).  labels may be None: then no labels are written, and scores and cover must be None too.
+        Complete on return."""
+        fs, keep = self._frame_spec(weight, bias, tap, final_norm, fill_label, n_labels, weight_stride)
+        if values is not None and not isinstance(values, (DeviceBuffer, int, C.c_void_p)):
+            values = DeviceBuffer.from_numpy(np.ascontiguousarray(values, dtype=np.float32))
+        soft = DenseSoftSpecC(float(logit_scale), _device_ptr(values))
+        bufs = FrameBuffers(_device_ptr(labels), _device_ptr(scores), _device_ptr(cover))
+        maps = DenseSoftBuffers(_device_ptr(prob), _device_ptr(expect), _device_ptr(entropy))
+        check(self.L.vit_hip_segment_frame_soft_device_u8(self.ctx, image_descs([d_frame]), box_array(windows), len(windows),
+                                                          PIXEL_LAYOUTS[layout], RESIZE_FILTERS[filter], C.byref(norm), C.byref(fs),
+                                                          C.byref(soft), C.byref(bufs), C.byref(maps)),
+              "vit_hip_segment_frame_soft_device_u8")
+        del keep, values
+
+    def segment_frame_soft(self, frame, weight, bias=None, values=None, logit_scale: float = 1.0, tile=None, stride=None, windows=None,
+                           want=("prob",), labels: bool = True, scores: bool = False, cover: bool = False, filter: str = "bilinear",
+                           mean=None, std=None, layout: str = "hwc", tap: int = -1, final_norm: bool = True, fill_label: int = 255):
+        """A whole 8-bit frame -> {name: array [H][W]}: segment_frame's sliding-window protocol followed by its softmax.  `want`
+        names the float32 maps: "prob" (the softmax probability of the pixel's label), "expect" (sum_c p_c * values[c]: with
+        values the bin centres of a depth head, the depth map) and "entropy" (nats), over logit_scale times the mean of the
+        covering windows' logits; a pixel no window covers is NaN in all of them.  labels / scores / cover add segment_frame's
+        outputs under those names (scores and cover need labels).  frame, weight, bias, tile, stride, windows and the rest as
+        segment_frame takes them."""
+        names = ("prob", "expect", "entropy")
+        want = tuple(want)
+        if not want or any(o not in names for o in want):
+            raise ValueError(f"segment_frame_soft: want must be a non-empty subset of {names}")
+        if ("expect" in want) != (values is not None):
+            raise ValueError("segment_frame_soft: values must be given exactly when \"expect\" is in want")
+        if (scores or cover) and not labels:
+            raise ValueError("segment_frame_soft: scores and cover need labels")
+        descs, keep = host_image_descs([frame], layout)
+        H, W = descs[0].height, descs[0].width
+        if windows is None:
+            tile = int(tile or self.cfg.img_size)
+            windows = tile_boxes(H, W, tile, int(stride or 2 * tile // 3))
+        norm = mean if isinstance(mean, PixelNorm) else pixel_norm(mean, std)
+        fs, head_keep = self._frame_spec(weight, bias, tap, final_norm, fill_label)
+        if values is not None and not isinstance(values, (DeviceBuffer, int, C.c_void_p)):
+            values = DeviceBuffer.from_numpy(np.ascontiguousarray(values, dtype=np.float32))
+        soft = DenseSoftSpecC(float(logit_scale), _device_ptr(values))
+        got = {o: np.empty((H, W), dtype=np.float32) for o in want}
+        for name, asked, dtype in (("labels", labels, np.uint8), ("scores", scores, np.float32), ("cover", cover, np.uint8)):
+            if asked:
+                got[name] = np.empty((H, W), dtype=dtype)
+        bufs = FrameBuffers(*[_host_ptr(got[o]) if o in got else None for o in ("labels", "scores", "cover")])
+        maps = DenseSoftBuffers(*[_host_ptr(got[o]) if o in got else None for o in names])
+        check(self.L.vit_hip_segment_frame_soft_u8(self.ctx, descs, box_array(windows), len(windows), PIXEL_LAYOUTS[layout],
+                                                   RESIZE_FILTERS[filter], C.byref(norm), C.byref(fs), C.byref(soft), C.byref(bufs),
+                                                   C.byref(maps)), "vit_hip_segment_frame_soft_u8")
+        del keep, head_keep, values
+        return got
 
     def read_tokens(self, n: int) -> np.ndarray:
         out = np.empty((n * self.tokens, self.cfg.embed_dim), dtype=np.float32)
